@@ -10,7 +10,11 @@ workload  = hill scene (synthetic hill cloud; map built by the dev
             the line also carries B = 256 / 4096 / 8192).  --workload km2: BASELINE.json configs[4] (analytic 1 km^2 terrain, fp32 cells).
 value     = (B * n_gpus * K) / max-over-ranks wall time of K steps.
 roofline  = dominant kernel uph_solver_kernel: algorithmic bytes of one launch / its HIP-event duration, against 8 TB/s HBM.
-cpu_baseline = the CPU oracle (single thread, kind "port") on a bounded sample of the same batch, rank 0, N = 1 only.
+cpu_baseline = the CPU oracle (single thread, kind "port") on a bounded sample of the same batch, rank 0, N = 1 only (--full).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the line can carry: the
+single-trajectory latency, the penalty-kernel / small-batch / front-end extras, the live counter passes, the per-config block,
+cpu_baseline and the parity tables.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -65,8 +69,8 @@ LIVE_PMC = None      # filled by live_counter_passes(): the same dict shape as p
 
 
 def live_counter_passes(args, workload_flag):
-    """rocprofv3 --pmc passes of this very command, run as children of this bench.py invocation (N = 1, default run): one pass per counter group, each a
-    `bench.py --steps 1 --warmup 0 --no-cpu --no-extras --no-configs --no-live-counters` under `rocprofv3 --pmc ... ` (counters only: no tracing domains beside them),
+    """rocprofv3 --pmc passes of this very command, run as children of this bench.py invocation (N = 1, --full run): one pass per counter group, each a
+    `bench.py --full --steps 1 --warmup 0 --no-cpu --no-extras --no-configs --no-live-counters` under `rocprofv3 --pmc ... ` (counters only: no tracing domains beside them),
     the solve kernel's rows (MODE 2) summed.  Returns a dict like profiles/pmc_traffic.json or None (no rocprofv3, a pass failed or timed out: the line then falls back to
     the committed pass).  ~20 s per pass."""
     import csv
@@ -84,7 +88,7 @@ def live_counter_passes(args, workload_flag):
     try:
         for g in groups:
             out = os.path.join(tmp, g[0])
-            cmd = [exe, "--pmc"] + list(g) + ["--output-format", "csv", "-d", out, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0",
+            cmd = [exe, "--pmc"] + list(g) + ["--output-format", "csv", "-d", out, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "1", "--warmup", "0",
                                                "--no-cpu", "--no-extras", "--no-configs", "--no-live-counters", "--batch", str(args.batch)] + workload_flag + (["--lanes", str(args.lanes)] if args.lanes else []) + (["--fp32"] if args.fp32 else [])
             try:
                 r = subprocess.run(cmd, cwd=os.environ.get("TMPDIR", "/tmp"), capture_output=True, text=True, timeout=float(os.environ.get("UPH_BENCH_PMC_LIMIT", "150")))
@@ -212,6 +216,36 @@ def cpu_model():
     return "unknown"
 
 
+DUMP_DATA_BYTES = 60 * 10 ** 6     # --dump-outputs: below 64 MB in all, .npy headers included
+RESULT_SCALARS = ("ret", "alm_iters", "lbfgs_iters", "evals", "last_lbfgs_ret", "cost", "jerk_cost", "T_xy", "T_yaw", "rho_final", "scale_fx")
+
+
+def dump_outputs(path, out):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last step -- ALMTrajOpt.download(full=False): per trajectory the
+    final decision vector x, the coefficients c_xy / c_yaw and the scalar results -- as float64 DIR/<name>.npy.  The variable-length arrays
+    are written end to end in row order (x.npy, c_xy.npy of shape (., 2), c_yaw.npy) with every row's length in n_x.npy, n_c_xy.npy and
+    n_c_yaw.npy, so that every written value is one the solver returned.  A batch whose arrays exceed DUMP_DATA_BYTES is written as a fixed
+    sample of its trajectories (a PCG64 seed-0 permutation of the batch, taken while it fits: the row lengths depend on the inputs only, so
+    every run with the same arguments writes the same rows); rows.npy holds the batch index of every written row."""
+    B = len(out)
+    row_bytes = np.array([8 * (len(r["x"]) + r["c_xy"].size + len(r["c_yaw"]) + len(RESULT_SCALARS) + 4) for r in out])
+    if row_bytes.sum() <= DUMP_DATA_BYTES:
+        rows = np.arange(B)
+    else:
+        order = np.random.Generator(np.random.PCG64(0)).permutation(B)
+        rows = np.sort(order[:int(np.searchsorted(np.cumsum(row_bytes[order]), DUMP_DATA_BYTES, side="right"))])
+    sel = [out[i] for i in rows]
+    arrays = {"rows": rows.astype(np.float64),
+              "x": np.concatenate([r["x"] for r in sel]), "c_xy": np.concatenate([r["c_xy"] for r in sel]), "c_yaw": np.concatenate([r["c_yaw"] for r in sel]),
+              "n_x": np.array([len(r["x"]) for r in sel], dtype=np.float64), "n_c_xy": np.array([r["c_xy"].shape[0] for r in sel], dtype=np.float64),
+              "n_c_yaw": np.array([len(r["c_yaw"]) for r in sel], dtype=np.float64)}
+    for name in RESULT_SCALARS:
+        arrays[name] = np.array([float(r[name]) for r in sel])
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def single_process(args):
     """--single-process: what a one-process host (the reference's ROS node) gets from N GPUs through the C-ABI alone.  Map: uph_map_build_multi
     (x-slab fits on N host threads + one in-library ncclAllGather).  Batch: one context per device, every device its own B problems
@@ -282,6 +316,8 @@ def single_process(args):
         sync()
         dt = time.perf_counter() - t0
     rets = np.array([r["ret"] for r in opts[0].download(full=False)])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [r for o in opts for r in o.download(full=False)])
     res = single_process_line(args, N, B, dt, np.mean(np.array(kms), axis=0), float((rets == 0).mean()), [nx, ny, int(m0.voxel_num[2])], stages, stages2, map_build_s, map_build_warm_s,
                               [mm.build_stats()["stages_ms"] for mm in maps])
     res["rccl_selftest"] = selftest
@@ -627,12 +663,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well: single-trajectory latency, extras, live counter passes, "
+                                                        "the per-config block, cpu_baseline and the parity tables (a plain run only sets up, warms up, times and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; rank 0's batch)")
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU per step (hill, default 16384) / in total (km2, default 4096)")
     ap.add_argument("--cpu-sample", type=int, default=256, help="problems solved by the CPU oracle for cpu_baseline (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the penalty-kernel and small-batch measurements (profiling runs)")
     ap.add_argument("--extras-multi", action="store_true", help="run rank 0's single-GPU extras (penalty kernel, small batches, front end ...) even when N > 1 (default: N = 1 only)")
-    ap.add_argument("--no-live-counters", action="store_true", help="do not run the rocprofv3 --pmc passes of this command as children (N = 1 default run); roofline.traffic / valu_busy / mfma then "
+    ap.add_argument("--no-live-counters", action="store_true", help="do not run the rocprofv3 --pmc passes of this command as children (N = 1 --full run); roofline.traffic / valu_busy / mfma then "
                                                                      "come from the committed counter pass under profiles/, if it matches this build")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config block (BASELINE.json configs[0..4]: desert B = 256, volcano map build, km^2 B = 4096 fp64 / fp32 ...)")
     ap.add_argument("--workload", choices=("hill", "astar", "km2"), default="hill",
@@ -719,8 +758,9 @@ def main():
         else:
             m.build(xyz, download=False)    # uph_map_build: cloud upload, crop + voxel filter, bucketing, plane fits, commit -- all on the device
             map_device_s = time.time() - t0
-            m.build(xyz, download=False)    # (second call: the build scratch exists)
-            map_device_warm_s = time.time() - t0 - map_device_s
+            if args.full:
+                m.build(xyz, download=False)    # (second call: the build scratch exists)
+                map_device_warm_s = time.time() - t0 - map_device_s
             td = time.time()
             m.download()                    # host copies of map_buffer / c_buffer / occupancy for the untouched host consumers: 105 MB into fresh numpy arrays
             map_download_s = time.time() - td
@@ -766,18 +806,20 @@ def main():
         for _ in range(args.warmup):
             opt.set_rho(1.0)
             opt.solve()
-    # single-trajectory latency on the hill problem of configs[0]/[1] (not part of the timed region)
-    single = U.ALMTrajOpt(m)
-    single.upload([probs[0] if km2 else scenes.hill_problem()])
-    single.set_rho(1.0); single.solve()
-    single.set_rho(1.0); single.solve()
-    sst = single.stats()
-    single_ms = sst["kernel_ms"] + sst["prepare_ms"]
-    single_ms_per_iter = sst["kernel_ms"] / max(1, sst["lbfgs_iters"])
-    single_iters = sst["lbfgs_iters"]
-    del single
+    single_line = {}
+    if args.full:
+        # single-trajectory latency on the hill problem of configs[0]/[1] (not part of the timed region)
+        single = U.ALMTrajOpt(m)
+        single.upload([probs[0] if km2 else scenes.hill_problem()])
+        single.set_rho(1.0); single.solve()
+        single.set_rho(1.0); single.solve()
+        sst = single.stats()
+        single_line = {
+            "ms_per_lbfgs_iter": sst["kernel_ms"] / max(1, sst["lbfgs_iters"]),      # single hill trajectory alone on the GPU (configs[1]): solve kernel ms / its L-BFGS iterations
+            "single_traj_ms": sst["kernel_ms"] + sst["prepare_ms"], "single_traj_lbfgs_iters": sst["lbfgs_iters"]}      # (the solve is chaotic: a rounding-level change of the arithmetic moves this ONE problem's iteration count -- 216 / 253 in round 5 -- read ms_per_lbfgs_iter for the kernel)
+        del single
     extras = {}
-    if rank == 0 and not args.no_extras and not km2 and not astar_wl and (world == 1 or args.extras_multi):      # N > 1: the other ranks would sit at the barrier for the ~50 s these take
+    if args.full and rank == 0 and not args.no_extras and not km2 and not astar_wl and (world == 1 or args.extras_multi):      # N > 1: the other ranks would sit at the barrier for the ~50 s these take
         # BASELINE configs[1]: the penalty kernel alone (uph_eval_batch: `repeat` objective+gradient evaluations per trajectory inside
         # one launch), on the hill trajectory x 256 and on the whole batch; algorithmic bytes = samples x 376 B
         R = 20
@@ -976,6 +1018,8 @@ def main():
 
     out = opt.download(full=False)
     rets = np.array([o["ret"] for o in out])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     pipelined = None
     if args.pipelined:
         # two contexts, each with its own stream and its own copy of the batch, launched alternately: K solves in total
@@ -1012,7 +1056,7 @@ def main():
         avg_ms = float(np.mean(kernel_ms))
         achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
         live_why = None
-        if world == 1 and not km2 and not args.no_live_counters and not args.no_extras and not args.no_cpu:
+        if args.full and world == 1 and not km2 and not args.no_live_counters and not args.no_extras and not args.no_cpu:
             # driver-observed counters: the --pmc passes of this command run here, now; a failure falls back to the committed pass
             global LIVE_PMC
             try:
@@ -1062,8 +1106,7 @@ def main():
                        "rccl_world": dist.get_world_size() if distributed else 1, "parallelism": ("dp%d" % world) + (" (grid tiled by x-slab owner + 20 m halo)" if km2 and m.tile is not None else "")},
             "per_rank_ms_per_step": per_rank_ms, "per_rank_spread": (max(per_rank_ms) - min(per_rank_ms)) / max(per_rank_ms),
             "rccl_selftest": selftest, "map_hash": map_hash, "map_hash_identical_on_all_ranks": map_hash_same,
-            "ms_per_lbfgs_iter": single_ms_per_iter,       # single hill trajectory alone on the GPU (configs[1]): solve kernel ms / its L-BFGS iterations
-            "single_traj_ms": single_ms, "single_traj_lbfgs_iters": single_iters,      # (the solve is chaotic: a rounding-level change of the arithmetic moves this ONE problem's iteration count -- 216 / 253 in round 5 -- read ms_per_lbfgs_iter for the kernel)
+            **single_line,
             "batch_lbfgs_iters_per_s": iters / dt,
             "lbfgs_iters_per_traj": iters / K / args.batch, "evals_per_traj": evals / K / args.batch,
             "scaling_kernel_ms": float(np.mean(prepare_ms)),
@@ -1105,12 +1148,12 @@ def main():
                                                                 "frac_a5_only: calConstrainCostGrad alone (uph_penalty_batch, uph_solver_kernel<128,2,8>: samples + scatter, residuals stored by every call) at 376 B, all of them moved",
                                                  "target": 0.70}
         res.update(extras)
-        if world == 1 and not km2 and not args.no_configs and not args.no_extras and not args.no_cpu:
+        if args.full and world == 1 and not km2 and not args.no_configs and not args.no_extras and not args.no_cpu:
             # every BASELINE.json config in this one line (outside the timed region; N = 1 only -- for N > 1 the other ranks would wait at the barrier)
             res["configs"] = measure_configs(args, torch, U, scenes, m, res, extras.get("penalty_kernel"))
         if pipelined:
             res["pipelined"] = pipelined
-        if world == 1 and not args.no_cpu and args.cpu_sample > 0:
+        if args.full and world == 1 and not args.no_cpu and args.cpu_sample > 0:
             from oracle import oracle_py as O
             nsamp = min(args.cpu_sample, len(probs))
             if not km2:

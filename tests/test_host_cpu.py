@@ -298,3 +298,42 @@ def test_isa_scan_flags_a_load_with_a_dead_destination(tmp_path):
     assert "WAW-suspect wait at 3" in out and "v_lshlrev_b64 v[38:39]" in out, out
     out = subprocess.run([sys.executable, tool, str(f), "kernel_clean", "vm"], capture_output=True, text=True, check=True).stdout
     assert "WAW-suspect" not in out, out
+
+
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every array float64 and finite, the variable-length rows end to end with their lengths, the whole batch when
+    it fits and otherwise the same seeded sample of rows on every call, below 64 MB in all"""
+    import bench
+    rng = np.random.default_rng(5)
+
+    def fake(B):
+        out = []
+        for i in range(B):
+            nxy, nyaw = int(rng.integers(2, 41)), int(rng.integers(2, 81))
+            r = dict(x=rng.random(2 * nxy + nyaw), c_xy=rng.random((6 * nxy, 2)), c_yaw=rng.random(6 * nyaw))
+            r.update({k: float(rng.integers(0, 9)) for k in bench.RESULT_SCALARS})
+            out.append(r)
+        return out
+
+    names = ("rows", "x", "c_xy", "c_yaw", "n_x", "n_c_xy", "n_c_yaw") + bench.RESULT_SCALARS
+    for B, whole in ((7, True), (16384, False)):
+        out = fake(B)
+        bench.dump_outputs(str(tmp_path / "a"), out)
+        bench.dump_outputs(str(tmp_path / "b"), out)
+        files = sorted(os.listdir(tmp_path / "a"))
+        assert files == sorted(os.listdir(tmp_path / "b")) and set(files) == {n + ".npy" for n in names}
+        assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64e6
+        d = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in d.values())
+        assert all(np.array_equal(d[f[:-4]], np.load(tmp_path / "b" / f)) for f in files)
+        rows = d["rows"].astype(int)
+        assert (len(rows) == B) == whole and np.all(np.diff(rows) > 0) and rows[-1] < B
+        ox, oc, oy = (np.concatenate([[0], np.cumsum(d[n]).astype(int)]) for n in ("n_x", "n_c_xy", "n_c_yaw"))
+        assert (ox[-1], oc[-1], oy[-1]) == (len(d["x"]), len(d["c_xy"]), len(d["c_yaw"]))
+        for j, i in enumerate(rows):
+            r = out[i]
+            assert np.array_equal(d["x"][ox[j]:ox[j + 1]], r["x"]) and np.array_equal(d["c_xy"][oc[j]:oc[j + 1]], r["c_xy"])
+            assert np.array_equal(d["c_yaw"][oy[j]:oy[j + 1]], r["c_yaw"]) and all(d[k][j] == r[k] for k in bench.RESULT_SCALARS)
+        for sub in ("a", "b"):
+            for f in files:
+                os.remove(tmp_path / sub / f)

@@ -1,9 +1,10 @@
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r02c; mkdir -p $OUT
 rocprofv3 -L 2>/dev/null | grep -i -E "ICACHE|IFETCH|SQ_WAIT_INST|SQ_INSTS_SMEM|SQC_" | head -40 > $OUT/counters.txt
 cat $OUT/counters.txt | cut -c1-160
 run() { name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o $name -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu > $OUT/$name.json 2> $OUT/$name.err
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o $name -- python $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu > $OUT/$name.json 2> $OUT/$name.err
   f=$(find $OUT/$name -name "*counter_collection.csv" | head -1)
   python - "$f" <<'PY'
 import sys, csv, collections

@@ -2,6 +2,7 @@
 # WL=astar: the same passes for `bench.py --workload astar` (its own pmc_traffic_astar.json; no calibration / penalty-kernel passes)
 # 1. bench line un-profiled  2. rocprofv3 --kernel-trace --stats of the same command (no counters)  3. separate --pmc passes (counters only)
 # 4. FETCH_SIZE / WRITE_SIZE calibration on known-byte microkernels (tools/micro/fetch_calib.hip)  5. penalty-kernel-only trace (configs[1])
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $GRAFT_REPO_ROOT
 TAG=${1:-r02}
 WLF=""; [ "${WL:-hill}" = astar ] && WLF="--workload astar"
@@ -9,10 +10,10 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 make -C oracle -s 2>&1 | tail -2
-python bench.py $WLF --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py $WLF --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json; echo
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $GRAFT_REPO_ROOT/bench.py $WLF --steps 3 --warmup 1 --no-cpu --no-extras > $OUT/bench_profiled.json 2> $OUT/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python $ROOT/bench.py $WLF --full --steps 3 --warmup 1 --no-cpu --no-extras > $OUT/bench_profiled.json 2> $OUT/rocprof.err
 for f in $(find $OUT/kt -name "*kernel_stats*.csv"); do cp $f $OUT/kernel_stats.csv; done
 head -6 $OUT/kernel_stats.csv | cut -c1-200
 if [ -z "$WLF" ]; then
@@ -36,7 +37,7 @@ for f in $(find $OUT/ev -name "*kernel_stats*.csv"); do cp $f $OUT/eval_kernel_s
 grep "Li0EE\|, 0>\|Li8EE\|, 8>" $OUT/eval_kernel_stats.csv | cut -c1-200
 fi
 pmc() { name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o $name -- python $GRAFT_REPO_ROOT/bench.py $WLF --steps 1 --warmup 0 --no-cpu --no-extras > $OUT/$name.json 2> $OUT/$name.err
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o $name -- python $ROOT/bench.py $WLF --full --steps 1 --warmup 0 --no-cpu --no-extras > $OUT/$name.json 2> $OUT/$name.err
   f=$(find $OUT/$name -name "*counter_collection.csv" | head -1)
   python - "$f" "$OUT/pmc_summary.txt" <<'PY'
 import sys, csv, collections, re
