@@ -27,6 +27,12 @@
  *   uph_init_scaling_batch  <- ALMTrajOpt::initScaling  alm_traj_opt.cpp:349-661 (test hook)
  *   uph_report_batch        <- ALMTrajOpt::getMaxVxAxAyCurAttSig alm_traj_opt.h:170-229 + SE2Trajectory::getNonHolError
  *                              se2traj.hpp:551-561
+ *   uph_rollout_batch / uph_rollout_batch_dev
+ *                           <- ALMTrajOpt::visSE3Traj  back_end/src/alm_traj_opt.cpp:1102-1135 (SE2Trajectory::getNormSE2Pos every dt, then
+ *                              UnevenMap::getTerrainPos, + the end point) and the per-sample terms behind getMaxVxAxAyCurAttSig
+ *                              (alm_traj_opt.h:170-229): the resident batch sampled on the device
+ *   uph_rollout_sizes / uph_rollout_plan
+ *                           <- the sample count of their `for (t = 0; t < total; t += dt)` loops (total: se2traj.hpp getTotalDuration)
  *   uph_map_build_multi     <- UnevenMap::constructMap (as above) sharded over the GPUs of one node from ONE host process -- the reference
  *                              is a single process (plan_manager/src/manager_node.cpp): x-slabs + one RCCL all-gather (BASELINE.json configs[3])
  *   uph_optimize_batch_multi<- B x ALMTrajOpt::optimizeSE2Traj split over per-device contexts (BASELINE.json configs[2], [4])
@@ -441,6 +447,31 @@ int uph_batch_lbfgs_resume(uph_ctx* c, int32_t budget, int32_t finish_pass);
 int uph_batch_get_lbfgs_state(uph_ctx* c, double* g, double* d, double* pf, double* lm_s, double* lm_y, double* lm_ys, double* scal8);
 /* post-solve feasibility report per trajectory: out[B][7] = max vx, ax, ay, cur, att(-cos xi), sigma, non-holonomic error; B = uph_batch_count */
 int uph_report_batch(uph_ctx* c, double* out7);
+
+/* ---- trajectory rollout: the resident batch (coefficients and piece durations of the last solve / evaluation, what uph_report_batch reads)
+ * sampled on the device.  Sample q of a trajectory sits at t_q = the value after q additions of dt to 0.0 (the reference's running sum
+ * `for (t = 0; t < total; t += dt)`, not q * dt); a trajectory has the first q with t_q >= total samples, total = min(Nxy x T_xy, Nyaw x T_yaw)
+ * as running sums piece by piece; with_end != 0 appends one row at t = total (visSE3Traj's closing pose).  Columns per row, in this order,
+ * only the groups selected by `channels`: */
+#define UPH_ROLLOUT_STATE 1     /* 9:  t, x, y, yaw (normSO2, as getNormSE2Pos), dx, dy, ddx, ddy, dyaw                                         */
+#define UPH_ROLLOUT_TERRAIN 2   /* 7:  vx, ax, ay, cur, att (-1 / cos xi), sigma, non-holonomic error: the terms uph_report_batch reduces       */
+#define UPH_ROLLOUT_POSE 4      /* 12: UnevenMap::getTerrainPos at (x, y, yaw), the layout of uph_terrain_pose_query (R column-major, then p)   */
+#define UPH_ROLLOUT_ALL 7
+#define UPH_ROLLOUT_MAX_SAMPLES 262144   /* samples of one trajectory (>= the 200 000 of the report's own loop)                      */
+/* host only, no device needed: offsets[B + 1] = exclusive prefix sum of the row counts of B trajectories of n_xy[b] pieces of T_xy[b] and
+ * n_yaw[b] pieces of T_yaw[b].  UPH_ERR_INVALID for dt <= 0 / not finite, a negative piece count or a null pointer; UPH_ERR_LIMIT when a
+ * trajectory needs more than UPH_ROLLOUT_MAX_SAMPLES samples (or the running sum stops growing before it reaches the total). */
+int uph_rollout_sizes(int32_t B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, double dt, int32_t with_end,
+                      int64_t* offsets);
+/* the same for the resident batch of c (B = uph_batch_count): what uph_rollout_batch writes.  A problem with ret_code UPH_RET_UNSUPPORTED has
+ * no rows.  UPH_ERR_INVALID when no trajectory is resident (after uph_batch_upload and before a solve / uph_eval_batch). */
+int uph_rollout_plan(uph_ctx* c, double dt, int32_t with_end, int64_t* offsets);
+/* rows of trajectories [b0, b1) of the resident batch, row-major [row][column], positions in map coordinates (as uph_batch_download's):
+ * out holds offsets[b1] - offsets[b0] rows.  Staged through a bounded device buffer (a few hundred MB) in chunks of trajectories. */
+int uph_rollout_batch(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, double* out);
+/* the same rows written straight into device memory of the context's device (e.g. a torch tensor's data_ptr()), on the context's stream;
+ * returns after the stream has synchronised */
+int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, void* out_dev);
 
 #ifdef __cplusplus
 }

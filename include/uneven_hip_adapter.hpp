@@ -8,7 +8,8 @@
 //                                                            (MinJerkOpt::getTraj, back_end/include/utils/se2traj.hpp:682-695)
 //   ALMTrajOpt::setEnvironment    alm_traj_opt.h:127-130
 //   public parameter members      alm_traj_opt.h:29-53
-//   getMaxVxAxAyCurAttSig         alm_traj_opt.h:170-229 (device report), init / setFrontend / visSE2Traj / visSE3Traj (no-ops here)
+//   getMaxVxAxAyCurAttSig         alm_traj_opt.h:170-229 (device report), init / setFrontend / visSE2Traj / visSE3Traj (no-ops here);
+//   getSE3Path / getSE3PathBatch  visSE3Traj's path (alm_traj_opt.cpp:1102-1135) from the device rollout (uph_rollout_batch)
 //   Piece / PolyTrajectory / SE2Trajectory   back_end/include/utils/se2traj.hpp:30-150, 253-406, 408-562 (evaluation members, getNonHolError)
 //   mpc_controller/SE2Traj filler  plan_manager.cpp:150-182, mpc_controller/msg/SE2Traj.msg:1-9
 //   KinoAstar::plan / setEnvironment / init   front_end/include/front_end/kino_astar.h:147-154, front_end/src/kino_astar.cpp:5-43, 67-236
@@ -272,6 +273,12 @@ private:
     uph_map* m_ = nullptr;
 };
 
+// one pose of the SE(3) path visSE3Traj publishes (UnevenMap::getTerrainPos, uneven_map.h:203-218): R column-major (x_b, y_b, z_b), then p
+struct SE3Pose {
+    double R[9];
+    double p[3];
+};
+
 class ALMTrajOpt {
 public:
     // ---- the reference's public parameter members (alm_traj_opt.h:29-53); defaults = plan_manager/params/run_hill.yaml:32-55
@@ -426,7 +433,7 @@ public:
         in_opt = true;
         std::vector<uph_ctx*> cs(1, ctx_);
         for (ALMTrajOpt* q : peers) cs.push_back(q->ctx_);
-        last_report_.clear(); last_multi_ = false;
+        last_report_.clear(); last_multi_ = false; last_ctxs_ = cs; last_B_ = B;
         const int rc = uph_optimize_batch_multi(cs.data(), (int32_t)cs.size(), B, pr.data(), rs.data());
         in_opt = false;
         if (rc != UPH_OK) throw std::runtime_error(std::string("uph_optimize_batch_multi: ") + uph_last_error());
@@ -480,6 +487,35 @@ public:
     void visSE2Traj(const SE2Trajectory&) {}
     void visSE3Traj(const SE2Trajectory&) {}
 
+    // visSE3Traj's path (alm_traj_opt.cpp:1102-1135) without the publishing: the trajectory of the last optimizeSE2Traj sampled at
+    // t = 0, dt, 2 dt ... (the running sum t += dt) below its duration, plus the end point, each as UnevenMap::getTerrainPos of
+    // getNormSE2Pos(t) -- rolled out on the device (uph_rollout_batch)
+    std::vector<SE3Pose> getSE3Path(double dt = 0.03) {
+        if (last_multi_) return getSE3PathBatch(dt).at(0);
+        return rolloutPoses(ctx_, dt, 0, 1).at(0);
+    }
+    // the same for every trajectory of the last call, in the caller's order (an UPH_RET_UNSUPPORTED problem has an empty path).  After a call with
+    // `peers` the rows come from every device's share: the peers must still hold that batch (not destroyed, no other batch uploaded since)
+    std::vector<std::vector<SE3Pose>> getSE3PathBatch(double dt = 0.03) {
+        if (!last_multi_) return rolloutPoses(ctx_, dt, 0, -1);
+        std::vector<std::vector<SE3Pose>> out((size_t)last_B_);
+        int32_t seen = 0;
+        for (uph_ctx* c : last_ctxs_) {
+            const int n = uph_batch_count(c);
+            if (n <= 0) continue;
+            std::vector<int32_t> idx(n);
+            if (uph_batch_origin(c, idx.data()) != UPH_OK) throw std::runtime_error(std::string("uph_batch_origin: ") + uph_last_error());
+            std::vector<std::vector<SE3Pose>> part = rolloutPoses(c, dt, 0, n);
+            for (int k = 0; k < n; k++) {
+                if (idx[k] < 0 || idx[k] >= last_B_) throw std::runtime_error("getSE3PathBatch: a device no longer holds the last batch");
+                out[(size_t)idx[k]] = std::move(part[(size_t)k]);
+                seen++;
+            }
+        }
+        if (seen != last_B_) throw std::runtime_error("getSE3PathBatch: the devices no longer hold the last batch");
+        return out;
+    }
+
 private:
     // coefficient blocks of the C-ABI (lowest order first, xy interleaved per row) -> pieces with the highest order first (se2traj.hpp:682-695)
     static SE2Trajectory makeTraj(const double* cxy, int Nxy, double Txy, const double* cyaw, int Nyaw, double Tyaw) {
@@ -497,12 +533,37 @@ private:
         return t;
     }
 
+    // trajectories [b0, b1) (b1 < 0: all) of context c as visSE3Traj's poses: the POSE channel at dt with the end point
+    static std::vector<std::vector<SE3Pose>> rolloutPoses(uph_ctx* c, double dt, int32_t b0, int32_t b1) {
+        const int B = uph_batch_count(c);
+        if (B <= 0) throw std::runtime_error("getSE3Path: no trajectory has been optimised on this object");
+        if (b1 < 0) b1 = B;
+        std::vector<int64_t> off((size_t)B + 1, 0);
+        if (uph_rollout_plan(c, dt, 1, off.data()) != UPH_OK) throw std::runtime_error(std::string("uph_rollout_plan: ") + uph_last_error());
+        std::vector<double> rows((size_t)12 * (size_t)(off[b1] - off[b0]) + 1);
+        if (uph_rollout_batch(c, dt, 1, UPH_ROLLOUT_POSE, b0, b1, rows.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_rollout_batch: ") + uph_last_error());
+        std::vector<std::vector<SE3Pose>> out((size_t)(b1 - b0));
+        for (int32_t b = b0; b < b1; b++) {
+            std::vector<SE3Pose>& path = out[(size_t)(b - b0)];
+            path.resize((size_t)(off[b + 1] - off[b]));
+            for (size_t i = 0; i < path.size(); i++) {
+                const double* r = rows.data() + (size_t)12 * ((size_t)(off[b] - off[b0]) + i);
+                for (int k = 0; k < 9; k++) path[i].R[k] = r[k];
+                for (int k = 0; k < 3; k++) path[i].p[k] = r[9 + k];
+            }
+        }
+        return out;
+    }
+
     UnevenMapHandle* env_ = nullptr;
     uph_ctx* ctx_ = nullptr;
     uph_result last_{};
     std::vector<double> cxy_, cyaw_, x_;
     std::vector<double> last_report_;       // [B][7] of the last optimizeSE2TrajBatch over several devices, in the caller's order
     bool last_multi_ = false;
+    std::vector<uph_ctx*> last_ctxs_;       // the contexts of the last optimizeSE2TrajBatch (getSE3PathBatch after a call with peers)
+    int32_t last_B_ = 0;
 };
 
 

@@ -136,6 +136,10 @@ SYMBOLS = {
     "uph_microbench_batch": (C.c_int, [_VP, _I32]),
     "uph_batch_set_state": (C.c_int, [_VP, DP, DP, DP, DP, DP]),
     "uph_report_batch": (C.c_int, [_VP, DP]),
+    "uph_rollout_sizes": (C.c_int, [_I32, C.POINTER(_I32), DP, C.POINTER(_I32), DP, C.c_double, _I32, C.POINTER(_I64)]),
+    "uph_rollout_plan": (C.c_int, [_VP, C.c_double, _I32, C.POINTER(_I64)]),
+    "uph_rollout_batch": (C.c_int, [_VP, C.c_double, _I32, _I32, _I32, _I32, DP]),
+    "uph_rollout_batch_dev": (C.c_int, [_VP, C.c_double, _I32, _I32, _I32, _I32, _VP]),
     "uph_batch_set_x": (C.c_int, [_VP, DP]),
     "uph_batch_alm_passes": (C.c_int, [_VP, _I32]),
     "uph_batch_set_lbfgs_state": (C.c_int, [_VP, DP, DP, DP, DP, DP, DP, DP]),

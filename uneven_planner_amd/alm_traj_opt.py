@@ -109,6 +109,38 @@ class SE2Traj:
         return m["pos_pts"][:, :2], m["angle_pts"][:, 0]
 
 
+# uph_rollout_* channel groups (include/uneven_hip.h): columns of a rollout row, in this order when selected
+ROLLOUT_STATE, ROLLOUT_TERRAIN, ROLLOUT_POSE = 1, 2, 4
+ROLLOUT_ALL = 7
+ROLLOUT_MAX_SAMPLES = 262144
+ROLLOUT_COLUMNS = {ROLLOUT_STATE: ("t", "x", "y", "yaw", "dx", "dy", "ddx", "ddy", "dyaw"),
+                   ROLLOUT_TERRAIN: ("vx", "ax", "ay", "cur", "att", "sigma", "nonhol"),
+                   ROLLOUT_POSE: ("R00", "R10", "R20", "R01", "R11", "R21", "R02", "R12", "R22", "px", "py", "pz")}
+
+
+def rollout_columns(channels=ROLLOUT_ALL):
+    """names of the columns of a rollout row for a channel mask"""
+    return [n for g in (ROLLOUT_STATE, ROLLOUT_TERRAIN, ROLLOUT_POSE) if channels & g for n in ROLLOUT_COLUMNS[g]]
+
+
+def rollout_sizes(n_xy, T_xy, n_yaw, T_yaw, dt=0.01, with_end=False):
+    """uph_rollout_sizes (host only): offsets[B + 1] of the rows of trajectories of n_xy pieces of T_xy and n_yaw pieces of T_yaw"""
+    n_xy, n_yaw = np.ascontiguousarray(n_xy, dtype=np.int32), np.ascontiguousarray(n_yaw, dtype=np.int32)
+    T_xy, T_yaw = np.ascontiguousarray(T_xy, dtype=np.float64), np.ascontiguousarray(T_yaw, dtype=np.float64)
+    B = n_xy.shape[0]
+    offs = np.zeros(B + 1, dtype=np.int64)
+    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.load().uph_rollout_sizes(B, pi(n_xy), _dp(T_xy), pi(n_yaw), _dp(T_yaw), float(dt), int(bool(with_end)),
+                                             offs.ctypes.data_as(C.POINTER(C.c_int64))), "uph_rollout_sizes")
+    return offs
+
+
+def split_rollout(offsets, rows):
+    """(offsets, rows) of a rollout -> one view of rows per trajectory (offsets relative to the first trajectory of the range)"""
+    o = np.asarray(offsets) - int(offsets[0])
+    return [rows[int(o[i]):int(o[i + 1])] for i in range(len(o) - 1)]
+
+
 class ALMTrajOpt:
     def __init__(self, uneven_map=None, params=None):
         self.L = _lib.load()
@@ -312,6 +344,62 @@ class ALMTrajOpt:
         out = np.zeros((max(0, self.L.uph_batch_count(self.h)), 7))      # rows = this context's problems (see origin() after optimize_batch_multi)
         _lib.check(self.L.uph_report_batch(self.h, _dp(out)), "uph_report_batch")
         return out
+
+    # ---- trajectory rollout ------------------------------------------------------------------------------------------
+    def rollout_plan(self, dt=0.01, with_end=False):
+        """uph_rollout_plan: row offsets [B + 1] of the resident batch (rows = the samples of `for (t = 0; t < total; t += dt)` [+ the end point])"""
+        n = max(0, self.L.uph_batch_count(self.h))
+        offs = np.zeros(n + 1, dtype=np.int64)
+        _lib.check(self.L.uph_rollout_plan(self.h, float(dt), int(bool(with_end)), offs.ctypes.data_as(C.POINTER(C.c_int64))), "uph_rollout_plan")
+        return offs
+
+    def rollout(self, dt=0.01, channels=ROLLOUT_ALL, with_end=False, b0=0, b1=None, device=False):
+        """The resident trajectories sampled every dt on the device (uph_rollout_batch): returns (offsets, rows).  offsets[b - b0] .. offsets[b + 1 - b0]
+        are the rows of trajectory b of [b0, b1); rows [n, ncol] (columns: rollout_columns(channels)), positions in map coordinates.  device = True:
+        rows is a torch.float64 tensor on the context's device, written there by uph_rollout_batch_dev."""
+        offs_all = self.rollout_plan(dt, with_end)
+        B = offs_all.shape[0] - 1
+        b1 = B if b1 is None else int(b1)
+        b0 = int(b0)
+        if not (0 <= b0 <= b1 <= B):
+            raise _lib.UnevenHipError("rollout: trajectory range [%d, %d) outside the batch of %d" % (b0, b1, B))
+        offs = offs_all[b0:b1 + 1] - offs_all[b0]
+        ncol = len(rollout_columns(int(channels)))
+        if ncol == 0:
+            raise _lib.UnevenHipError("rollout: empty channel mask")
+        n = int(offs[-1])
+        if device:
+            import torch
+            rows = torch.empty((n, ncol), dtype=torch.float64, device="cuda:%d" % self.uneven_map.device)
+            ptr = C.c_void_p(rows.data_ptr() if n > 0 else 0)
+            if n == 0:                    # (a null pointer is refused; nothing is written for an empty range)
+                return offs, rows
+            _lib.check(self.L.uph_rollout_batch_dev(self.h, float(dt), int(bool(with_end)), int(channels), b0, b1, ptr), "uph_rollout_batch_dev")
+            return offs, rows
+        rows = np.zeros((n, ncol))
+        buf = rows if n > 0 else np.zeros((1, ncol))
+        _lib.check(self.L.uph_rollout_batch(self.h, float(dt), int(bool(with_end)), int(channels), b0, b1, _dp(buf)), "uph_rollout_batch")
+        return offs, rows
+
+    @staticmethod
+    def rollout_multi(opts, dt=0.01, channels=ROLLOUT_ALL, with_end=False):
+        """rollout of a batch solved by optimize_batch_multi over the contexts `opts`: (offsets, rows) in the caller's order (uph_batch_origin
+        maps each context's rows back, as for the report)"""
+        parts = {}
+        for o in opts:
+            if o.L.uph_batch_count(o.h) <= 0:
+                continue
+            offs, rows = o.rollout(dt, channels, with_end)
+            for k, i in enumerate(o.origin()):
+                parts[int(i)] = rows[int(offs[k]):int(offs[k + 1])]
+        B = len(parts)
+        if sorted(parts) != list(range(B)):
+            raise _lib.UnevenHipError("rollout_multi: the contexts do not hold one batch (origins %s)" % sorted(parts)[:8])
+        counts = np.array([parts[i].shape[0] for i in range(B)], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        ncol = len(rollout_columns(int(channels)))
+        rows = np.concatenate([parts[i] for i in range(B)]) if B else np.zeros((0, ncol))
+        return offs, rows.reshape(-1, ncol)
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------
     def x0_packed(self, probs):

@@ -621,8 +621,8 @@ __global__ void uph_frontend_kernel(GridDev g, const char* __restrict__ occ, con
     occxy_out[i] = in ? (int)occ2[(size_t)ixh * g.ny + iy] : -1;
 }
 
-// UnevenMap::getTerrainPos (uneven_map.h:203-218): SE(3) pose on the terrain, one query per lane.  out[12] = R column-major
-// (x_b, y_b, z_b) then p
+// UnevenMap::getTerrainPos (uneven_map.h:203-218): SE(3) pose on the terrain, one query per lane (terrainPoseFrom, terrain_dev.hpp).  out[12] = R
+// column-major (x_b, y_b, z_b) then p
 __global__ void uph_pose_kernel(GridDev g, const double* __restrict__ pos, int n, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -631,16 +631,7 @@ __global__ void uph_pose_kernel(GridDev g, const double* __restrict__ pos, int n
     locate(g, x, y, w, c);
     double tv[4];
     terrainValues(g, c, tv);
-    const double z = tv[3], zx = tv[1], zy = tv[2];
-    const double zz = sqrt(1.0 - zx * zx - zy * zy);                 // RXS2::getC
-    const double cw = cos(w), sw = sin(w);
-    double y0 = zy * 0.0 - zz * sw, y1 = zz * cw - zx * 0.0, y2 = zx * sw - zy * cw;      // zb x xyaw
-    const double yn = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
-    y0 /= yn; y1 /= yn; y2 /= yn;
-    const double x0 = y1 * zz - y2 * zy, x1 = y2 * zx - y0 * zz, x2 = y0 * zy - y1 * zx; // yb x zb
-    double* o = out + 12 * (size_t)i;
-    o[0] = x0; o[1] = x1; o[2] = x2; o[3] = y0; o[4] = y1; o[5] = y2; o[6] = zx; o[7] = zy; o[8] = zz;
-    o[9] = x; o[10] = y; o[11] = z;
+    terrainPoseFrom(x, y, w, tv, out + 12 * (size_t)i);
 }
 
 extern "C" {

@@ -29,6 +29,7 @@
 // for why this matters (scratch reloads of "uniform" VGPRs drain the memory pipeline).
 #pragma once
 #include "terrain_dev.hpp"
+#include "trajectory_dev.hpp"
 #include "uph_common.hpp"
 
 namespace uph {
@@ -1559,47 +1560,8 @@ struct Solver {
         auto sampleAt = [&](int q, double out[7]) {
             if (q < qcur) { tcur = 0.0; qcur = 0; }
             for (; qcur < q; qcur++) tcur += 0.01;
-            const double t = tcur;
-            // locatePieceIdx (se2traj.hpp:343-361) with uniform durations
-            double tl = t; int ix = 0;
-            for (; ix < Nxy && tl > Tx; ix++) tl -= Tx;
-            if (ix == Nxy) { ix--; tl += Tx; }
-            double tw = t; int iw = 0;
-            for (; iw < Nyaw && tw > Ty; iw++) tw -= Ty;
-            if (iw == Nyaw) { iw--; tw += Ty; }
-            double p[2], v[2], a[2];
-            for (int dd = 0; dd < 2; dd++) {
-                const double* c = cxy + 12 * ix + dd;
-                double val = 0, tn = 1.0;
-                for (int kk = 0; kk <= 5; kk++) { val += tn * c[kk * 2]; tn *= tl; }
-                double dv = 0; tn = 1.0;
-                for (int kk = 1; kk <= 5; kk++) { dv += kk * tn * c[kk * 2]; tn *= tl; }
-                double da = 0; tn = 1.0;
-                for (int kk = 2; kk <= 5; kk++) { da += (kk - 1) * kk * tn * c[kk * 2]; tn *= tl; }
-                p[dd] = val; v[dd] = dv; a[dd] = da;
-            }
-            const double* c = cyaw + 6 * iw;
-            double yaw = 0, tn = 1.0;
-            for (int kk = 0; kk <= 5; kk++) { yaw += tn * c[kk]; tn *= tw; }
-            double dyaw = 0; tn = 1.0;
-            for (int kk = 1; kk <= 5; kk++) { dyaw += kk * tn * c[kk]; tn *= tw; }
-            const double yawn = normSO2(yaw);
-            double cy_, sy_;
-            sincosFast(yaw, sy_, cy_);
-            const double cw = cy_, sw = sy_;
-            double tv[7];
-            terrainVariables(fgrid, p[0], p[1], yawn, cw, sw, tv, nullptr);
-            const double vnorm = sqrt(v[0] * v[0] + v[1] * v[1]);
-            const double lon = a[0] * cy_ + a[1] * sy_;
-            const double lat = -a[0] * sy_ + a[1] * cy_;
-            const double vx = vnorm * tv[0];
-            out[0] = vx;
-            out[1] = lon * tv[0] + gravity * tv[1];
-            out[2] = lat * tv[2] + gravity * tv[3];
-            out[3] = (dyaw * tv[5]) / sqrt(vx * vx + delta_sigl);
-            out[4] = -1.0 / tv[5];
-            out[5] = tv[6];
-            out[6] = fabs(v[0] * sy_ + v[1] * (-cy_));
+            TrajSample smp;
+            trajectorySample<true>(cxy, cyaw, Nxy, Nyaw, Tx, Ty, tcur, fgrid, gravity, smp, out);        // (trajectory_dev.hpp, shared with the rollout)
         };
         // two passes: max of +v and of -v for vx, ax, ay, cur (signed value of largest magnitude, alm_traj_opt.h:201-216), att
         // (= -cos xi, started at -1, :177: shifted by one so that the floor is 0), sigma, and the non-holonomic error sum

@@ -248,4 +248,19 @@ UPH_HD void terrainVariables(const GridDev& g, double x, double y, double yaw, d
     if (zout) *zout = zz;
 }
 
+// UnevenMap::getTerrainPos (uneven_map.h:203-218): SE(3) pose on the terrain at (x, y, w) from the value lookup there (tv = terrainValues of
+// locate(g, x, y, w)).  o[12] = R column-major (x_b, y_b, z_b), then p.  One definition for uph_terrain_pose_query (map_build.hip) and the pose
+// channel of the trajectory rollout (unevenhip.hip).
+UPH_HD void terrainPoseFrom(double x, double y, double w, const double tv[4], double o[12]) {
+    const double z = tv[3], zx = tv[1], zy = tv[2];
+    const double zz = sqrt(1.0 - zx * zx - zy * zy);                 // RXS2::getC
+    const double cw = cos(w), sw = sin(w);
+    double y0 = zy * 0.0 - zz * sw, y1 = zz * cw - zx * 0.0, y2 = zx * sw - zy * cw;      // zb x xyaw
+    const double yn = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
+    y0 /= yn; y1 /= yn; y2 /= yn;
+    const double x0 = y1 * zz - y2 * zy, x1 = y2 * zx - y0 * zz, x2 = y0 * zy - y1 * zx; // yb x zb
+    o[0] = x0; o[1] = x1; o[2] = x2; o[3] = y0; o[4] = y1; o[5] = y2; o[6] = zx; o[7] = zy; o[8] = zz;
+    o[9] = x; o[10] = y; o[11] = z;
+}
+
 }  // namespace uph

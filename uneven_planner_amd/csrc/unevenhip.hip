@@ -662,6 +662,96 @@ __global__ void uph_terrain_kernel(GridDev grid, const double* __restrict__ pos,
     }
 }
 
+// ---- trajectory rollout (uph_rollout_batch): every sample of the resident trajectories, one lane per sample, one 64-lane workgroup per
+// (trajectory, chunk of 64 samples).  Trajectory-uniform data -- descriptor, state (T_xy, T_yaw), launch record, grid descriptor -- is indexed
+// by blockIdx only (scalar loads); the coefficients come from L2.  The rows of a chunk are contiguous in the output: each lane writes its row
+// to LDS and the workgroup then streams the chunk out with consecutive lanes on consecutive doubles (a lane-per-row store of a 224-byte row
+// would touch a different cache line in every lane of every store).
+struct RolloutTraj {            // one trajectory of a rollout launch (formed on the host)
+    int64_t row0;               // its first row in the launch's output
+    int cnt, rows;              // samples of the t += dt loop; rows = cnt (+ 1 with the end point)
+    double total;               // getTotalDuration: t of the end point
+    double shift[2];            // map coordinate of the trajectory's frame corner (local frames, TrajFrame); unused in the map's own frame
+};
+struct RolloutArgs {
+    const TrajDesc* desc;
+    const TrajState* state;
+    const double* cxy;
+    const double* cyaw;
+    const GridDev* grid_mem;    // per-trajectory (framed) grid descriptors, or nullptr: the map's own frame (the kernel's grid argument)
+    const RolloutTraj* traj;    // [trajectories of the launch]
+    const double* tt;           // t_q: q additions of dt to 0.0, shared by the batch
+    double* out;                // [rows of the launch][ncol]
+    int b0, channels, ncol;
+};
+constexpr int ROLL_NT = 64;
+constexpr int ROLL_MAXCOL = 9 + 7 + 12;
+
+// the pose of one sample from its (x, y, yaw) in LDS: the statements of uph_pose_kernel (map_build.hip) on inputs the compiler cannot see
+// through, so that the two kernels contract the same arithmetic the same way (rows equal uph_terrain_pose_query bit for bit)
+__device__ __forceinline__ void rolloutPose(const GridDev& g, const double* in, double* o) {
+    const double x = in[0], y = in[1], w = in[2];
+    Corners c;
+    locate(g, x, y, w, c);
+    double tv[4];
+    terrainValues(g, c, tv);
+    terrainPoseFrom(x, y, w, tv, o);
+}
+
+__global__ __launch_bounds__(ROLL_NT) void uph_rollout_kernel(GridDev grid, RolloutArgs a) {
+    __shared__ double stage[ROLL_NT * ROLL_MAXCOL];
+    const RolloutTraj rt = a.traj[blockIdx.x];
+    const int q0 = (int)blockIdx.y * ROLL_NT;
+    if (q0 >= rt.rows) return;
+    const int nq = rt.rows - q0 < ROLL_NT ? rt.rows - q0 : ROLL_NT;
+    const int b = a.b0 + (int)blockIdx.x;
+    const int ncol = a.ncol;
+    const bool framed = a.grid_mem != nullptr;
+    const int pcol = ncol - 12;             // first pose column (when selected)
+    if ((int)threadIdx.x < nq) {
+        const int q = q0 + (int)threadIdx.x;
+        const TrajDesc& td = a.desc[b];
+        const double Tx = a.state[b].T_xy, Ty = a.state[b].T_yaw;
+        const GridDev g = framed ? a.grid_mem[b] : grid;
+        const double sx = framed ? rt.shift[0] : 0.0, sy = framed ? rt.shift[1] : 0.0;
+        const double t = q < rt.cnt ? a.tt[q] : rt.total;
+        const double* cx = a.cxy + td.off_cxy;
+        const double* cy = a.cyaw + td.off_cyaw;
+        TrajSample s;
+        double tm[7];
+        if (a.channels & UPH_ROLLOUT_TERRAIN) trajectorySample<true>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
+        else trajectorySample<false>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
+        double* r = stage + threadIdx.x * ncol;
+        if (a.channels & UPH_ROLLOUT_STATE) {
+            r[0] = t; r[1] = framed ? s.p[0] + sx : s.p[0]; r[2] = framed ? s.p[1] + sy : s.p[1]; r[3] = s.yawn;
+            r[4] = s.v[0]; r[5] = s.v[1]; r[6] = s.a[0]; r[7] = s.a[1]; r[8] = s.dyaw;
+            r += 9;
+        }
+        if (a.channels & UPH_ROLLOUT_TERRAIN) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) r[k] = tm[k];
+            r += 7;
+        }
+        if (a.channels & UPH_ROLLOUT_POSE) { r[0] = s.p[0]; r[1] = s.p[1]; r[2] = s.yawn; }       // (the pose's input, in the trajectory's frame)
+    }
+    __syncthreads();
+    if ((a.channels & UPH_ROLLOUT_POSE) && (int)threadIdx.x < nq) {
+        double* r = stage + threadIdx.x * ncol + pcol;
+        double in[3] = {r[0], r[1], r[2]}, o[12];
+        if (framed) {
+            rolloutPose(a.grid_mem[b], in, o);
+            o[9] += rt.shift[0]; o[10] += rt.shift[1];
+        } else {
+            rolloutPose(grid, in, o);
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) r[k] = o[k];
+    }
+    __syncthreads();
+    double* o = a.out + (size_t)(rt.row0 + q0) * ncol;
+    for (int i = (int)threadIdx.x; i < nq * ncol; i += ROLL_NT) o[i] = stage[i];
+}
+
 #ifdef UPH_ONE_KERNEL
 // device-only build of ONE instantiation (tools/one_kernel.sh: registers, spills and ISA of a kernel in seconds instead of the whole library's minutes)
 #ifndef UPH_OK_F32
@@ -753,6 +843,8 @@ struct uph_ctx {
     GridDev grid_host;                      // source of the descriptor copy (outlives the asynchronous copy)
     DevBuf d_desc, d_state, d_x, d_x0, d_gout, d_dual, d_res, d_scl, d_cxy, d_cyaw, d_hist, d_report, d_order, d_trace;
     DevBuf d_pen_gxy, d_pen_gyaw, d_pen_out;      // uph_penalty_batch outputs (allocated at its first call)
+    DevBuf d_roll_tt, d_roll_traj, d_roll_stage;  // uph_rollout_*: time table, launch records, staging of the host variant (allocated at the first call)
+    bool traj_resident = false;             // the resident coefficients / durations are those of a solve or evaluation of the current batch (rollout input)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -816,12 +908,9 @@ static int ensureOp(uph_ctx* c, int N) {
     return idx;
 }
 
-// async: enqueue only (events evb / eve bracket the launch on the context's stream); the caller synchronises and reads the time later
-static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hipEvent_t evb = nullptr, hipEvent_t eve = nullptr) {
-    if (!async && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
-    if (!evb) { evb = c->ev0; eve = c->ev1; }
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    GridDev grid = uphMapGrid(c->map);
+// the map's grid descriptor -> grid, and the descriptors the kernels read from memory (BatchDev::grid_mem) brought up to date on the context's stream
+static int syncGridMem(uph_ctx* c, GridDev& grid) {
+    grid = uphMapGrid(c->map);
     c->grid_host = grid;
     if (c->frames.empty()) {
         c->framed_valid = false;
@@ -847,6 +936,17 @@ static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hi
             c->framed_valid = true;
         }
     }
+    return UPH_OK;
+}
+
+// async: enqueue only (events evb / eve bracket the launch on the context's stream); the caller synchronises and reads the time later
+static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hipEvent_t evb = nullptr, hipEvent_t eve = nullptr) {
+    if (!async && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
+    if (!evb) { evb = c->ev0; eve = c->ev1; }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    GridDev grid;
+    const int rg = syncGridMem(c, grid);
+    if (rg != UPH_OK) return rg;
     if (c->d_parammem.ensure(sizeof(OptParams))) return UPH_ERR_HIP;
     HIPCHK(hipMemcpyAsync(c->d_parammem.p, &c->P, sizeof(OptParams), hipMemcpyHostToDevice, c->stream));
     BatchDev bd = makeBatchDev(c);
@@ -928,6 +1028,7 @@ static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hi
 #undef UPH_LAUNCH32
 #undef UPH_LAUNCH
     HIPCHK(hipGetLastError());
+    if (mode == 0 || mode == 2 || mode == 4 || mode == 7) c->traj_resident = true;      // the launches that store the trajectory (Solver::storeTrajectory)
     HIPCHK(hipEventRecord(eve, c->stream));
     if (async) return UPH_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1005,7 +1106,7 @@ void uph_ctx_destroy(uph_ctx* c) {
     for (void* p : c->op_allocs) hipFree(p);
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
-                      &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out};
+                      &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -1063,6 +1164,7 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     const int K1 = c->P.int_K + 1, mem = c->P.mem_size;
     c->B = 0;                       // the context holds no batch until this upload has succeeded as a whole
+    c->traj_resident = false;
     c->origin.clear(); c->all_rejected = false;
     int first_rj = 0;
     c->desc.assign(B, TrajDesc());
@@ -1708,6 +1810,188 @@ int uph_terrain_query(uph_map* m, const double* pos, int32_t n, double* values7,
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(values7, tv.p, 8 * 7 * (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(grads21, tg.p, 8 * 21 * (size_t)n, hipMemcpyDeviceToHost));
+    return UPH_OK;
+}
+
+
+// ---- trajectory rollout (include/uneven_hip.h uph_rollout_*) -------------------------------------------------------------------------------
+// Sample times: t_q = the value after q additions of dt to 0.0 -- the running sum of the reference's `for (t = 0; t < total; t += dt)` loops
+// (alm_traj_opt.h:182, alm_traj_opt.cpp:1109) and of Solver::report -- built ONCE per call, serially in fp64, up to the longest trajectory and
+// shared by the batch; a trajectory's count is the first q with t_q >= total (binary search).  A NaN duration has no samples, as in the loop.
+static int rolloutTimes(double dt, double tmax, std::vector<double>& tab) {
+    tab.assign(1, 0.0);
+    double t = 0.0;
+    while (t < tmax && (int64_t)tab.size() <= UPH_ROLLOUT_MAX_SAMPLES) {
+        const double tn = t + dt;
+        if (!(tn > t)) { setError("uph_rollout: the running sum t += dt stops growing before it reaches the trajectory's duration"); return UPH_ERR_LIMIT; }
+        t = tn;
+        tab.push_back(t);
+    }
+    return UPH_OK;
+}
+
+struct RolloutSizes {
+    std::vector<double> tab;        // t_q
+    std::vector<int32_t> cnt;       // samples of the loop per trajectory
+    std::vector<double> total;      // durations
+    std::vector<int64_t> offs;      // [B + 1] row offsets
+};
+
+// durations piece by piece as Solver::report forms them; skip[b] != 0: no rows
+static int rolloutSizes(int B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, const int* skip, double dt, int with_end,
+                        RolloutSizes& rs) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_rollout: dt must be positive and finite"); return UPH_ERR_INVALID; }
+    rs.cnt.assign(B, 0); rs.total.assign(B, 0.0); rs.offs.assign((size_t)B + 1, 0);
+    double tmax = 0.0;
+    for (int b = 0; b < B; b++) {
+        if (n_xy[b] < 0 || n_yaw[b] < 0) { setError("uph_rollout_sizes: negative piece count"); return UPH_ERR_INVALID; }
+        if (skip && skip[b]) continue;
+        double durx = 0.0, dury = 0.0;
+        for (int i = 0; i < n_xy[b]; i++) durx += T_xy[b];
+        for (int i = 0; i < n_yaw[b]; i++) dury += T_yaw[b];
+        rs.total[b] = durx < dury ? durx : dury;          // (dmin, as Solver::report)
+        if (rs.total[b] > tmax) tmax = rs.total[b];
+    }
+    const int r = rolloutTimes(dt, tmax, rs.tab);
+    if (r != UPH_OK) return r;
+    for (int b = 0; b < B; b++) {
+        int64_t rows = 0;
+        if (!(skip && skip[b])) {
+            const int64_t q = std::lower_bound(rs.tab.begin(), rs.tab.end(), rs.total[b]) - rs.tab.begin();
+            if (q >= (int64_t)rs.tab.size()) {
+                setError("uph_rollout: trajectory " + std::to_string(b) + " needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt");
+                return UPH_ERR_LIMIT;
+            }
+            rs.cnt[b] = (int32_t)q;
+            rows = q + (with_end ? 1 : 0);
+        }
+        rs.offs[b + 1] = rs.offs[b] + rows;
+    }
+    return UPH_OK;
+}
+
+static int rolloutColumns(int channels) {
+    return (channels & UPH_ROLLOUT_STATE ? 9 : 0) + (channels & UPH_ROLLOUT_TERRAIN ? 7 : 0) + (channels & UPH_ROLLOUT_POSE ? 12 : 0);
+}
+
+// the resident batch of c: checks + sizes
+static int rolloutPlanCtx(uph_ctx* c, double dt, int with_end, RolloutSizes& rs, const char* who) {
+    if (!c || c->B <= 0) { setError(std::string(who) + ": no batch uploaded"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    if (!c->traj_resident) {
+        setError(std::string(who) + ": no trajectory is resident -- the batch was uploaded but not solved or evaluated since (uph_batch_solve / uph_eval_batch first)");
+        return UPH_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    const int r = refreshStates(c);
+    if (r != UPH_OK) return r;
+    const int B = c->B;
+    std::vector<int32_t> nx(B), ny(B);
+    std::vector<double> tx(B), ty(B);
+    for (int b = 0; b < B; b++) { nx[b] = c->desc[b].Nxy; ny[b] = c->desc[b].Nyaw; tx[b] = c->state_host[b].T_xy; ty[b] = c->state_host[b].T_yaw; }
+    return rolloutSizes(B, nx.data(), tx.data(), ny.data(), ty.data(), c->rejected.data(), dt, with_end, rs);
+}
+
+// enqueue the kernel for trajectories [b0, b1) writing rows offs[b0] .. offs[b1] to out_dev (row offs[b0] first); the time table is resident
+static int rolloutLaunch(uph_ctx* c, const GridDev& grid, const RolloutSizes& rs, int channels, int b0, int b1, double* out_dev, std::vector<RolloutTraj>& rec) {
+    const int n = b1 - b0;
+    if (n <= 0 || rs.offs[b1] == rs.offs[b0]) return UPH_OK;
+    rec.assign(n, RolloutTraj());
+    int ychunks = 0;
+    for (int k = 0; k < n; k++) {
+        const int b = b0 + k;
+        RolloutTraj& t = rec[k];
+        t.row0 = rs.offs[b] - rs.offs[b0];
+        t.cnt = rs.cnt[b];
+        t.rows = (int)(rs.offs[b + 1] - rs.offs[b]);
+        t.total = rs.total[b];
+        t.shift[0] = c->frames.empty() ? 0.0 : c->frames[b].shift[0];
+        t.shift[1] = c->frames.empty() ? 0.0 : c->frames[b].shift[1];
+        ychunks = std::max(ychunks, (t.rows + ROLL_NT - 1) / ROLL_NT);
+    }
+    if (c->d_roll_traj.ensure(sizeof(RolloutTraj) * n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_traj.p, rec.data(), sizeof(RolloutTraj) * n, hipMemcpyHostToDevice, c->stream));
+    RolloutArgs a;
+    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
+    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
+    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
+    a.traj = c->d_roll_traj.as<RolloutTraj>(); a.tt = c->d_roll_tt.as<double>(); a.out = out_dev;
+    a.b0 = b0; a.channels = channels; a.ncol = rolloutColumns(channels);
+    hipLaunchKernelGGL(uph_rollout_kernel, dim3(n, ychunks), dim3(ROLL_NT), 0, c->stream, grid, a);
+    HIPCHK(hipGetLastError());
+    return UPH_OK;
+}
+
+// common part of the two variants: arguments, sizes, grid descriptors, time table
+static int rolloutBegin(uph_ctx* c, double dt, int with_end, int channels, int b0, int b1, const void* out, RolloutSizes& rs, GridDev& grid, const char* who) {
+    if (!c || !out || (channels & ~UPH_ROLLOUT_ALL) || !(channels & UPH_ROLLOUT_ALL)) { setError(std::string(who) + ": bad arguments (null pointer or channel mask)"); return UPH_ERR_INVALID; }
+    if (b0 < 0 || b1 < b0 || b1 > c->B) { setError(std::string(who) + ": trajectory range [b0, b1) outside the batch"); return UPH_ERR_INVALID; }
+    int r = rolloutPlanCtx(c, dt, with_end, rs, who);
+    if (r != UPH_OK) return r;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    if (c->d_roll_tt.ensure(8 * rs.tab.size())) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
+    return UPH_OK;
+}
+
+int uph_rollout_sizes(int32_t B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, double dt, int32_t with_end,
+                      int64_t* offsets) {
+    if (B < 0 || !offsets || (B > 0 && (!n_xy || !T_xy || !n_yaw || !T_yaw))) { setError("uph_rollout_sizes: bad arguments"); return UPH_ERR_INVALID; }
+    RolloutSizes rs;
+    const int r = rolloutSizes(B, n_xy, T_xy, n_yaw, T_yaw, nullptr, dt, with_end, rs);
+    if (r != UPH_OK) return r;
+    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)B + 1));
+    return UPH_OK;
+}
+
+int uph_rollout_plan(uph_ctx* c, double dt, int32_t with_end, int64_t* offsets) {
+    if (!offsets) { setError("uph_rollout_plan: bad arguments"); return UPH_ERR_INVALID; }
+    RolloutSizes rs;
+    const int r = rolloutPlanCtx(c, dt, with_end, rs, "uph_rollout_plan");
+    if (r != UPH_OK) return r;
+    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)c->B + 1));
+    return UPH_OK;
+}
+
+// the host variant stages chunks of whole trajectories through a device buffer of at most this size (one trajectory at the sample cap: 59 MB)
+static const size_t ROLL_STAGE_BYTES = (size_t)256 << 20;
+
+int uph_rollout_batch(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, double* out) {
+    RolloutSizes rs;
+    GridDev grid;
+    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out, rs, grid, "uph_rollout_batch");
+    if (r != UPH_OK) return r;
+    const size_t row_bytes = 8 * (size_t)rolloutColumns(channels);
+    const size_t need = row_bytes * (size_t)(rs.offs[b1] - rs.offs[b0]);
+    if (need > 0 && c->d_roll_stage.ensure(std::min(need, ROLL_STAGE_BYTES))) return UPH_ERR_HIP;
+    std::vector<RolloutTraj> rec;
+    for (int k0 = b0; k0 < b1;) {
+        int k1 = k0 + 1;           // whole trajectories while they fit the staging buffer (one always does)
+        while (k1 < b1 && row_bytes * (size_t)(rs.offs[k1 + 1] - rs.offs[k0]) <= ROLL_STAGE_BYTES) k1++;
+        const size_t bytes = row_bytes * (size_t)(rs.offs[k1] - rs.offs[k0]);
+        if (bytes > 0) {
+            r = rolloutLaunch(c, grid, rs, channels, k0, k1, c->d_roll_stage.as<double>(), rec);
+            if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
+            HIPCHK(hipMemcpyAsync((char*)out + row_bytes * (size_t)(rs.offs[k0] - rs.offs[b0]), c->d_roll_stage.p, bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        k0 = k1;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return UPH_OK;
+}
+
+int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, void* out_dev) {
+    RolloutSizes rs;
+    GridDev grid;
+    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out_dev, rs, grid, "uph_rollout_batch_dev");
+    if (r != UPH_OK) return r;
+    std::vector<RolloutTraj> rec;
+    r = rolloutLaunch(c, grid, rs, channels, b0, b1, (double*)out_dev, rec);
+    const hipError_t e = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
+    if (r != UPH_OK) return r;
+    if (e != hipSuccess) { setError(std::string("uph_rollout_batch_dev: ") + hipGetErrorString(e)); return UPH_ERR_HIP; }
     return UPH_OK;
 }
 
