@@ -38,6 +38,8 @@
  *   uph_optimize_batch_multi<- B x ALMTrajOpt::optimizeSE2Traj split over per-device contexts (BASELINE.json configs[2], [4])
  *   uph_kino_plan_batch     <- KinoAstar::plan  front_end/src/kino_astar.cpp:67-236 (one call per query; B = 1 reproduces one call), the caller of
  *                              the map's query interface and the producer of the front-end path PlanManager resamples (plan_manager.cpp:59-60)
+ *   uph_plan_upload         <- PlanManager::rcvWpsCallBack's chain up to the optimiser (plan_manager.cpp:43-134): kino_astar->plan (:59-60), the
+ *                              initial-guess stage (:62-132) and the arguments of optimizeSE2Traj, for a batch of goals with the paths kept on the device
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -341,6 +343,30 @@ int uph_kino_plan_batch(uph_kino* k, int32_t B, const double* starts, const doub
 /* kernel milliseconds (HIP events) of the last uph_kino_plan_batch */
 int uph_kino_stats(uph_kino* k, double* kernel_ms);
 
+/* ---- goals -> resident trajectories in one call: PlanManager::rcvWpsCallBack (plan_manager.cpp:43-134) for a batch of goals with every stage on the device.
+ * The search of uph_kino_plan_batch (kino_astar->plan, :59-60) runs into device memory; a path longer than path_cap (0: UPH_PLAN_PATH_CAP) is searched
+ * again with room for all its poses, so no clipped path is resampled; the stage of uph_resample_batch (:62-132, or the test node's with mp->test_mode,
+ * alm_traj_opt.cpp:73-144) runs on the device over the paths where the search left them, bit for bit the host routine's results (the boundary
+ * velocities sig_vel * cos / sin of the end headings, :94-95, are formed on the host); only a header per goal crosses PCIe; the problems are uploaded
+ * to c as uph_batch_upload uploads them (same limits: a problem beyond UPH_MAX_PIECE_* keeps its slot as UPH_RET_UNSUPPORTED).  k and c must be bound
+ * to the same map.  The resident batch = the goals whose search succeeded, in goal order; uph_batch_origin returns each one's goal index.
+ * Outputs [B]: status = UPH_KINO_*, traj_of = the goal's index in the resident batch or -1, n_inner_xy / n_inner_yaw = its way-point counts (0 for a
+ * goal without a path): what sizes the uph_result arrays of uph_batch_download.  Then uph_batch_solve / _solve_async / _wait / _download,
+ * uph_report_batch and uph_rollout_* work as after uph_batch_upload.  The four outputs are written together, once every search and the resampling
+ * have run; a return before that point (bad arguments, contexts on different maps, a pending asynchronous solve, a HIP failure) leaves them
+ * untouched.  No goal produced a path: UPH_ERR_INVALID WITH the outputs written and no status[b] == UPH_KINO_OK, the context holding no batch -- the
+ * only UPH_ERR_INVALID with written outputs that has no UPH_KINO_OK in them (pre-fill status with a value that is no UPH_KINO_* code, e.g. -1,
+ * to tell it apart).  A found path of fewer than two poses (not produced by the search) keeps its slot as UPH_RET_UNSUPPORTED with
+ * last_lbfgs_ret UPH_ERR_INVALID, where uph_resample_batch refuses its whole batch.  Blocking. */
+#define UPH_PLAN_PATH_CAP 1024
+int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
+                    int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw);
+/* test hook: the resident problems of a batch uploaded by uph_plan_upload exactly as the device staged them, in uph_resample_batch's output layout
+ * and the resident order (boundary velocities included).  UPH_ERR_LIMIT when a problem has more way-points than cap_xy / cap_yaw or than the staging
+ * holds (UPH_MAX_PIECE_* - 1; the counts are still written); UPH_ERR_INVALID when the resident batch did not come from uph_plan_upload. */
+int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy, double* end_xy, double* init_yaw, double* end_yaw, double* inner_xy,
+                    double* inner_yaw, int32_t* n_inner_xy, int32_t* n_inner_yaw, double* total_time);
+
 /* ---- optimiser */
 int uph_ctx_create(uph_map* m, const uph_opt_params* p, uph_ctx** out);
 void uph_ctx_destroy(uph_ctx* c);
@@ -386,7 +412,7 @@ int uph_multi_batch_plan(int32_t n_gpus, int32_t B, const uph_problem* probs, in
 int uph_batch_count(const uph_ctx* c);
 /* after uph_optimize_batch_multi every context holds ITS SHARE of the batch (uph_batch_count problems, in share order): idx[k] = the caller's index
  * of problem k of this context -- what maps the rows of uph_report_batch / uph_batch_cycles of a context back to the caller's problems.  Identity
- * after uph_batch_upload / uph_optimize_batch. */
+ * after uph_batch_upload / uph_optimize_batch; after uph_plan_upload the goal index of each resident problem. */
 int uph_batch_origin(const uph_ctx* c, int32_t* idx);
 /* split form (inputs resident in HBM before the timed region): upload -> solve (kernel only, blocking) -> download */
 int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs);

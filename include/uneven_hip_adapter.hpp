@@ -14,6 +14,7 @@
 //   mpc_controller/SE2Traj filler  plan_manager.cpp:150-182, mpc_controller/msg/SE2Traj.msg:1-9
 //   KinoAstar::plan / setEnvironment / init   front_end/include/front_end/kino_astar.h:147-154, front_end/src/kino_astar.cpp:5-43, 67-236
 //                                  (the batched device search, uph_kino_plan_batch; planBatch = many goals in one call)
+//   planSE2TrajBatch               PlanManager::rcvWpsCallBack plan_manager.cpp:43-134 for many goals in one call, every stage on the device (uph_plan_upload)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -28,6 +29,8 @@
 #include "uneven_hip.h"
 
 namespace uneven_hip {
+
+class KinoAstar;
 
 struct Mat {                       // minimal column-major stand-in with the Eigen accessors the adapter touches
     int r = 0, c = 0;
@@ -463,6 +466,17 @@ public:
         }
         return out;
     }
+    // ---- goals in, trajectories out: PlanManager::rcvWpsCallBack (plan_manager.cpp:43-134) for many goals in one call with every stage on the
+    // device (uph_plan_upload: kino->plan, the resampling stage of plan_manager.cpp:62-132 with `mgr`, the upload; then one solve).  One entry
+    // per goal: status[b] = UPH_KINO_* of its search; a goal without a path has ret[b] = -1 and an empty trajectory (as planBatch returns an empty
+    // path), traj_of[b] = -1; otherwise traj_of[b] = its index in the resident batch (getSE3PathBatch / getMaxVxAxAyCurAttSigBatch rows).  The
+    // search context must be bound to the same map.  total_time[b] is the solved trajectory's duration Nxy x T_xy (the initial guess stays on the
+    // device).  Defined after KinoAstar.
+    struct GoalPlan : BatchPlan {
+        std::vector<int32_t> status, traj_of;
+    };
+    template <class V3>
+    GoalPlan planSE2TrajBatch(KinoAstar& kino, const std::vector<V3>& starts, const std::vector<V3>& goals, const uph_manager_params& mgr, int32_t path_cap = 0);
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)
 
     // getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229): max vx, ax, ay, curvature, attitude (-cos xi), sigma sampled every 0.01 s -- evaluated
@@ -660,9 +674,72 @@ public:
     std::vector<int32_t> status, iter_num;      // of the last plan / planBatch
     void visFrontEnd() {}                        // RViz output stays with the host (no device side)
     void visExpanded() {}
+    uph_kino* handle() const { return k_; }      // the search context (ALMTrajOpt::planSE2TrajBatch)
 
 private:
     uph_kino* k_ = nullptr;
 };
+
+template <class V3>
+ALMTrajOpt::GoalPlan ALMTrajOpt::planSE2TrajBatch(KinoAstar& kino, const std::vector<V3>& starts, const std::vector<V3>& goals, const uph_manager_params& mgr,
+                                                  int32_t path_cap) {
+    if (!kino.handle()) throw std::runtime_error("planSE2TrajBatch: KinoAstar::setEnvironment has not been called");
+    if (goals.size() != starts.size()) throw std::runtime_error("planSE2TrajBatch: starts and goals differ in number");
+    const int32_t B = (int32_t)starts.size();
+    GoalPlan out;
+    if (B == 0) return out;
+    std::vector<double> s((size_t)3 * B), g((size_t)3 * B);
+    for (int32_t b = 0; b < B; b++) for (int k = 0; k < 3; k++) { s[(size_t)3 * b + k] = starts[b][k]; g[(size_t)3 * b + k] = goals[b][k]; }
+    std::vector<int32_t> nxy(B), nyw(B);
+    out.status.assign((size_t)B, -1); out.traj_of.assign((size_t)B, -1);      // (-1: no UPH_KINO_* code -- tells whether the call wrote the outputs)
+    in_opt = true;
+    last_report_.clear(); last_multi_ = false; last_ctxs_.assign(1, ctx_); last_B_ = 0;
+    const int rc = uph_plan_upload(kino.handle(), ctx_, &mgr, B, s.data(), g.data(), path_cap, out.status.data(), out.traj_of.data(), nxy.data(), nyw.data());
+    const int F = uph_batch_count(ctx_);
+    // "no goal produced a path" is the one UPH_ERR_INVALID returned with the outputs written and no UPH_KINO_OK among them: every entry empty, no
+    // throw.  Every other failure (a HIP error in the search included) leaves the outputs untouched and throws.
+    bool written = true, any_ok = false;
+    for (int32_t b = 0; b < B; b++) { written = written && out.status[b] >= 0; any_ok = any_ok || out.status[b] == UPH_KINO_OK; }
+    if (rc != UPH_OK && !(rc == UPH_ERR_INVALID && written && !any_ok)) {
+        in_opt = false;
+        throw std::runtime_error(std::string("uph_plan_upload: ") + uph_last_error());
+    }
+    std::vector<size_t> ox(B, 0), oc(B, 0), oy(B, 0);
+    size_t sx = 0, sc = 0, sy = 0;
+    for (int32_t b = 0; b < B; b++) {
+        if (out.traj_of[b] < 0) continue;
+        ox[b] = sx; oc[b] = sc; oy[b] = sy;
+        sx += (size_t)2 * nxy[b] + nyw[b] + 1; sc += (size_t)12 * (nxy[b] + 1); sy += (size_t)6 * (nyw[b] + 1);
+    }
+    std::vector<double> xs(sx + 1, 0.0), cx(sc + 1, 0.0), cy(sy + 1, 0.0);
+    std::vector<uph_result> rs((size_t)std::max(F, 0));
+    for (int32_t b = 0; b < B; b++) {
+        const int32_t j = out.traj_of[b];
+        if (j < 0) continue;
+        rs[j] = uph_result{};
+        rs[j].x_final = xs.data() + ox[b]; rs[j].c_xy = cx.data() + oc[b]; rs[j].c_yaw = cy.data() + oy[b];
+    }
+    if (F > 0) {
+        if (uph_batch_solve(ctx_) != UPH_OK || uph_batch_download(ctx_, rs.data()) != UPH_OK) {
+            in_opt = false;
+            throw std::runtime_error(std::string("planSE2TrajBatch: ") + uph_last_error());
+        }
+        last_B_ = F;
+    }
+    in_opt = false;
+    for (int32_t b = 0; b < B; b++) {
+        const int32_t j = out.traj_of[b];
+        if (j < 0) {
+            out.ret.push_back(-1); out.jerk_cost.push_back(0.0); out.total_time.push_back(0.0); out.traj.push_back(SE2Trajectory());
+            continue;
+        }
+        out.ret.push_back(rs[j].ret_code);
+        out.jerk_cost.push_back(rs[j].jerk_cost);
+        out.total_time.push_back(rs[j].ret_code == UPH_RET_UNSUPPORTED ? 0.0 : (nxy[b] + 1) * rs[j].piece_T_xy);
+        out.traj.push_back(rs[j].ret_code == UPH_RET_UNSUPPORTED ? SE2Trajectory()
+                               : makeTraj(cx.data() + oc[b], nxy[b] + 1, rs[j].piece_T_xy, cy.data() + oy[b], nyw[b] + 1, rs[j].piece_T_yaw));
+    }
+    return out;
+}
 
 }  // namespace uneven_hip

@@ -153,12 +153,20 @@ SYMBOLS = {
     "uph_kino_primitives": (C.c_int, [_VP]),
     "uph_kino_plan_batch": (C.c_int, [_VP, _I32, DP, DP, _I32, DP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32, _I32, C.POINTER(_I32)]),
     "uph_kino_stats": (C.c_int, [_VP, DP]),
+    "uph_plan_upload": (C.c_int, [_VP, _VP, C.POINTER(ManagerParams), _I32, DP, DP, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_plan_staged": (C.c_int, [_VP, _I32, _I32, DP, DP, DP, DP, DP, DP, C.POINTER(_I32), C.POINTER(_I32), DP]),
 }
 
 _LIB = None
 
 
 UPH_ERR_NO_CACHE = -5      # include/uneven_hip.h: uph_map_load_cache found no readable cache (build the map)
+UPH_PLAN_PATH_CAP = 1024   # include/uneven_hip.h: uph_plan_upload's first-search path capacity for path_cap = 0
+UPH_MAX_PIECE_XY = 128     # include/uneven_hip.h: compiled piece limits; uph_plan_upload stages at most UPH_MAX_PIECE_* - 1 way-points per problem
+UPH_MAX_PIECE_YAW = 256
+PLAN_STAGE_XY, PLAN_STAGE_YAW = UPH_MAX_PIECE_XY - 1, UPH_MAX_PIECE_YAW - 1
+UPH_ERR_INVALID, UPH_ERR_LIMIT = -1, -4
+UPH_KINO_OK = 0
 
 
 class UnevenHipError(RuntimeError):

@@ -321,6 +321,113 @@ class ALMTrajOpt:
             o._B, o._sizes, o._last = int(n), [sizes[i] for i in idx], [out[i] for i in idx]
         return out
 
+    # ---- goals -> trajectories in one call (uph_plan_upload) ---------------------------------------------------------
+    def plan_goals_upload(self, kino, starts, goals, path_cap=0, **manager_params):
+        """PlanManager::rcvWpsCallBack's chain (plan_manager.cpp:43-134) for a batch of goals with the paths kept on the device: the search of
+        `kino` (a KinoAstar on the same map), a second search with room for every clipped path, PlanManager's resampling stage on the device
+        (manager_params: resample.MANAGER_PARAMS keys, test_mode included) and the upload of the found goals' problems, in goal order.  Then
+        solve() / solve_async() + wait() and download() work as after upload().  Returns dict of [B] arrays: status (UPH_KINO_*), traj_of (index in
+        the resident batch, -1 without a path), n_inner_xy, n_inner_yaw.  A batch in which no goal has a path leaves the context empty (no raise);
+        every failure of the call raises."""
+        from .resample import MANAGER_PARAMS
+        unknown = set(manager_params) - set(MANAGER_PARAMS)
+        if unknown:
+            raise TypeError("plan_goals: unknown manager parameter(s) %s" % sorted(unknown))
+        mk = dict(MANAGER_PARAMS)
+        mk.update(manager_params)
+        mp = _lib.ManagerParams(**{k: (int(bool(v)) if k == "test_mode" else float(v)) for k, v in mk.items()})
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        if s.shape != g.shape or s.shape[0] == 0:
+            raise _lib.UnevenHipError("plan_goals: starts and goals must be the same non-empty (B, 3)")
+        B = s.shape[0]
+        st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+        nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._B, self._sizes, self._last = 0, [], []
+        rc = self.L.uph_plan_upload(kino.h, self.h, C.byref(mp), B, _dp(s), _dp(g), int(path_cap), ip(st), ip(to), ip(nx), ip(ny))
+        plan = dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny)
+        self.last_plan = plan
+        # "no goal produced a path" is the one UPH_ERR_INVALID returned with the outputs written (statuses no longer the -1 they were filled with)
+        # and no UPH_KINO_OK among them: an empty batch, not an error.  Every other return code -- a HIP failure in the search included -- raises.
+        no_path = rc == _lib.UPH_ERR_INVALID and (st >= 0).all() and not (st == _lib.UPH_KINO_OK).any()
+        if rc != 0 and not no_path:
+            _lib.check(rc, "uph_plan_upload")
+        found = np.nonzero(to >= 0)[0]
+        K1 = int(self.int_K) + 1
+        self._sizes = [dict(Nxy=int(nx[b]) + 1, Nyaw=int(ny[b]) + 1, n=2 * int(nx[b]) + int(ny[b]) + 1, S=(int(nx[b]) + 1) * K1) for b in found]
+        self._B = len(found)
+        self._trace_cap_up = getattr(self, "_trace_cap", 0)
+        return plan
+
+    def plan_goals(self, kino, starts, goals, full=False, path_cap=0, **manager_params):
+        """goals in, trajectories out (plan_goals_upload + solve + download): one dict per goal with its search `status`; a goal with a path also
+        carries `traj_of` and the result dict optimize_batch returns.  The batch stays resident: rollout(), getMaxVxAxAyCurAttSig() and origin()
+        (= the goal index of each resident trajectory) work afterwards."""
+        plan = self.plan_goals_upload(kino, starts, goals, path_cap=path_cap, **manager_params)
+        out = [dict(status=int(v)) for v in plan["status"]]
+        if self._B == 0:
+            return out
+        self.solve()
+        found = np.nonzero(plan["traj_of"] >= 0)[0]
+        res = self._download_block(plan["n_inner_xy"][found], plan["n_inner_yaw"][found], full)
+        for j, b in enumerate(found):
+            r = dict(res[j])
+            r.update(status=int(plan["status"][b]), traj_of=j)
+            out[b] = r
+        return out
+
+    def _download_block(self, nxy, nyw, full):
+        """download() for a whole resident batch into a few contiguous arrays: the uph_result array is a numpy record array whose pointer fields
+        are filled at once (no per-problem ctypes work), every result dict holds views of the blocks.  Same dicts as download(full)."""
+        nxy, nyw = np.asarray(nxy, dtype=np.int64), np.asarray(nyw, dtype=np.int64)
+        F = nxy.shape[0]
+        sizes = {"x": 2 * nxy + nyw + 1, "c_xy": 12 * (nxy + 1), "c_yaw": 6 * (nyw + 1)}
+        if full:
+            S = (nxy + 1) * (int(self.int_K) + 1)
+            sizes.update(hx=S, gx=6 * S, lam=S, mu=6 * S, scale_cx=7 * S)
+        field = dict(x="x_final", c_xy="c_xy", c_yaw="c_yaw", hx="hx", gx="gx", lam="lambda_", mu="mu", scale_cx="scale_cx")
+        R_ = _lib.Result
+        fmt = {C.c_int32: "<i4", C.c_double: "<f8"}
+        dt = np.dtype(dict(names=[f for f, _ in R_._fields_], formats=[fmt.get(t, "<u8") for _, t in R_._fields_],
+                           offsets=[getattr(R_, f).offset for f, _ in R_._fields_], itemsize=C.sizeof(R_)))
+        rec = np.zeros(F, dtype=dt)
+        blocks, offs = {}, {}
+        for k, n in sizes.items():
+            offs[k] = np.concatenate([[0], np.cumsum(n)])
+            blocks[k] = np.zeros(max(1, int(offs[k][-1])))
+            rec[field[k]] = blocks[k].ctypes.data + 8 * offs[k][:-1]
+        _lib.check(self.L.uph_batch_download(self.h, rec.ctypes.data_as(C.POINTER(R_))), "uph_batch_download")
+        sc = {k: rec[f].tolist() for k, f in (("ret", "ret_code"), ("alm_iters", "alm_iters"), ("lbfgs_iters", "lbfgs_iters"), ("evals", "evals"),
+                                              ("last_lbfgs_ret", "last_lbfgs_ret"), ("cost", "cost"), ("jerk_cost", "jerk_cost"), ("T_xy", "piece_T_xy"),
+                                              ("T_yaw", "piece_T_yaw"), ("rho_final", "rho_final"), ("scale_fx", "scale_fx"))}
+        ol = {k: o.tolist() for k, o in offs.items()}
+        out = []
+        for j in range(F):
+            d = {k: blocks[k][ol[k][j]:ol[k][j + 1]] for k in sizes}
+            d["c_xy"] = d["c_xy"].reshape(-1, 2)
+            d.update({k: v[j] for k, v in sc.items()})
+            out.append(d)
+        self._last = out
+        return out
+
+    def plan_staged(self, cap_xy=_lib.PLAN_STAGE_XY, cap_yaw=_lib.PLAN_STAGE_YAW):
+        """test hook (uph_plan_staged): the resident problems of the last plan_goals_upload as the device staged them, resident order, in
+        resample.resample_batch's dict layout plus the counts; complete = False marks a problem with more way-points than the staging holds
+        (UPH_MAX_PIECE_* - 1: an UNSUPPORTED slot) or cap_*: its way-point arrays are then the first ones only"""
+        B = max(0, self.L.uph_batch_count(self.h))
+        ixy, exy, iyw, eyw = np.zeros((B, 6)), np.zeros((B, 6)), np.zeros((B, 3)), np.zeros((B, 3))
+        oxy, oyw = np.zeros((B, 2 * max(cap_xy, 1))), np.zeros((B, max(cap_yaw, 1)))
+        nxy, nyw, tt = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.L.uph_plan_staged(self.h, int(cap_xy), int(cap_yaw), _dp(ixy), _dp(exy), _dp(iyw), _dp(eyw), _dp(oxy), _dp(oyw), ip(nxy), ip(nyw), _dp(tt))
+        if rc != _lib.UPH_ERR_LIMIT:      # a problem had more way-points than fit (complete = False below), the rest is written
+            _lib.check(rc, "uph_plan_staged")
+        kx, ky = min(cap_xy, _lib.PLAN_STAGE_XY), min(cap_yaw, _lib.PLAN_STAGE_YAW)
+        return [dict(init_xy=ixy[b].reshape(3, 2).T.copy(), end_xy=exy[b].reshape(3, 2).T.copy(), inner_xy=oxy[b, :2 * min(nxy[b], kx)].reshape(-1, 2).T.copy(),
+                     init_yaw=iyw[b].copy(), end_yaw=eyw[b].copy(), inner_yaw=oyw[b, :min(nyw[b], ky)].copy(), total_time=float(tt[b]),
+                     n_inner_xy=int(nxy[b]), n_inner_yaw=int(nyw[b]), complete=bool(nxy[b] <= kx and nyw[b] <= ky)) for b in range(B)]
+
     # ---- the reference's entry point -------------------------------------------------------------------------------
     def optimizeSE2Traj(self, initStateXY, endStateXY, innerPtsXY, initYaw, endYaw, innerPtsYaw, totalTime):
         """ALMTrajOpt::optimizeSE2Traj (alm_traj_opt.h:92-98, alm_traj_opt.cpp:168-278).  Returns 0 / 1 / 2."""

@@ -817,11 +817,10 @@ int uph_kino_set_wps(uph_kino* k, int32_t wps) {
 }
 int uph_kino_primitives(const uph_kino* k) { return k ? k->P.n_inputs : UPH_ERR_INVALID; }
 
-int uph_kino_plan_batch(uph_kino* k, int32_t B, const double* starts, const double* goals, int32_t path_cap, double* paths, int32_t* n_path, int32_t* status,
-                        int32_t* iter_num, int32_t* use_node_num, int32_t max_expand, int32_t exp_cap, int32_t* expanded) {
-    if (!k || B <= 0 || !starts || !goals || path_cap < 0 || (path_cap > 0 && !paths) || !n_path || !status || exp_cap < 0 || (exp_cap > 0 && !expanded)) {
-        setError("uph_kino_plan_batch: bad arguments"); return UPH_ERR_INVALID;
-    }
+}  // extern "C"
+
+// the search of uph_kino_plan_batch without the downloads: the B queries' results stay in the context's device buffers (valid until its next search)
+int uphKinoSearch(uph_kino* k, int32_t B, const double* starts, const double* goals, int32_t path_cap, int32_t max_expand, int32_t exp_cap, UphKinoOut& out) {
     KHIPCHK(hipSetDevice(k->device));
     if (k->auto_slots && k->slots < std::min((int)B, k->slots_cap)) {
         // automatic workspaces follow the batch, GEOMETRICALLY: first call, or a larger batch than any before -> at least twice the previous capacity, so a
@@ -881,11 +880,27 @@ int uph_kino_plan_batch(uph_kino* k, int32_t B, const double* starts, const doub
     float ms = 0.f;
     KHIPCHK(hipEventElapsedTime(&ms, k->e0, k->e1));
     k->last_ms = ms;
-    if (path_cap > 0) KHIPCHK(hipMemcpy(paths, k->d_io[2], sizeof(double) * 3 * (size_t)B * path_cap, hipMemcpyDeviceToHost));
-    KHIPCHK(hipMemcpy(n_path, k->d_io[3], need[3], hipMemcpyDeviceToHost));
-    KHIPCHK(hipMemcpy(status, k->d_io[4], need[4], hipMemcpyDeviceToHost));
-    if (iter_num) KHIPCHK(hipMemcpy(iter_num, k->d_io[5], need[5], hipMemcpyDeviceToHost));
-    if (use_node_num) KHIPCHK(hipMemcpy(use_node_num, k->d_io[6], need[6], hipMemcpyDeviceToHost));
+    out.paths = (const double*)k->d_io[2];
+    out.n_path = (const int*)k->d_io[3]; out.status = (const int*)k->d_io[4];
+    return UPH_OK;
+}
+const uph_map* uphKinoMap(const uph_kino* k) { return k ? k->map : nullptr; }
+
+extern "C" {
+
+int uph_kino_plan_batch(uph_kino* k, int32_t B, const double* starts, const double* goals, int32_t path_cap, double* paths, int32_t* n_path, int32_t* status,
+                        int32_t* iter_num, int32_t* use_node_num, int32_t max_expand, int32_t exp_cap, int32_t* expanded) {
+    if (!k || B <= 0 || !starts || !goals || path_cap < 0 || (path_cap > 0 && !paths) || !n_path || !status || exp_cap < 0 || (exp_cap > 0 && !expanded)) {
+        setError("uph_kino_plan_batch: bad arguments"); return UPH_ERR_INVALID;
+    }
+    UphKinoOut io;
+    const int r = uphKinoSearch(k, B, starts, goals, path_cap, max_expand, exp_cap, io);
+    if (r != UPH_OK) return r;
+    if (path_cap > 0) KHIPCHK(hipMemcpy(paths, io.paths, sizeof(double) * 3 * (size_t)B * path_cap, hipMemcpyDeviceToHost));
+    KHIPCHK(hipMemcpy(n_path, io.n_path, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    KHIPCHK(hipMemcpy(status, io.status, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    if (iter_num) KHIPCHK(hipMemcpy(iter_num, k->d_io[5], sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    if (use_node_num) KHIPCHK(hipMemcpy(use_node_num, k->d_io[6], sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
     if (exp_cap > 0) KHIPCHK(hipMemcpy(expanded, k->d_io[7], sizeof(int) * 3 * (size_t)B * exp_cap, hipMemcpyDeviceToHost));
     return UPH_OK;
 }

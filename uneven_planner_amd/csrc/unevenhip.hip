@@ -18,6 +18,7 @@
 
 #include "../../include/uneven_hip.h"
 #include "minco_op_host.hpp"
+#include "resample_walk.hpp"
 #include "solver_program.hpp"
 #include "uph_internal.hpp"
 
@@ -752,6 +753,104 @@ __global__ __launch_bounds__(ROLL_NT) void uph_rollout_kernel(GridDev grid, Roll
     for (int i = (int)threadIdx.x; i < nq * ncol; i += ROLL_NT) o[i] = stage[i];
 }
 
+// ---- goals -> resident batch (uph_plan_upload): PlanManager's initial-guess stage (plan_manager.cpp:62-132; with mp.test_mode the test node's,
+// alm_traj_opt.cpp:73-144) over the paths the front-end search left in HBM, then x0 scattered from the staging into the resident batch.
+// Staging (owned by the context, indexed by GOAL): way-points [goal][PLAN_SX][2] and [goal][PLAN_SY], and one PlanHead per goal -- the only
+// part that crosses PCIe.  A path that needs more way-points than the staging holds is counted, not written: the upload makes it a placeholder
+// (UPH_RET_UNSUPPORTED), as uph_batch_upload treats a problem beyond UPH_MAX_PIECE_*.
+constexpr int PLAN_SX = UPH_MAX_PIECE_XY - 1, PLAN_SY = UPH_MAX_PIECE_YAW - 1;
+struct PlanHead {
+    int32_t n_inner_xy, n_inner_yaw;
+    int32_t short_path, pad;        // short_path: fewer than two poses (uph_resample_batch refuses such a path)
+    double p_init[2], p_end[2];     // P of the init / end states (:87-90)
+    double yaw_init, yaw_end;       // unwrapped yaw of the first / last pose (:91-92)
+    double total_time;              // :122 / alm_traj_opt.cpp:137
+    double lo[2], hi[2];            // bounding box of the way-points with init / end (local frames, tile check)
+    double turn, kink;              // heading changes along init yaw, inner yaw..., end yaw in predictedCost's order (launch order)
+};
+struct PlanPath {
+    const double* p;
+    __host__ __device__ double operator()(int64_t k, int j) const { return p[3 * k + j]; }
+};
+struct PlanSink {
+    double *oxy, *oyw;
+    int nxy, nyw;
+    double nlo[2], nhi[2], prev, turn, kink;
+    __device__ void xy(double x, double y) {
+        if (nxy < PLAN_SX) { oxy[2 * nxy] = x; oxy[2 * nxy + 1] = y; }
+        nxy++;
+        nlo[0] = x < nlo[0] ? x : nlo[0]; nlo[1] = y < nlo[1] ? y : nlo[1];
+        nhi[0] = nhi[0] < x ? x : nhi[0]; nhi[1] = nhi[1] < y ? y : nhi[1];
+    }
+    __device__ void yaw(double v) {
+        if (nyw < PLAN_SY) oyw[nyw] = v;
+        nyw++;
+        const double d = fabs(v - prev);
+        turn += d; kink = kink < d ? d : kink; prev = v;
+    }
+    __device__ void unwrapped(int64_t, double) {}
+};
+// one lane per query (the comb walk is sequential).  Query q of this launch is goal goal_of[q] (nullptr: q); queries the search did not solve, or
+// whose path it clipped at path_cap, are left alone (the clipped ones come again from a search with room for their whole path)
+__global__ __launch_bounds__(64) void uph_plan_resample_kernel(uph_manager_params mp, const double* __restrict__ paths, int path_cap, const int* __restrict__ n_path,
+                                                               const int* __restrict__ status, int nq, const int* __restrict__ goal_of, double* __restrict__ st_xy,
+                                                               double* __restrict__ st_yaw, PlanHead* __restrict__ heads) {
+#pragma clang fp contract(off)
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int m = n_path[q];
+    if (status[q] != UPH_KINO_OK || m > path_cap) return;
+    const int g = goal_of ? goal_of[q] : q;
+    PlanHead h = PlanHead{};
+    if (m < 2) { h.short_path = 1; heads[g] = h; return; }
+    const double* p = paths + (size_t)q * path_cap * 3;
+    const WalkSetup ws = walkSetup(mp);
+    PlanSink s;
+    s.oxy = st_xy + (size_t)g * PLAN_SX * 2; s.oyw = st_yaw + (size_t)g * PLAN_SY;
+    s.nxy = s.nyw = 0;
+    s.nlo[0] = s.nlo[1] = __builtin_huge_val(); s.nhi[0] = s.nhi[1] = -__builtin_huge_val();
+    s.prev = p[2]; s.turn = 0.0; s.kink = 0.0;
+    const WalkEnd e = resampleWalk(ws, PlanPath{p}, (int64_t)m, s);
+    h.n_inner_xy = s.nxy; h.n_inner_yaw = s.nyw;
+    h.p_init[0] = p[0]; h.p_init[1] = p[1]; h.p_end[0] = p[3 * (m - 1)]; h.p_end[1] = p[3 * (m - 1) + 1];
+    h.yaw_init = e.yaw_first; h.yaw_end = e.yaw_last;
+    h.total_time = walkTotalTime(ws, mp, e.len);
+    for (int d = 0; d < 2; d++) {
+        const double a = h.p_init[d] < h.p_end[d] ? h.p_init[d] : h.p_end[d], b = h.p_init[d] < h.p_end[d] ? h.p_end[d] : h.p_init[d];
+        h.lo[d] = s.nlo[d] < a ? s.nlo[d] : a;
+        h.hi[d] = b < s.nhi[d] ? s.nhi[d] : b;
+    }
+    const double d = fabs(e.yaw_last - s.prev);         // the end yaw closes the sequence (predictedCost)
+    h.turn = s.turn + d; h.kink = s.kink < d ? d : s.kink;
+    heads[g] = h;
+}
+// x0 = [logC2(T) | inner_xy - frame shift | inner_yaw] (alm_traj_opt.cpp:206-216) of every resident problem from the staging, into x and x0 at the
+// descriptor offsets: one 64-lane workgroup per problem.  src < 0: uph_batch_upload's two-piece placeholder of an unsupported problem.
+struct PlanScatter {
+    int64_t off_x;
+    int32_t src, nxy, nyw, pad;
+    double shift[2];
+    double tau;                     // logC2(total_time), formed on the host as uph_batch_upload forms it
+};
+__global__ __launch_bounds__(64) void uph_plan_scatter_kernel(const PlanScatter* __restrict__ rec, const double* __restrict__ st_xy, const double* __restrict__ st_yaw,
+                                                              double* __restrict__ x, double* __restrict__ x0) {
+    const PlanScatter r = rec[blockIdx.x];
+    const int n = 1 + 2 * r.nxy + r.nyw;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double v;
+        if (i == 0) v = r.tau;
+        else if (i <= 2 * r.nxy) {
+            const int j = i - 1;
+            v = (r.src >= 0 ? st_xy[(size_t)r.src * PLAN_SX * 2 + j] : (j == 0 ? 0.3 : 0.0)) - r.shift[j & 1];
+        } else {
+            const int j = i - 1 - 2 * r.nxy;
+            v = r.src >= 0 ? st_yaw[(size_t)r.src * PLAN_SY + j] : 0.0;
+        }
+        x[r.off_x + i] = v;
+        x0[r.off_x + i] = v;
+    }
+}
+
 #ifdef UPH_ONE_KERNEL
 // device-only build of ONE instantiation (tools/one_kernel.sh: registers, spills and ISA of a kernel in seconds instead of the whole library's minutes)
 #ifndef UPH_OK_F32
@@ -798,6 +897,16 @@ struct HostBuf {
     template <class T> T* as() { return (T*)p; }
 };
 
+// What the admission of a batch reads of a problem: its scalars, the bounding box of its initial path and the heading changes of its yaw way-points --
+// not the way-points themselves.  uph_batch_upload forms it from the caller's uph_problem, uph_plan_upload from the headers the device staged.
+struct ProblemHead {
+    int32_t n_inner_xy = 0, n_inner_yaw = 0;
+    int refused = 0;                // != 0: refused before the limit checks (that UPH_ERR_* reason, message `why`)
+    const char* why = nullptr;
+    double init_xy[6], end_xy[6], init_yaw[3], end_yaw[3], total_time = 0.0;
+    double lo[2], hi[2];            // bounding box of the inner way-points together with the init / end positions
+    double turn = 0.0, kink = 0.0;  // yawTurnKink
+};
 struct uph_ctx {
     uph_map* map = nullptr;
     int device = 0;                         // copied at creation: the context must never dereference the map during teardown
@@ -845,6 +954,10 @@ struct uph_ctx {
     DevBuf d_pen_gxy, d_pen_gyaw, d_pen_out;      // uph_penalty_batch outputs (allocated at its first call)
     DevBuf d_roll_tt, d_roll_traj, d_roll_stage;  // uph_rollout_*: time table, launch records, staging of the host variant (allocated at the first call)
     bool traj_resident = false;             // the resident coefficients / durations are those of a solve or evaluation of the current batch (rollout input)
+    // uph_plan_upload: staging indexed by goal (PlanHead, way-points), re-searched goals' indices, scatter records; the resident problems as staged
+    DevBuf d_plan_head, d_plan_xy, d_plan_yaw, d_plan_goal, d_plan_rec;
+    bool planned = false;                   // the resident batch came from uph_plan_upload (uph_plan_staged may read the staging)
+    std::vector<ProblemHead> plan_probs;   // [B] the staged problems in resident order, boundary velocities formed on the host
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -1106,7 +1219,8 @@ void uph_ctx_destroy(uph_ctx* c) {
     for (void* p : c->op_allocs) hipFree(p);
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
-                      &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage};
+                      &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
+                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -1147,24 +1261,62 @@ int uph_ctx_get_trace(uph_ctx* c, double* out /* B x cap */) {
 }
 
 // a-priori cost of one solve (relative units): the launch order inside a batch and the split of a batch over several GPUs use it
-static double predictedCost(const uph_problem& pr) {
-    double turn = 0.0, kink = 0.0, prev = pr.init_yaw[0];
+static void yawTurnKink(const uph_problem& pr, double& turn, double& kink) {
+    double prev = pr.init_yaw[0];
+    turn = 0.0; kink = 0.0;
     for (int i = 0; i <= pr.n_inner_yaw; i++) {
         const double cur = i < pr.n_inner_yaw ? pr.inner_yaw[i] : pr.end_yaw[0];
         const double dy = std::fabs(cur - prev);
         turn += dy; kink = std::max(kink, dy); prev = cur;
     }
-    const double n = 2.0 * pr.n_inner_xy + pr.n_inner_yaw + 1.0;
+}
+static double predictedCostOf(int32_t n_inner_xy, int32_t n_inner_yaw, double turn, double kink) {
+    const double n = 2.0 * n_inner_xy + n_inner_yaw + 1.0;
     return std::pow(n, 0.831) * std::exp(0.129 * turn) * std::pow(1.0 + kink, 0.408);
 }
+static double predictedCost(const uph_problem& pr) {
+    double turn, kink;
+    yawTurnKink(pr, turn, kink);
+    return predictedCostOf(pr.n_inner_xy, pr.n_inner_yaw, turn, kink);
+}
 
-int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
-    if (!c || B <= 0 || !probs) { setError("uph_batch_upload: bad arguments"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError("uph_batch_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+static ProblemHead headOf(const uph_problem& q) {
+    ProblemHead h;
+    h.n_inner_xy = q.n_inner_xy; h.n_inner_yaw = q.n_inner_yaw;
+    for (int k = 0; k < 6; k++) { h.init_xy[k] = q.init_xy[k]; h.end_xy[k] = q.end_xy[k]; }
+    for (int k = 0; k < 3; k++) { h.init_yaw[k] = q.init_yaw[k]; h.end_yaw[k] = q.end_yaw[k]; }
+    h.total_time = q.total_time;
+    if (q.n_inner_xy < 0 || q.n_inner_yaw < 0 || (q.n_inner_xy > 0 && !q.inner_xy) || (q.n_inner_yaw > 0 && !q.inner_yaw)) {
+        h.refused = UPH_ERR_INVALID; h.why = "uph_batch_upload: negative way-point count or missing way-point array";
+        return h;
+    }
+    for (int d = 0; d < 2; d++) { h.lo[d] = std::min(q.init_xy[d], q.end_xy[d]); h.hi[d] = std::max(q.init_xy[d], q.end_xy[d]); }
+    for (int i = 0; i < q.n_inner_xy; i++)
+        for (int d = 0; d < 2; d++) { h.lo[d] = std::min(h.lo[d], q.inner_xy[2 * i + d]); h.hi[d] = std::max(h.hi[d], q.inner_xy[2 * i + d]); }
+    yawTurnKink(q, h.turn, h.kink);
+    return h;
+}
+// A problem outside the compiled limits (more pieces than UPH_MAX_PIECE_*; fewer yaw pieces than position pieces; on a tile map a
+// path outside the tile) does not fail its neighbours: a two-piece placeholder takes its slot and its result carries ret_code
+// UPH_RET_UNSUPPORTED.  Only a batch with no supported problem at all is an error.  (A goal closer than one piece length -- a single
+// quintic per block, no inner way-point -- IS solved, as the reference solves it.)
+static const double ph_inner_xy[2] = {0.3, 0.0}, ph_inner_yaw[1] = {0.0};
+static uph_problem placeholderProblem() {
+    uph_problem placeholder;
+    std::memset(&placeholder, 0, sizeof(placeholder));
+    placeholder.n_inner_xy = 1; placeholder.n_inner_yaw = 1; placeholder.inner_xy = ph_inner_xy; placeholder.inner_yaw = ph_inner_yaw;
+    placeholder.init_xy[2] = 0.05; placeholder.end_xy[0] = 0.6; placeholder.end_xy[2] = 0.05; placeholder.total_time = 1.44;
+    return placeholder;
+}
+
+// First half of an upload: admit B problems from their heads -- limit / tile checks (refused ones become the placeholder), local frames, the
+// descriptors, the device buffers, the LPT launch order and the residency classes.  The caller then fills x / x0 and calls commitBatch.
+// pp[b] = the head the slot is solved from (the placeholder's for a refused problem).
+static int admitBatch(uph_ctx* c, int32_t B, const ProblemHead* heads, std::vector<const ProblemHead*>& pp) {
     const int K1 = c->P.int_K + 1, mem = c->P.mem_size;
     c->B = 0;                       // the context holds no batch until this upload has succeeded as a whole
     c->traj_resident = false;
+    c->planned = false;
     c->origin.clear(); c->all_rejected = false;
     int first_rj = 0;
     c->desc.assign(B, TrajDesc());
@@ -1176,33 +1328,23 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     c->lanes = c->lanes_forced ? c->lanes_forced : (B >= 2304 ? 128 : (B <= 256 ? 512 : 256));      // up to one trajectory per CU: eight waves each (shortest latency)
     c->wps = c->wps_forced ? c->wps_forced : ((B >= 512) ? 2 : 1);
     c->fp_bytes.assign(B, 0);
-    // A problem outside the compiled limits (more pieces than UPH_MAX_PIECE_*; fewer yaw pieces than position pieces; on a tile map a
-    // path outside the tile) does not fail its neighbours: a two-piece placeholder takes its slot and its result carries ret_code
-    // UPH_RET_UNSUPPORTED.  Only a batch with no supported problem at all is an error.  (A goal closer than one piece length -- a single
-    // quintic per block, no inner way-point -- IS solved, as the reference solves it.)
-    static const double ph_inner_xy[2] = {0.3, 0.0}, ph_inner_yaw[1] = {0.0};
-    uph_problem placeholder;
-    std::memset(&placeholder, 0, sizeof(placeholder));
-    placeholder.n_inner_xy = 1; placeholder.n_inner_yaw = 1; placeholder.inner_xy = ph_inner_xy; placeholder.inner_yaw = ph_inner_yaw;
-    placeholder.init_xy[2] = 0.05; placeholder.end_xy[0] = 0.6; placeholder.end_xy[2] = 0.05; placeholder.total_time = 1.44;
-    std::vector<const uph_problem*> pp(B);
+    static const ProblemHead placeholder = headOf(placeholderProblem());
+    pp.assign(B, nullptr);
     c->rejected.assign(B, 0); c->n_rejected = 0;
     const GridDev tg = uphMapGrid(c->map);
     const bool tiled = tg.nx_hold < tg.nx;
     const double tile_lo = tg.origin[0] + tg.x_off * tg.xy_res, tile_hi = tg.origin[0] + (tg.x_off + tg.nx_hold) * tg.xy_res;
     std::string why;
     for (int b = 0; b < B; b++) {
-        const uph_problem& q = probs[b];
+        const ProblemHead& q = heads[b];
         int rj = 0;
         const char* msg = nullptr;
         // (a block without inner way-points is a single quintic piece -- a goal closer than one piece length; the reference solves it, and so does this)
-        if (q.n_inner_xy < 0 || q.n_inner_yaw < 0 || (q.n_inner_xy > 0 && !q.inner_xy) || (q.n_inner_yaw > 0 && !q.inner_yaw)) { rj = UPH_ERR_INVALID; msg = "uph_batch_upload: negative way-point count or missing way-point array"; }
+        if (q.refused) { rj = q.refused; msg = q.why; }
         else if (q.n_inner_xy + 1 > UPH_MAX_PIECE_XY || q.n_inner_yaw + 1 > UPH_MAX_PIECE_YAW) { rj = UPH_ERR_LIMIT; msg = "uph_batch_upload: piece count exceeds UPH_MAX_PIECE_*"; }
         else if (q.n_inner_yaw < q.n_inner_xy) { rj = UPH_ERR_INVALID; msg = "uph_batch_upload: piece_yaw < piece_xy (the reference indexes yaw_minco.T1 with the xy piece index, alm_traj_opt.cpp:749)"; }
         else if (tiled) {                // a tile map serves the problems routed to it: the initial path must lie well inside the held rows (the grid's own border is no tile border)
-            double lo = std::min(q.init_xy[0], q.end_xy[0]), hi = std::max(q.init_xy[0], q.end_xy[0]);
-            for (int i = 0; i < q.n_inner_xy; i++) { lo = std::min(lo, q.inner_xy[2 * i]); hi = std::max(hi, q.inner_xy[2 * i]); }
-            if ((tg.x_off > 0 && lo < tile_lo + UPH_TILE_MARGIN) || (tg.x_off + tg.nx_hold < tg.nx && hi > tile_hi - UPH_TILE_MARGIN)) { rj = UPH_ERR_INVALID; msg = "uph_batch_upload: the path does not lie inside this map tile (route it to the tile's owner)"; }
+            if ((tg.x_off > 0 && q.lo[0] < tile_lo + UPH_TILE_MARGIN) || (tg.x_off + tg.nx_hold < tg.nx && q.hi[0] > tile_hi - UPH_TILE_MARGIN)) { rj = UPH_ERR_INVALID; msg = "uph_batch_upload: the path does not lie inside this map tile (route it to the tile's owner)"; }
         }
         c->rejected[b] = rj;
         pp[b] = rj ? &placeholder : &q;
@@ -1219,15 +1361,11 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     if (std::max(std::max(std::fabs(tg.minb[0]), std::fabs(tg.maxb[0])), std::max(std::fabs(tg.minb[1]), std::fabs(tg.maxb[1]))) > FRAME_EXTENT) {
         c->frames.resize(B);
         for (int b = 0; b < B; b++) {
-            const uph_problem& q = *pp[b];
-            double lo[2] = {std::min(q.init_xy[0], q.end_xy[0]), std::min(q.init_xy[1], q.end_xy[1])};
-            double hi[2] = {std::max(q.init_xy[0], q.end_xy[0]), std::max(q.init_xy[1], q.end_xy[1])};
-            for (int i = 0; i < q.n_inner_xy; i++)
-                for (int d = 0; d < 2; d++) { lo[d] = std::min(lo[d], q.inner_xy[2 * i + d]); hi[d] = std::max(hi[d], q.inner_xy[2 * i + d]); }
+            const ProblemHead& q = *pp[b];
             TrajFrame& f = c->frames[b];
             const int nn[2] = {tg.nx, tg.ny};
             for (int d = 0; d < 2; d++) {
-                long long ci = std::llround((0.5 * (lo[d] + hi[d]) - tg.origin[d]) * tg.xy_inv);
+                long long ci = std::llround((0.5 * (q.lo[d] + q.hi[d]) - tg.origin[d]) * tg.xy_inv);
                 ci = ci < 0 ? 0 : (ci > nn[d] ? nn[d] : ci);                     // (a path outside the map: the frame stays at the map's edge)
                 f.ioff[d] = (int)ci;
                 f.shift[d] = tg.origin[d] + (double)ci * tg.xy_res;
@@ -1238,7 +1376,7 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
         }
     }
     for (int b = 0; b < B; b++) {
-        const uph_problem& pr = *pp[b];
+        const ProblemHead& pr = *pp[b];
         const int Nxy = pr.n_inner_xy + 1, Nyaw = pr.n_inner_yaw + 1;
         TrajDesc& t = c->desc[b];
         std::memset(&t, 0, sizeof(t));
@@ -1267,15 +1405,6 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
         c->d_hist.ensure(8 * oh) || c->d_report.ensure(8 * 7 * B) || c->d_order.ensure(4 * B) ||
         c->d_trace.ensure(8 * (size_t)std::max(1, c->trace_cap) * B))
         return UPH_ERR_HIP;
-    // x0 = [tau | Pxy | Pyaw]  (alm_traj_opt.cpp:206-216)
-    std::vector<double> x0(on);
-    for (int b = 0; b < B; b++) {
-        const uph_problem& pr = *pp[b];
-        double* x = x0.data() + c->desc[b].off_x;
-        x[0] = logC2(pr.total_time);
-        for (int i = 0; i < 2 * pr.n_inner_xy; i++) x[1 + i] = pr.inner_xy[i] - (c->frames.empty() ? 0.0 : c->frames[b].shift[i & 1]);
-        for (int i = 0; i < pr.n_inner_yaw; i++) x[1 + 2 * pr.n_inner_xy + i] = pr.inner_yaw[i];
-    }
     // Launch order: most expensive solves first (longest-processing-time list scheduling), so that the tail of a launch -- workgroups
     // finishing below full residency -- is made of short solves.  Predicted cost = n^0.83 exp(0.13 turn) (1 + kink)^0.41 with n = number of
     // variables, turn = total heading change of the initial path and kink = its largest heading change between two consecutive yaw
@@ -1286,7 +1415,7 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     // affects results.  (Tried and dropped: cutting the sorted list into per-XCD chunks for L2 locality -- 8 % slower.)
     {
         std::vector<double> cost(B);
-        for (int b = 0; b < B; b++) cost[b] = predictedCost(*pp[b]);
+        for (int b = 0; b < B; b++) cost[b] = predictedCostOf(pp[b]->n_inner_xy, pp[b]->n_inner_yaw, pp[b]->turn, pp[b]->kink);
         c->order.resize(B);
         std::iota(c->order.begin(), c->order.end(), 0);
         std::stable_sort(c->order.begin(), c->order.end(), [&](int a, int b2) { return cost[a] > cost[b2]; });
@@ -1296,7 +1425,7 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
         if (c->xcd_group >= 16) {
             const GridDev gg = uphMapGrid(c->map);
             auto octant = [&](int b) {
-                const uph_problem& q = *pp[b];
+                const ProblemHead& q = *pp[b];
                 const double mx = 0.5 * (q.init_xy[0] + q.end_xy[0]), my = 0.5 * (q.init_xy[1] + q.end_xy[1]);
                 const int ix = mx < 0.5 * (gg.minb[0] + gg.maxb[0]) ? 0 : 1;
                 int iy = (int)((my - gg.minb[1]) / (gg.maxb[1] - gg.minb[1]) * 4.0);
@@ -1331,24 +1460,189 @@ int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     }
     c->state_host.assign(B, TrajState());
     for (int b = 0; b < B; b++) { std::memset(&c->state_host[b], 0, sizeof(TrajState)); c->state_host[b].rho = c->rho; c->state_host[b].scale_fx = 1.0; }
-    HIPCHK(hipMemcpy(c->d_desc.p, c->desc.data(), sizeof(TrajDesc) * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_x.p, x0.data(), 8 * on, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_x0.p, x0.data(), 8 * on, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_order.p, c->order.data(), 4 * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_state.p, c->state_host.data(), sizeof(TrajState) * B, hipMemcpyHostToDevice));
+    return UPH_OK;
+}
+
+// Second half of an upload, after x / x0 are in place: descriptors, launch order and states up, duals / residuals / history zeroed, scales 1.
+static int commitBatch(uph_ctx* c, int32_t B) {
+    HIPCHK(hipMemcpyAsync(c->d_desc.p, c->desc.data(), sizeof(TrajDesc) * B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_order.p, c->order.data(), 4 * B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_state.p, c->state_host.data(), sizeof(TrajState) * B, hipMemcpyHostToDevice, c->stream));
     // duals = 0, residuals = 0, scales = 1 (alm_traj_opt.cpp:193-203) so that the test hooks see a defined state
     // (all on the context's own stream, waited for with a STREAM synchronise: a device-wide one would block this host thread on every other
     // context's solve in flight on the device -- and uploading batch k+1 while batch k solves is what uph_batch_solve_async is for)
-    HIPCHK(hipMemsetAsync(c->d_hist.p, 0, 8 * oh, c->stream));          // the pads of the history rows must be (and stay) zero
-    HIPCHK(hipMemsetAsync(c->d_dual.p, 0, 8 * 7 * os, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_res.p, 0, 8 * 7 * os, c->stream));
-    hipLaunchKernelGGL(uph_fill_kernel, dim3(1024), dim3(256), 0, c->stream, c->d_scl.as<double>(), (size_t)7 * os, 1.0);
+    HIPCHK(hipMemsetAsync(c->d_hist.p, 0, 8 * c->sum_hist, c->stream));          // the pads of the history rows must be (and stay) zero
+    HIPCHK(hipMemsetAsync(c->d_dual.p, 0, 8 * 7 * c->sum_S, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_res.p, 0, 8 * 7 * c->sum_S, c->stream));
+    hipLaunchKernelGGL(uph_fill_kernel, dim3(1024), dim3(256), 0, c->stream, c->d_scl.as<double>(), (size_t)7 * c->sum_S, 1.0);
     HIPCHK(hipGetLastError());
     if (c->trace_cap > 0) HIPCHK(hipMemsetAsync(c->d_trace.p, 0, 8 * (size_t)c->trace_cap * B, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->trace_cap_up = c->trace_cap;
     c->B = B;
     return UPH_OK;
+}
+
+int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
+    if (!c || B <= 0 || !probs) { setError("uph_batch_upload: bad arguments"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_batch_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    std::vector<ProblemHead> heads(B);
+    for (int b = 0; b < B; b++) heads[b] = headOf(probs[b]);
+    std::vector<const ProblemHead*> pp;
+    const int r = admitBatch(c, B, heads.data(), pp);
+    if (r != UPH_OK) return r;
+    // x0 = [tau | Pxy | Pyaw]  (alm_traj_opt.cpp:206-216)
+    static const uph_problem placeholder = placeholderProblem();
+    std::vector<double> x0(c->sum_n);
+    for (int b = 0; b < B; b++) {
+        const uph_problem& pr = c->rejected[b] ? placeholder : probs[b];
+        double* x = x0.data() + c->desc[b].off_x;
+        x[0] = logC2(pr.total_time);
+        for (int i = 0; i < 2 * pr.n_inner_xy; i++) x[1 + i] = pr.inner_xy[i] - (c->frames.empty() ? 0.0 : c->frames[b].shift[i & 1]);
+        for (int i = 0; i < pr.n_inner_yaw; i++) x[1 + 2 * pr.n_inner_xy + i] = pr.inner_yaw[i];
+    }
+    HIPCHK(hipMemcpy(c->d_x.p, x0.data(), 8 * c->sum_n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_x0.p, x0.data(), 8 * c->sum_n, hipMemcpyHostToDevice));
+    return commitBatch(c, B);
+}
+
+static bool managerParamsOk(const uph_manager_params* mp) {
+    return mp->test_mode ? mp->test_max_vel > 0.0 : (mp->piece_len > 0.0 && mp->yaw_piece_times > 0.0 && mp->mean_vel > 0.0);
+}
+
+// goals in, resident batch out: search (uphKinoSearch) -> clipped paths searched again with room for all their poses -> PlanManager's stage on the
+// device (uph_plan_resample_kernel) -> headers down (the paths never cross PCIe) -> admission on the host (admitBatch, as uph_batch_upload) -> x0
+// scattered from the staging (uph_plan_scatter_kernel) -> commitBatch.  The resident batch = the goals whose search succeeded, in goal order.
+int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
+                    int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
+    if (!k || !c || !mp || B <= 0 || !starts || !goals || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
+        setError("uph_plan_upload: bad arguments"); return UPH_ERR_INVALID;
+    }
+    if (uphKinoMap(k) != c->map) { setError("uph_plan_upload: the search context and the optimiser context are bound to different maps"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_plan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    c->B = 0;                       // the context holds no batch until this call has succeeded as a whole
+    c->traj_resident = false; c->planned = false; c->origin.clear(); c->plan_probs.clear();
+    const int cap = path_cap > 0 ? path_cap : UPH_PLAN_PATH_CAP;
+    UphKinoOut io;
+    int r = uphKinoSearch(k, B, starts, goals, cap, 0, 0, io);
+    if (r != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    std::vector<int> st((size_t)B), np((size_t)B);
+    HIPCHK(hipMemcpy(st.data(), io.status, 4 * (size_t)B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(np.data(), io.n_path, 4 * (size_t)B, hipMemcpyDeviceToHost));
+    if (c->d_plan_head.ensure(sizeof(PlanHead) * (size_t)B) || c->d_plan_xy.ensure(sizeof(double) * 2 * PLAN_SX * (size_t)B) ||
+        c->d_plan_yaw.ensure(sizeof(double) * PLAN_SY * (size_t)B))
+        return UPH_ERR_HIP;
+    const uph_manager_params mpv = *mp;
+    hipLaunchKernelGGL(uph_plan_resample_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, mpv, io.paths, cap, io.n_path, io.status, (int)B, (const int*)nullptr,
+                       c->d_plan_xy.as<double>(), c->d_plan_yaw.as<double>(), c->d_plan_head.as<PlanHead>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the next search reuses the buffers the kernel read)
+    // a front_end_path longer than the cap was clipped by the search: searched again with room for all its poses (the reference returns the whole path)
+    std::vector<int> longer;
+    int need = 0;
+    for (int b = 0; b < B; b++) if (st[b] == UPH_KINO_OK && np[b] > cap) { longer.push_back(b); need = std::max(need, np[b]); }
+    if (!longer.empty()) {
+        const int L = (int)longer.size();
+        std::vector<double> s2((size_t)3 * L), g2((size_t)3 * L);
+        for (int j = 0; j < L; j++) for (int q = 0; q < 3; q++) { s2[(size_t)3 * j + q] = starts[(size_t)3 * longer[j] + q]; g2[(size_t)3 * j + q] = goals[(size_t)3 * longer[j] + q]; }
+        UphKinoOut io2;
+        r = uphKinoSearch(k, L, s2.data(), g2.data(), need, 0, 0, io2);
+        if (r != UPH_OK) return r;
+        HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+        std::vector<int> st2((size_t)L), np2((size_t)L);
+        HIPCHK(hipMemcpy(st2.data(), io2.status, 4 * (size_t)L, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(np2.data(), io2.n_path, 4 * (size_t)L, hipMemcpyDeviceToHost));
+        for (int j = 0; j < L; j++) if (st2[j] != UPH_KINO_OK || np2[j] > need) st[longer[j]] = UPH_KINO_INTERNAL;      // (the search is deterministic: not expected)
+        if (c->d_plan_goal.ensure(4 * (size_t)L)) return UPH_ERR_HIP;
+        HIPCHK(hipMemcpy(c->d_plan_goal.p, longer.data(), 4 * (size_t)L, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(uph_plan_resample_kernel, dim3((L + 63) / 64), dim3(64), 0, c->stream, mpv, io2.paths, need, io2.n_path, io2.status, L,
+                           (const int*)c->d_plan_goal.p, c->d_plan_xy.as<double>(), c->d_plan_yaw.as<double>(), c->d_plan_head.as<PlanHead>());
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<PlanHead> ph((size_t)B);
+    HIPCHK(hipMemcpyAsync(ph.data(), c->d_plan_head.p, sizeof(PlanHead) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<int> found;
+    // every search and the resampling have run: the outputs are written now, all together (a failure before this point leaves them untouched, so a
+    // caller can tell "no goal produced a path" -- the one UPH_ERR_INVALID returned with them written -- from every other failure)
+    for (int b = 0; b < B; b++) {
+        status[b] = st[b]; traj_of[b] = -1;
+        n_inner_xy[b] = st[b] == UPH_KINO_OK ? ph[(size_t)b].n_inner_xy : 0; n_inner_yaw[b] = st[b] == UPH_KINO_OK ? ph[(size_t)b].n_inner_yaw : 0;
+        if (st[b] == UPH_KINO_OK) found.push_back(b);
+    }
+    const int F = (int)found.size();
+    if (F == 0) { setError("uph_plan_upload: no goal produced a path"); return UPH_ERR_INVALID; }
+    // the problems as uph_resample_batch forms them; the boundary velocities sig_vel * (cos, sin) of the end headings (:94-95) on the host
+    const WalkSetup ws = walkSetup(*mp);
+    std::vector<ProblemHead> heads((size_t)F);
+    for (int j = 0; j < F; j++) {
+        const PlanHead& g = ph[(size_t)found[j]];
+        ProblemHead& h = heads[(size_t)j];
+        h.n_inner_xy = g.n_inner_xy; h.n_inner_yaw = g.n_inner_yaw;
+        if (g.short_path) { h.refused = UPH_ERR_INVALID; h.why = "uph_plan_upload: a path needs at least two poses"; }
+        h.init_xy[0] = g.p_init[0]; h.init_xy[1] = g.p_init[1]; h.end_xy[0] = g.p_end[0]; h.end_xy[1] = g.p_end[1];
+        h.init_xy[2] = ws.sig_vel * std::cos(g.yaw_init); h.init_xy[3] = ws.sig_vel * std::sin(g.yaw_init);
+        h.end_xy[2] = ws.sig_vel * std::cos(g.yaw_end); h.end_xy[3] = ws.sig_vel * std::sin(g.yaw_end);
+        h.init_xy[4] = h.init_xy[5] = h.end_xy[4] = h.end_xy[5] = 0.0;
+        h.init_yaw[0] = g.yaw_init; h.init_yaw[1] = h.init_yaw[2] = 0.0;
+        h.end_yaw[0] = g.yaw_end; h.end_yaw[1] = h.end_yaw[2] = 0.0;
+        h.total_time = g.total_time;
+        for (int d = 0; d < 2; d++) { h.lo[d] = g.lo[d]; h.hi[d] = g.hi[d]; }
+        h.turn = g.turn; h.kink = g.kink;
+    }
+    std::vector<const ProblemHead*> pp;
+    r = admitBatch(c, F, heads.data(), pp);
+    if (r != UPH_OK) return r;
+    // x0 from the staging: a refused problem's slot runs uph_batch_upload's placeholder; every other one has all its way-points staged (<= UPH_MAX_PIECE_* - 1)
+    std::vector<PlanScatter> rec((size_t)F);
+    for (int j = 0; j < F; j++) {
+        PlanScatter& q = rec[(size_t)j];
+        const TrajDesc& t = c->desc[(size_t)j];
+        q.off_x = t.off_x; q.src = c->rejected[(size_t)j] ? -1 : found[j]; q.nxy = t.Nxy - 1; q.nyw = t.Nyaw - 1; q.pad = 0;
+        for (int d = 0; d < 2; d++) q.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)j].shift[d];
+        q.tau = logC2(pp[(size_t)j]->total_time);
+    }
+    if (c->d_plan_rec.ensure(sizeof(PlanScatter) * (size_t)F)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_plan_rec.p, rec.data(), sizeof(PlanScatter) * (size_t)F, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(uph_plan_scatter_kernel, dim3(F), dim3(64), 0, c->stream, c->d_plan_rec.as<PlanScatter>(), c->d_plan_xy.as<double>(), c->d_plan_yaw.as<double>(),
+                       c->d_x.as<double>(), c->d_x0.as<double>());
+    HIPCHK(hipGetLastError());
+    r = commitBatch(c, F);          // (synchronises the stream: the records above are consumed before `rec` goes)
+    if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
+    c->origin = found;
+    c->planned = true;
+    c->plan_probs = heads;
+    for (int j = 0; j < F; j++) traj_of[found[j]] = j;
+    return UPH_OK;
+}
+
+// test hook: the resident problems of a planned batch as the device staged them, in uph_resample_batch's output layout and resident order
+int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy, double* end_xy, double* init_yaw, double* end_yaw, double* inner_xy, double* inner_yaw,
+                    int32_t* n_inner_xy, int32_t* n_inner_yaw, double* total_time) {
+    if (!c || cap_xy < 0 || cap_yaw < 0 || !init_xy || !end_xy || !init_yaw || !end_yaw || !inner_xy || !inner_yaw || !n_inner_xy || !n_inner_yaw || !total_time) {
+        setError("uph_plan_staged: bad arguments"); return UPH_ERR_INVALID;
+    }
+    if (c->B <= 0 || !c->planned) { setError("uph_plan_staged: the resident batch did not come from uph_plan_upload"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_plan_staged: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    int status = UPH_OK;
+    for (int j = 0; j < c->B; j++) {
+        const ProblemHead& h = c->plan_probs[(size_t)j];
+        const int g = c->origin[(size_t)j];
+        for (int q = 0; q < 6; q++) { init_xy[(size_t)6 * j + q] = h.init_xy[q]; end_xy[(size_t)6 * j + q] = h.end_xy[q]; }
+        for (int q = 0; q < 3; q++) { init_yaw[(size_t)3 * j + q] = h.init_yaw[q]; end_yaw[(size_t)3 * j + q] = h.end_yaw[q]; }
+        total_time[j] = h.total_time;
+        n_inner_xy[j] = h.n_inner_xy; n_inner_yaw[j] = h.n_inner_yaw;
+        // way-points beyond the staging capacity were counted, not written
+        const int nx = std::min(std::min(h.n_inner_xy, PLAN_SX), cap_xy), ny = std::min(std::min(h.n_inner_yaw, PLAN_SY), cap_yaw);
+        if (h.n_inner_xy > cap_xy || h.n_inner_yaw > cap_yaw || h.n_inner_xy > PLAN_SX || h.n_inner_yaw > PLAN_SY) status = UPH_ERR_LIMIT;
+        if (nx > 0) HIPCHK(hipMemcpy(inner_xy + (size_t)2 * cap_xy * j, c->d_plan_xy.as<double>() + (size_t)2 * PLAN_SX * g, sizeof(double) * 2 * nx, hipMemcpyDeviceToHost));
+        if (ny > 0) HIPCHK(hipMemcpy(inner_yaw + (size_t)cap_yaw * j, c->d_plan_yaw.as<double>() + (size_t)PLAN_SY * g, sizeof(double) * ny, hipMemcpyDeviceToHost));
+    }
+    if (status == UPH_ERR_LIMIT) setError("uph_plan_staged: a problem has more way-points than the caller's capacity or the staging's");
+    return status;
 }
 
 static int refreshStates(uph_ctx* c) {

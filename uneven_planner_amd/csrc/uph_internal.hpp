@@ -31,3 +31,14 @@ struct UphEventTmp {
     void* e = nullptr;          // hipEvent_t
     ~UphEventTmp();
 };
+
+// the front-end search (kino_search.hip) into its own device buffers, without the downloads of uph_kino_plan_batch: uph_plan_upload resamples the
+// paths where the search left them.  out: device pointers into the context's buffers, valid until its next search -- paths [B][path_cap][3] (path_cap as passed),
+// n_path [B] (may exceed path_cap: clipped), status [B] (UPH_KINO_*).  Blocking (the device is synchronised).
+struct UphKinoOut {
+    const double* paths = nullptr;
+    const int* n_path = nullptr;
+    const int* status = nullptr;
+};
+int uphKinoSearch(uph_kino* k, int32_t B, const double* starts, const double* goals, int32_t path_cap, int32_t max_expand, int32_t exp_cap, UphKinoOut& out);
+const uph_map* uphKinoMap(const uph_kino* k);
