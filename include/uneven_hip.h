@@ -40,6 +40,8 @@
  *                              the map's query interface and the producer of the front-end path PlanManager resamples (plan_manager.cpp:59-60)
  *   uph_plan_upload         <- PlanManager::rcvWpsCallBack's chain up to the optimiser (plan_manager.cpp:43-134): kino_astar->plan (:59-60), the
  *                              initial-guess stage (:62-132) and the arguments of optimizeSE2Traj, for a batch of goals with the paths kept on the device
+ *   uph_replan_upload       <- the same chain for a vehicle in motion: the start of each plan is a resident trajectory's state at a switch time
+ *                              (getPos / getVel / getAcc of SE2Trajectory, se2traj.hpp:343-361, 106-140) instead of plan_manager.cpp:86-94's start
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -361,9 +363,23 @@ int uph_kino_stats(uph_kino* k, double* kernel_ms);
 #define UPH_PLAN_PATH_CAP 1024
 int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
                     int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw);
+/* ---- re-plan from states on resident trajectories: uph_plan_upload for a vehicle that follows trajectory src_traj[q] of src's resident batch and
+ * switches to a new plan at t_switch[q] (seconds from that trajectory's start, the clock of uph_rollout_batch; t <= 0 is the start, t >= its duration
+ * the end, the duration as the rollout forms it).  The switch state (x, y in map coordinates, dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw) is
+ * evaluated on the device from src's coefficients, as the rollout evaluates its rows; the search runs from (x, y, yaw) to goals[q] (NULL: the
+ * source problem's end pose -- end position, normSO2 of its end yaw: "the map changed, same goal"); the resampling is uph_plan_upload's; the problem's
+ * start boundary is init_xy = {x, y, dx, dy, ddx, ddy} and init_yaw = {yaw of the path's first pose, dyaw, ddyaw} (the yaw way-points unwrap from
+ * that pose as in PlanManager), its end boundary, way-points and total_time uph_plan_upload's.  Upload, admission, uph_batch_origin (= the query
+ * index), uph_plan_staged and the four outputs [B] follow uph_plan_upload, into dst; switch_states [B][9] (or NULL) is written together with them.
+ * dst == src is allowed (every state is taken before dst is reset).  Refused with UPH_ERR_INVALID, outputs untouched and dst's batch as it was:
+ * bad arguments, src holding no resident trajectory (uph_rollout_batch's rule), an src_traj[q] out of range or naming an UPH_RET_UNSUPPORTED slot,
+ * a non-finite t_switch[q], k / src / dst bound to different maps, an asynchronous solve pending on src or dst.  Blocking. */
+int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager_params* mp, int32_t B, const int32_t* src_traj, const double* t_switch,
+                      const double* goals, int32_t path_cap, double* switch_states, int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw);
 /* test hook: the resident problems of a batch uploaded by uph_plan_upload exactly as the device staged them, in uph_resample_batch's output layout
  * and the resident order (boundary velocities included).  UPH_ERR_LIMIT when a problem has more way-points than cap_xy / cap_yaw or than the staging
- * holds (UPH_MAX_PIECE_* - 1; the counts are still written); UPH_ERR_INVALID when the resident batch did not come from uph_plan_upload. */
+ * holds (UPH_MAX_PIECE_* - 1; the counts are still written); UPH_ERR_INVALID when the resident batch did not come from uph_plan_upload or
+ * uph_replan_upload. */
 int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy, double* end_xy, double* init_yaw, double* end_yaw, double* inner_xy,
                     double* inner_yaw, int32_t* n_inner_xy, int32_t* n_inner_yaw, double* total_time);
 

@@ -15,6 +15,7 @@
 //   KinoAstar::plan / setEnvironment / init   front_end/include/front_end/kino_astar.h:147-154, front_end/src/kino_astar.cpp:5-43, 67-236
 //                                  (the batched device search, uph_kino_plan_batch; planBatch = many goals in one call)
 //   planSE2TrajBatch               PlanManager::rcvWpsCallBack plan_manager.cpp:43-134 for many goals in one call, every stage on the device (uph_plan_upload)
+//   replanSE2TrajBatch             the same from states on the last batch's trajectories: re-planning a vehicle in motion (uph_replan_upload)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -477,6 +478,17 @@ public:
     };
     template <class V3>
     GoalPlan planSE2TrajBatch(KinoAstar& kino, const std::vector<V3>& starts, const std::vector<V3>& goals, const uph_manager_params& mgr, int32_t path_cap = 0);
+    // the same for a vehicle in motion (PlanManager's goal callback while a trajectory is being followed; uph_replan_upload): query q starts where
+    // trajectory traj[q] of this object's last batch (index in it, as traj_of / getSE3PathBatch rows) is at t_switch[q] seconds from its start, with
+    // its velocity, acceleration, yaw rate and yaw acceleration; goals (one per query) or nullptr: each source trajectory's own end pose (the map
+    // changed, same goal).  The new batch replaces the last one on this object.  Same GoalPlan as planSE2TrajBatch.  Defined after KinoAstar.
+    template <class V3 = VecN<3>>
+    GoalPlan replanSE2TrajBatch(KinoAstar& kino, const std::vector<int>& traj, const std::vector<double>& t_switch, const std::vector<V3>* goals,
+                                const uph_manager_params& mgr, int32_t path_cap = 0);
+    GoalPlan replanSE2TrajBatch(KinoAstar& kino, const std::vector<int>& traj, const std::vector<double>& t_switch, std::nullptr_t, const uph_manager_params& mgr,
+                                int32_t path_cap = 0) {
+        return replanSE2TrajBatch<VecN<3>>(kino, traj, t_switch, static_cast<const std::vector<VecN<3>>*>(nullptr), mgr, path_cap);
+    }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)
 
     // getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229): max vx, ax, ay, curvature, attitude (-cos xi), sigma sampled every 0.01 s -- evaluated
@@ -531,6 +543,7 @@ public:
     }
 
 private:
+    GoalPlan finishGoalPlan(int rc, int32_t B, GoalPlan& out, const std::vector<int32_t>& nxy, const std::vector<int32_t>& nyw, const char* who, const char* caller);
     // coefficient blocks of the C-ABI (lowest order first, xy interleaved per row) -> pieces with the highest order first (se2traj.hpp:682-695)
     static SE2Trajectory makeTraj(const double* cxy, int Nxy, double Txy, const double* cyaw, int Nyaw, double Tyaw) {
         SE2Trajectory t;
@@ -695,6 +708,39 @@ ALMTrajOpt::GoalPlan ALMTrajOpt::planSE2TrajBatch(KinoAstar& kino, const std::ve
     in_opt = true;
     last_report_.clear(); last_multi_ = false; last_ctxs_.assign(1, ctx_); last_B_ = 0;
     const int rc = uph_plan_upload(kino.handle(), ctx_, &mgr, B, s.data(), g.data(), path_cap, out.status.data(), out.traj_of.data(), nxy.data(), nyw.data());
+    return finishGoalPlan(rc, B, out, nxy, nyw, "uph_plan_upload", "planSE2TrajBatch");
+}
+
+template <class V3>
+ALMTrajOpt::GoalPlan ALMTrajOpt::replanSE2TrajBatch(KinoAstar& kino, const std::vector<int>& traj, const std::vector<double>& t_switch, const std::vector<V3>* goals,
+                                                    const uph_manager_params& mgr, int32_t path_cap) {
+    if (!kino.handle()) throw std::runtime_error("replanSE2TrajBatch: KinoAstar::setEnvironment has not been called");
+    if (t_switch.size() != traj.size() || (goals && goals->size() != traj.size())) throw std::runtime_error("replanSE2TrajBatch: traj, t_switch and goals differ in number");
+    if (last_multi_) throw std::runtime_error("replanSE2TrajBatch: the last batch was split over several devices");
+    const int32_t B = (int32_t)traj.size();
+    GoalPlan out;
+    if (B == 0) return out;
+    std::vector<int32_t> tr(traj.begin(), traj.end()), nxy(B), nyw(B);
+    std::vector<double> g;
+    if (goals) {
+        g.resize((size_t)3 * B);
+        for (int32_t b = 0; b < B; b++) for (int k = 0; k < 3; k++) g[(size_t)3 * b + k] = (*goals)[b][k];
+    }
+    out.status.assign((size_t)B, -1); out.traj_of.assign((size_t)B, -1);
+    in_opt = true;
+    const int rc = uph_replan_upload(kino.handle(), ctx_, ctx_, &mgr, B, tr.data(), t_switch.data(), goals ? g.data() : nullptr, path_cap, nullptr, out.status.data(),
+                                     out.traj_of.data(), nxy.data(), nyw.data());
+    if (rc == UPH_ERR_INVALID && out.status[0] < 0) {            // refused: the last batch is still resident, nothing of it changes
+        in_opt = false;
+        throw std::runtime_error(std::string("uph_replan_upload: ") + uph_last_error());
+    }
+    last_report_.clear(); last_multi_ = false; last_ctxs_.assign(1, ctx_); last_B_ = 0;
+    return finishGoalPlan(rc, B, out, nxy, nyw, "uph_replan_upload", "replanSE2TrajBatch");
+}
+
+// after uph_plan_upload / uph_replan_upload into ctx_: solve and download the found goals, one GoalPlan entry per goal
+inline ALMTrajOpt::GoalPlan ALMTrajOpt::finishGoalPlan(int rc, int32_t B, GoalPlan& out, const std::vector<int32_t>& nxy, const std::vector<int32_t>& nyw, const char* who,
+                                                     const char* caller) {
     const int F = uph_batch_count(ctx_);
     // "no goal produced a path" is the one UPH_ERR_INVALID returned with the outputs written and no UPH_KINO_OK among them: every entry empty, no
     // throw.  Every other failure (a HIP error in the search included) leaves the outputs untouched and throws.
@@ -702,7 +748,7 @@ ALMTrajOpt::GoalPlan ALMTrajOpt::planSE2TrajBatch(KinoAstar& kino, const std::ve
     for (int32_t b = 0; b < B; b++) { written = written && out.status[b] >= 0; any_ok = any_ok || out.status[b] == UPH_KINO_OK; }
     if (rc != UPH_OK && !(rc == UPH_ERR_INVALID && written && !any_ok)) {
         in_opt = false;
-        throw std::runtime_error(std::string("uph_plan_upload: ") + uph_last_error());
+        throw std::runtime_error(std::string(who) + ": " + uph_last_error());
     }
     std::vector<size_t> ox(B, 0), oc(B, 0), oy(B, 0);
     size_t sx = 0, sc = 0, sy = 0;
@@ -722,7 +768,7 @@ ALMTrajOpt::GoalPlan ALMTrajOpt::planSE2TrajBatch(KinoAstar& kino, const std::ve
     if (F > 0) {
         if (uph_batch_solve(ctx_) != UPH_OK || uph_batch_download(ctx_, rs.data()) != UPH_OK) {
             in_opt = false;
-            throw std::runtime_error(std::string("planSE2TrajBatch: ") + uph_last_error());
+            throw std::runtime_error(std::string(caller) + ": " + uph_last_error());
         }
         last_B_ = F;
     }
@@ -739,7 +785,7 @@ ALMTrajOpt::GoalPlan ALMTrajOpt::planSE2TrajBatch(KinoAstar& kino, const std::ve
         out.traj.push_back(rs[j].ret_code == UPH_RET_UNSUPPORTED ? SE2Trajectory()
                                : makeTraj(cx.data() + oc[b], nxy[b] + 1, rs[j].piece_T_xy, cy.data() + oy[b], nyw[b] + 1, rs[j].piece_T_yaw));
     }
-    return out;
+    return std::move(out);
 }
 
 }  // namespace uneven_hip

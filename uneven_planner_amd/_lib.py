@@ -155,6 +155,8 @@ SYMBOLS = {
     "uph_kino_stats": (C.c_int, [_VP, DP]),
     "uph_plan_upload": (C.c_int, [_VP, _VP, C.POINTER(ManagerParams), _I32, DP, DP, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_plan_staged": (C.c_int, [_VP, _I32, _I32, DP, DP, DP, DP, DP, DP, C.POINTER(_I32), C.POINTER(_I32), DP]),
+    "uph_replan_upload": (C.c_int, [_VP, _VP, _VP, C.POINTER(ManagerParams), _I32, C.POINTER(_I32), DP, DP, _I32, DP, C.POINTER(_I32), C.POINTER(_I32),
+                                    C.POINTER(_I32), C.POINTER(_I32)]),
 }
 
 _LIB = None

@@ -42,6 +42,20 @@ def _dp(a):
     return a.ctypes.data_as(_lib.DP)
 
 
+def norm_so2(yaw):
+    """UnevenMap::normSO2 (uneven_map.cpp:63-70) as the device forms it (csrc/uph_common.hpp): whole turns added / removed one at a time"""
+    y = float(yaw)
+    for _ in range(4096):
+        if not y < -np.pi:
+            break
+        y += 2 * np.pi
+    for _ in range(4096):
+        if not y > np.pi:
+            break
+        y -= 2 * np.pi
+    return y
+
+
 class SE2Traj:
     """What MINCO_SE2::getTraj() yields (se2traj.hpp:682-695, 844-850): per piece a duration and a D x 6 coefficient
     matrix, highest order first."""
@@ -86,6 +100,43 @@ class SE2Traj:
             total += d_
         idx, tl = self._locate(list(durs), total if t is None else t)
         return np.array([self._value(co[idx, d], tl) for d in range(co.shape[1])])
+
+    @staticmethod
+    def _derivs(c_desc, t):
+        """value, first and second derivative of one piece polynomial at t, in the device's order (trajectory_dev.hpp): ascending powers, tn *= t"""
+        v = dv = dd = 0.0
+        tn = 1.0
+        for k in range(6):
+            v += tn * c_desc[5 - k]
+            tn *= t
+        tn = 1.0
+        for k in range(1, 6):
+            dv += k * tn * c_desc[5 - k]
+            tn *= t
+        tn = 1.0
+        for k in range(2, 6):
+            dd += (k - 1) * k * tn * c_desc[5 - k]
+            tn *= t
+        return v, dv, dd
+
+    def getState(self, t):
+        """host mirror of the switch state uph_replan_upload evaluates on the device: at t clamped to [0, getTotalDuration()] (the running sums of
+        the piece durations, the smaller one, as the rollout forms the duration), x, y, dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw -- the pieces
+        located by locatePieceIdx (se2traj.hpp:343-361).  Coordinates of the coefficients' frame (a batch solved in local frames: add the shift)."""
+        tx = ty = 0.0
+        for d_ in self.pos_durations:
+            tx += d_
+        for d_ in self.yaw_durations:
+            ty += d_
+        total = tx if tx < ty else ty
+        t = float(t)
+        t = 0.0 if t <= 0.0 else (total if t >= total else t)
+        ix, tl = self._locate(list(self.pos_durations), t)
+        iw, tw = self._locate(list(self.yaw_durations), t)
+        px, vx, ax = self._derivs(self.pos_coeffs[ix, 0], tl)
+        py, vy, ay = self._derivs(self.pos_coeffs[ix, 1], tl)
+        w, dw, ddw = self._derivs(self.yaw_coeffs[iw, 0], tw)
+        return np.array([px, py, vx, vy, ax, ay, norm_so2(w), dw, ddw])
 
     def to_msg(self):
         """the mpc_controller/SE2Traj message PlanManager publishes (mpc_controller/msg/SE2Traj.msg:1-9, filled as at
@@ -329,13 +380,7 @@ class ALMTrajOpt:
         solve() / solve_async() + wait() and download() work as after upload().  Returns dict of [B] arrays: status (UPH_KINO_*), traj_of (index in
         the resident batch, -1 without a path), n_inner_xy, n_inner_yaw.  A batch in which no goal has a path leaves the context empty (no raise);
         every failure of the call raises."""
-        from .resample import MANAGER_PARAMS
-        unknown = set(manager_params) - set(MANAGER_PARAMS)
-        if unknown:
-            raise TypeError("plan_goals: unknown manager parameter(s) %s" % sorted(unknown))
-        mk = dict(MANAGER_PARAMS)
-        mk.update(manager_params)
-        mp = _lib.ManagerParams(**{k: (int(bool(v)) if k == "test_mode" else float(v)) for k, v in mk.items()})
+        mp = self._manager_params("plan_goals", manager_params)
         s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
         g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
         if s.shape != g.shape or s.shape[0] == 0:
@@ -346,13 +391,27 @@ class ALMTrajOpt:
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         self._B, self._sizes, self._last = 0, [], []
         rc = self.L.uph_plan_upload(kino.h, self.h, C.byref(mp), B, _dp(s), _dp(g), int(path_cap), ip(st), ip(to), ip(nx), ip(ny))
-        plan = dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny)
+        return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny), "uph_plan_upload")
+
+    @staticmethod
+    def _manager_params(who, manager_params):
+        from .resample import MANAGER_PARAMS
+        unknown = set(manager_params) - set(MANAGER_PARAMS)
+        if unknown:
+            raise TypeError("%s: unknown manager parameter(s) %s" % (who, sorted(unknown)))
+        mk = dict(MANAGER_PARAMS)
+        mk.update(manager_params)
+        return _lib.ManagerParams(**{k: (int(bool(v)) if k == "test_mode" else float(v)) for k, v in mk.items()})
+
+    def _planned(self, rc, plan, who):
+        """the outputs of uph_plan_upload / uph_replan_upload -> the resident batch's sizes, or a raise"""
+        st, to, nx, ny = plan["status"], plan["traj_of"], plan["n_inner_xy"], plan["n_inner_yaw"]
         self.last_plan = plan
         # "no goal produced a path" is the one UPH_ERR_INVALID returned with the outputs written (statuses no longer the -1 they were filled with)
         # and no UPH_KINO_OK among them: an empty batch, not an error.  Every other return code -- a HIP failure in the search included -- raises.
         no_path = rc == _lib.UPH_ERR_INVALID and (st >= 0).all() and not (st == _lib.UPH_KINO_OK).any()
         if rc != 0 and not no_path:
-            _lib.check(rc, "uph_plan_upload")
+            _lib.check(rc, who)
         found = np.nonzero(to >= 0)[0]
         K1 = int(self.int_K) + 1
         self._sizes = [dict(Nxy=int(nx[b]) + 1, Nyaw=int(ny[b]) + 1, n=2 * int(nx[b]) + int(ny[b]) + 1, S=(int(nx[b]) + 1) * K1) for b in found]
@@ -364,7 +423,9 @@ class ALMTrajOpt:
         """goals in, trajectories out (plan_goals_upload + solve + download): one dict per goal with its search `status`; a goal with a path also
         carries `traj_of` and the result dict optimize_batch returns.  The batch stays resident: rollout(), getMaxVxAxAyCurAttSig() and origin()
         (= the goal index of each resident trajectory) work afterwards."""
-        plan = self.plan_goals_upload(kino, starts, goals, path_cap=path_cap, **manager_params)
+        return self._solve_planned(self.plan_goals_upload(kino, starts, goals, path_cap=path_cap, **manager_params), full)
+
+    def _solve_planned(self, plan, full):
         out = [dict(status=int(v)) for v in plan["status"]]
         if self._B == 0:
             return out
@@ -376,6 +437,38 @@ class ALMTrajOpt:
             r.update(status=int(plan["status"][b]), traj_of=j)
             out[b] = r
         return out
+
+    # ---- re-plan from states on resident trajectories (uph_replan_upload) ------------------------------------------
+    def replan_goals_upload(self, kino, src, src_traj, t_switch, goals=None, path_cap=0, **manager_params):
+        """plan_goals_upload for a vehicle in motion: query q starts where trajectory src_traj[q] of `src`'s resident batch (an ALMTrajOpt on the same
+        map, self included) is at t_switch[q] (the rollout's clock, clamped to [0, duration]), with that trajectory's velocity, acceleration, yaw rate and
+        yaw acceleration as the new problem's start boundary; goals (B, 3), or None: each source problem's end pose.  The batch is uploaded to self.
+        Returns plan_goals_upload's dict plus switch_states (B, 9): x, y, dx, dy, ddx, ddy, yaw (normSO2), dyaw, ddyaw."""
+        mp = self._manager_params("replan_goals", manager_params)
+        tr = np.ascontiguousarray(src_traj, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(t_switch, dtype=np.float64).reshape(-1)
+        B = tr.shape[0]
+        if B == 0 or ts.shape[0] != B:
+            raise _lib.UnevenHipError("replan_goals: src_traj and t_switch must be the same non-empty length")
+        g = None
+        if goals is not None:
+            g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+            if g.shape[0] != B:
+                raise _lib.UnevenHipError("replan_goals: goals must be (B, 3)")
+        st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+        nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        sw = np.full((B, 9), np.nan)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.L.uph_replan_upload(kino.h, src.h, self.h, C.byref(mp), B, ip(tr), _dp(ts), None if g is None else _dp(g), int(path_cap), _dp(sw),
+                                      ip(st), ip(to), ip(nx), ip(ny))
+        if rc not in (0, _lib.UPH_ERR_INVALID):        # a failure past the refusals (which leave self's batch as it was): no batch is resident
+            self._B, self._sizes, self._last = 0, [], []
+        return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny, switch_states=sw), "uph_replan_upload")
+
+    def replan_goals(self, kino, src, src_traj, t_switch, goals=None, full=False, path_cap=0, **manager_params):
+        """replan_goals_upload + solve + download, as plan_goals: one dict per query with its search `status` (and `traj_of` + the result dict when
+        it has a path); the new batch stays resident on self.  The switch states are in self.last_plan["switch_states"]."""
+        return self._solve_planned(self.replan_goals_upload(kino, src, src_traj, t_switch, goals=goals, path_cap=path_cap, **manager_params), full)
 
     def _download_block(self, nxy, nyw, full):
         """download() for a whole resident batch into a few contiguous arrays: the uph_result array is a numpy record array whose pointer fields

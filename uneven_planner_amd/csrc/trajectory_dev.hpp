@@ -11,12 +11,14 @@ namespace uph {
 struct TrajSample {
     double p[2], v[2], a[2];    // position (the trajectory's frame), velocity, acceleration
     double yawn, dyaw;          // normSO2(yaw), yaw rate
+    double yaw, ddyaw;          // raw (unwrapped) yaw, yaw acceleration: written only by the YAW2 form (the switch states of uph_replan_upload)
 };
 
 // Trajectory of Nxy uniform pieces of Tx (c_xy: 12 coefficients per piece, power k of dim d at 2 k + d) and Nyaw pieces of Ty (c_yaw: 6 per
 // piece), sampled at t.  TERMS: out[7] = vx, ax, ay, cur, att (-1 / cos xi), sigma, non-holonomic error, the terrain looked up on `fgrid`
-// (the grid descriptor of the trajectory's frame).
-template <bool TERMS>
+// (the grid descriptor of the trajectory's frame).  YAW2: also the raw yaw and the yaw acceleration (a separate instantiation, so that the report and the
+// rollout compile to what they were without it).
+template <bool TERMS, bool YAW2 = false>
 UPH_HD void trajectorySample(const double* cxy, const double* cyaw, int Nxy, int Nyaw, double Tx, double Ty, double t, const GridDev& fgrid, double gravity,
                              TrajSample& s, double out[7]) {
     // locatePieceIdx (se2traj.hpp:343-361) with uniform durations
@@ -46,6 +48,11 @@ UPH_HD void trajectorySample(const double* cxy, const double* cyaw, int Nxy, int
     for (int kk = 1; kk <= 5; kk++) { dyaw += kk * tn * c[kk]; tn *= tw; }
     const double yawn = normSO2(yaw);
     s.yawn = yawn; s.dyaw = dyaw;
+    if (YAW2) {
+        double ddyaw = 0; tn = 1.0;
+        for (int kk = 2; kk <= 5; kk++) { ddyaw += (kk - 1) * kk * tn * c[kk]; tn *= tw; }
+        s.yaw = yaw; s.ddyaw = ddyaw;
+    }
     if (!TERMS) return;
     double cy_, sy_;
     sincosFast(yaw, sy_, cy_);

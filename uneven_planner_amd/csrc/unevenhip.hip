@@ -851,6 +851,37 @@ __global__ __launch_bounds__(64) void uph_plan_scatter_kernel(const PlanScatter*
     }
 }
 
+// ---- switch states (uph_replan_upload): trajectory b of the resident batch at its clamped time, one lane per query.  The sample is the rollout's
+// (trajectorySample, same piece location, same statements), so at a rollout row's t the state equals that row bit for bit; the duration is the
+// rollout's too (running sums of the piece durations, the smaller of the two).  Row q: x, y (map coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw.
+struct SwitchQuery {            // formed on the host
+    int32_t b, framed;          // resident trajectory; framed: the batch solves in local frames (add shift, as the rollout does)
+    double t;                   // switch time (finite)
+    double shift[2];
+};
+constexpr int SWITCH_COLS = 9;
+__global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __restrict__ desc, const TrajState* __restrict__ state, const double* __restrict__ cxy,
+                                                              const double* __restrict__ cyaw, const SwitchQuery* __restrict__ qs, int nq, double* __restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const SwitchQuery sq = qs[q];
+    const TrajDesc& td = desc[sq.b];
+    const double Tx = state[sq.b].T_xy, Ty = state[sq.b].T_yaw;
+    double durx = 0.0, dury = 0.0;
+    for (int i = 0; i < td.Nxy; i++) durx += Tx;
+    for (int i = 0; i < td.Nyaw; i++) dury += Ty;
+    const double total = durx < dury ? durx : dury;
+    const double t = sq.t <= 0.0 ? 0.0 : (sq.t >= total ? total : sq.t);
+    TrajSample s;
+    double unused[7];
+    GridDev none;
+    trajectorySample<false, true>(cxy + td.off_cxy, cyaw + td.off_cyaw, td.Nxy, td.Nyaw, Tx, Ty, t, none, 0.0, s, unused);
+    double* o = out + (size_t)q * SWITCH_COLS;
+    o[0] = sq.framed ? s.p[0] + sq.shift[0] : s.p[0]; o[1] = sq.framed ? s.p[1] + sq.shift[1] : s.p[1];
+    o[2] = s.v[0]; o[3] = s.v[1]; o[4] = s.a[0]; o[5] = s.a[1];
+    o[6] = s.yawn; o[7] = s.dyaw; o[8] = s.ddyaw;
+}
+
 #ifdef UPH_ONE_KERNEL
 // device-only build of ONE instantiation (tools/one_kernel.sh: registers, spills and ISA of a kernel in seconds instead of the whole library's minutes)
 #ifndef UPH_OK_F32
@@ -958,6 +989,8 @@ struct uph_ctx {
     DevBuf d_plan_head, d_plan_xy, d_plan_yaw, d_plan_goal, d_plan_rec;
     bool planned = false;                   // the resident batch came from uph_plan_upload (uph_plan_staged may read the staging)
     std::vector<ProblemHead> plan_probs;   // [B] the staged problems in resident order, boundary velocities formed on the host
+    std::vector<double> end_pose;          // [B][3] each problem's end position (map coordinates) and end yaw as uploaded (uph_replan_upload, goals == NULL)
+    DevBuf d_sw_q, d_sw_out;               // uph_replan_upload: switch queries and states (allocated at the first call)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -1220,7 +1253,7 @@ void uph_ctx_destroy(uph_ctx* c) {
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
-                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec};
+                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -1331,6 +1364,7 @@ static int admitBatch(uph_ctx* c, int32_t B, const ProblemHead* heads, std::vect
     static const ProblemHead placeholder = headOf(placeholderProblem());
     pp.assign(B, nullptr);
     c->rejected.assign(B, 0); c->n_rejected = 0;
+    c->end_pose.assign((size_t)3 * B, 0.0);
     const GridDev tg = uphMapGrid(c->map);
     const bool tiled = tg.nx_hold < tg.nx;
     const double tile_lo = tg.origin[0] + tg.x_off * tg.xy_res, tile_hi = tg.origin[0] + (tg.x_off + tg.nx_hold) * tg.xy_res;
@@ -1347,6 +1381,7 @@ static int admitBatch(uph_ctx* c, int32_t B, const ProblemHead* heads, std::vect
             if ((tg.x_off > 0 && q.lo[0] < tile_lo + UPH_TILE_MARGIN) || (tg.x_off + tg.nx_hold < tg.nx && q.hi[0] > tile_hi - UPH_TILE_MARGIN)) { rj = UPH_ERR_INVALID; msg = "uph_batch_upload: the path does not lie inside this map tile (route it to the tile's owner)"; }
         }
         c->rejected[b] = rj;
+        c->end_pose[(size_t)3 * b] = q.end_xy[0]; c->end_pose[(size_t)3 * b + 1] = q.end_xy[1]; c->end_pose[(size_t)3 * b + 2] = q.end_yaw[0];
         pp[b] = rj ? &placeholder : &q;
         if (rj) { if (!c->n_rejected) { why = msg; first_rj = rj; } c->n_rejected++; }
     }
@@ -1514,13 +1549,11 @@ static bool managerParamsOk(const uph_manager_params* mp) {
 // goals in, resident batch out: search (uphKinoSearch) -> clipped paths searched again with room for all their poses -> PlanManager's stage on the
 // device (uph_plan_resample_kernel) -> headers down (the paths never cross PCIe) -> admission on the host (admitBatch, as uph_batch_upload) -> x0
 // scattered from the staging (uph_plan_scatter_kernel) -> commitBatch.  The resident batch = the goals whose search succeeded, in goal order.
-int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
-                    int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
-    if (!k || !c || !mp || B <= 0 || !starts || !goals || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
-        setError("uph_plan_upload: bad arguments"); return UPH_ERR_INVALID;
-    }
-    if (uphKinoMap(k) != c->map) { setError("uph_plan_upload: the search context and the optimiser context are bound to different maps"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError("uph_plan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+// init_state [B][9] (x, y, dx, dy, ddx, ddy, yaw, dyaw, ddyaw) or nullptr: the start boundary's velocity / acceleration and yaw rate / acceleration of
+// goal b replace PlanManager's (sig_vel along the start heading, zeros) -- uph_replan_upload; nullptr: uph_plan_upload's problems, unchanged.
+// init_out (or nullptr): receives init_state together with the other outputs.  Arguments checked by the caller.
+static int planUpload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
+                      const double* init_state, double* init_out, const char* who, int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
     c->B = 0;                       // the context holds no batch until this call has succeeded as a whole
     c->traj_resident = false; c->planned = false; c->origin.clear(); c->plan_probs.clear();
     const int cap = path_cap > 0 ? path_cap : UPH_PLAN_PATH_CAP;
@@ -1567,13 +1600,14 @@ int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32
     std::vector<int> found;
     // every search and the resampling have run: the outputs are written now, all together (a failure before this point leaves them untouched, so a
     // caller can tell "no goal produced a path" -- the one UPH_ERR_INVALID returned with them written -- from every other failure)
+    if (init_state && init_out) std::memcpy(init_out, init_state, sizeof(double) * 9 * (size_t)B);
     for (int b = 0; b < B; b++) {
         status[b] = st[b]; traj_of[b] = -1;
         n_inner_xy[b] = st[b] == UPH_KINO_OK ? ph[(size_t)b].n_inner_xy : 0; n_inner_yaw[b] = st[b] == UPH_KINO_OK ? ph[(size_t)b].n_inner_yaw : 0;
         if (st[b] == UPH_KINO_OK) found.push_back(b);
     }
     const int F = (int)found.size();
-    if (F == 0) { setError("uph_plan_upload: no goal produced a path"); return UPH_ERR_INVALID; }
+    if (F == 0) { setError(std::string(who) + ": no goal produced a path"); return UPH_ERR_INVALID; }
     // the problems as uph_resample_batch forms them; the boundary velocities sig_vel * (cos, sin) of the end headings (:94-95) on the host
     const WalkSetup ws = walkSetup(*mp);
     std::vector<ProblemHead> heads((size_t)F);
@@ -1581,13 +1615,18 @@ int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32
         const PlanHead& g = ph[(size_t)found[j]];
         ProblemHead& h = heads[(size_t)j];
         h.n_inner_xy = g.n_inner_xy; h.n_inner_yaw = g.n_inner_yaw;
-        if (g.short_path) { h.refused = UPH_ERR_INVALID; h.why = "uph_plan_upload: a path needs at least two poses"; }
+        if (g.short_path) { h.refused = UPH_ERR_INVALID; h.why = init_state ? "uph_replan_upload: a path needs at least two poses" : "uph_plan_upload: a path needs at least two poses"; }
         h.init_xy[0] = g.p_init[0]; h.init_xy[1] = g.p_init[1]; h.end_xy[0] = g.p_end[0]; h.end_xy[1] = g.p_end[1];
         h.init_xy[2] = ws.sig_vel * std::cos(g.yaw_init); h.init_xy[3] = ws.sig_vel * std::sin(g.yaw_init);
         h.end_xy[2] = ws.sig_vel * std::cos(g.yaw_end); h.end_xy[3] = ws.sig_vel * std::sin(g.yaw_end);
         h.init_xy[4] = h.init_xy[5] = h.end_xy[4] = h.end_xy[5] = 0.0;
         h.init_yaw[0] = g.yaw_init; h.init_yaw[1] = h.init_yaw[2] = 0.0;
         h.end_yaw[0] = g.yaw_end; h.end_yaw[1] = h.end_yaw[2] = 0.0;
+        if (init_state) {           // the start boundary of a vehicle in motion: {P, V, A} and {yaw, dyaw, ddyaw}; P and yaw stay the path's first pose
+            const double* z = init_state + (size_t)9 * found[j];
+            for (int q = 2; q < 6; q++) h.init_xy[q] = z[q];
+            h.init_yaw[1] = z[7]; h.init_yaw[2] = z[8];
+        }
         h.total_time = g.total_time;
         for (int d = 0; d < 2; d++) { h.lo[d] = g.lo[d]; h.hi[d] = g.hi[d]; }
         h.turn = g.turn; h.kink = g.kink;
@@ -1616,6 +1655,67 @@ int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32
     c->plan_probs = heads;
     for (int j = 0; j < F; j++) traj_of[found[j]] = j;
     return UPH_OK;
+}
+
+int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
+                    int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
+    if (!k || !c || !mp || B <= 0 || !starts || !goals || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
+        setError("uph_plan_upload: bad arguments"); return UPH_ERR_INVALID;
+    }
+    if (uphKinoMap(k) != c->map) { setError("uph_plan_upload: the search context and the optimiser context are bound to different maps"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_plan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    return planUpload(k, c, mp, B, starts, goals, path_cap, nullptr, nullptr, "uph_plan_upload", status, traj_of, n_inner_xy, n_inner_yaw);
+}
+
+// re-plan from states on resident trajectories: every refusal first (dst untouched) -> switch states on the device (uph_switch_state_kernel over
+// src's coefficients; only the [B][9] states come down) -> goals (the caller's, or each source problem's end pose) -> planUpload with the states as
+// start boundaries.  Everything read from src is on the host before planUpload resets dst, so dst == src works.
+int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager_params* mp, int32_t B, const int32_t* src_traj, const double* t_switch,
+                      const double* goals, int32_t path_cap, double* switch_states, int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
+    if (!k || !src || !dst || !mp || B <= 0 || !src_traj || !t_switch || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
+        setError("uph_replan_upload: bad arguments"); return UPH_ERR_INVALID;
+    }
+    if (uphKinoMap(k) != src->map || dst->map != src->map) { setError("uph_replan_upload: the search context and the optimiser contexts are bound to different maps"); return UPH_ERR_INVALID; }
+    if (src->pending || dst->pending) { setError("uph_replan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    if (src->B <= 0 || !src->traj_resident) {
+        setError("uph_replan_upload: the source holds no resident trajectory (uph_batch_solve / uph_eval_batch after its upload first)"); return UPH_ERR_INVALID;
+    }
+    for (int32_t q = 0; q < B; q++) {
+        const int32_t b = src_traj[q];
+        if (b < 0 || b >= src->B) { setError("uph_replan_upload: query " + std::to_string(q) + " names no trajectory of the source batch"); return UPH_ERR_INVALID; }
+        if (!src->rejected.empty() && src->rejected[(size_t)b]) {
+            setError("uph_replan_upload: query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
+        }
+        if (!std::isfinite(t_switch[q])) { setError("uph_replan_upload: query " + std::to_string(q) + " has a non-finite switch time"); return UPH_ERR_INVALID; }
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(src->map)));
+    std::vector<SwitchQuery> sq((size_t)B);
+    for (int32_t q = 0; q < B; q++) {
+        SwitchQuery& r = sq[(size_t)q];
+        r.b = src_traj[q]; r.framed = src->frames.empty() ? 0 : 1; r.t = t_switch[q];
+        for (int d = 0; d < 2; d++) r.shift[d] = src->frames.empty() ? 0.0 : src->frames[(size_t)r.b].shift[d];
+    }
+    if (src->d_sw_q.ensure(sizeof(SwitchQuery) * (size_t)B) || src->d_sw_out.ensure(sizeof(double) * SWITCH_COLS * (size_t)B)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(src->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * (size_t)B, hipMemcpyHostToDevice, src->stream));
+    hipLaunchKernelGGL(uph_switch_state_kernel, dim3((B + 63) / 64), dim3(64), 0, src->stream, src->d_desc.as<TrajDesc>(), src->d_state.as<TrajState>(),
+                       src->d_cxy.as<double>(), src->d_cyaw.as<double>(), src->d_sw_q.as<SwitchQuery>(), (int)B, src->d_sw_out.as<double>());
+    HIPCHK(hipGetLastError());
+    std::vector<double> zs((size_t)SWITCH_COLS * B);
+    HIPCHK(hipMemcpyAsync(zs.data(), src->d_sw_out.p, sizeof(double) * SWITCH_COLS * (size_t)B, hipMemcpyDeviceToHost, src->stream));
+    HIPCHK(hipStreamSynchronize(src->stream));
+    // the search's starts (x, y, normSO2(yaw)) and goals; "the same goal" = the source problem's end pose, its yaw as normSO2 (a goal heading)
+    std::vector<double> st3((size_t)3 * B), gl3;
+    for (int32_t q = 0; q < B; q++) { st3[(size_t)3 * q] = zs[(size_t)9 * q]; st3[(size_t)3 * q + 1] = zs[(size_t)9 * q + 1]; st3[(size_t)3 * q + 2] = zs[(size_t)9 * q + 6]; }
+    if (!goals) {
+        gl3.resize((size_t)3 * B);
+        for (int32_t q = 0; q < B; q++) {
+            const double* e = src->end_pose.data() + (size_t)3 * src_traj[q];
+            gl3[(size_t)3 * q] = e[0]; gl3[(size_t)3 * q + 1] = e[1]; gl3[(size_t)3 * q + 2] = normSO2(e[2]);
+        }
+    }
+    // dst is reset from here on; a failure leaves the outputs untouched as uph_plan_upload does
+    return planUpload(k, dst, mp, B, st3.data(), goals ? goals : gl3.data(), path_cap, zs.data(), switch_states, "uph_replan_upload", status, traj_of, n_inner_xy,
+                      n_inner_yaw);
 }
 
 // test hook: the resident problems of a planned batch as the device staged them, in uph_resample_batch's output layout and resident order
