@@ -42,6 +42,9 @@
  *                              initial-guess stage (:62-132) and the arguments of optimizeSE2Traj, for a batch of goals with the paths kept on the device
  *   uph_replan_upload       <- the same chain for a vehicle in motion: the start of each plan is a resident trajectory's state at a switch time
  *                              (getPos / getVel / getAcc of SE2Trajectory, se2traj.hpp:343-361, 106-140) instead of plan_manager.cpp:86-94's start
+ *   uph_traj_states         <- getPos / getVel / getAcc of resident trajectories at given (trajectory, time) pairs
+ *   uph_refine_upload       <- receding-horizon refinement: the rest of each resident trajectory as the initial guess of a new problem from its
+ *                              state at a switch time, no search
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -376,6 +379,29 @@ int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32
  * a non-finite t_switch[q], k / src / dst bound to different maps, an asynchronous solve pending on src or dst.  Blocking. */
 int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager_params* mp, int32_t B, const int32_t* src_traj, const double* t_switch,
                       const double* goals, int32_t path_cap, double* switch_states, int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw);
+/* ---- resident trajectories at given times: row q of out10 [n][10] is trajectory traj[q] of c's resident batch at t[q] seconds from its start, clamped
+ * to [0, duration] (the duration as uph_rollout_batch forms it: running sums of the piece durations, the smaller of the two).  Columns 0-8 are
+ * uph_replan_upload's switch-state columns -- x, y (map coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw -- and column 9 is the raw
+ * (unwrapped) yaw.  At a rollout row's t, columns 0-7 equal that row bit for bit.  Refused with UPH_ERR_INVALID, out10 untouched: bad arguments, no
+ * resident trajectory (uph_rollout_batch's rule), a traj[q] out of range or naming an UPH_RET_UNSUPPORTED slot, a non-finite t[q], an asynchronous
+ * solve pending on c.  Blocking. */
+int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10);
+/* ---- refine resident trajectories from a switch time without a new search: query q continues trajectory b = src_traj[q] of src's resident batch
+ * from its state at tc = t_switch[q] clamped to [0, D] (D: the duration as above) to the end boundary of b's problem as it was uploaded, with the
+ * rest of b as the initial guess.  With R = D - tc and b's piece durations T_xy / T_yaw: N' = max(1, nearbyint(R / T_xy)) position pieces and
+ * M' = max(N', nearbyint(R / T_yaw)) yaw pieces (tc = 0 gives back b's counts); the xy way-points are b's (x, y) at tc + k (R / N'), k = 1 .. N' - 1,
+ * the yaw way-points its raw yaw at tc + k (R / M'), k = 1 .. M' - 1 (the times formed without contraction, the values those of uph_traj_states at
+ * the same times bit for bit); init_xy = {x, y, dx, dy, ddx, ddy} and init_yaw = {raw yaw, dyaw, ddyaw} of the state at tc; end_xy / end_yaw b's
+ * uploaded end boundary; total_time = R.  R <= 0: status[q] = UPH_REFINE_AT_END and nothing is uploaded for q.  The other queries are uploaded to
+ * dst in query order as uph_plan_upload uploads its goals (same admission and local frames; uph_batch_origin = the query index; uph_plan_staged).
+ * Outputs [B]: status (UPH_KINO_OK or UPH_REFINE_AT_END), traj_of, n_inner_xy, n_inner_yaw, and switch_states [B][10] (may be NULL: uph_traj_states'
+ * columns at tc), written together once the device work has run.  No query left to refine: UPH_ERR_INVALID WITH the outputs written, dst holding
+ * no batch.  dst == src is allowed.  Refused with UPH_ERR_INVALID, outputs untouched and dst's batch as it was: bad arguments, src holding no resident
+ * trajectory, an src_traj[q] out of range or naming an UPH_RET_UNSUPPORTED slot, a non-finite t_switch[q] or piece duration of b, src / dst bound to
+ * different maps, an asynchronous solve pending on src or dst.  Blocking. */
+#define UPH_REFINE_AT_END 7     /* t_switch at or past the end: nothing left to refine (not uploaded) */
+int uph_refine_upload(uph_ctx* src, uph_ctx* dst, int32_t B, const int32_t* src_traj, const double* t_switch, double* switch_states /* B x 10, may be NULL */,
+                      int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw);
 /* test hook: the resident problems of a batch uploaded by uph_plan_upload exactly as the device staged them, in uph_resample_batch's output layout
  * and the resident order (boundary velocities included).  UPH_ERR_LIMIT when a problem has more way-points than cap_xy / cap_yaw or than the staging
  * holds (UPH_MAX_PIECE_* - 1; the counts are still written); UPH_ERR_INVALID when the resident batch did not come from uph_plan_upload or

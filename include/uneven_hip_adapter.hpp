@@ -16,6 +16,7 @@
 //                                  (the batched device search, uph_kino_plan_batch; planBatch = many goals in one call)
 //   planSE2TrajBatch               PlanManager::rcvWpsCallBack plan_manager.cpp:43-134 for many goals in one call, every stage on the device (uph_plan_upload)
 //   replanSE2TrajBatch             the same from states on the last batch's trajectories: re-planning a vehicle in motion (uph_replan_upload)
+//   refineSE2TrajBatch             the rest of the last batch's trajectories re-optimised from states at switch times, no search (uph_refine_upload)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -489,6 +490,27 @@ public:
                                 int32_t path_cap = 0) {
         return replanSE2TrajBatch<VecN<3>>(kino, traj, t_switch, static_cast<const std::vector<VecN<3>>*>(nullptr), mgr, path_cap);
     }
+    // receding-horizon refinement without a search (uph_refine_upload): query q re-optimises the rest of trajectory traj[q] of this object's last batch
+    // from its state at t_switch[q] to its problem's end boundary, the old trajectory as the initial guess, on the current map.  status[q] =
+    // UPH_KINO_OK, or UPH_REFINE_AT_END for a switch at or past the end (ret -1, empty trajectory).  The new batch replaces the last one on this
+    // object.  Same GoalPlan as planSE2TrajBatch; replanSE2TrajBatch (a new search) is the fallback for a refined solve that fails.
+    GoalPlan refineSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t_switch) {
+        if (t_switch.size() != traj.size()) throw std::runtime_error("refineSE2TrajBatch: traj and t_switch differ in number");
+        if (last_multi_) throw std::runtime_error("refineSE2TrajBatch: the last batch was split over several devices");
+        const int32_t B = (int32_t)traj.size();
+        GoalPlan out;
+        if (B == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end()), nxy(B), nyw(B);
+        out.status.assign((size_t)B, -1); out.traj_of.assign((size_t)B, -1);
+        in_opt = true;
+        const int rc = uph_refine_upload(ctx_, ctx_, B, tr.data(), t_switch.data(), nullptr, out.status.data(), out.traj_of.data(), nxy.data(), nyw.data());
+        if (rc == UPH_ERR_INVALID && out.status[0] < 0) {            // refused: the last batch is still resident, nothing of it changes
+            in_opt = false;
+            throw std::runtime_error(std::string("uph_refine_upload: ") + uph_last_error());
+        }
+        last_report_.clear(); last_multi_ = false; last_ctxs_.assign(1, ctx_); last_B_ = 0;
+        return finishGoalPlan(rc, B, out, nxy, nyw, "uph_refine_upload", "refineSE2TrajBatch");
+    }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)
 
     // getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229): max vx, ax, ay, curvature, attitude (-cos xi), sigma sampled every 0.01 s -- evaluated
@@ -738,7 +760,7 @@ ALMTrajOpt::GoalPlan ALMTrajOpt::replanSE2TrajBatch(KinoAstar& kino, const std::
     return finishGoalPlan(rc, B, out, nxy, nyw, "uph_replan_upload", "replanSE2TrajBatch");
 }
 
-// after uph_plan_upload / uph_replan_upload into ctx_: solve and download the found goals, one GoalPlan entry per goal
+// after uph_plan_upload / uph_replan_upload / uph_refine_upload into ctx_: solve and download the found goals, one GoalPlan entry per goal
 inline ALMTrajOpt::GoalPlan ALMTrajOpt::finishGoalPlan(int rc, int32_t B, GoalPlan& out, const std::vector<int32_t>& nxy, const std::vector<int32_t>& nyw, const char* who,
                                                      const char* caller) {
     const int F = uph_batch_count(ctx_);

@@ -157,6 +157,8 @@ SYMBOLS = {
     "uph_plan_staged": (C.c_int, [_VP, _I32, _I32, DP, DP, DP, DP, DP, DP, C.POINTER(_I32), C.POINTER(_I32), DP]),
     "uph_replan_upload": (C.c_int, [_VP, _VP, _VP, C.POINTER(ManagerParams), _I32, C.POINTER(_I32), DP, DP, _I32, DP, C.POINTER(_I32), C.POINTER(_I32),
                                     C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_traj_states": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP]),
+    "uph_refine_upload": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), DP, DP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
 }
 
 _LIB = None
@@ -169,6 +171,8 @@ UPH_MAX_PIECE_YAW = 256
 PLAN_STAGE_XY, PLAN_STAGE_YAW = UPH_MAX_PIECE_XY - 1, UPH_MAX_PIECE_YAW - 1
 UPH_ERR_INVALID, UPH_ERR_LIMIT = -1, -4
 UPH_KINO_OK = 0
+UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
+TRAJ_STATE_COLS = 10       # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
 
 
 class UnevenHipError(RuntimeError):

@@ -404,7 +404,7 @@ class ALMTrajOpt:
         return _lib.ManagerParams(**{k: (int(bool(v)) if k == "test_mode" else float(v)) for k, v in mk.items()})
 
     def _planned(self, rc, plan, who):
-        """the outputs of uph_plan_upload / uph_replan_upload -> the resident batch's sizes, or a raise"""
+        """the outputs of uph_plan_upload / uph_replan_upload / uph_refine_upload -> the resident batch's sizes, or a raise"""
         st, to, nx, ny = plan["status"], plan["traj_of"], plan["n_inner_xy"], plan["n_inner_yaw"]
         self.last_plan = plan
         # "no goal produced a path" is the one UPH_ERR_INVALID returned with the outputs written (statuses no longer the -1 they were filled with)
@@ -469,6 +469,43 @@ class ALMTrajOpt:
         """replan_goals_upload + solve + download, as plan_goals: one dict per query with its search `status` (and `traj_of` + the result dict when
         it has a path); the new batch stays resident on self.  The switch states are in self.last_plan["switch_states"]."""
         return self._solve_planned(self.replan_goals_upload(kino, src, src_traj, t_switch, goals=goals, path_cap=path_cap, **manager_params), full)
+
+    # ---- resident trajectories at given times (uph_traj_states), their tails refined without a search (uph_refine_upload) --------------------------
+    def traj_states(self, traj, t):
+        """resident trajectory traj[q] at t[q] seconds from its start (clamped to [0, duration], the rollout's clock), evaluated on the device: (n, 10)
+        rows x, y (map coordinates), dx, dy, ddx, ddy, yaw (normSO2), dyaw, ddyaw -- replan_goals_upload's switch states -- and the raw yaw"""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        n = tr.shape[0]
+        if n == 0 or ts.shape[0] != n:
+            raise _lib.UnevenHipError("traj_states: traj and t must be the same non-empty length")
+        out = np.zeros((n, _lib.TRAJ_STATE_COLS))
+        _lib.check(self.L.uph_traj_states(self.h, n, tr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(ts), _dp(out)), "uph_traj_states")
+        return out
+
+    def refine_upload(self, src, src_traj, t_switch):
+        """the rest of trajectory src_traj[q] of `src`'s resident batch (an ALMTrajOpt on the same map, self included) after t_switch[q] as a new problem
+        on self, without a search: start = its state at the switch time, end = its problem's uploaded end boundary, way-points = the trajectory itself
+        (uph_refine_upload).  Returns plan_goals_upload's dict -- status UPH_KINO_OK, or UPH_REFINE_AT_END for a switch at or past the end (not
+        uploaded) -- plus switch_states (B, 10) in traj_states' columns.  A batch in which every query is at its end leaves self empty (no raise)."""
+        tr = np.ascontiguousarray(src_traj, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(t_switch, dtype=np.float64).reshape(-1)
+        B = tr.shape[0]
+        if B == 0 or ts.shape[0] != B:
+            raise _lib.UnevenHipError("refine: src_traj and t_switch must be the same non-empty length")
+        st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+        nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        sw = np.full((B, _lib.TRAJ_STATE_COLS), np.nan)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.L.uph_refine_upload(src.h, self.h, B, ip(tr), _dp(ts), _dp(sw), ip(st), ip(to), ip(nx), ip(ny))
+        if rc != 0 and (rc != _lib.UPH_ERR_INVALID or (st >= 0).any()):      # past the refusals (which leave self's batch as it was): no batch is resident
+            self._B, self._sizes, self._last = 0, [], []
+        return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny, switch_states=sw), "uph_refine_upload")
+
+    def refine(self, src, src_traj, t_switch, full=False):
+        """refine_upload + solve + download, as replan_goals: one dict per query with its `status` (and `traj_of` + the result dict when it was
+        uploaded); the new batch stays resident on self.  The switch states are in self.last_plan["switch_states"]."""
+        return self._solve_planned(self.refine_upload(src, src_traj, t_switch), full)
 
     def _download_block(self, nxy, nyw, full):
         """download() for a whole resident batch into a few contiguous arrays: the uph_result array is a numpy record array whose pointer fields

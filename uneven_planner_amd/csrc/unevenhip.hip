@@ -853,13 +853,15 @@ __global__ __launch_bounds__(64) void uph_plan_scatter_kernel(const PlanScatter*
 
 // ---- switch states (uph_replan_upload): trajectory b of the resident batch at its clamped time, one lane per query.  The sample is the rollout's
 // (trajectorySample, same piece location, same statements), so at a rollout row's t the state equals that row bit for bit; the duration is the
-// rollout's too (running sums of the piece durations, the smaller of the two).  Row q: x, y (map coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw.
+// rollout's too (running sums of the piece durations, the smaller of the two).  Row q: x, y (map coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw;
+// COLS = TRAJ_STATE_COLS (uph_traj_states, uph_refine_upload) adds the raw yaw as column 9.  The 9-column instantiation is uph_replan_upload's.
 struct SwitchQuery {            // formed on the host
     int32_t b, framed;          // resident trajectory; framed: the batch solves in local frames (add shift, as the rollout does)
     double t;                   // switch time (finite)
     double shift[2];
 };
-constexpr int SWITCH_COLS = 9;
+constexpr int SWITCH_COLS = 9, TRAJ_STATE_COLS = 10;
+template <int COLS>
 __global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __restrict__ desc, const TrajState* __restrict__ state, const double* __restrict__ cxy,
                                                               const double* __restrict__ cyaw, const SwitchQuery* __restrict__ qs, int nq, double* __restrict__ out) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -876,10 +878,56 @@ __global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __
     double unused[7];
     GridDev none;
     trajectorySample<false, true>(cxy + td.off_cxy, cyaw + td.off_cyaw, td.Nxy, td.Nyaw, Tx, Ty, t, none, 0.0, s, unused);
-    double* o = out + (size_t)q * SWITCH_COLS;
+    double* o = out + (size_t)q * COLS;
     o[0] = sq.framed ? s.p[0] + sq.shift[0] : s.p[0]; o[1] = sq.framed ? s.p[1] + sq.shift[1] : s.p[1];
     o[2] = s.v[0]; o[3] = s.v[1]; o[4] = s.a[0]; o[5] = s.a[1];
     o[6] = s.yawn; o[7] = s.dyaw; o[8] = s.ddyaw;
+    if (COLS > SWITCH_COLS) o[9] = s.yaw;
+}
+
+// ---- refine (uph_refine_upload): the tail of a resident trajectory as a new problem, without a search.  uph_switch_state_kernel<TRAJ_STATE_COLS>
+// has evaluated the switch states (rows [0, B), one per query) and every way-point time of the batch into one table; one lane per uploaded query
+// copies its way-points into the plan staging (slot = query index) and forms its PlanHead in way-point order.  The bounding box and turn / kink
+// follow headOf / yawTurnKink statement for statement, so uph_batch_upload's admission of the same problem sees the same values.
+struct RefineStage {            // formed on the host
+    int32_t q, nxy, nyw, pad;   // staging slot (= query, = its switch-state row), inner way-point counts (<= PLAN_SX / PLAN_SY, checked on the host)
+    int64_t row_xy, row_yaw;    // first state row of the xy / yaw way-points
+    double p_end[2], yaw_end;   // the source problem's end boundary as uploaded (map coordinates)
+    double total_time;
+};
+__global__ __launch_bounds__(64) void uph_refine_stage_kernel(const RefineStage* __restrict__ rec, int n, const double* __restrict__ states,
+                                                              double* __restrict__ st_xy, double* __restrict__ st_yaw, PlanHead* __restrict__ heads) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const RefineStage r = rec[j];
+    const double* z = states + (size_t)r.q * TRAJ_STATE_COLS;
+    PlanHead h = PlanHead{};
+    h.n_inner_xy = r.nxy; h.n_inner_yaw = r.nyw;
+    h.p_init[0] = z[0]; h.p_init[1] = z[1]; h.p_end[0] = r.p_end[0]; h.p_end[1] = r.p_end[1];
+    h.yaw_init = z[9]; h.yaw_end = r.yaw_end;
+    h.total_time = r.total_time;
+    for (int d = 0; d < 2; d++) {
+        h.lo[d] = h.p_end[d] < h.p_init[d] ? h.p_end[d] : h.p_init[d];
+        h.hi[d] = h.p_init[d] < h.p_end[d] ? h.p_end[d] : h.p_init[d];
+    }
+    double* oxy = st_xy + (size_t)r.q * PLAN_SX * 2;
+    for (int k = 0; k < r.nxy; k++) {
+        const double* w = states + (size_t)(r.row_xy + k) * TRAJ_STATE_COLS;
+        for (int d = 0; d < 2; d++) {
+            oxy[2 * k + d] = w[d];
+            h.lo[d] = w[d] < h.lo[d] ? w[d] : h.lo[d];
+            h.hi[d] = h.hi[d] < w[d] ? w[d] : h.hi[d];
+        }
+    }
+    double* oyw = st_yaw + (size_t)r.q * PLAN_SY;
+    double prev = h.yaw_init;
+    for (int k = 0; k <= r.nyw; k++) {
+        const double cur = k < r.nyw ? states[(size_t)(r.row_yaw + k) * TRAJ_STATE_COLS + 9] : h.yaw_end;
+        if (k < r.nyw) oyw[k] = cur;
+        const double dy = fabs(cur - prev);
+        h.turn += dy; h.kink = h.kink < dy ? dy : h.kink; prev = cur;
+    }
+    heads[r.q] = h;
 }
 
 #ifdef UPH_ONE_KERNEL
@@ -990,7 +1038,9 @@ struct uph_ctx {
     bool planned = false;                   // the resident batch came from uph_plan_upload (uph_plan_staged may read the staging)
     std::vector<ProblemHead> plan_probs;   // [B] the staged problems in resident order, boundary velocities formed on the host
     std::vector<double> end_pose;          // [B][3] each problem's end position (map coordinates) and end yaw as uploaded (uph_replan_upload, goals == NULL)
-    DevBuf d_sw_q, d_sw_out;               // uph_replan_upload: switch queries and states (allocated at the first call)
+    std::vector<double> end_bnd;           // [B][9] each problem's whole end boundary as uploaded: end_xy {P, V, A} (map coordinates), end_yaw (uph_refine_upload)
+    DevBuf d_sw_q, d_sw_out;               // uph_replan_upload / uph_traj_states / uph_refine_upload: state queries and states (allocated at the first call)
+    DevBuf d_refine_rec;                   // uph_refine_upload: staging records
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -1253,7 +1303,7 @@ void uph_ctx_destroy(uph_ctx* c) {
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
-                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out};
+                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -1365,6 +1415,7 @@ static int admitBatch(uph_ctx* c, int32_t B, const ProblemHead* heads, std::vect
     pp.assign(B, nullptr);
     c->rejected.assign(B, 0); c->n_rejected = 0;
     c->end_pose.assign((size_t)3 * B, 0.0);
+    c->end_bnd.assign((size_t)9 * B, 0.0);
     const GridDev tg = uphMapGrid(c->map);
     const bool tiled = tg.nx_hold < tg.nx;
     const double tile_lo = tg.origin[0] + tg.x_off * tg.xy_res, tile_hi = tg.origin[0] + (tg.x_off + tg.nx_hold) * tg.xy_res;
@@ -1382,6 +1433,8 @@ static int admitBatch(uph_ctx* c, int32_t B, const ProblemHead* heads, std::vect
         }
         c->rejected[b] = rj;
         c->end_pose[(size_t)3 * b] = q.end_xy[0]; c->end_pose[(size_t)3 * b + 1] = q.end_xy[1]; c->end_pose[(size_t)3 * b + 2] = q.end_yaw[0];
+        for (int k = 0; k < 6; k++) c->end_bnd[(size_t)9 * b + k] = q.end_xy[k];
+        for (int k = 0; k < 3; k++) c->end_bnd[(size_t)9 * b + 6 + k] = q.end_yaw[k];
         pp[b] = rj ? &placeholder : &q;
         if (rj) { if (!c->n_rejected) { why = msg; first_rj = rj; } c->n_rejected++; }
     }
@@ -1552,6 +1605,7 @@ static bool managerParamsOk(const uph_manager_params* mp) {
 // init_state [B][9] (x, y, dx, dy, ddx, ddy, yaw, dyaw, ddyaw) or nullptr: the start boundary's velocity / acceleration and yaw rate / acceleration of
 // goal b replace PlanManager's (sig_vel along the start heading, zeros) -- uph_replan_upload; nullptr: uph_plan_upload's problems, unchanged.
 // init_out (or nullptr): receives init_state together with the other outputs.  Arguments checked by the caller.
+static int uploadStaged(uph_ctx* c, const std::vector<int>& found, const std::vector<ProblemHead>& heads, int32_t* traj_of);
 static int planUpload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32_t B, const double* starts, const double* goals, int32_t path_cap,
                       const double* init_state, double* init_out, const char* who, int32_t* status, int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
     c->B = 0;                       // the context holds no batch until this call has succeeded as a whole
@@ -1631,8 +1685,16 @@ static int planUpload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int
         for (int d = 0; d < 2; d++) { h.lo[d] = g.lo[d]; h.hi[d] = g.hi[d]; }
         h.turn = g.turn; h.kink = g.kink;
     }
+    return uploadStaged(c, found, heads, traj_of);
+}
+
+// Second half of a staged upload (uph_plan_upload, uph_replan_upload, uph_refine_upload): heads[j] is the problem of staging slot found[j] ->
+// admitBatch -> x0 scattered from the staging (uph_plan_scatter_kernel) -> commitBatch; the resident batch = the slots in that order
+// (uph_batch_origin: found, uph_plan_staged: heads), traj_of[found[j]] = j.
+static int uploadStaged(uph_ctx* c, const std::vector<int>& found, const std::vector<ProblemHead>& heads, int32_t* traj_of) {
+    const int F = (int)found.size();
     std::vector<const ProblemHead*> pp;
-    r = admitBatch(c, F, heads.data(), pp);
+    int r = admitBatch(c, F, heads.data(), pp);
     if (r != UPH_OK) return r;
     // x0 from the staging: a refused problem's slot runs uph_batch_upload's placeholder; every other one has all its way-points staged (<= UPH_MAX_PIECE_* - 1)
     std::vector<PlanScatter> rec((size_t)F);
@@ -1697,7 +1759,7 @@ int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager
     }
     if (src->d_sw_q.ensure(sizeof(SwitchQuery) * (size_t)B) || src->d_sw_out.ensure(sizeof(double) * SWITCH_COLS * (size_t)B)) return UPH_ERR_HIP;
     HIPCHK(hipMemcpyAsync(src->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * (size_t)B, hipMemcpyHostToDevice, src->stream));
-    hipLaunchKernelGGL(uph_switch_state_kernel, dim3((B + 63) / 64), dim3(64), 0, src->stream, src->d_desc.as<TrajDesc>(), src->d_state.as<TrajState>(),
+    hipLaunchKernelGGL(uph_switch_state_kernel<SWITCH_COLS>, dim3((B + 63) / 64), dim3(64), 0, src->stream, src->d_desc.as<TrajDesc>(), src->d_state.as<TrajState>(),
                        src->d_cxy.as<double>(), src->d_cyaw.as<double>(), src->d_sw_q.as<SwitchQuery>(), (int)B, src->d_sw_out.as<double>());
     HIPCHK(hipGetLastError());
     std::vector<double> zs((size_t)SWITCH_COLS * B);
@@ -1716,6 +1778,168 @@ int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager
     // dst is reset from here on; a failure leaves the outputs untouched as uph_plan_upload does
     return planUpload(k, dst, mp, B, st3.data(), goals ? goals : gl3.data(), path_cap, zs.data(), switch_states, "uph_replan_upload", status, traj_of, n_inner_xy,
                       n_inner_yaw);
+}
+
+// uph_traj_states / uph_refine_upload: c holds resident trajectories and every query names one of them at a finite time (uph_replan_upload's rules)
+static int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t, const char* who) {
+    if (c->B <= 0 || !c->traj_resident) {
+        setError(std::string(who) + ": no trajectory is resident (uph_batch_solve / uph_eval_batch after the upload first)"); return UPH_ERR_INVALID;
+    }
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t b = traj[q];
+        if (b < 0 || b >= c->B) { setError(std::string(who) + ": query " + std::to_string(q) + " names no trajectory of the resident batch"); return UPH_ERR_INVALID; }
+        if (!c->rejected.empty() && c->rejected[(size_t)b]) {
+            setError(std::string(who) + ": query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
+        }
+        if (!std::isfinite(t[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a non-finite time"); return UPH_ERR_INVALID; }
+    }
+    return UPH_OK;
+}
+
+// the states of queries sq on c's resident trajectories into c->d_sw_out [n][TRAJ_STATE_COLS] (enqueued on c's stream, not waited for)
+static int launchTrajStates(uph_ctx* c, const std::vector<SwitchQuery>& sq) {
+    const size_t n = sq.size();
+    if (c->d_sw_q.ensure(sizeof(SwitchQuery) * n) || c->d_sw_out.ensure(sizeof(double) * TRAJ_STATE_COLS * n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(uph_switch_state_kernel<TRAJ_STATE_COLS>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->d_desc.as<TrajDesc>(),
+                       c->d_state.as<TrajState>(), c->d_cxy.as<double>(), c->d_cyaw.as<double>(), c->d_sw_q.as<SwitchQuery>(), (int)n, c->d_sw_out.as<double>());
+    HIPCHK(hipGetLastError());
+    return UPH_OK;
+}
+
+static SwitchQuery trajQuery(const uph_ctx* c, int32_t b, double t) {
+    SwitchQuery r;
+    r.b = b; r.framed = c->frames.empty() ? 0 : 1; r.t = t;
+    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    return r;
+}
+
+int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
+    if (!c || n <= 0 || !traj || !t || !out10) { setError("uph_traj_states: bad arguments"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_traj_states: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t, "uph_traj_states");
+    if (r != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    std::vector<SwitchQuery> sq((size_t)n);
+    for (int32_t q = 0; q < n; q++) sq[(size_t)q] = trajQuery(c, traj[q], t[q]);
+    r = launchTrajStates(c, sq);
+    if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
+    HIPCHK(hipMemcpyAsync(out10, c->d_sw_out.p, sizeof(double) * TRAJ_STATE_COLS * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return UPH_OK;
+}
+
+// refine resident trajectories from a switch time without a search: every refusal first (dst untouched) -> the source's piece durations (one
+// download) -> remaining time and piece counts on the host -> the switch states and every way-point state of the batch on the device (one launch of
+// uph_switch_state_kernel<TRAJ_STATE_COLS> over src's coefficients) -> uph_refine_stage_kernel writes dst's plan staging and heads -> uploadStaged, as
+// planUpload.  Everything read from src is on the host or in src's state table before dst is reset, so dst == src works.
+static int refreshStates(uph_ctx* c);
+int uph_refine_upload(uph_ctx* src, uph_ctx* dst, int32_t B, const int32_t* src_traj, const double* t_switch, double* switch_states, int32_t* status,
+                      int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
+#pragma clang fp contract(off)
+    if (!src || !dst || B <= 0 || !src_traj || !t_switch || !status || !traj_of || !n_inner_xy || !n_inner_yaw) {
+        setError("uph_refine_upload: bad arguments"); return UPH_ERR_INVALID;
+    }
+    if (dst->map != src->map) { setError("uph_refine_upload: the source and destination contexts are bound to different maps"); return UPH_ERR_INVALID; }
+    if (src->pending || dst->pending) { setError("uph_refine_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(src, B, src_traj, t_switch, "uph_refine_upload");
+    if (r != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(src->map)));
+    r = refreshStates(src);
+    if (r != UPH_OK) return r;
+    // remaining time R and piece counts (restated by tests/test_refine_cpu.py refine_counts)
+    std::vector<double> rem((size_t)B), tcs((size_t)B);
+    std::vector<int> nxy((size_t)B, 0), nyw((size_t)B, 0);
+    for (int32_t q = 0; q < B; q++) {
+        const int32_t b = src_traj[q];
+        const double Tx = src->state_host[(size_t)b].T_xy, Ty = src->state_host[(size_t)b].T_yaw;
+        if (!std::isfinite(Tx) || !std::isfinite(Ty)) {
+            setError("uph_refine_upload: query " + std::to_string(q) + " names a trajectory with non-finite piece durations"); return UPH_ERR_INVALID;
+        }
+        double durx = 0.0, dury = 0.0;                 // the duration as uph_switch_state_kernel and the rollout form it
+        for (int i = 0; i < src->desc[(size_t)b].Nxy; i++) durx += Tx;
+        for (int i = 0; i < src->desc[(size_t)b].Nyaw; i++) dury += Ty;
+        const double D = durx < dury ? durx : dury;
+        const double tc = t_switch[q] <= 0.0 ? 0.0 : (t_switch[q] >= D ? D : t_switch[q]);
+        const double R = D - tc;
+        tcs[(size_t)q] = tc; rem[(size_t)q] = R;
+        if (!(R > 0.0)) continue;
+        const int n = std::max(1, (int)std::nearbyint(R / Tx));
+        const int m = std::max(n, (int)std::nearbyint(R / Ty));
+        if (n - 1 > PLAN_SX || m - 1 > PLAN_SY) {           // (not reached: n <= Nxy and m <= Nyaw of an admitted trajectory)
+            setError("uph_refine_upload: query " + std::to_string(q) + " needs more way-points than the staging holds"); return UPH_ERR_LIMIT;
+        }
+        nxy[(size_t)q] = n - 1; nyw[(size_t)q] = m - 1;
+    }
+    // the state table: rows [0, B) the switch states, then per refined query its xy and yaw way-point times tc + k (R / N'), tc + k (R / M')
+    std::vector<SwitchQuery> sq;
+    std::vector<RefineStage> rec;
+    std::vector<int> found;
+    std::vector<double> ends;                           // the refined queries' end boundaries (dst == src: admitBatch replaces src's)
+    for (int32_t q = 0; q < B; q++) sq.push_back(trajQuery(src, src_traj[q], t_switch[q]));
+    for (int32_t q = 0; q < B; q++) {
+        if (!(rem[(size_t)q] > 0.0)) continue;
+        const int32_t b = src_traj[q];
+        const double R = rem[(size_t)q], tc = tcs[(size_t)q];
+        RefineStage s;
+        s.q = q; s.nxy = nxy[(size_t)q]; s.nyw = nyw[(size_t)q]; s.pad = 0;
+        s.row_xy = (int64_t)sq.size();
+        const double hx = R / (nxy[(size_t)q] + 1), hy = R / (nyw[(size_t)q] + 1);
+        for (int k = 1; k <= s.nxy; k++) sq.push_back(trajQuery(src, b, tc + k * hx));
+        s.row_yaw = (int64_t)sq.size();
+        for (int k = 1; k <= s.nyw; k++) sq.push_back(trajQuery(src, b, tc + k * hy));
+        const double* e = src->end_bnd.data() + (size_t)9 * b;
+        s.p_end[0] = e[0]; s.p_end[1] = e[1]; s.yaw_end = e[6]; s.total_time = R;
+        rec.push_back(s);
+        found.push_back(q);
+        ends.insert(ends.end(), e, e + 9);
+    }
+    r = launchTrajStates(src, sq);
+    if (r != UPH_OK) { hipStreamSynchronize(src->stream); return r; }
+    std::vector<double> zs((size_t)TRAJ_STATE_COLS * B);
+    HIPCHK(hipMemcpyAsync(zs.data(), src->d_sw_out.p, sizeof(double) * TRAJ_STATE_COLS * (size_t)B, hipMemcpyDeviceToHost, src->stream));
+    HIPCHK(hipStreamSynchronize(src->stream));
+    // dst is reset from here on; a failure leaves the outputs untouched as uph_plan_upload does
+    dst->B = 0;
+    dst->traj_resident = false; dst->planned = false; dst->origin.clear(); dst->plan_probs.clear();
+    const int F = (int)found.size();
+    std::vector<PlanHead> ph((size_t)B);
+    if (F > 0) {
+        if (dst->d_plan_head.ensure(sizeof(PlanHead) * (size_t)B) || dst->d_plan_xy.ensure(sizeof(double) * 2 * PLAN_SX * (size_t)B) ||
+            dst->d_plan_yaw.ensure(sizeof(double) * PLAN_SY * (size_t)B) || dst->d_refine_rec.ensure(sizeof(RefineStage) * (size_t)F))
+            return UPH_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(dst->d_refine_rec.p, rec.data(), sizeof(RefineStage) * (size_t)F, hipMemcpyHostToDevice, src->stream));
+        hipLaunchKernelGGL(uph_refine_stage_kernel, dim3((F + 63) / 64), dim3(64), 0, src->stream, dst->d_refine_rec.as<RefineStage>(), F, src->d_sw_out.as<double>(),
+                           dst->d_plan_xy.as<double>(), dst->d_plan_yaw.as<double>(), dst->d_plan_head.as<PlanHead>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { hipStreamSynchronize(src->stream); setError(std::string("uph_refine_upload: ") + hipGetErrorString(e)); return UPH_ERR_HIP; }
+        HIPCHK(hipMemcpyAsync(ph.data(), dst->d_plan_head.p, sizeof(PlanHead) * (size_t)B, hipMemcpyDeviceToHost, src->stream));
+        HIPCHK(hipStreamSynchronize(src->stream));
+    }
+    // the device work has run: the outputs are written now, all together
+    if (switch_states) std::memcpy(switch_states, zs.data(), sizeof(double) * TRAJ_STATE_COLS * (size_t)B);
+    for (int32_t q = 0; q < B; q++) {
+        status[q] = rem[(size_t)q] > 0.0 ? UPH_KINO_OK : UPH_REFINE_AT_END; traj_of[q] = -1;
+        n_inner_xy[q] = nxy[(size_t)q]; n_inner_yaw[q] = nyw[(size_t)q];
+    }
+    if (F == 0) { setError("uph_refine_upload: no query left to refine (every switch time at or past its trajectory's end)"); return UPH_ERR_INVALID; }
+    // the problems: start = the switch state with its raw yaw, end = the source problem's end boundary as uploaded, total_time = R
+    std::vector<ProblemHead> heads((size_t)F);
+    for (int j = 0; j < F; j++) {
+        const int q = found[(size_t)j];
+        const PlanHead& g = ph[(size_t)q];
+        const double* z = zs.data() + (size_t)TRAJ_STATE_COLS * q;
+        const double* e = ends.data() + (size_t)9 * j;
+        ProblemHead& h = heads[(size_t)j];
+        h.n_inner_xy = nxy[(size_t)q]; h.n_inner_yaw = nyw[(size_t)q];
+        for (int k = 0; k < 6; k++) { h.init_xy[k] = z[k]; h.end_xy[k] = e[k]; }
+        h.init_yaw[0] = z[9]; h.init_yaw[1] = z[7]; h.init_yaw[2] = z[8];
+        for (int k = 0; k < 3; k++) h.end_yaw[k] = e[6 + k];
+        h.total_time = rem[(size_t)q];
+        for (int d = 0; d < 2; d++) { h.lo[d] = g.lo[d]; h.hi[d] = g.hi[d]; }
+        h.turn = g.turn; h.kink = g.kink;
+    }
+    return uploadStaged(dst, found, heads, traj_of);
 }
 
 // test hook: the resident problems of a planned batch as the device staged them, in uph_resample_batch's output layout and resident order
