@@ -45,6 +45,11 @@
  *   uph_traj_states         <- getPos / getVel / getAcc of resident trajectories at given (trajectory, time) pairs
  *   uph_refine_upload       <- receding-horizon refinement: the rest of each resident trajectory as the initial guess of a new problem from its
  *                              state at a switch time, no search
+ *   uph_check_batch         <- ALMTrajOpt::getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229) + SE2Trajectory::getNonHolError (se2traj.hpp:551-561) + UnevenMap::isOccupancy
+ *                              (uneven_map.h:471-488) per sample, over time windows of chosen resident trajectories, held against the optimiser's
+ *                              limits (alm_traj_opt.h:29-53) instead of printed
+ *   uph_check_window        <- the part of their `for (t = 0; t < total; t += dt)` loop a time window holds
+ *   uph_check_limits        <- the limits among ALMTrajOpt's parameter members  alm_traj_opt.h:33-38
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -540,6 +545,33 @@ int uph_rollout_batch(uph_ctx* c, double dt, int32_t with_end, int32_t channels,
 /* the same rows written straight into device memory of the context's device (e.g. a torch tensor's data_ptr()), on the context's stream;
  * returns after the stream has synchronised */
 int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, void* out_dev);
+
+/* ---- check resident trajectories against the map as it is now: query q reduces the samples of trajectory traj[q] of c's resident batch whose t lies in
+ * [t_from[q], t_to[q]] (t_from <= t and t <= t_to, literally; t_to == NULL: to the end).  The samples are exactly the rows uph_rollout_batch(dt, with_end)
+ * has for that trajectory -- same time table, same evaluation, the end row at t = total included when with_end is set.  Per sample a mask: bit k
+ * (k = 0..6, the UPH_ROLLOUT_TERRAIN columns vx, ax, ay, cur, att, sigma, non-holonomic error) is set when !(fabs(v) <= lim7[k]) for k < 4 and when
+ * !(v <= lim7[k]) for k >= 4, so a NaN term violates; bit UPH_CHECK_OCC_BIT is set when the map's occupancy at the row's (x, y, yaw) -- what
+ * uph_frontend_query returns as occ -- is not 0 (-1, outside the map, counts as occupied).  Outputs per query, any of them may be NULL:
+ *   first_t [n]      t of the first sample with a non-zero mask (NaN: none), first_mask [n] its mask (0: none)
+ *   counts  [n][3]   samples in the window, samples with a non-zero mask, samples with the occupancy bit
+ *   worst   [n][7]   per term the largest fabs(v) (k < 4) or v (k >= 4) over the window; a non-finite term counts as +inf; -inf for an empty window
+ *   worst_t [n][7]   t of the sample that set worst[k], the earliest one among equals (NaN for an empty window)
+ * lim7 == NULL: uph_check_limits(c).  The same trajectory may be named by several queries.  Deterministic: no floating-point atomics, a selection whose
+ * result does not depend on the order of the reduction.  Blocking, on the context's stream.  Refused with UPH_ERR_INVALID, outputs untouched: bad
+ * arguments, dt <= 0 or not finite, no resident trajectory (uph_rollout_batch's rule), a traj[q] out of range or naming an UPH_RET_UNSUPPORTED slot, a
+ * non-finite t_from[q], a NaN t_to[q] (+-inf is allowed), an asynchronous solve pending on c.  UPH_ERR_LIMIT as uph_rollout_plan. */
+#define UPH_CHECK_OCC_BIT 7
+/* host only: lim7 = { max_vel, max_acc_lon, max_acc_lat, max_kap, -min_cxi, max_sig, +inf } of the context's uph_opt_params */
+int uph_check_limits(const uph_ctx* c, double* lim7);
+/* host only, no device needed: the samples of a trajectory of duration `total` that the window [t_from, t_to] holds -- table samples [q_lo, q_hi) of the
+ * running sum t += dt, and end_row != 0 when with_end is set and the end row (t = total) lies in the window.  UPH_ERR_INVALID for dt <= 0 / not finite,
+ * a NaN bound or a null pointer; UPH_ERR_LIMIT as uph_rollout_sizes. */
+int uph_check_window(double dt, int32_t with_end, double total, double t_from, double t_to, int32_t* q_lo, int32_t* q_hi, int32_t* end_row);
+int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to /* NULL: to the end */, double dt, int32_t with_end,
+                    const double* lim7 /* NULL: defaults */, double* first_t /* [n], NaN: none */, int32_t* first_mask /* [n] */,
+                    int32_t* counts /* [n][3]: samples, violating, occupied */, double* worst /* [n][7] */, double* worst_t /* [n][7] */);
+/* milliseconds of uph_check_kernel in the last uph_check_batch of c (events on the context's stream) */
+int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 #ifdef __cplusplus
 }

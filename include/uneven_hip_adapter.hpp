@@ -17,6 +17,7 @@
 //   planSE2TrajBatch               PlanManager::rcvWpsCallBack plan_manager.cpp:43-134 for many goals in one call, every stage on the device (uph_plan_upload)
 //   replanSE2TrajBatch             the same from states on the last batch's trajectories: re-planning a vehicle in motion (uph_replan_upload)
 //   refineSE2TrajBatch             the rest of the last batch's trajectories re-optimised from states at switch times, no search (uph_refine_upload)
+//   checkSE2TrajBatch              time windows of the last batch's trajectories held against limits on the map as it is now (uph_check_batch)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -510,6 +511,37 @@ public:
         }
         last_report_.clear(); last_multi_ = false; last_ctxs_.assign(1, ctx_); last_B_ = 0;
         return finishGoalPlan(rc, B, out, nxy, nyw, "uph_refine_upload", "refineSE2TrajBatch");
+    }
+    // the map changed: which trajectories of this object's last batch does it invalidate, from when on and by which constraint (uph_check_batch).
+    // Query q reduces the samples (every dt, + the end point with with_end) of trajectory traj[q] with t in [t_from[q], t_to[q]] (t_to empty: to the
+    // end) on the map as it is now against lim7 (nullptr: the optimiser's own limits, checkLimits()).  Feeds refineSE2TrajBatch / replanSE2TrajBatch:
+    // refine the violators from a little before first_t, check again, re-plan what is still bad.
+    struct TrajCheck {
+        std::vector<double> first_t;        // [n] t of the first violating sample (NaN: none)
+        std::vector<int32_t> first_mask;    // [n] bit k: term k (vx, ax, ay, cur, att, sigma, non-holonomic error), bit UPH_CHECK_OCC_BIT: occupied
+        std::vector<int32_t> counts;        // [n][3] samples, violating, occupied
+        std::vector<double> worst, worst_t; // [n][7]
+        bool violates(size_t q) const { return first_mask[q] != 0; }
+    };
+    std::vector<double> checkLimits() const {
+        std::vector<double> lim(7);
+        if (uph_check_limits(ctx_, lim.data()) != UPH_OK) throw std::runtime_error(std::string("uph_check_limits: ") + uph_last_error());
+        return lim;
+    }
+    TrajCheck checkSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t_from, const std::vector<double>& t_to = std::vector<double>(),
+                                double dt = 0.01, bool with_end = true, const double* lim7 = nullptr) {
+        if (t_from.size() != traj.size() || (!t_to.empty() && t_to.size() != traj.size())) throw std::runtime_error("checkSE2TrajBatch: traj, t_from and t_to differ in number");
+        if (last_multi_) throw std::runtime_error("checkSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajCheck out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        out.first_t.assign((size_t)n, 0.0); out.first_mask.assign((size_t)n, 0); out.counts.assign((size_t)3 * n, 0);
+        out.worst.assign((size_t)7 * n, 0.0); out.worst_t.assign((size_t)7 * n, 0.0);
+        if (uph_check_batch(ctx_, n, tr.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, lim7, out.first_t.data(),
+                            out.first_mask.data(), out.counts.data(), out.worst.data(), out.worst_t.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_check_batch: ") + uph_last_error());
+        return out;
     }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)
 

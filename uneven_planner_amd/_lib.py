@@ -159,6 +159,10 @@ SYMBOLS = {
                                     C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_traj_states": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP]),
     "uph_refine_upload": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), DP, DP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_check_limits": (C.c_int, [_VP, DP]),
+    "uph_check_window": (C.c_int, [C.c_double, _I32, C.c_double, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_check_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32), C.POINTER(_I32), DP, DP]),
+    "uph_check_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None
@@ -172,6 +176,7 @@ PLAN_STAGE_XY, PLAN_STAGE_YAW = UPH_MAX_PIECE_XY - 1, UPH_MAX_PIECE_YAW - 1
 UPH_ERR_INVALID, UPH_ERR_LIMIT = -1, -4
 UPH_KINO_OK = 0
 UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
+UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
 TRAJ_STATE_COLS = 10       # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
 
 

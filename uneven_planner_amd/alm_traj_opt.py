@@ -192,6 +192,48 @@ def split_rollout(offsets, rows):
     return [rows[int(o[i]):int(o[i + 1])] for i in range(len(o) - 1)]
 
 
+# uph_check_batch (include/uneven_hip.h): the seven terms of a mask are the ROLLOUT_TERRAIN columns, bit CHECK_OCC_BIT is the occupancy
+CHECK_OCC_BIT = _lib.UPH_CHECK_OCC_BIT
+CHECK_TERMS = ROLLOUT_COLUMNS[ROLLOUT_TERRAIN]
+
+
+def check_window(dt, with_end, total, t_from, t_to):
+    """uph_check_window (host only): (q_lo, q_hi, end_row) -- the samples q_lo <= q < q_hi of the running sum t += dt, and whether the end row at
+    t = total, that the window [t_from, t_to] holds of a trajectory of duration total"""
+    v = [C.c_int32(0) for _ in range(3)]
+    _lib.check(_lib.load().uph_check_window(float(dt), int(bool(with_end)), float(total), float(t_from), float(t_to), *[C.byref(x) for x in v]),
+               "uph_check_window")
+    return v[0].value, v[1].value, bool(v[2].value)
+
+
+def check_rows(t, terms, occ, lim, t_from=-np.inf, t_to=np.inf):
+    """Host mirror of one uph_check_batch query, written from the rule and not from the kernel: reduces one trajectory's rollout rows -- t (n,), terms
+    (n, 7) the ROLLOUT_TERRAIN columns, occ (n,) uph_frontend_query's occ at the rows' (x, y, yaw) -- whose t lies in [t_from, t_to].
+    Term k violates when not (|v| <= lim[k]) for k < 4 and when not (v <= lim[k]) for k >= 4 (a NaN violates); occ != 0 sets bit CHECK_OCC_BIT.
+    Returns the dict of ALMTrajOpt.check for that query: first_t, first_mask, counts (3,), worst (7,), worst_t (7,)."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    terms = np.asarray(terms, dtype=np.float64).reshape(-1, 7)
+    occ = np.asarray(occ).reshape(-1)
+    lim = np.asarray(lim, dtype=np.float64).reshape(7)
+    with np.errstate(invalid="ignore"):
+        sel = (t_from <= t) & (t <= t_to)
+    t, v, occ = t[sel], terms[sel], occ[sel]
+    m = np.concatenate([np.abs(v[:, :4]), v[:, 4:]], axis=1)
+    with np.errstate(invalid="ignore"):
+        viol = ~(m <= lim[None, :])                                 # a NaN compares false: it violates
+    occupied = occ != 0
+    mask = (viol.astype(np.int64) << np.arange(7)[None, :]).sum(axis=1) + (occupied.astype(np.int64) << CHECK_OCC_BIT)
+    counts = np.array([t.shape[0], np.count_nonzero(mask), np.count_nonzero(occupied)], dtype=np.int32)
+    bad = np.nonzero(mask)[0]
+    first_t, first_mask = (t[bad[0]], int(mask[bad[0]])) if bad.size else (np.nan, 0)
+    worst, worst_t = np.full(7, -np.inf), np.full(7, np.nan)
+    if t.shape[0]:
+        key = np.where(np.isfinite(v), m, np.inf)
+        at = np.argmax(key, axis=0)                                 # the first occurrence of the maximum: a tie stays with the earlier sample
+        worst, worst_t = key[at, np.arange(7)], t[at]
+    return dict(first_t=first_t, first_mask=first_mask, counts=counts, worst=worst, worst_t=worst_t)
+
+
 class ALMTrajOpt:
     def __init__(self, uneven_map=None, params=None):
         self.L = _lib.load()
@@ -637,6 +679,40 @@ class ALMTrajOpt:
         ncol = len(rollout_columns(int(channels)))
         rows = np.concatenate([parts[i] for i in range(B)]) if B else np.zeros((0, ncol))
         return offs, rows.reshape(-1, ncol)
+
+    # ---- resident trajectories against the map as it is now (uph_check_batch) -----------------------------------------------------------------------
+    def check_limits(self):
+        """the default limits of check(): max_vel, max_acc_lon, max_acc_lat, max_kap, -min_cxi, max_sig of the context's parameters and +inf for the
+        non-holonomic error (uph_check_limits)"""
+        lim = np.zeros(7)
+        _lib.check(self.L.uph_check_limits(self.h, _dp(lim)), "uph_check_limits")
+        return lim
+
+    def check(self, traj, t_from=0.0, t_to=None, dt=0.01, with_end=True, limits=None):
+        """Reduce, on the device and on the bound map as it is now, the rollout(dt, with_end) samples of resident trajectory traj[q] with t in
+        [t_from[q], t_to[q]] (scalars are broadcast; t_to = None: to the end) against `limits` (7 values, None: check_limits()).  Returns a dict of
+        arrays over the queries: first_t (NaN: no violation), first_mask (bit k: term k of CHECK_TERMS, bit CHECK_OCC_BIT: occupied or outside the
+        map), counts (n, 3: samples, violating, occupied), worst and worst_t (n, 7); see check_rows for the rule."""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        n = tr.shape[0]
+        if n == 0:
+            raise _lib.UnevenHipError("check: no query")
+        tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, dtype=np.float64), (n,)))
+        tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, dtype=np.float64), (n,)))
+        lim = None if limits is None else np.ascontiguousarray(limits, dtype=np.float64).reshape(7)
+        out = dict(first_t=np.full(n, np.nan), first_mask=np.zeros(n, dtype=np.int32), counts=np.zeros((n, 3), dtype=np.int32),
+                   worst=np.full((n, 7), -np.inf), worst_t=np.full((n, 7), np.nan))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_check_batch(self.h, n, ip(tr), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                          None if lim is None else _dp(lim), _dp(out["first_t"]), ip(out["first_mask"]), ip(out["counts"]),
+                                          _dp(out["worst"]), _dp(out["worst_t"])), "uph_check_batch")
+        return out
+
+    def check_kernel_ms(self):
+        """milliseconds of uph_check_kernel in the last check() (events on the context's stream)"""
+        ms = C.c_double(0)
+        _lib.check(self.L.uph_check_kernel_ms(self.h, C.byref(ms)), "uph_check_kernel_ms")
+        return ms.value
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------
     def x0_packed(self, probs):

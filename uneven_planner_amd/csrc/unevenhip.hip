@@ -753,6 +753,179 @@ __global__ __launch_bounds__(ROLL_NT) void uph_rollout_kernel(GridDev grid, Roll
     for (int i = (int)threadIdx.x; i < nq * ncol; i += ROLL_NT) o[i] = stage[i];
 }
 
+// ---- check (uph_check_batch): (trajectory, time window) pairs of the resident batch reduced against limits on the map as it is now.  One 256-lane
+// workgroup per query; lane l takes samples l, l + 256, ... of the window, each sample the rollout's (same time table, trajectorySample<true>, same
+// grid descriptor), and keeps in registers: the first sample with a violation and its mask, per term the worst value and its sample, two counters.
+// The reduction is a selection under a total order (value, then the smaller sample index), so the order in which lanes and waves are combined
+// cannot change a bit: DPP row rotations inside a wave, LDS across the four waves, lane 0 writes.  Query-uniform data -- query record, descriptor,
+// T_xy / T_yaw, grid descriptor, limits -- is indexed by blockIdx only (scalar loads).
+struct CheckQuery {             // one query of a check launch (formed on the host, in launch order)
+    int32_t b, out;             // resident trajectory; row of the output (the caller's query index)
+    int32_t q_lo, n_tab;        // the window's first sample in the time table and the number of samples taken from it
+    int32_t end_row, pad;       // != 0: the end point (t = total) closes the window
+    double total;               // getTotalDuration: t of the end point
+    double shift[2];            // as RolloutTraj
+};
+struct CheckOut {               // one row per query
+    double first_t;             // NaN: no sample violates
+    int32_t first_mask, counts[3];      // samples, violating, occupied
+    double worst[7], worst_t[7];
+};
+struct CheckArgs {
+    const TrajDesc* desc;
+    const TrajState* state;
+    const double* cxy;
+    const double* cyaw;
+    const GridDev* grid_mem;    // as RolloutArgs
+    const CheckQuery* qs;
+    const double* tt;           // the rollout's time table
+    const char* occ;            // the map's occupancy layer [nx_hold][ny][nyaw] (uph_frontend_query's)
+    CheckOut* out;
+    double lim[7];
+};
+constexpr int CHECK_NT = 256, CHECK_NW = CHECK_NT / 64;
+constexpr unsigned long long CHECK_NONE = ~0ull;
+
+template <int CTRL>
+__device__ __forceinline__ int dppMovI(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false); }
+// (value, sample) pairs: the larger value wins, equal values go to the smaller sample (no NaN reaches here: a non-finite term is +inf)
+__device__ __forceinline__ void checkTake(double& v, int& i, double ov, int oi) {
+    const bool o = ov > v || (ov == v && oi < i);
+    v = o ? ov : v; i = o ? oi : i;
+}
+template <int CTRL>
+__device__ __forceinline__ void checkStepWorst(double& v, int& i) { const double ov = dppMov<CTRL>(v); const int oi = dppMovI<CTRL>(i); checkTake(v, i, ov, oi); }
+template <int CTRL>
+__device__ __forceinline__ void checkStepFirst(unsigned long long& k) {
+    const unsigned lo = (unsigned)dppMovI<CTRL>((int)(unsigned)k), hi = (unsigned)dppMovI<CTRL>((int)(unsigned)(k >> 32));
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    k = o < k ? o : k;
+}
+template <int CTRL>
+__device__ __forceinline__ void checkStepSum(int& a, int& b) { a += dppMovI<CTRL>(a); b += dppMovI<CTRL>(b); }
+
+// build knobs of the measurements in DESIGN.md 7i (tools/build_variants.sh): UPH_CHECK_WPE = waves per SIMD the kernel is compiled for (2: 200 VGPRs, no
+// scratch; 3 caps it at 168 and spills), UPH_CHECK_LDS_STATE keeps the per-lane worst values in LDS instead of registers.  Neither variant was faster.
+#ifndef UPH_CHECK_WPE
+#define UPH_CHECK_WPE 2
+#endif
+__global__ __launch_bounds__(CHECK_NT, UPH_CHECK_WPE) void uph_check_kernel(GridDev grid, CheckArgs a) {
+    __shared__ double s_wv[CHECK_NW][7];
+    __shared__ int s_wi[CHECK_NW][7];
+    __shared__ unsigned long long s_first[CHECK_NW];
+    __shared__ int s_cnt[CHECK_NW][2];
+    const CheckQuery cq = a.qs[blockIdx.x];
+    const int b = cq.b;
+    const TrajDesc& td = a.desc[b];
+    const double Tx = a.state[b].T_xy, Ty = a.state[b].T_yaw;
+    const bool framed = a.grid_mem != nullptr;
+    const GridDev g = framed ? a.grid_mem[b] : grid;
+    const double sx = framed ? cq.shift[0] : 0.0, sy = framed ? cq.shift[1] : 0.0;
+    const double* cx = a.cxy + td.off_cxy;
+    const double* cy = a.cyaw + td.off_cyaw;
+    const int n = cq.n_tab + (cq.end_row ? 1 : 0);
+    // first: (sample << 8) | mask of the first violating sample, so that one unsigned minimum carries both
+    unsigned long long first = CHECK_NONE;
+    double wv[7];
+    int wi[7];
+#ifdef UPH_CHECK_LDS_STATE
+    __shared__ double l_wv[7][CHECK_NT];
+    __shared__ int l_wi[7][CHECK_NT];
+#pragma unroll
+    for (int k = 0; k < 7; k++) { l_wv[k][threadIdx.x] = -__builtin_huge_val(); l_wi[k][threadIdx.x] = 0x7fffffff; }
+#else
+#pragma unroll
+    for (int k = 0; k < 7; k++) { wv[k] = -__builtin_huge_val(); wi[k] = 0x7fffffff; }
+#endif
+    int nviol = 0, nocc = 0;
+    for (int j = (int)threadIdx.x; j < n; j += CHECK_NT) {
+        const double t = j < cq.n_tab ? a.tt[cq.q_lo + j] : cq.total;
+        TrajSample s;
+        double tm[7];
+        trajectorySample<true>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
+        // the sample's values leave trajectorySample as they leave it in the rollout (stored, there): nothing below may be contracted into its arithmetic
+        double px = s.p[0], py = s.p[1], w = s.yawn;
+        asm volatile("" : "+v"(px), "+v"(py), "+v"(w));
+#pragma unroll
+        for (int k = 0; k < 7; k++) asm volatile("" : "+v"(tm[k]));
+        // isOccupancy at the STATE row's (x, y, yaw), map coordinates, on the map's own grid: the statements of uph_frontend_kernel (map_build.hip)
+        const double x = framed ? px + sx : px, y = framed ? py + sy : py;
+        const int ix = (int)floor((x - grid.origin[0]) * grid.xy_inv), iy = (int)floor((y - grid.origin[1]) * grid.xy_inv), iw = (int)floor((w - grid.origin[2]) * grid.yaw_inv);
+        const int ixh = ix - grid.x_off;
+        const bool in = ix >= 0 && iy >= 0 && iw >= 0 && ix <= grid.nx - 1 && iy <= grid.ny - 1 && iw <= grid.nyaw - 1 && ixh >= 0 && ixh <= grid.nx_hold - 1;
+        const int occ = in ? (int)a.occ[((size_t)ixh * grid.ny + iy) * grid.nyaw + iw] : -1;
+        int mask = occ != 0 ? 1 << UPH_CHECK_OCC_BIT : 0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const double v = tm[k], m = k < 4 ? fabs(v) : v;
+            if (!(m <= a.lim[k])) mask |= 1 << k;
+            const double key = fabs(v) < __builtin_huge_val() ? m : __builtin_huge_val();      // non-finite (NaN included): +inf
+#ifdef UPH_CHECK_LDS_STATE
+            if (key > l_wv[k][threadIdx.x]) { l_wv[k][threadIdx.x] = key; l_wi[k][threadIdx.x] = j; }
+#else
+            if (key > wv[k]) { wv[k] = key; wi[k] = j; }
+#endif
+        }
+        if (mask != 0) {
+            nviol++;
+            if (first == CHECK_NONE) first = ((unsigned long long)(unsigned)j << 8) | (unsigned)mask;
+        }
+        nocc += occ != 0 ? 1 : 0;
+    }
+#ifdef UPH_CHECK_LDS_STATE
+#pragma unroll
+    for (int k = 0; k < 7; k++) { wv[k] = l_wv[k][threadIdx.x]; wi[k] = l_wi[k][threadIdx.x]; }
+#endif
+    // inside each row of 16 lanes, then the four rows of the wave
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        checkStepWorst<0x128>(wv[k], wi[k]); checkStepWorst<0x124>(wv[k], wi[k]); checkStepWorst<0x122>(wv[k], wi[k]); checkStepWorst<0x121>(wv[k], wi[k]);
+    }
+    checkStepFirst<0x128>(first); checkStepFirst<0x124>(first); checkStepFirst<0x122>(first); checkStepFirst<0x121>(first);
+    checkStepSum<0x128>(nviol, nocc); checkStepSum<0x124>(nviol, nocc); checkStepSum<0x122>(nviol, nocc); checkStepSum<0x121>(nviol, nocc);
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        double v = readLane(wv[k], 0);
+        int i = __builtin_amdgcn_readlane(wi[k], 0);
+#pragma unroll
+        for (int r = 16; r < 64; r += 16) checkTake(v, i, readLane(wv[k], r), __builtin_amdgcn_readlane(wi[k], r));
+        if (lane == 0) { s_wv[wave][k] = v; s_wi[wave][k] = i; }
+    }
+    {
+        unsigned long long f = CHECK_NONE;
+        int cv = 0, co = 0;
+#pragma unroll
+        for (int r = 0; r < 64; r += 16) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)first, r), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(first >> 32), r);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            f = o < f ? o : f;
+            cv += __builtin_amdgcn_readlane(nviol, r); co += __builtin_amdgcn_readlane(nocc, r);
+        }
+        if (lane == 0) { s_first[wave] = f; s_cnt[wave][0] = cv; s_cnt[wave][1] = co; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        CheckOut o;
+        unsigned long long f = s_first[0];
+        int cv = s_cnt[0][0], co = s_cnt[0][1];
+        for (int wq = 1; wq < CHECK_NW; wq++) { f = s_first[wq] < f ? s_first[wq] : f; cv += s_cnt[wq][0]; co += s_cnt[wq][1]; }
+        const double nan = __builtin_nan("");
+        const int fj = (int)(f >> 8);
+        o.first_t = f == CHECK_NONE ? nan : (fj < cq.n_tab ? a.tt[cq.q_lo + fj] : cq.total);
+        o.first_mask = f == CHECK_NONE ? 0 : (int)(f & 0xff);
+        o.counts[0] = n; o.counts[1] = cv; o.counts[2] = co;
+        for (int k = 0; k < 7; k++) {
+            double v = s_wv[0][k];
+            int i = s_wi[0][k];
+            for (int wq = 1; wq < CHECK_NW; wq++) checkTake(v, i, s_wv[wq][k], s_wi[wq][k]);
+            o.worst[k] = v;
+            o.worst_t[k] = i == 0x7fffffff ? nan : (i < cq.n_tab ? a.tt[cq.q_lo + i] : cq.total);
+        }
+        a.out[cq.out] = o;
+    }
+}
+
 // ---- goals -> resident batch (uph_plan_upload): PlanManager's initial-guess stage (plan_manager.cpp:62-132; with mp.test_mode the test node's,
 // alm_traj_opt.cpp:73-144) over the paths the front-end search left in HBM, then x0 scattered from the staging into the resident batch.
 // Staging (owned by the context, indexed by GOAL): way-points [goal][PLAN_SX][2] and [goal][PLAN_SY], and one PlanHead per goal -- the only
@@ -1041,6 +1214,8 @@ struct uph_ctx {
     std::vector<double> end_bnd;           // [B][9] each problem's whole end boundary as uploaded: end_xy {P, V, A} (map coordinates), end_yaw (uph_refine_upload)
     DevBuf d_sw_q, d_sw_out;               // uph_replan_upload / uph_traj_states / uph_refine_upload: state queries and states (allocated at the first call)
     DevBuf d_refine_rec;                   // uph_refine_upload: staging records
+    DevBuf d_chk_q, d_chk_out;             // uph_check_batch: query records and result rows (allocated at the first call)
+    double last_check_ms = 0.0;            // uph_check_kernel of the last uph_check_batch (events on the context's stream)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -1303,7 +1478,8 @@ void uph_ctx_destroy(uph_ctx* c) {
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
-                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec};
+                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec, &c->d_chk_q,
+                      &c->d_chk_out};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -2610,6 +2786,105 @@ int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t chann
     const hipError_t e = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
     if (r != UPH_OK) return r;
     if (e != hipSuccess) { setError(std::string("uph_rollout_batch_dev: ") + hipGetErrorString(e)); return UPH_ERR_HIP; }
+    return UPH_OK;
+}
+
+// ---- check (include/uneven_hip.h uph_check_*) ------------------------------------------------------------------------------------------------
+// the window [t_from, t_to] in the first cnt entries of the time table (strictly increasing): samples [q_lo, q_hi) have t_from <= t_q and t_q <= t_to
+static void checkWindow(const std::vector<double>& tab, int64_t cnt, int with_end, double total, double t_from, double t_to, int32_t& q_lo, int32_t& q_hi,
+                        int32_t& end_row) {
+    const auto b = tab.begin(), e = tab.begin() + cnt;
+    const int64_t lo = std::lower_bound(b, e, t_from) - b;            // the first q with t_from <= t_q
+    const int64_t hi = std::upper_bound(b, e, t_to) - b;              // the first q with t_to < t_q
+    q_lo = (int32_t)lo; q_hi = (int32_t)(hi < lo ? lo : hi);
+    end_row = (with_end && t_from <= total && total <= t_to) ? 1 : 0;
+}
+
+int uph_check_limits(const uph_ctx* c, double* lim7) {
+    if (!c || !lim7) { setError("uph_check_limits: bad arguments"); return UPH_ERR_INVALID; }
+    const OptParams& P = c->P;
+    const double l[7] = {P.max_vel, P.max_acc_lon, P.max_acc_lat, P.max_kap, -P.min_cxi, P.max_sig, __builtin_huge_val()};
+    std::memcpy(lim7, l, sizeof(l));
+    return UPH_OK;
+}
+
+int uph_check_window(double dt, int32_t with_end, double total, double t_from, double t_to, int32_t* q_lo, int32_t* q_hi, int32_t* end_row) {
+    if (!q_lo || !q_hi || !end_row) { setError("uph_check_window: bad arguments"); return UPH_ERR_INVALID; }
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_check_window: dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (std::isnan(t_from) || std::isnan(t_to)) { setError("uph_check_window: a window bound is NaN"); return UPH_ERR_INVALID; }
+    std::vector<double> tab;
+    const int r = rolloutTimes(dt, total, tab);
+    if (r != UPH_OK) return r;
+    const int64_t cnt = std::lower_bound(tab.begin(), tab.end(), total) - tab.begin();       // (a NaN total: no samples, as in the loop)
+    if (cnt >= (int64_t)tab.size()) { setError("uph_check_window: the trajectory needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt"); return UPH_ERR_LIMIT; }
+    checkWindow(tab, cnt, with_end, total, t_from, t_to, *q_lo, *q_hi, *end_row);
+    return UPH_OK;
+}
+
+int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* lim7,
+                    double* first_t, int32_t* first_mask, int32_t* counts, double* worst, double* worst_t) {
+    if (!c || n <= 0 || !traj || !t_from) { setError("uph_check_batch: bad arguments"); return UPH_ERR_INVALID; }
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_check_batch: dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_check_batch: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t_from, "uph_check_batch");
+    if (r != UPH_OK) return r;
+    if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError("uph_check_batch: query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
+    RolloutSizes rs;
+    r = rolloutPlanCtx(c, dt, with_end, rs, "uph_check_batch");
+    if (r != UPH_OK) return r;
+    GridDev grid;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    std::vector<CheckQuery> qs((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t b = traj[q];
+        CheckQuery& k = qs[(size_t)q];
+        int32_t q_hi = 0;
+        k.b = b; k.out = q; k.pad = 0;
+        checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
+        k.n_tab = q_hi - k.q_lo;
+        k.total = rs.total[(size_t)b];
+        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    }
+    // the longest windows first (as the uploads order the solves by predicted cost): the tail of the launch is made of short workgroups
+    std::stable_sort(qs.begin(), qs.end(), [](const CheckQuery& x, const CheckQuery& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
+    if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_chk_q.ensure(sizeof(CheckQuery) * (size_t)n) || c->d_chk_out.ensure(sizeof(CheckOut) * (size_t)n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_chk_q.p, qs.data(), sizeof(CheckQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    CheckArgs a;
+    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
+    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
+    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
+    a.qs = c->d_chk_q.as<CheckQuery>(); a.tt = c->d_roll_tt.as<double>(); a.out = c->d_chk_out.as<CheckOut>();
+    const char* occ_r2 = nullptr;
+    uphMapOcc(c->map, &a.occ, &occ_r2);
+    if (lim7) std::memcpy(a.lim, lim7, sizeof(a.lim));
+    else uph_check_limits(c, a.lim);
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(uph_check_kernel, dim3((unsigned)n), dim3(CHECK_NT), 0, c->stream, grid, a);
+    const hipError_t le = hipGetLastError();
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    std::vector<CheckOut> out((size_t)n);
+    const hipError_t ce = hipMemcpyAsync(out.data(), c->d_chk_out.p, sizeof(CheckOut) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued, and the host copies above outlive it)
+    HIPCHK(le); HIPCHK(ce); HIPCHK(se);
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_check_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const CheckOut& o = out[(size_t)q];
+        if (first_t) first_t[q] = o.first_t;
+        if (first_mask) first_mask[q] = o.first_mask;
+        if (counts) for (int k = 0; k < 3; k++) counts[3 * (size_t)q + k] = o.counts[k];
+        if (worst) for (int k = 0; k < 7; k++) worst[7 * (size_t)q + k] = o.worst[k];
+        if (worst_t) for (int k = 0; k < 7; k++) worst_t[7 * (size_t)q + k] = o.worst_t[k];
+    }
+    return UPH_OK;
+}
+
+int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_check_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_check_ms;
     return UPH_OK;
 }
 
