@@ -1,0 +1,322 @@
+"""Sweep over every position piece count and yaw ratio for the solve / scaling / penalty kernels (TEST INFRASTRUCTURE).
+
+The workgroup program (uneven_planner_amd/csrc/solver_program.hpp) branches on the pair (position pieces Nxy, lanes per trajectory CH):
+aligned or plain sample chunks, one to four MFMA scatter tiles with a partly empty last one, pieces straddling two chunks, the L-BFGS
+register classes at n = 64, 128, 256.  This module generates one problem for EVERY Nxy in 1..128 at the yaw ratios 1, 1.7, 2 and 3 (a slice
+of one winding curve), deterministic duals / scales for them, and the oracle's answers -- computed once per process and shared by
+tests/test_pieces_cpu.py (the emulator) and tests/test_gpu_pieces.py (the device through the C-ABI), like tests/forced_cases.py is shared
+by the forced-state tests.  No fixtures here: the callers hand in the `oracle` module and its grid.
+"""
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+NXY_ALL = list(range(1, 129))                   # 1 .. UPH_MAX_PIECE_XY
+RATIOS = (1.0, 1.7, 2.0, 3.0)                   # yaw pieces per position piece: 1:1, ragged, PlanManager's 2, the test node's 3
+MAX_PIECE_YAW = 256                             # UPH_MAX_PIECE_YAW
+# capped solves: every small count, the neighbours of the chunk / tile / knot-table (THOMAS_J = 26) boundaries, and -- at ratio 2, n = 4 Nxy - 3 --
+# n crossing 64 (Nxy 16 | 17), 128 (32 | 33), 256 (64 | 65) and the largest n = 509
+SOLVE_NXY = [1, 2, 3, 4, 8, 9, 16, 17, 18, 26, 27, 28, 32, 33, 43, 44, 64, 65, 86, 87, 127, 128]
+SOLVE_PARAMS = dict(inner_max_iter=12.0, max_iter=1.0)
+RHO, SCALE_FX = 3.0, 0.37                       # of the single evaluation and the penalty call
+PIECE_LEN, PATH_STEP = 0.3, 0.06
+MIN_CASES = 440
+
+_LOCK = threading.Lock()
+_CACHE = {}
+MEASURED = {}                                   # (test, variant) -> {quantity: (worst error, where)}: filled by record(), written by write_report()
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.abs(a - b).max() / max(1e-300, np.abs(a).max()))
+
+
+def rel1(ref, got):
+    return float(abs(got - ref) / max(1e-300, abs(ref)))
+
+
+# ---- generator ----------------------------------------------------------------------------------------------------------------------------
+def _curve():
+    """y = -0.5 + 3.2 sin(3.3 x), x in [-4.6, 4.6], as a fine polyline with its running arc length (61.98 m in all)"""
+    if "curve" not in _CACHE:
+        x = np.linspace(-4.6, 4.6, 40001)
+        y = -0.5 + 3.2 * np.sin(3.3 * x)
+        arc = np.concatenate([[0.0], np.cumsum(np.hypot(np.diff(x), np.diff(y)))])
+        _CACHE["curve"] = (x, y, arc)
+    return _CACHE["curve"]
+
+
+def sweep_path(nxy):
+    """the first 0.3 (nxy - 0.5) metres of the curve sampled every 0.06 m like a front-end path; yaw = unwrapped tangent"""
+    x, y, arc = _curve()
+    length = PIECE_LEN * (nxy - 0.5)
+    assert length < arc[-1]
+    sq = np.linspace(0.0, length, max(2, int(round(length / PATH_STEP)) + 1))
+    xs, ys = np.interp(sq, arc, x), np.interp(sq, arc, y)
+    yaw = np.unwrap(np.arctan2(np.gradient(ys), np.gradient(xs)))
+    return np.column_stack([xs, ys, yaw])
+
+
+def sweep_problem(nxy, ratio, int_K=16):
+    """the optimizeSE2Traj arguments of the sweep's problem with `nxy` position pieces and `ratio` yaw pieces per position piece
+    (int_K does not enter the resampling stage; it is accepted so that callers can pass one key everywhere)"""
+    key = ("prob", int(nxy), float(ratio))
+    if key not in _CACHE:
+        from uneven_planner_amd import resample
+        _CACHE[key] = resample.resample_path(sweep_path(nxy), piece_len=PIECE_LEN, yaw_piece_times=float(ratio))
+    return _CACHE[key]
+
+
+def pieces(prob):
+    return prob["inner_xy"].shape[1] + 1, prob["inner_yaw"].shape[0] + 1
+
+
+def sweep_cases(ratios=RATIOS, nxys=NXY_ALL):
+    """the (nxy, ratio) pairs of the sweep.  A pair is left out only when its problem lies outside the compiled limits: Nyaw > 256 (ratio 3
+    above Nxy = 85) or Nyaw < Nxy.  Everything else must be there, and the generator must be exact."""
+    out = []
+    for r in ratios:
+        for nxy in nxys:
+            got, nyaw = pieces(sweep_problem(nxy, r))
+            assert got == nxy, ("the generator missed the requested piece count", nxy, r, got)
+            if nyaw > MAX_PIECE_YAW or nyaw < nxy:
+                continue
+            out.append((nxy, r))
+    return out
+
+
+def all_cases():
+    if "cases" not in _CACHE:
+        c = sweep_cases()
+        assert len(c) >= MIN_CASES, len(c)
+        _CACHE["cases"] = c
+    return _CACHE["cases"]
+
+
+def sweep_state(problem, seed, int_K=16):
+    """deterministic duals and scales for one problem: lambda ~ 0.1 N(0, 1); mu >= 0 with about 30 % exact zeros (both branches of the PHR
+    penalty occur); constraint scales in [0.2, 1]"""
+    rng = np.random.default_rng(int(seed))
+    S = pieces(problem)[0] * (int(int_K) + 1)
+    lam = rng.normal(size=S) * 0.1
+    mu = np.abs(rng.normal(size=6 * S)) * 0.1 * (rng.uniform(size=6 * S) < 0.7)
+    sc = rng.uniform(0.2, 1.0, size=7 * S)
+    return dict(lam=lam, mu=mu, scale_cx=sc, scale_fx=SCALE_FX, rho=RHO)
+
+
+def case_seed(nxy, ratio):
+    return 100000 + 1000 * int(round(10 * ratio)) + int(nxy)
+
+
+def case_state(nxy, ratio, int_K=16):
+    key = ("state", int(nxy), float(ratio), int(int_K))
+    if key not in _CACHE:
+        _CACHE[key] = sweep_state(sweep_problem(nxy, ratio), case_seed(nxy, ratio), int_K)
+    return _CACHE[key]
+
+
+# ---- which code path a (piece count, lane count) pair takes -------------------------------------------------------------------------------
+LANE_COUNTS = (64, 128, 256, 512)
+
+
+def chunk_class(nxy, lanes, K=16):
+    """Restates the constructor of Solver (solver_program.hpp, "Chunks of whole pieces where that costs no extra chunk") and the tile count of
+    DevWG::scatterXY17: returns (aligned, n_chunks, max pieces touched by one chunk, max 16-column MFMA tiles of one chunk).  For COVERAGE
+    assertions only -- never an expected value of a result."""
+    K1 = K + 1
+    S = nxy * K1
+    ppc = lanes // K1
+    aligned = ppc >= 1 and (nxy + ppc - 1) // ppc == (S + lanes - 1) // lanes
+    chs = ppc * K1 if aligned else lanes
+    n_chunks, pmax = 0, 0
+    for s0 in range(0, S, chs):
+        cnt = min(S - s0, chs)
+        pmax = max(pmax, (s0 + cnt - 1) // K1 - s0 // K1 + 1)
+        n_chunks += 1
+    return bool(aligned), n_chunks, pmax, (2 * pmax + 15) // 16
+
+
+def tiles_possible(lanes, K=16):
+    """every tile count a chunk of `lanes` record slots can need: a window of CH consecutive samples touches at most floor((CH - 2) / (K + 1)) + 2
+    pieces of K + 1 samples (5 at 64 lanes, 9 at 128, 16 at 256, 32 at 512), fewer for short trajectories"""
+    pmax = (lanes - 2) // (K + 1) + 2
+    return {(2 * p + 15) // 16 for p in range(1, pmax + 1)}
+
+
+def chunkings_possible(lanes, K=16):
+    """which chunkings exist at all within the compiled limit of 128 pieces.  The plain chunking needs ceil(Nxy / ppc) > ceil(Nxy (K + 1) / CH),
+    ppc = floor(CH / (K + 1)): for K = 16 that happens at 64 lanes (ppc 3 against 3.76 pieces per chunk) and at 128 lanes (7 against 7.53), but
+    never at 256 (15 against 15.06) or 512 lanes (30 against 30.12) below Nxy = 241 -- there every trajectory the library accepts has aligned chunks."""
+    return {chunk_class(n, lanes, K)[0] for n in NXY_ALL}
+
+
+def assert_chunk_coverage(nxys, lanes, K=16):
+    """the piece counts `nxys` reach, at this lane count, every chunking that exists (with a piece straddling two chunks and a partial last chunk
+    where the plain one does), every tile count, and a partly empty last tile"""
+    cls = [chunk_class(n, lanes, K) for n in nxys]
+    assert {c[0] for c in cls} == chunkings_possible(lanes, K), ("chunkings", lanes, K)
+    assert {c[3] for c in cls} == tiles_possible(lanes, K), ("tile counts", lanes, sorted({c[3] for c in cls}), sorted(tiles_possible(lanes, K)))
+    assert any((2 * c[2]) % 16 != 0 for c in cls), ("no partly empty last tile", lanes)
+    if False in chunkings_possible(lanes, K):
+        K1 = K + 1
+        plain = [n for n, c in zip(nxys, cls) if not c[0] and c[1] > 1]
+        # plain chunks start at multiples of the lane count, which is no multiple of K + 1: the second chunk begins inside a piece
+        assert plain and lanes % K1 != 0, ("no multi-chunk plain chunking: no piece straddles two chunks", lanes)
+        assert any((n * K1) % lanes != 0 for n in plain), ("no partial last chunk", lanes)
+
+
+# ---- the oracle's answers, once per process -----------------------------------------------------------------------------------------------
+def _threads():
+    return max(1, min(8, os.cpu_count() or 1))
+
+
+def _fill(kind, tag, keys, make):
+    """compute the missing entries (kind, tag, key) of the cache with make(key) on a few host threads (the oracle's C entry points release the
+    GIL; every evaluation has its own OracleALM, the grid is only read); entries are never recomputed and never modified afterwards"""
+    with _LOCK:
+        todo = [k for k in keys if (kind, tag, k) not in _CACHE]
+        if todo:
+            for k in todo:                       # the resampler's output is cached from one thread only
+                sweep_problem(*k)
+            with ThreadPoolExecutor(max_workers=_threads()) as ex:
+                for k, v in zip(todo, ex.map(make, todo)):
+                    _CACHE[(kind, tag, k)] = v
+    return {k: _CACHE[(kind, tag, k)] for k in keys}
+
+
+def _params(int_K, extra=None):
+    p = dict(extra or {})
+    if int_K != 16:
+        p["int_K"] = float(int_K)
+    return p or None
+
+
+def oracle_evals(O, og, cases, int_K=16, tag="f64"):
+    """one innerCallback evaluation at x0 with case_state() per case, and calConstrainCostGrad alone at the same point: dict case ->
+    dict(x0, f, g, hx, gx, c_xy, c_yaw, T_xy, T_yaw, pen_cost, gdCxy, gdCyaw, gdTxy, gdTyaw, pen_hx, pen_gx).  `tag` names the grid `og` in the cache."""
+    def make(case):
+        p, st = sweep_problem(*case), case_state(case[0], case[1], int_K)
+        a = O.OracleALM(og, _params(int_K))
+        x0 = a.setup(p)
+        a.set_state(lam=st["lam"], mu=st["mu"], scale_cx=st["scale_cx"], scale_fx=st["scale_fx"])
+        a.set_rho(st["rho"])
+        f, g, _ = a.eval(x0)
+        s = a.get_state()
+        cxy, cyaw, txy, tyaw, _ = a.coeffs()
+        cost, gcx, gtx, gcy, gty = a.constrain(x0)
+        s2 = a.get_state()
+        return dict(x0=x0, f=f, g=g, hx=s["hx"], gx=s["gx"], c_xy=cxy, c_yaw=cyaw, T_xy=txy, T_yaw=tyaw, pen_cost=cost, gdCxy=gcx, gdCyaw=gcy,
+                    gdTxy=gtx, gdTyaw=gty, pen_hx=s2["hx"], pen_gx=s2["gx"])
+    return _fill("eval", (tag, int(int_K)), list(cases), make)
+
+
+def oracle_scalings(O, og, cases, tag="f64"):
+    """initScaling at x0 per case: dict case -> dict(scale_fx, scale_cx)"""
+    def make(case):
+        a = O.OracleALM(og)
+        a.init_scaling(a.setup(sweep_problem(*case)))
+        s = a.get_state()
+        return dict(scale_fx=s["scale_fx"], scale_cx=s["scale_cx"])
+    return _fill("scaling", tag, list(cases), make)
+
+
+def oracle_solves(O, og, cases, tag="f64"):
+    """the capped solve (SOLVE_PARAMS: two ALM passes of at most 12 L-BFGS iterations each, rho = 1) per case: dict case -> OracleALM.optimize's dict"""
+    def make(case):
+        return O.OracleALM(og, SOLVE_PARAMS).optimize(sweep_problem(*case))
+    return _fill("solve", tag, list(cases), make)
+
+
+# ---- comparisons shared by the two tiers --------------------------------------------------------------------------------------------------
+def eval_errors(ref, got):
+    """relative errors of one evaluation: got has f, g, hx, gx, c_xy, c_yaw, T_xy, T_yaw (T: absolute, as test_gpu_parity compares it)"""
+    return dict(f=rel1(ref["f"], got["f"]), grad=rel(ref["g"], got["g"]), hx=rel(ref["hx"], got["hx"]), gx=rel(ref["gx"], got["gx"]),
+                c_xy=rel(ref["c_xy"], got["c_xy"]), c_yaw=rel(ref["c_yaw"], got["c_yaw"]),
+                T=max(abs(got["T_xy"] - ref["T_xy"]), abs(got["T_yaw"] - ref["T_yaw"])))
+
+
+def penalty_errors(ref, got, hx, gx):
+    """the quantities of test_gpu_lanes::test_penalty_kernel_alone_for_every_lane_count"""
+    gtx, gty = ref["gdTxy"], ref["gdTyaw"]
+    return dict(cost=rel1(ref["pen_cost"], got["cost"]), gdCxy=rel(ref["gdCxy"], got["gdCxy"]), gdCyaw=rel(ref["gdCyaw"], got["gdCyaw"]),
+                gdTxy_sum=abs(got["gdTxy_sum"] - gtx.sum()) / max(1e-300, np.abs(gtx).sum()),
+                gdTyaw_sum=abs(got["gdTyaw_sum"] - gty.sum()) / max(1e-300, np.abs(gty).sum()),
+                hx=rel(ref["pen_hx"], hx), gx=rel(ref["pen_gx"], gx))
+
+
+def record(test, variant, errs_by_case):
+    """keep the worst error of a (test, variant), overall and per quantity, and where it occurred; errs_by_case: {(nxy, nyaw): {quantity: error}}.
+    Returns the overall worst (error, (where, quantity))."""
+    MEASURED[(test, str(variant))] = _worst_each(errs_by_case)
+    return _worst(errs_by_case)
+
+
+def _line(test, variant, per_q):
+    q, (e, where) = max(per_q.items(), key=lambda kv: kv[1][0])
+    rest = "  ".join("%s %.1e @%s" % (k, v[0], v[1]) for k, v in sorted(per_q.items()))
+    return "%-32s %-11s %-10.3e %s %s\n%46s%s\n" % (test, variant, e, where, q, "", rest)
+
+
+def write_report(path, floor=None, header=""):
+    """the worst error of every (variant, test) recorded in this process -- overall, then per quantity with the (Nxy, Nyaw) it occurred at -- and,
+    when given, the oracle's own floor (oracle against its FMA build) in the same form"""
+    with open(path, "w") as fh:
+        if header:
+            fh.write(header.rstrip("\n") + "\n")
+        fh.write("%-32s %-11s %-10s %s\n" % ("test", "variant", "worst", "at (Nxy, Nyaw[, ratio]), quantity; then every quantity's worst"))
+        for (test, variant), per_q in sorted(MEASURED.items()):
+            fh.write(_line(test, variant, per_q))
+        if floor:
+            fh.write("\noracle against the oracle rebuilt with -march=native -ffp-contract=fast, same problems (its own rounding floor)\n")
+            for test, per_q in sorted(floor.items()):
+                fh.write(_line(test, "oracle/fma", per_q))
+
+
+def fma_floor(O, og, cells):
+    """worst difference between the oracle and its FMA rebuild over the sweep: single evaluation (all cases), initScaling and the capped solves
+    (ratio 2).  Uses the cached plain results."""
+    import sensitivity
+    cases = all_cases()
+    r2 = [c for c in cases if c[1] == 2.0]
+    sol = [(n, 2.0) for n in SOLVE_NXY]
+    plain_e, plain_s, plain_o = oracle_evals(O, og, cases), oracle_scalings(O, og, r2), oracle_solves(O, og, sol)
+    with sensitivity.fma_session() as F:
+        fg = F.OracleGrid()
+        fg.set_cells(cells)
+        fe, fs, fo = oracle_evals(F, fg, cases, tag="fma"), oracle_scalings(F, fg, r2, tag="fma"), oracle_solves(F, fg, sol, tag="fma")
+    out = {}
+    w = {pieces(sweep_problem(*c)): eval_errors(plain_e[c], fe[c]) for c in cases if c[1] == 2.0}
+    out["single_evaluation (ratio 2)"] = _worst_each(w)
+    w = {pieces(sweep_problem(*c)) + (c[1],): eval_errors(plain_e[c], fe[c]) for c in cases}
+    out["single_evaluation (all ratios)"] = _worst_each(w)
+    w = {pieces(sweep_problem(*c)): penalty_errors(plain_e[c], dict(cost=fe[c]["pen_cost"], gdCxy=fe[c]["gdCxy"], gdCyaw=fe[c]["gdCyaw"],
+                                                                      gdTxy_sum=fe[c]["gdTxy"].sum(), gdTyaw_sum=fe[c]["gdTyaw"].sum()),
+                                                   fe[c]["pen_hx"], fe[c]["pen_gx"]) for c in r2}
+    out["penalty (ratio 2)"] = _worst_each(w)
+    w = {pieces(sweep_problem(*c)): dict(scale_fx=rel1(plain_s[c]["scale_fx"], fs[c]["scale_fx"]), scale_cx=rel(plain_s[c]["scale_cx"], fs[c]["scale_cx"])) for c in r2}
+    out["init_scaling (ratio 2)"] = _worst_each(w)
+    w = {pieces(sweep_problem(*c)): dict(x=rel(plain_o[c]["x"], fo[c]["x"]), cost=rel1(plain_o[c]["cost"], fo[c]["cost"]),
+                                          counters=float(any(plain_o[c][k] != fo[c][k] for k in ("ret", "lbfgs_iters", "evals")))) for c in sol}
+    out["capped_solves (ratio 2)"] = _worst_each(w)
+    return out
+
+
+def _worst(errs_by_case):
+    worst = (-1.0, None)
+    for where, errs in errs_by_case.items():
+        for q, e in errs.items():
+            if e > worst[0]:
+                worst = (float(e), (where, q))
+    return worst
+
+
+def _worst_each(errs_by_case):
+    out = {}
+    for where, errs in errs_by_case.items():
+        for q, e in errs.items():
+            if q not in out or e > out[q][0]:
+                out[q] = (float(e), where)
+    return out
