@@ -226,7 +226,8 @@ void emu_terrain(void* h, const double* pos, int n, double* values, double* grad
 }
 
 // mode 0: eval at x (state as given); 1: initScaling at x; 2: full optimize from x; 3: optimize then report;
-// 4: ALM passes from the given x / duals / scales / rho, at most g_cap passes (no reset, no initScaling); 5: resume the L-BFGS loop from the hook state
+// 4: ALM passes from the given x / duals / scales / rho, at most g_cap passes (no reset, no initScaling); 5: resume the L-BFGS loop from the hook state;
+// 6: eval at x (state as given), then report on the trajectory that evaluation stored -- the report without a solve in front of it
 // state arrays in the reference's order: lambda[S], mu[6S] (sample-major), scale_cx[7S] (7 per sample); io = in/out
 // scal[8]: in: rho, scale_fx; out: rho, scale_fx, f, jerk, Txy, Tyaw, (unused)   istat[6]: ret, alm_iters, lbfgs_iters, evals, last_ret, hist_reads
 void emu_run(void* h, int mode, int n_inner_xy, int n_inner_yaw, const double* init_xy, const double* end_xy, const double* init_yaw,
@@ -266,6 +267,7 @@ void emu_run(void* h, int mode, int n_inner_xy, int n_inner_yaw, const double* i
     std::vector<double> rsd(n, 0.0), rs(24, 0.0);
     bd.rs_d = rsd.data(); bd.rs = rs.data();
     if (mode == 0) sol.evalOnly(st, 1);
+    else if (mode == 6) { sol.evalOnly(st, 1); sol.report(st); }
     else if (mode == 1) sol.scalingOnly(st);
     else if (mode == 4) sol.optimize(st, g_cap);
     else if (mode == 5) {

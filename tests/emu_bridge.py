@@ -66,6 +66,10 @@ class Emu:
         self.L.emu_terrain(self.h, _dp(pos), pos.shape[0], _dp(v), _dp(g))
         return v, g
 
+    def eval_report(self, prob, x, **state):
+        """mode 6: one evaluation at x with the given state, then Solver::report on the trajectory it stored; run()'s dict, "report" = the seven values"""
+        return self.run(6, prob, x, **state)
+
     def alm_passes(self, prob, x, cap, **state):
         """mode 4: ALM passes from (x, duals, scales, rho) without reset / initScaling, at most `cap` passes"""
         z = np.zeros(8)

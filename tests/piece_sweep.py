@@ -6,6 +6,10 @@ register classes at n = 64, 128, 256.  This module generates one problem for EVE
 of one winding curve), deterministic duals / scales for them, and the oracle's answers -- computed once per process and shared by
 tests/test_pieces_cpu.py (the emulator) and tests/test_gpu_pieces.py (the device through the C-ABI), like tests/forced_cases.py is shared
 by the forced-state tests.  No fixtures here: the callers hand in the `oracle` module and its grid.
+
+For the kernels that read a finished trajectory back (report, rollout, states at given times, check, refine staging: tests/test_gpu_resident_sweep.py
+and the emulator's report in tests/test_pieces_cpu.py) it also holds the references: the oracle's report on handed-in coefficients
+(oracle_reports) and plain numpy restatements of the trajectory evaluation and of the report's rule (ref_states, ref_terms, report_from_terms).
 """
 import os
 import threading
@@ -230,6 +234,142 @@ def oracle_solves(O, og, cases, tag="f64"):
     return _fill("solve", tag, list(cases), make)
 
 
+def oracle_reports(O, og, coeffs_by_case, tag):
+    """getMaxVxAxAyCurAttSig + the non-holonomic error of the oracle on HANDED-IN trajectories: coeffs_by_case = {case: dict with c_xy, c_yaw,
+    T_xy, T_yaw} (a device's or the emulator's downloaded ones, as test_gpu_parity::test_report_matches_oracle_on_same_trajectory hands them
+    over); dict case -> the seven values.  `tag` names whose coefficients these are (the kernel variant): they differ at rounding level
+    between variants, so every variant has its own cache entries."""
+    def make(case):
+        d = coeffs_by_case[case]
+        a = O.OracleALM(og)
+        a.setup(sweep_problem(*case))
+        a.set_coeffs(d["c_xy"], d["c_yaw"], d["T_xy"], d["T_yaw"])
+        return a.report()
+    return _fill("report", str(tag), list(coeffs_by_case), make)
+
+
+# ---- plain references of the kernels that read a resident trajectory back ------------------------------------------------------------------
+STATE_COLS = ("x", "y", "dx", "dy", "ddx", "ddy", "yaw_norm", "dyaw", "ddyaw", "yaw")      # uph_traj_states' columns
+ROW_OF_STATE = [0, 1, 6, 2, 3, 4, 5, 7]         # ref_states' columns in the order of a rollout row's x y yaw dx dy ddx ddy dyaw
+
+
+def running_sum(step, n):
+    """the value after n additions of `step` to 0.0, one rounding per addition (how the reference and the library form durations)"""
+    t = 0.0
+    for _ in range(int(n)):
+        t += step
+    return t
+
+
+def total_duration(T_xy, T_yaw, Nxy, Nyaw):
+    """SE2Trajectory::getTotalDuration as the library documents it: the two running sums of the piece durations, the smaller one"""
+    dx, dy = running_sum(float(T_xy), Nxy), running_sum(float(T_yaw), Nyaw)
+    return dx if dx < dy else dy
+
+
+def time_table(dt, total):
+    """t_q of `for (t = 0; t < total; t += dt)`: every t_q < total and the first one at or beyond it (the running sum, never q * dt)"""
+    out, t = [0.0], 0.0
+    while t < total:
+        t += dt
+        out.append(t)
+    return np.array(out)
+
+
+def _locate(T, N, t):
+    """PolyTrajectory::locatePieceIdx (se2traj.hpp:343-361) with uniform durations, in double, by repeated subtraction, with the i == N fall-back --
+    over an array of times.  The decision is discrete: it is restated, not improved."""
+    T = float(T)
+    tl = np.array(t, dtype=np.float64).reshape(-1).copy()
+    idx = np.zeros(tl.shape[0], dtype=np.int64)
+    act = np.nonzero(tl > T)[0] if N > 0 else np.zeros(0, dtype=np.int64)
+    for _ in range(int(N)):
+        if act.size == 0:
+            break
+        tl[act] -= T
+        idx[act] += 1
+        act = act[tl[act] > T]
+    end = idx == N
+    idx[end] -= 1
+    tl[end] += T
+    return idx, tl
+
+
+def _quintic(c6, tl):
+    """value, first and second derivative of sum_k c6[:, k] tl^k by Horner in np.longdouble, rounded to double once at the end"""
+    c = np.asarray(c6, dtype=np.longdouble)
+    x = np.asarray(tl, dtype=np.longdouble)
+    v = c[:, 5]
+    for k in (4, 3, 2, 1, 0):
+        v = v * x + c[:, k]
+    d = 5 * c[:, 5]
+    for k in (4, 3, 2, 1):
+        d = d * x + k * c[:, k]
+    a = 20 * c[:, 5]
+    for k in (4, 3, 2):
+        a = a * x + (k * (k - 1)) * c[:, k]
+    return v.astype(np.float64), d.astype(np.float64), a.astype(np.float64)
+
+
+def norm_so2(y):
+    """UnevenMap::normSO2 (uneven_map.cpp:63-70) over an array: whole turns added, then removed, one at a time"""
+    y = np.array(y, dtype=np.float64).reshape(-1).copy()
+    for _ in range(4096):
+        m = y < -np.pi
+        if not m.any():
+            break
+        y[m] += 2 * np.pi
+    for _ in range(4096):
+        m = y > np.pi
+        if not m.any():
+            break
+        y[m] -= 2 * np.pi
+    return y
+
+
+def ref_states(c_xy, c_yaw, T_xy, T_yaw, Nxy, Nyaw, t):
+    """SE2Trajectory's getNormSE2Pos / getVel / getAcc (se2traj.hpp:106-140, 343-361) of ONE trajectory given by its coefficients (c_xy (6 Nxy, 2),
+    c_yaw (6 Nyaw,), ascending powers per piece) at the times t (any shape, used as given: the caller clamps): (n, 10) rows in STATE_COLS --
+    x, y, dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw, raw yaw.  Written from the reference's rule, with no product code: numpy only."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    cx = np.asarray(c_xy, dtype=np.float64).reshape(int(Nxy), 6, 2)
+    cw = np.asarray(c_yaw, dtype=np.float64).reshape(int(Nyaw), 6)
+    ix, tl = _locate(T_xy, Nxy, t)
+    iw, tw = _locate(T_yaw, Nyaw, t)
+    px, vx, ax = _quintic(cx[ix, :, 0], tl)
+    py, vy, ay = _quintic(cx[ix, :, 1], tl)
+    w, dw, ddw = _quintic(cw[iw], tw)
+    return np.column_stack([px, py, vx, vy, ax, ay, norm_so2(w), dw, ddw, w])
+
+
+def ref_terms(og, state, gravity):
+    """the seven report terms (alm_traj_opt.h:170-229, se2traj.hpp:551-561) assembled in numpy from the oracle's terrain variables; state (n, 8):
+    x, y, normSO2(yaw), dx, dy, ddx, ddy, dyaw -- the STATE columns of a rollout row after its time"""
+    x, y, w, dx, dy, ddx, ddy, dw = state.T
+    tv = og.terrain_variables(np.column_stack([x, y, w]))
+    c, s = np.cos(w), np.sin(w)
+    vx = np.hypot(dx, dy) * tv[:, 0]
+    lon, lat = ddx * c + ddy * s, -ddx * s + ddy * c
+    return np.column_stack([vx, lon * tv[:, 0] + gravity * tv[:, 1], lat * tv[:, 2] + gravity * tv[:, 3], dw * tv[:, 5] / np.sqrt(vx * vx + 0.01),
+                            -1.0 / tv[:, 5], tv[:, 6], np.abs(dx * s - dy * c)])
+
+
+def report_from_terms(terms):
+    """the rule of getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229) on the (n, 7) terms of a trajectory's samples: vx, ax, ay, cur as the signed value
+    of largest magnitude with both maxima started from 0, att started from -1, sigma from 0, and the sum of the non-holonomic error"""
+    T = np.asarray(terms, dtype=np.float64).reshape(-1, 7)
+    smax = lambda v: max(0.0, v.max()) if max(0.0, v.max()) >= max(0.0, (-v).max()) else -max(0.0, (-v).max())   # signed largest magnitude, maxima from 0
+    return np.array([smax(T[:, 0]), smax(T[:, 1]), smax(T[:, 2]), smax(T[:, 3]), max(0.0, (T[:, 4] + 1.0).max()) - 1.0, max(0.0, T[:, 5].max()),
+                     T[:, 6].sum()])
+
+
+def report_errors(ref, got):
+    """the project's bar for the report (test_gpu_parity::test_report_matches_oracle_on_same_trajectory) as two numbers to hold below 1e-9:
+    columns 0-5 |d| <= 1e-12 + 1e-9 |ref| is |d| / (|ref| + 1e-3) <= 1e-9; column 6 |d| / max(1, ref)"""
+    ref, got = np.asarray(ref, dtype=np.float64), np.asarray(got, dtype=np.float64)
+    return dict(maxima=float((np.abs(got[:6] - ref[:6]) / (np.abs(ref[:6]) + 1e-3)).max()), nonhol=float(abs(got[6] - ref[6]) / max(1.0, ref[6])))
+
+
 # ---- comparisons shared by the two tiers --------------------------------------------------------------------------------------------------
 def eval_errors(ref, got):
     """relative errors of one evaluation: got has f, g, hx, gx, c_xy, c_yaw, T_xy, T_yaw (T: absolute, as test_gpu_parity compares it)"""
@@ -260,14 +400,16 @@ def _line(test, variant, per_q):
     return "%-32s %-11s %-10.3e %s %s\n%46s%s\n" % (test, variant, e, where, q, "", rest)
 
 
-def write_report(path, floor=None, header=""):
+def write_report(path, floor=None, header="", only=None):
     """the worst error of every (variant, test) recorded in this process -- overall, then per quantity with the (Nxy, Nyaw) it occurred at -- and,
-    when given, the oracle's own floor (oracle against its FMA build) in the same form"""
+    when given, the oracle's own floor (oracle against its FMA build) in the same form; only(test name) selects the recorded tests"""
     with open(path, "w") as fh:
         if header:
             fh.write(header.rstrip("\n") + "\n")
         fh.write("%-32s %-11s %-10s %s\n" % ("test", "variant", "worst", "at (Nxy, Nyaw[, ratio]), quantity; then every quantity's worst"))
         for (test, variant), per_q in sorted(MEASURED.items()):
+            if only is not None and not only(test):
+                continue
             fh.write(_line(test, variant, per_q))
         if floor:
             fh.write("\noracle against the oracle rebuilt with -march=native -ffp-contract=fast, same problems (its own rounding floor)\n")
@@ -301,6 +443,23 @@ def fma_floor(O, og, cells):
     w = {pieces(sweep_problem(*c)): dict(x=rel(plain_o[c]["x"], fo[c]["x"]), cost=rel1(plain_o[c]["cost"], fo[c]["cost"]),
                                           counters=float(any(plain_o[c][k] != fo[c][k] for k in ("ret", "lbfgs_iters", "evals")))) for c in sol}
     out["capped_solves (ratio 2)"] = _worst_each(w)
+    return out
+
+
+def report_floor(O, og, cells):
+    """the oracle's report against its FMA rebuild's on the same coefficients -- the oracle's own at x0 -- for every case of the sweep, in
+    report_errors' two numbers (ratio 2, and all ratios)"""
+    import sensitivity
+    cases = all_cases()
+    ev = oracle_evals(O, og, cases)
+    plain = oracle_reports(O, og, {c: ev[c] for c in cases}, "oracle-x0")
+    with sensitivity.fma_session() as F:
+        fg = F.OracleGrid()
+        fg.set_cells(cells)
+        fma = oracle_reports(F, fg, {c: ev[c] for c in cases}, "oracle-x0/fma")
+    out = {}
+    out["report (ratio 2)"] = _worst_each({pieces(sweep_problem(*c)): report_errors(plain[c], fma[c]) for c in cases if c[1] == 2.0})
+    out["report (all ratios)"] = _worst_each({pieces(sweep_problem(*c)) + (c[1],): report_errors(plain[c], fma[c]) for c in cases})
     return out
 
 

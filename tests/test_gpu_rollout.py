@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from piece_sweep import ref_terms, report_from_terms
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ST, TR, PO = 1, 2, 4
@@ -70,17 +72,6 @@ def running_times(total, dt):
     return np.array(out)
 
 
-def terms_from(og, state, gravity):
-    """the seven report terms (alm_traj_opt.h:170-229, se2traj.hpp:551-561) assembled in numpy from the oracle's terrain variables"""
-    x, y, w, dx, dy, ddx, ddy, dw = state.T
-    tv = og.terrain_variables(np.column_stack([x, y, w]))
-    c, s = np.cos(w), np.sin(w)
-    vx = np.hypot(dx, dy) * tv[:, 0]
-    lon, lat = ddx * c + ddy * s, -ddx * s + ddy * c
-    return np.column_stack([vx, lon * tv[:, 0] + gravity * tv[:, 1], lat * tv[:, 2] + gravity * tv[:, 3], dw * tv[:, 5] / np.sqrt(vx * vx + 0.01),
-                            -1.0 / tv[:, 5], tv[:, 6], np.abs(dx * s - dy * c)])
-
-
 def close(a, b, tol=1e-12):
     a, b = np.asarray(a), np.asarray(b)
     scale = np.maximum(1.0, np.abs(b).max(axis=0))
@@ -137,7 +128,7 @@ def test_states_match_host_evaluation(solved):
 def test_terrain_terms_match_oracle(solved, oracle_grid, hill):
     opt, probs, out = solved
     offs, rows = opt.rollout(0.01, ST | TR)
-    ref = terms_from(oracle_grid, rows[:, 1:9], hill.params["gravity"])
+    ref = ref_terms(oracle_grid, rows[:, 1:9], hill.params["gravity"])
     close(rows[:, 9:16], ref)
 
 
@@ -157,13 +148,10 @@ def test_report_follows_from_terrain_columns(solved):
     rep = opt.getMaxVxAxAyCurAttSig()
     offs, rows = opt.rollout(0.01, TR)
     for b in range(len(out)):
-        T = rows[offs[b]:offs[b + 1]]
-        smax = lambda v: max(0.0, v.max()) if max(0.0, v.max()) >= max(0.0, (-v).max()) else -max(0.0, (-v).max())   # signed largest magnitude, maxima from 0
-        for k in range(4):
-            assert rep[b, k] == smax(T[:, k]), (b, k)
-        assert rep[b, 4] == max(0.0, (T[:, 4] + 1.0).max()) - 1.0
-        assert rep[b, 5] == max(0.0, T[:, 5].max())
-        assert abs(rep[b, 6] - T[:, 6].sum()) <= 1e-12 * abs(rep[b, 6])
+        want = report_from_terms(rows[offs[b]:offs[b + 1]])          # (piece_sweep: signed largest magnitude with maxima from 0, att from -1, sigma from 0)
+        for k in range(6):
+            assert rep[b, k] == want[k], (b, k)
+        assert abs(rep[b, 6] - want[6]) <= 1e-12 * abs(rep[b, 6])
 
 
 def test_vis_se3_grid_ends_at_the_end_pose(solved, hill):
@@ -219,7 +207,7 @@ def test_fp32_cells_and_fp32_sample_context(oracle):
         opt.optimize_batch(probs)
         offs, rows = opt.rollout(0.01, ST | TR)
         assert offs[-1] > 0
-        close(rows[:, 9:16], terms_from(og, rows[:, 1:9], m32.params["gravity"]))
+        close(rows[:, 9:16], ref_terms(og, rows[:, 1:9], m32.params["gravity"]))
 
 
 def test_call_forms_agree_bit_for_bit(solved):

@@ -147,3 +147,30 @@ def test_emu_capped_solves(oracle, oracle_grid, analytic_cells, lanes):
     E.lib().emu_set_lanes(256)
     print("emulator capped solves, %d lanes: worst" % lanes, PS.record("cpu_capped_solves", lanes, errs))
     assert not bad, bad[:8]
+
+
+@pytest.mark.parametrize("lanes", EMU_LANES)
+def test_emu_report_every_piece_count(oracle, oracle_grid, analytic_cells, lanes):
+    """Solver::report (the sample count by wg.sum, about 70 samples per piece reduced by wg.sumMax) after ONE evaluation at x0, ratio 2 at every Nxy
+    plus the ragged ratio 1.7 at the solve list: the emulator's seven values against the oracle's report on the emulator's own coefficients, at the
+    device's bar (test_gpu_parity::test_report_matches_oracle_on_same_trajectory: columns 0-5 rtol 1e-9 / atol 1e-12, column 6 1e-9 max(1, ref))"""
+    cases = [c for c in PS.all_cases() if c[1] == 2.0] + [(n, 1.7) for n in PS.SOLVE_NXY]
+    assert [c[0] for c in cases[:len(PS.NXY_ALL)]] == PS.NXY_ALL and set(cases) <= set(PS.all_cases())
+    ev = PS.oracle_evals(oracle, oracle_grid, cases)
+    emu = _emu(oracle, analytic_cells)
+    E.lib().emu_set_lanes(lanes)
+    got = {}
+    for c in cases:
+        st = PS.case_state(*c)
+        got[c] = emu.eval_report(PS.sweep_problem(*c), ev[c]["x0"], lam=st["lam"], mu=st["mu"], scale_cx=st["scale_cx"], rho=st["rho"], scale_fx=st["scale_fx"])
+    E.lib().emu_set_lanes(256)
+    ref = PS.oracle_reports(oracle, oracle_grid, got, "emu%d" % lanes)
+    bad, errs = [], {}
+    for c in cases:
+        where = PS.pieces(PS.sweep_problem(*c)) + (c[1],)
+        assert np.isfinite(got[c]["report"]).all() and got[c]["report"][0] > 0.0 and got[c]["report"][6] > 0.0, (lanes, where, got[c]["report"])
+        e = PS.report_errors(ref[c], got[c]["report"])
+        errs[where] = e
+        bad += [(lanes, where, q, v) for q, v in e.items() if not v < 1e-9]
+    print("emulator report, %d lanes: worst" % lanes, PS.record("cpu_report", lanes, errs))
+    assert not bad, bad[:8]
