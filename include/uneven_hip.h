@@ -274,6 +274,38 @@ int uph_map_load_cache(uph_map* m, const char* csv_path, const char* bin_path, i
 /* constructMap on the x-slab [x0, x1): crop box + 1 cm voxel filter, xy bucketing and plane fits all on the device (the host uploads the cloud).
  * xyz: n x 3 float32 (what pcl::PCDReader delivers).  Cells outside the slab are untouched.  Blocking. */
 int uph_map_build(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1);
+/* uph_map_build with the VoxelGrid stage skipped: the cloud passes the crop box and keeps its order -- for callers that hold a filtered cloud already
+ * (uph_map_filter_cloud's output, or uph_map_built_cloud's).  Refusals as uph_map_build. */
+int uph_map_build_filtered(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1);
+/* ---- the map from a new scan in a box (csrc/map_build.hip).  After a uph_map_build / uph_map_build_filtered of the WHOLE grid, or a
+ * uph_map_update, the map owns the filtered cloud W its cells derive from ("resident"; uph_map_built_cloud reads it).  uph_map_set_cells,
+ * uph_map_import_cells_dev, uph_map_load_cache, uph_map_fill_fbm and uph_map_commit end the residency: the cells then no longer derive from W.
+ * uph_map_update: box = {x_min, x_max, y_min, y_max}, closed, compared in float.  The new resident cloud is
+ *     W' = (W without the points whose (x, y) lie in the box, order kept) ++ cropAndVoxel(points of xyz that are finite and lie in the box, input order)
+ * (crop box and 1 cm voxel grid of uph_map_build, applied to the new points alone; n = 0 with xyz = NULL removes only), and afterwards cells, c and both
+ * occupancy layers equal uph_map_build_filtered(W') on a fresh map bit for bit.  Only the columns of uph_map_update_rect plus those whose last fit took
+ * the global nearest-neighbour search are refitted -- unless the minimum x or y of W' differs from W's (the bucket origin moves): then every column is
+ * (full_refit = 1, dirty = the whole grid).  Blocking, on the build's stream.  Refused with UPH_ERR_INVALID, cells, occupancy and W as they were: an
+ * fp32 or tile map, no resident cloud, a reversed box or one with a NaN, n < 0, n > 0 with xyz = NULL, an update that would leave W' empty;
+ * UPH_ERR_LIMIT: a disc of W' too dense for the staging window (as uph_map_build).  info may be NULL. */
+typedef struct uph_map_update_info {
+    int32_t dirty[4];     /* {x0, x1, y0, y1}, half-open column rect: uph_map_update_rect's, or the whole grid on a full refit */
+    int32_t changed[4];   /* tight bounding rect (half-open) of the columns with a cell, c or occupancy byte that changed; zeros when none */
+    int32_t n_refit;      /* columns refitted = area of dirty + n_far */
+    int32_t n_far;        /* refitted columns OUTSIDE dirty: their last fit took the global nearest-neighbour search (0 on a full refit) */
+    int32_t n_changed;    /* columns that changed */
+    int32_t full_refit;
+    int64_t n_removed, n_added, n_cloud;   /* points of W inside the box, filtered new points, size of W' */
+} uph_map_update_info;
+int uph_map_update(uph_map* m, const float box[4], const float* xyz, int64_t n, uph_map_update_info* info);
+/* the columns whose fit can see a point of the box (host function: no device needed): column x belongs when
+ *     box[0] - Rm <= (x + 0.5) res + origin_x <= box[1] + Rm     (in double; y alike),
+ * Rm = (double)Rst + res, Rst = (float)(0.12 + max ellipsoid axis) + 1e-3f the fit's staging radius, origin = -map_size / 2, clipped to the grid.
+ * rect = {x0, x1, y0, y1} half-open, all zeros when empty.  UPH_ERR_INVALID for a reversed box or one with a NaN. */
+int uph_map_update_rect(const uph_map_params* mp, const float box[4], int32_t rect[4]);
+/* stages of the last uph_map_update, milliseconds: out6 = upload of the new points, cloud edit + filter, bucketing + column list + LDS sizing,
+ * fit kernel (HIP events), windowed commit, the whole call (wall) */
+int uph_map_update_stages(uph_map* m, double* out6);
 /* ---- several GPUs, one host process.  maps[g] = one map per device (same parameters and storage, whole-grid maps).  Device g produces the
  * x-slab [g per, min(nx, (g + 1) per)), per = ceil(nx / n_gpus), of the cell array -- all devices concurrently, one host thread each --, ONE
  * ncclAllGather over an in-process RCCL clique (ncclCommInitAll; in place on the cell arrays when n_gpus divides nx) leaves the complete array

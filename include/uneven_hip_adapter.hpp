@@ -242,6 +242,19 @@ public:
         uph_map_dims(m_, d);
         if (uph_map_build(m_, xyz, n, 0, d[0]) != UPH_OK) throw std::runtime_error(std::string("uph_map_build: ") + uph_last_error());
     }
+    // constructMap from a cloud that is filtered already (crop box only, order kept; uph_map_build_filtered)
+    void buildFilteredMap(const float* xyz, long n) {
+        int32_t d[3];
+        uph_map_dims(m_, d);
+        if (uph_map_build_filtered(m_, xyz, n, 0, d[0]) != UPH_OK) throw std::runtime_error(std::string("uph_map_build_filtered: ") + uph_last_error());
+    }
+    // a new scan of a box (no counterpart in the reference): the world inside box = {x_min, x_max, y_min, y_max} is now `cloud` (n x 3 float; n = 0 removes
+    // only).  Refits the columns the box reaches on the device; info.changed is the rect of columns whose cells or occupancy changed -- the trajectories to
+    // hand to ALMTrajOpt::checkSE2TrajBatch are those that cross it (uph_map_update)
+    void updateMap(const float box[4], const float* cloud, long n, uph_map_update_info& info) {
+        if (uph_map_update(m_, box, n > 0 ? cloud : nullptr, n, &info) != UPH_OK) throw std::runtime_error(std::string("uph_map_update: ") + uph_last_error());
+    }
+    void updateMap(const float box[4], const std::vector<float>& cloud, uph_map_update_info& info) { updateMap(box, cloud.data(), (long)(cloud.size() / 3), info); }
     // UnevenMap::constructMapInput replacement: cells from the `.map` cache (ncell x 4: z, sigma, zb.x, zb.y in the reference's address order)
     void setCells(const double* rxs2) {
         if (uph_map_set_cells(m_, rxs2) != UPH_OK) throw std::runtime_error(std::string("uph_map_set_cells: ") + uph_last_error());

@@ -42,6 +42,11 @@ class KinoParams(C.Structure):
                 ("max_vel", C.c_double)]
 
 
+class MapUpdateInfo(C.Structure):
+    _fields_ = [("dirty", C.c_int32 * 4), ("changed", C.c_int32 * 4), ("n_refit", C.c_int32), ("n_far", C.c_int32), ("n_changed", C.c_int32),
+                ("full_refit", C.c_int32), ("n_removed", C.c_int64), ("n_added", C.c_int64), ("n_cloud", C.c_int64)]
+
+
 FBM_MAX_WAVES = 48
 FBM_TABLE_DOUBLES = 4 * FBM_MAX_WAVES + 12 + 9
 DP = C.POINTER(C.c_double)
@@ -88,6 +93,10 @@ SYMBOLS = {
     "uph_map_set_cells": (C.c_int, [_VP, DP]),
     "uph_map_get_cells": (C.c_int, [_VP, DP, DP, C.c_char_p, C.c_char_p]),
     "uph_map_build": (C.c_int, [_VP, C.POINTER(C.c_float), _I64, _I32, _I32]),
+    "uph_map_build_filtered": (C.c_int, [_VP, C.POINTER(C.c_float), _I64, _I32, _I32]),
+    "uph_map_update": (C.c_int, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I64, C.POINTER(MapUpdateInfo)]),
+    "uph_map_update_rect": (C.c_int, [C.POINTER(MapParams), C.POINTER(C.c_float), C.POINTER(_I32)]),
+    "uph_map_update_stages": (C.c_int, [_VP, DP]),
     "uph_map_build_multi": (C.c_int, [C.POINTER(_VP), _I32, C.POINTER(C.c_float), _I64]),
     "uph_map_fill_fbm_multi": (C.c_int, [C.POINTER(_VP), _I32, C.POINTER(FbmParams)]),
     "uph_multi_slab_plan": (C.c_int, [_I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),

@@ -36,6 +36,7 @@
 
 using namespace uph;
 
+constexpr int UPH_BSCR_SLOTS = 24;
 struct uph_map {
     int device = 0;
     uph_map_params mp;
@@ -51,8 +52,15 @@ struct uph_map {
     double last_build_ms = 0.0, last_query_ms = 0.0;
     int64_t last_cell_iters = 0, last_cloud = 0;
     // build scratch (grow-only, reused by every build: no allocation per call once warm) and the events of the kernel timing
-    void* bscr[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t bscr_cap[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* bscr[UPH_BSCR_SLOTS] = {};
+    size_t bscr_cap[UPH_BSCR_SLOTS] = {};
+    // resident cloud (uph_map_update): while `resident`, the cells derive from the filtered cloud W in bscr[10..12] (x, y, z in filtered-cloud order, last_cloud
+    // points) and its bucketed form in bscr[13] (origin res_bx0 / res_by0).  An update writes W' and its buckets into the alternates bscr[16..19] and swaps the
+    // slots on success, so a refused or failed update leaves W as it was.  d_far: one byte per held column, set by the fit that took the global search there.
+    bool resident = false, far_dirty = false;
+    float res_bx0 = 0.f, res_by0 = 0.f;
+    char* d_far = nullptr;
+    double ustage_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // last update: upload, cloud edit + filter, bucketing + list + sizing, fit kernel (HIP events), commit, total wall
     hipEvent_t bev0 = nullptr, bev1 = nullptr;
     double stage_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // last build: cloud upload, crop + voxel filter, bucketing, plane-fit kernel (HIP events), commit, total wall
     int64_t last_raw = 0;
@@ -190,14 +198,15 @@ __device__ __forceinline__ void walkDisc(const DiscWalk& w, const CloudDev& cd, 
     }
 }
 
-// one wave64 per (x,y) column of the slab [x0, x1)
-__global__ __launch_bounds__(64) void uph_map_build_kernel(GridDev g, CloudDev cd, double* __restrict__ cells, int x0, int x1, int iter_num,
-                                                           double ell_x, double ell_y, double ell_z, int lds_cap, int* __restrict__ overflow) {
-    extern __shared__ float4 spts[];
-    const int col = blockIdx.x;
-    const int x = x0 + col / g.ny, y = col % g.ny;
-    if (x >= x1) return;
+// The fit of one (x,y) column by one wave64, lane = yaw bin: the ONE body of uph_map_build_kernel (columns of a slab) and uph_map_fit_list_kernel (listed
+// columns, uph_map_update), so the two cannot diverge.  far_out (one byte per held column) is set when any yaw lane took nearest2DGlobal in iteration 0 and
+// cleared otherwise: only such a column's result can depend on points outside its staged disc.  CMP: each lane compares its four new values bitwise with
+// the cell it overwrites; the wave's ballot goes to *changed_out.
+template <bool CMP>
+__device__ __forceinline__ void fitColumn(const GridDev& g, const CloudDev& cd, double* __restrict__ cells, float4* spts, int x, int y, int iter_num, double ell_x,
+                                          double ell_y, double ell_z, int lds_cap, int* __restrict__ overflow, char* __restrict__ far_out, char* __restrict__ changed_out) {
     const int lane = threadIdx.x;
+    bool far_lane = false, diff_lane = false;
     const double ccx = (x + 0.5) * g.xy_res + g.origin[0];           // indexToPos, uneven_map.h:419-425
     const double ccy = (y + 0.5) * g.xy_res + g.origin[1];
     const double box_r = fmax(fmax(ell_x, ell_y), ell_z);            // uneven_map.cpp:319
@@ -248,7 +257,7 @@ __global__ __launch_bounds__(64) void uph_map_build_kernel(GridDev g, CloudDev c
                 // the staged disc proves the answer only if the best distance fits inside it
                 const float dq = sqrtf((qx - fcx) * (qx - fcx) + (qy - fcy) * (qy - fcy));
                 const float slack = Rst - dq - 1.0e-4f;
-                if (best < 0 || slack <= 0.f || bestd > slack * slack) best = nearest2DGlobal(cd, qx, qy, &bestz);
+                if (best < 0 || slack <= 0.f || bestd > slack * slack) { best = nearest2DGlobal(cd, qx, qy, &bestz); far_lane = true; }
                 if (best >= 0) wz = (double)bestz;
             }
             // radius search (float predicate) + ellipsoid test (fp64), two passes: mean, then covariance (:5-20, :363-377)
@@ -301,16 +310,46 @@ __global__ __launch_bounds__(64) void uph_map_build_kernel(GridDev g, CloudDev c
             cz = mz; csig = sig; czbx = n0; czby = n1;
             cc = sqrt(1.0 - czbx * czbx - czby * czby);
         }
+        if (CMP) {
+            const double o0 = cells[addr * 4 + 0], o1 = cells[addr * 4 + 1], o2 = cells[addr * 4 + 2], o3 = cells[addr * 4 + 3];
+            diff_lane |= __double_as_longlong(o0) != __double_as_longlong(cz) || __double_as_longlong(o1) != __double_as_longlong(csig) ||
+                         __double_as_longlong(o2) != __double_as_longlong(czbx) || __double_as_longlong(o3) != __double_as_longlong(czby);
+        }
         cells[addr * 4 + 0] = cz; cells[addr * 4 + 1] = csig; cells[addr * 4 + 2] = czbx; cells[addr * 4 + 3] = czby;
+    }
+    const unsigned long long far_any = __ballot(far_lane);
+    if (lane == 0) far_out[(size_t)(x - g.x_off) * g.ny + y] = far_any ? 1 : 0;
+    if (CMP) {
+        const unsigned long long diff_any = __ballot(diff_lane);
+        if (lane == 0) *changed_out = diff_any ? 1 : 0;
     }
 }
 
+// one wave64 per (x,y) column of the slab [x0, x1)
+__global__ __launch_bounds__(64) void uph_map_build_kernel(GridDev g, CloudDev cd, double* __restrict__ cells, int x0, int x1, int iter_num,
+                                                           double ell_x, double ell_y, double ell_z, int lds_cap, int* __restrict__ overflow, char* __restrict__ far_out) {
+    extern __shared__ float4 spts[];
+    const int col = blockIdx.x;
+    const int x = x0 + col / g.ny, y = col % g.ny;
+    if (x >= x1) return;
+    fitColumn<false>(g, cd, cells, spts, x, y, iter_num, ell_x, ell_y, ell_z, lds_cap, overflow, far_out, nullptr);
+}
+// one wave64 per LISTED column (uph_map_update): list[] holds held-column indices (x - x_off) * ny + y; changed[i] = the fit rewrote list[i] with other bits
+__global__ __launch_bounds__(64) void uph_map_fit_list_kernel(GridDev g, CloudDev cd, double* __restrict__ cells, const int* __restrict__ list, int iter_num,
+                                                              double ell_x, double ell_y, double ell_z, int lds_cap, int* __restrict__ overflow, char* __restrict__ far_out,
+                                                              char* __restrict__ changed) {
+    extern __shared__ float4 spts[];
+    const int col = list[blockIdx.x];
+    fitColumn<true>(g, cd, cells, spts, g.x_off + col / g.ny, col % g.ny, iter_num, ell_x, ell_y, ell_z, lds_cap, overflow, far_out, changed + blockIdx.x);
+}
+
 // cells -> c_buffer + occupancy (uneven_map.cpp:170-179, 385, 390).  One thread per (x,y) column.
-__global__ void uph_map_commit_kernel(int nx, int ny, int nyaw, const double* __restrict__ cells, const float* __restrict__ cells32, double* __restrict__ cbuf,
-                                      char* __restrict__ occ, char* __restrict__ occ2, double min_cnormal, double max_rho) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= nx * ny) return;
+// (commitColumn: the ONE body of uph_map_commit_kernel and uph_map_commit_list_kernel; TRACK: returns whether an occupancy byte of the column changed)
+template <bool TRACK>
+__device__ __forceinline__ bool commitColumn(int col, int nyaw, const double* __restrict__ cells, const float* __restrict__ cells32, double* __restrict__ cbuf,
+                                             char* __restrict__ occ, char* __restrict__ occ2, double min_cnormal, double max_rho) {
     char any = 0;
+    bool moved = false;
     for (int w = 0; w < nyaw; w++) {
         const size_t a = (size_t)col * nyaw + w;
         double sg, zx, zy;
@@ -319,10 +358,33 @@ __global__ void uph_map_commit_kernel(int nx, int ny, int nyaw, const double* __
         const double c = sqrt(1.0 - zx * zx - zy * zy);
         if (cbuf) cbuf[a] = c;
         const char o = (c < min_cnormal || sg > max_rho) ? 1 : 0;
+        if (TRACK) moved |= occ[a] != o;
         occ[a] = o;
         any |= o;
     }
+    if (TRACK) moved |= occ2[col] != any;
     occ2[col] = any;
+    return moved;
+}
+__global__ void uph_map_commit_kernel(int nx, int ny, int nyaw, const double* __restrict__ cells, const float* __restrict__ cells32, double* __restrict__ cbuf,
+                                      char* __restrict__ occ, char* __restrict__ occ2, double min_cnormal, double max_rho) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= nx * ny) return;
+    (void)commitColumn<false>(col, nyaw, cells, cells32, cbuf, occ, occ2, min_cnormal, max_rho);
+}
+// the commit over the listed columns only (uph_map_update).  A column counts as changed when its fit rewrote a cell with other bits (changed[i], from
+// uph_map_fit_list_kernel) or an occupancy byte moved; info[0..3] = min x, max x, min y, max y of the changed columns (held indices), info[4] = their count
+__global__ void uph_map_commit_list_kernel(int ny, int nyaw, const double* __restrict__ cells, double* __restrict__ cbuf, char* __restrict__ occ, char* __restrict__ occ2,
+                                           double min_cnormal, double max_rho, const int* __restrict__ list, int nlist, const char* __restrict__ changed, int* __restrict__ info) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nlist) return;
+    const int col = list[i];
+    const bool moved = commitColumn<true>(col, nyaw, cells, nullptr, cbuf, occ, occ2, min_cnormal, max_rho);
+    if (moved || changed[i]) {
+        const int x = col / ny, y = col % ny;
+        atomicMin(&info[0], x); atomicMax(&info[1], x); atomicMin(&info[2], y); atomicMax(&info[3], y);
+        atomicAdd(&info[4], 1);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ analytic fractal terrain (BASELINE.json configs[4])
@@ -536,6 +598,54 @@ __global__ __launch_bounds__(64) void uph_disc_cap_kernel(GridDev g, CloudDev cd
     if (lane == 0) atomicMax(cap, count);
 }
 
+// ---- uph_map_update: edit of the resident cloud, list of the columns to refit
+// ... the disc sizing over LISTED columns (the fit's own walk, as uph_disc_cap_kernel)
+__global__ __launch_bounds__(64) void uph_disc_cap_list_kernel(GridDev g, CloudDev cd, const int* __restrict__ list, double ell_x, double ell_y, double ell_z, int* __restrict__ cap) {
+    const int col = list[blockIdx.x];
+    const int lane = threadIdx.x;
+    int count = 0;
+    walkDisc(discOf(g, cd, g.x_off + col / g.ny, col % g.ny, ell_x, ell_y, ell_z), cd, lane, [&](bool, const float4&, unsigned long long mask) { count += __popcll(mask); });
+    if (lane == 0) atomicMax(cap, count);
+}
+// keep[i] = the resident point's (x, y) lies outside the closed box {x_min, x_max, y_min, y_max} (float compares)
+__global__ void uph_box_keep_flag_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, float b0, float b1, float b2, float b3, int* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float px = x[i], py = y[i];
+    flag[i] = (px >= b0 && px <= b1 && py >= b2 && py <= b3) ? 0 : 1;
+}
+__global__ void uph_compact3_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, const int* __restrict__ flag, const int* __restrict__ pos,
+                                    float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const int o = pos[i];
+    ox[o] = x[i]; oy[o] = y[i]; oz[o] = z[i];
+}
+// new points: finite, inside the update box, inside the build's crop box (uph_crop_flag_kernel's predicate)
+__global__ void uph_crop_box_flag_kernel(const float* __restrict__ xyz, int n, float b0, float b1, float b2, float b3, int* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
+    const bool fin = isfinite(px) && isfinite(py) && isfinite(pz);
+    const bool inbox = px >= b0 && px <= b1 && py >= b2 && py <= b3;
+    flag[i] = (fin && inbox && !(px < -10.0f || py < -10.0f || pz < -0.01f || px > 10.0f || py > 10.0f || pz > 5.0f)) ? 1 : 0;
+}
+// flag[c] = held column c is refitted: all of them, or those of the rect {x0, x1, y0, y1} (held indices, half-open) plus every column whose far flag is set;
+// *n_far counts the latter
+__global__ void uph_col_flag_kernel(int ncol, int ny, int all, int rx0, int rx1, int ry0, int ry1, const char* __restrict__ far, int* __restrict__ flag, int* __restrict__ n_far) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncol) return;
+    const int x = c / ny, y = c % ny;
+    const bool in_rect = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
+    const bool f = far[c] != 0;
+    flag[c] = (all || in_rect || f) ? 1 : 0;
+    if (f && !in_rect) atomicAdd(n_far, 1);
+}
+__global__ void uph_col_compact_kernel(int ncol, const int* __restrict__ flag, const int* __restrict__ pos, int* __restrict__ list) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < ncol && flag[c]) list[pos[c]] = c;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 namespace {
 
@@ -597,6 +707,16 @@ int commitMap(uph_map* m) {
                        m->d_occ2, m->mp.min_cnormal, m->mp.max_rho);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
+    return UPH_OK;
+}
+
+// the cells stop deriving from the resident cloud (foreign write): an update is refused until the next build, the far flags go back to zero
+int endResidency(uph_map* m) {
+    m->resident = false;
+    if (m->far_dirty) {
+        HIPCHK(hipMemset(m->d_far, 0, (size_t)m->g.nx_hold * m->g.ny));
+        m->far_dirty = false;
+    }
     return UPH_OK;
 }
 
@@ -674,6 +794,8 @@ static int createMap(const uph_map_params* mp, int device, uph_map** out, bool f
     }
     alloc((void**)&m->d_occ, m->ncell);
     alloc((void**)&m->d_occ2, (size_t)g.nx_hold * g.ny);
+    alloc((void**)&m->d_far, (size_t)g.nx_hold * g.ny);
+    if (r == UPH_OK && hipMemset(m->d_far, 0, (size_t)g.nx_hold * g.ny) != hipSuccess) r = UPH_ERR_HIP;
     if (r == UPH_OK) r = commitMap(m);
     if (r != UPH_OK) { uph_map_destroy(m); return r; }
     *out = m;
@@ -695,7 +817,8 @@ void uph_map_destroy(uph_map* m) {
     hipSetDevice(m->device);
     hipFree(m->d_cells); hipFree(m->d_cells32); hipFree(m->d_c); hipFree(m->d_occ); hipFree(m->d_occ2);
     for (int k = 0; k < 4; k++) hipFree(m->scratch[k]);
-    for (int k = 0; k < 16; k++) hipFree(m->bscr[k]);
+    for (int k = 0; k < UPH_BSCR_SLOTS; k++) hipFree(m->bscr[k]);
+    hipFree(m->d_far);
     if (m->bev0) hipEventDestroy(m->bev0);
     if (m->bev1) hipEventDestroy(m->bev1);
     delete m;
@@ -730,6 +853,7 @@ static int copyCellsF32(uph_map* m, const double* from_host, double* to_host) {
 int uph_map_set_cells(uph_map* m, const double* rxs2) {
     if (!m || !rxs2) { setError("uph_map_set_cells: null argument"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(m->device));
+    { const int r = endResidency(m); if (r != UPH_OK) return r; }
     if (m->d_cells32) { const int r = copyCellsF32(m, rxs2, nullptr); if (r != UPH_OK) return r; }
     else HIPCHK(hipMemcpy(m->d_cells, rxs2, m->ncell * 4 * sizeof(double), hipMemcpyHostToDevice));
     return commitMap(m);
@@ -826,6 +950,7 @@ int uph_map_export_slab_dev(uph_map* m, int32_t x0, int32_t x1, void* dst_dev) {
 int uph_map_import_cells_dev(uph_map* m, const void* src_dev) {
     if (!m || !src_dev) { setError("uph_map_import_cells_dev: bad arguments"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(m->device));
+    { const int r = endResidency(m); if (r != UPH_OK) return r; }
     HIPCHK(hipMemcpy(cellBase(m), src_dev, m->ncell * cellBytes(m), hipMemcpyDeviceToDevice));
     return commitMap(m);
 }
@@ -833,6 +958,7 @@ int uph_map_import_cells_dev(uph_map* m, const void* src_dev) {
 int uph_map_commit(uph_map* m) {
     if (!m) return UPH_ERR_INVALID;
     HIPCHK(hipSetDevice(m->device));
+    { const int r = endResidency(m); if (r != UPH_OK) return r; }      // (the caller wrote the cells: they no longer derive from the resident cloud)
     return commitMap(m);
 }
 
@@ -897,6 +1023,7 @@ static int fillSlab(uph_map* m, const uph_fbm_params* fp, int32_t x0, int32_t x1
     if (x1 <= 0) { x0 = m->g.x_off; x1 = m->g.x_off + m->g.nx_hold; }
     if (x0 < m->g.x_off || x1 > m->g.x_off + m->g.nx_hold || x0 >= x1) { setError("uph_map_fill_fbm: slab outside the rows this map holds"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(m->device));
+    { const int r = endResidency(m); if (r != UPH_OK) return r; }
     FbmDev f;
     buildFbm(*fp, f);
     UphEventTmp e0, e1;
@@ -925,9 +1052,118 @@ int uph_map_build_stats(uph_map* m, double* kernel_ms, int64_t* cell_iters, int6
     return UPH_OK;
 }
 
-static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1, bool commit);
+// grow-only build scratch of the map handle (reused by every build and update: no allocation per call once warm): slot -> bytes
+// slots: 0 raw xyz | 1 flag / head | 2 scan | 3,4,5 cropped x y z | 6 key | 7 idx | 8 sorted key | 9 sorted idx | 10,11,12 filtered x y z (the resident cloud W) |
+//        13 pts + bstart (W bucketed) | 14 cub temp | 15 small | 16,17,18 + 19 the alternates of 10,11,12 + 13 (uph_map_update) | 20 column list | 21 column flag |
+//        22 column scan | 23 changed bytes
+static void* buildScr(uph_map* m, int slot, size_t bytes) {
+    if (bytes <= m->bscr_cap[slot]) return m->bscr[slot];
+    if (m->bscr[slot]) hipFree(m->bscr[slot]);
+    m->bscr[slot] = nullptr; m->bscr_cap[slot] = 0;
+    const size_t want = bytes + bytes / 4 + 256;
+    if (hipMalloc(&m->bscr[slot], want) != hipSuccess) { setError("uph_map_build: hipMalloc of build scratch failed"); return nullptr; }
+    m->bscr_cap[slot] = want;
+    return m->bscr[slot];
+}
+struct BuildScratch {
+    int *flag, *scan, *key, *idx, *skey, *sidx;
+    float *cx, *cy, *cz;
+    unsigned* small;
+    void* tmp;
+    size_t tb;
+};
+// the scratch both the build and the update need for `cap` points (and `ncol` columns to scan)
+static int buildScratch(uph_map* m, int cap, int ncol, BuildScratch& b) {
+    const size_t N = (size_t)std::max(cap, 1);
+    b.flag = (int*)buildScr(m, 1, sizeof(int) * N);
+    b.scan = (int*)buildScr(m, 2, sizeof(int) * N);
+    b.cx = (float*)buildScr(m, 3, 4 * N); b.cy = (float*)buildScr(m, 4, 4 * N); b.cz = (float*)buildScr(m, 5, 4 * N);
+    b.key = (int*)buildScr(m, 6, 4 * N); b.idx = (int*)buildScr(m, 7, 4 * N); b.skey = (int*)buildScr(m, 8, 4 * N); b.sidx = (int*)buildScr(m, 9, 4 * N);
+    b.small = (unsigned*)buildScr(m, 15, 64);
+    if (!b.flag || !b.scan || !b.cx || !b.cy || !b.cz || !b.key || !b.idx || !b.skey || !b.sidx || !b.small) return UPH_ERR_HIP;
+    size_t tb_scan = 0, tb_sort = 0;
+    hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, b.flag, b.scan, std::max((int)N, ncol), 0);
+    hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, b.key, b.skey, b.idx, b.sidx, (int)N, 0, 32, 0);
+    b.tb = std::max(tb_scan, tb_sort);
+    b.tmp = buildScr(m, 14, b.tb);
+    return b.tmp ? UPH_OK : UPH_ERR_HIP;
+}
+// count of the flagged among n after flag -> ExclusiveSum -> scan
+static int flaggedCount(const BuildScratch& b, int n, int* out) {
+    int last_flag = 0, last_pos = 0;
+    HIPCHK(hipMemcpy(&last_flag, b.flag + (n - 1), 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&last_pos, b.scan + (n - 1), 4, hipMemcpyDeviceToHost));
+    *out = last_pos + last_flag;
+    return UPH_OK;
+}
+// ---- pcl::VoxelGrid, 1 cm leaf (:139-143) on the cropped cloud b.cx / cy / cz (nc points): extent -> min_b / div_b on the host (six floats cross), keys +
+// stable sort + per-leaf centroid on the device, into ox / oy / oz (*np points).  voxel = false (uph_map_build_filtered), or a leaf too small for the extent
+// (PCL passes the cloud through unfiltered): the cropped cloud is copied as it is.
+static int voxelStage(const BuildScratch& b, int nc, bool voxel, float* ox, float* oy, float* oz, int* np) {
+    const float inv = 1.0f / 0.01f;
+    int64_t dx = 0, dy = 0, dz = 0;
+    float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
+    if (voxel) {
+        unsigned mm[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+        HIPCHK(hipMemcpy(b.small, mm, sizeof(mm), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(uph_minmax3_kernel, dim3(std::min(1024, (nc + 255) / 256)), dim3(256), 0, 0, b.cx, b.cy, b.cz, nc, b.small);
+        HIPCHK(hipMemcpy(mm, b.small, sizeof(mm), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; k++) { lo[k] = fOrdInv(mm[k]); hi[k] = fOrdInv(mm[3 + k]); }
+        dx = (int64_t)((hi[0] - lo[0]) * inv) + 1; dy = (int64_t)((hi[1] - lo[1]) * inv) + 1; dz = (int64_t)((hi[2] - lo[2]) * inv) + 1;
+    }
+    if (!voxel || dx * dy * dz > (int64_t)INT32_MAX) {
+        HIPCHK(hipMemcpyAsync(ox, b.cx, 4 * (size_t)nc, hipMemcpyDeviceToDevice, 0));
+        HIPCHK(hipMemcpyAsync(oy, b.cy, 4 * (size_t)nc, hipMemcpyDeviceToDevice, 0));
+        HIPCHK(hipMemcpyAsync(oz, b.cz, 4 * (size_t)nc, hipMemcpyDeviceToDevice, 0));
+        *np = nc;
+    } else {
+        int minb[3], divb[3];
+        for (int k = 0; k < 3; k++) { minb[k] = (int)std::floor(lo[k] * inv); divb[k] = (int)std::floor(hi[k] * inv) - minb[k] + 1; }
+        const unsigned nbc = (unsigned)((nc + 255) / 256);
+        hipLaunchKernelGGL(uph_voxel_key_kernel, dim3(nbc), dim3(256), 0, 0, b.cx, b.cy, b.cz, nc, inv, (float)minb[0], (float)minb[1], (float)minb[2], divb[0], divb[0] * divb[1], b.key, b.idx);
+        size_t tb = b.tb;
+        hipcub::DeviceRadixSort::SortPairs(b.tmp, tb, b.key, b.skey, b.idx, b.sidx, nc, 0, 32, 0);
+        hipLaunchKernelGGL(uph_head_kernel, dim3(nbc), dim3(256), 0, 0, b.skey, nc, b.flag);
+        hipcub::DeviceScan::ExclusiveSum(b.tmp, tb, b.flag, b.scan, nc, 0);
+        hipLaunchKernelGGL(uph_centroid_kernel, dim3(nbc), dim3(256), 0, 0, b.skey, b.sidx, b.flag, b.scan, nc, b.cx, b.cy, b.cz, ox, oy, oz);
+        const int r = flaggedCount(b, nc, np);
+        if (r != UPH_OK) return r;
+    }
+    HIPCHK(hipGetLastError());
+    return UPH_OK;
+}
+// ---- xy buckets of 0.16 m over the filtered cloud fx / fy / fz (np points): a query disc of 0.32 m around a cell centre touches at most 5 x 5 buckets.
+// pts + bstart go to build-scratch slot `slot`; cd describes them.
+static int bucketStage(uph_map* m, const BuildScratch& b, const float* fx, const float* fy, const float* fz, int np, int slot, CloudDev& cd) {
+    const float bsize = 0.16f;
+    unsigned mm2[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+    HIPCHK(hipMemcpy(b.small, mm2, sizeof(mm2), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(uph_minmax3_kernel, dim3(std::min(1024, (np + 255) / 256)), dim3(256), 0, 0, fx, fy, fz, np, b.small);
+    HIPCHK(hipMemcpy(mm2, b.small, sizeof(mm2), hipMemcpyDeviceToHost));
+    const float bx0 = fOrdInv(mm2[0]), by0 = fOrdInv(mm2[1]), bx1 = fOrdInv(mm2[3]), by1 = fOrdInv(mm2[4]);
+    const int bnx = (int)((bx1 - bx0) / bsize) + 1, bny = (int)((by1 - by0) / bsize) + 1;
+    const size_t nbuck = (size_t)bnx * bny;
+    char* d_pb = (char*)buildScr(m, slot, sizeof(float4) * (size_t)np + sizeof(int) * (nbuck + 1) + 64);
+    if (!d_pb) return UPH_ERR_HIP;
+    float4* d_pts = (float4*)d_pb;
+    int* d_bstart = (int*)(d_pb + sizeof(float4) * (size_t)np);
+    const unsigned nbp = (unsigned)((np + 255) / 256);
+    hipLaunchKernelGGL(uph_bucket_key_kernel, dim3(nbp), dim3(256), 0, 0, fx, fy, np, bx0, by0, bsize, bnx, bny, b.key, b.idx);
+    int key_bits = 1;
+    while (((size_t)1 << key_bits) < nbuck + 1 && key_bits < 31) key_bits++;
+    size_t tb = b.tb;
+    hipcub::DeviceRadixSort::SortPairs(b.tmp, tb, b.key, b.skey, b.idx, b.sidx, np, 0, key_bits, 0);      // stable: filtered-cloud order inside a bucket
+    hipLaunchKernelGGL(uph_pack_pts_kernel, dim3(nbp), dim3(256), 0, 0, b.sidx, np, fx, fy, fz, d_pts);
+    hipLaunchKernelGGL(uph_bstart_kernel, dim3((unsigned)((nbuck + 1 + 255) / 256)), dim3(256), 0, 0, b.skey, np, (int)nbuck, d_bstart);
+    cd.pts = d_pts; cd.bstart = d_bstart; cd.bx0 = bx0; cd.by0 = by0; cd.bsize = bsize; cd.bnx = bnx; cd.bny = bny; cd.npts = np;
+    return UPH_OK;
+}
+
+static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1, bool commit, bool voxel = true);
 int uph_map_build(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1) { return buildSlab(m, xyz, n, x0, x1, true); }
-static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1, bool commit) {
+// uph_map_build with the VoxelGrid stage skipped: the cloud passes the crop box and keeps its order (callers that hold a filtered cloud)
+int uph_map_build_filtered(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1) { return buildSlab(m, xyz, n, x0, x1, true, false); }
+static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_t x1, bool commit, bool voxel) {
     if (m && m->d_cells32) { setError("uph_map_build: the plane fit writes fp64 cells; create the map with uph_map_create"); return UPH_ERR_INVALID; }
     if (!m || !xyz || n <= 0) { setError("uph_map_build: bad arguments"); return UPH_ERR_INVALID; }
     if (n > (int64_t)INT32_MAX) { setError("uph_map_build: more than 2^31 points"); return UPH_ERR_LIMIT; }
@@ -937,97 +1173,31 @@ static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_
     const auto t_begin = std::chrono::steady_clock::now();
     auto t_mark = t_begin;
     auto lap = [&]() { const auto now = std::chrono::steady_clock::now(); const double ms = std::chrono::duration<double, std::milli>(now - t_mark).count(); t_mark = now; return ms; };
-    // grow-only scratch of the map handle: slot -> bytes
-    auto scr = [&](int slot, size_t bytes) -> void* {
-        if (bytes <= m->bscr_cap[slot]) return m->bscr[slot];
-        if (m->bscr[slot]) hipFree(m->bscr[slot]);
-        m->bscr[slot] = nullptr; m->bscr_cap[slot] = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        if (hipMalloc(&m->bscr[slot], want) != hipSuccess) { setError("uph_map_build: hipMalloc of build scratch failed"); return nullptr; }
-        m->bscr_cap[slot] = want;
-        return m->bscr[slot];
-    };
+    m->resident = false;                                       // the build replaces the resident cloud; residency returns when it succeeds
     const int N = (int)n;
     const unsigned nb_ = (unsigned)((N + 255) / 256);
-    // slots: 0 raw xyz | 1 flag / head | 2 scan | 3,4,5 cropped x y z | 6 key | 7 idx | 8 sorted key | 9 sorted idx | 10,11,12 filtered x y z | 13 pts + bstart | 14 cub temp | 15 small
-    float* d_raw = (float*)scr(0, sizeof(float) * 3 * (size_t)N);
-    int* d_flag = (int*)scr(1, sizeof(int) * (size_t)N);
-    int* d_scan = (int*)scr(2, sizeof(int) * (size_t)N);
-    float *d_cx = (float*)scr(3, 4 * (size_t)N), *d_cy = (float*)scr(4, 4 * (size_t)N), *d_cz = (float*)scr(5, 4 * (size_t)N);
-    int *d_key = (int*)scr(6, 4 * (size_t)N), *d_idx = (int*)scr(7, 4 * (size_t)N), *d_skey = (int*)scr(8, 4 * (size_t)N), *d_sidx = (int*)scr(9, 4 * (size_t)N);
-    float *d_fx = (float*)scr(10, 4 * (size_t)N), *d_fy = (float*)scr(11, 4 * (size_t)N), *d_fz = (float*)scr(12, 4 * (size_t)N);
-    unsigned* d_small = (unsigned*)scr(15, 64);
-    if (!d_raw || !d_flag || !d_scan || !d_cx || !d_cy || !d_cz || !d_key || !d_idx || !d_skey || !d_sidx || !d_fx || !d_fy || !d_fz || !d_small) return UPH_ERR_HIP;
-    size_t tb_scan = 0, tb_sort = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, d_flag, d_scan, N, 0);
-    hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, d_key, d_skey, d_idx, d_sidx, N, 0, 32, 0);
-    size_t tb = std::max(tb_scan, tb_sort);
-    void* d_tmp = scr(14, tb);
-    if (!d_tmp) return UPH_ERR_HIP;
+    BuildScratch b;
+    float* d_raw = (float*)buildScr(m, 0, sizeof(float) * 3 * (size_t)N);
+    float *d_fx = (float*)buildScr(m, 10, 4 * (size_t)N), *d_fy = (float*)buildScr(m, 11, 4 * (size_t)N), *d_fz = (float*)buildScr(m, 12, 4 * (size_t)N);
+    if (!d_raw || !d_fx || !d_fy || !d_fz || buildScratch(m, N, 0, b) != UPH_OK) return UPH_ERR_HIP;
+    unsigned* d_small = b.small;
     HIPCHK(hipMemcpy(d_raw, xyz, sizeof(float) * 3 * (size_t)N, hipMemcpyHostToDevice));
     m->stage_ms[0] = lap();
     // ---- pcl::CropBox (:133-137): inclusive float box, finite points, order kept
-    hipLaunchKernelGGL(uph_crop_flag_kernel, dim3(nb_), dim3(256), 0, 0, d_raw, N, d_flag);
-    hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_flag, d_scan, N, 0);
-    hipLaunchKernelGGL(uph_compact_kernel, dim3(nb_), dim3(256), 0, 0, d_raw, N, d_flag, d_scan, d_cx, d_cy, d_cz);
-    int last_flag = 0, last_pos = 0;
-    HIPCHK(hipMemcpy(&last_flag, d_flag + (N - 1), 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&last_pos, d_scan + (N - 1), 4, hipMemcpyDeviceToHost));
-    const int nc = last_pos + last_flag;                       // points inside the crop box
+    size_t tb = b.tb;
+    hipLaunchKernelGGL(uph_crop_flag_kernel, dim3(nb_), dim3(256), 0, 0, d_raw, N, b.flag);
+    hipcub::DeviceScan::ExclusiveSum(b.tmp, tb, b.flag, b.scan, N, 0);
+    hipLaunchKernelGGL(uph_compact_kernel, dim3(nb_), dim3(256), 0, 0, d_raw, N, b.flag, b.scan, b.cx, b.cy, b.cz);
+    int nc = 0;                                                // points inside the crop box
+    { const int r = flaggedCount(b, N, &nc); if (r != UPH_OK) return r; }
     if (nc == 0) { setError("uph_map_build: no points inside the crop box"); return UPH_ERR_INVALID; }
-    // ---- pcl::VoxelGrid, 1 cm leaf (:139-143): extent -> min_b / div_b on the host (six floats cross), keys + stable sort + per-leaf centroid on the device
-    unsigned mm[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    HIPCHK(hipMemcpy(d_small, mm, sizeof(mm), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(uph_minmax3_kernel, dim3(std::min(1024, (nc + 255) / 256)), dim3(256), 0, 0, d_cx, d_cy, d_cz, nc, d_small);
-    HIPCHK(hipMemcpy(mm, d_small, sizeof(mm), hipMemcpyDeviceToHost));
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; k++) { lo[k] = fOrdInv(mm[k]); hi[k] = fOrdInv(mm[3 + k]); }
-    const float inv = 1.0f / 0.01f;
-    const int64_t dx = (int64_t)((hi[0] - lo[0]) * inv) + 1, dy = (int64_t)((hi[1] - lo[1]) * inv) + 1, dz = (int64_t)((hi[2] - lo[2]) * inv) + 1;
     int np = 0;
-    const float *fx = d_cx, *fy = d_cy, *fz = d_cz;            // the filtered cloud (device)
-    if (dx * dy * dz > (int64_t)INT32_MAX) {
-        np = nc;                                               // PCL: leaf too small for the extent -> the cropped cloud passes through unfiltered
-    } else {
-        int minb[3], divb[3];
-        for (int k = 0; k < 3; k++) { minb[k] = (int)std::floor(lo[k] * inv); divb[k] = (int)std::floor(hi[k] * inv) - minb[k] + 1; }
-        const unsigned nbc = (unsigned)((nc + 255) / 256);
-        hipLaunchKernelGGL(uph_voxel_key_kernel, dim3(nbc), dim3(256), 0, 0, d_cx, d_cy, d_cz, nc, inv, (float)minb[0], (float)minb[1], (float)minb[2], divb[0], divb[0] * divb[1], d_key, d_idx);
-        hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_key, d_skey, d_idx, d_sidx, nc, 0, 32, 0);
-        hipLaunchKernelGGL(uph_head_kernel, dim3(nbc), dim3(256), 0, 0, d_skey, nc, d_flag);
-        hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_flag, d_scan, nc, 0);
-        hipLaunchKernelGGL(uph_centroid_kernel, dim3(nbc), dim3(256), 0, 0, d_skey, d_sidx, d_flag, d_scan, nc, d_cx, d_cy, d_cz, d_fx, d_fy, d_fz);
-        HIPCHK(hipMemcpy(&last_flag, d_flag + (nc - 1), 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&last_pos, d_scan + (nc - 1), 4, hipMemcpyDeviceToHost));
-        np = last_pos + last_flag;
-        fx = d_fx; fy = d_fy; fz = d_fz;
-    }
-    HIPCHK(hipGetLastError());
+    { const int r = voxelStage(b, nc, voxel, d_fx, d_fy, d_fz, &np); if (r != UPH_OK) return r; }
     m->stage_ms[1] = lap();
-    // ---- xy buckets of 0.16 m: a query disc of 0.32 m around a cell centre touches at most 5 x 5 buckets
-    const float bsize = 0.16f;
-    unsigned mm2[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    HIPCHK(hipMemcpy(d_small, mm2, sizeof(mm2), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(uph_minmax3_kernel, dim3(std::min(1024, (np + 255) / 256)), dim3(256), 0, 0, fx, fy, fz, np, d_small);
-    HIPCHK(hipMemcpy(mm2, d_small, sizeof(mm2), hipMemcpyDeviceToHost));
-    const float bx0 = fOrdInv(mm2[0]), by0 = fOrdInv(mm2[1]), bx1 = fOrdInv(mm2[3]), by1 = fOrdInv(mm2[4]);
-    const int bnx = (int)((bx1 - bx0) / bsize) + 1, bny = (int)((by1 - by0) / bsize) + 1;
-    const size_t nbuck = (size_t)bnx * bny;
-    char* d_pb = (char*)scr(13, sizeof(float4) * (size_t)np + sizeof(int) * (nbuck + 1) + 64);
-    if (!d_pb) return UPH_ERR_HIP;
-    float4* d_pts = (float4*)d_pb;
-    int* d_bstart = (int*)(d_pb + sizeof(float4) * (size_t)np);
-    const unsigned nbp = (unsigned)((np + 255) / 256);
-    hipLaunchKernelGGL(uph_bucket_key_kernel, dim3(nbp), dim3(256), 0, 0, fx, fy, np, bx0, by0, bsize, bnx, bny, d_key, d_idx);
-    int key_bits = 1;
-    while (((size_t)1 << key_bits) < nbuck + 1 && key_bits < 31) key_bits++;
-    hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_key, d_skey, d_idx, d_sidx, np, 0, key_bits, 0);      // stable: filtered-cloud order inside a bucket
-    hipLaunchKernelGGL(uph_pack_pts_kernel, dim3(nbp), dim3(256), 0, 0, d_sidx, np, fx, fy, fz, d_pts);
-    hipLaunchKernelGGL(uph_bstart_kernel, dim3((unsigned)((nbuck + 1 + 255) / 256)), dim3(256), 0, 0, d_skey, np, (int)nbuck, d_bstart);
+    CloudDev cd;
+    { const int r = bucketStage(m, b, d_fx, d_fy, d_fz, np, 13, cd); if (r != UPH_OK) return r; }
     // LDS capacity of the staging area: the largest point count of any disc the kernel stages (uph_disc_cap_kernel: the kernel's own predicate over
     // the columns of this slab) -- exact, so a cloud fits whenever its densest disc does (9 600 points = 150 KB)
-    CloudDev cd;
-    cd.pts = d_pts; cd.bstart = d_bstart; cd.bx0 = bx0; cd.by0 = by0; cd.bsize = bsize; cd.bnx = bnx; cd.bny = bny; cd.npts = np;
     const int ncol = (x1 - x0) * g.ny;
     int cap = 64;
     HIPCHK(hipMemcpy(d_small + 8, &cap, 4, hipMemcpyHostToDevice));
@@ -1042,8 +1212,9 @@ static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_
     HIPCHK(hipFuncSetAttribute((const void*)uph_map_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     if (!m->bev0) { HIPCHK(hipEventCreate(&m->bev0)); HIPCHK(hipEventCreate(&m->bev1)); }
     HIPCHK(hipEventRecord(m->bev0, 0));
+    m->far_dirty = true;
     hipLaunchKernelGGL(uph_map_build_kernel, dim3(ncol), dim3(64), lds_bytes, 0, g, cd, m->d_cells, (int)x0, (int)x1, (int)m->mp.iter_num, m->mp.ellipsoid_x,
-                       m->mp.ellipsoid_y, m->mp.ellipsoid_z, cap, (int*)(d_small + 9));
+                       m->mp.ellipsoid_y, m->mp.ellipsoid_z, cap, (int*)(d_small + 9), m->d_far);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->bev1, 0));
     int ovf = 0;
@@ -1059,6 +1230,8 @@ static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_
     const int rc = commit ? commitMap(m) : UPH_OK;
     m->stage_ms[4] = lap();
     m->stage_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    // every held cell now derives from this cloud: it stays resident for uph_map_update (whole-grid fp64 maps; a slab build or an uncommitted one does not qualify)
+    if (rc == UPH_OK && commit && g.nx_hold == g.nx && x0 == 0 && x1 == g.nx) { m->resident = true; m->res_bx0 = cd.bx0; m->res_by0 = cd.by0; }
     return rc;
 }
 
@@ -1067,6 +1240,157 @@ static int buildSlab(uph_map* m, const float* xyz, int64_t n, int32_t x0, int32_
 int uph_map_build_stages(uph_map* m, double* out6) {
     if (!m || !out6) return UPH_ERR_INVALID;
     for (int k = 0; k < 6; k++) out6[k] = m->stage_ms[k];
+    return UPH_OK;
+}
+
+// ---- uph_map_update ------------------------------------------------------------------------------------------------------------------------
+// first / one past last index whose centre (i + 0.5) res + origin lies in [lo, hi], by the predicate itself (an estimate, then stepped to the exact edge)
+static void centreRange(double lo, double hi, double res, double origin, int n, int* a, int* b) {
+    double ea = std::floor((lo - origin) / res - 0.5) - 1.0, eb = std::ceil((hi - origin) / res - 0.5) + 1.0;
+    ea = std::min(std::max(ea, 0.0), (double)n); eb = std::min(std::max(eb, -1.0), (double)(n - 1));
+    int i = (int)ea, j = (int)eb;
+    while (i < n && !(lo <= (i + 0.5) * res + origin)) i++;
+    while (j >= 0 && !((j + 0.5) * res + origin <= hi)) j--;
+    *a = i; *b = j + 1;
+}
+int uph_map_update_rect(const uph_map_params* mp, const float box[4], int32_t rect[4]) {
+    if (!mp || !box || !rect) { setError("uph_map_update_rect: null argument"); return UPH_ERR_INVALID; }
+    if (!(box[0] <= box[1]) || !(box[2] <= box[3])) { setError("uph_map_update_rect: the box is reversed or holds a NaN"); return UPH_ERR_INVALID; }
+    const double res = mp->xy_resolution;
+    const int nx = (int)std::ceil(mp->map_size_x / res), ny = (int)std::ceil(mp->map_size_y / res);
+    const double box_r = std::max(std::max(mp->ellipsoid_x, mp->ellipsoid_y), mp->ellipsoid_z);
+    const float Rst = (float)(0.12 + box_r) + 1.0e-3f;          // discOf's staging radius
+    const double Rm = (double)Rst + res;
+    int a[2], b[2];
+    centreRange((double)box[0] - Rm, (double)box[1] + Rm, res, -mp->map_size_x / 2.0, nx, &a[0], &b[0]);
+    centreRange((double)box[2] - Rm, (double)box[3] + Rm, res, -mp->map_size_y / 2.0, ny, &a[1], &b[1]);
+    if (a[0] >= b[0] || a[1] >= b[1]) { rect[0] = rect[1] = rect[2] = rect[3] = 0; return UPH_OK; }
+    rect[0] = a[0]; rect[1] = b[0]; rect[2] = a[1]; rect[3] = b[1];
+    return UPH_OK;
+}
+
+int uph_map_update(uph_map* m, const float box[4], const float* xyz, int64_t n, uph_map_update_info* info) {
+    if (!m || !box) { setError("uph_map_update: null argument"); return UPH_ERR_INVALID; }
+    if (m->d_cells32) { setError("uph_map_update: the plane fit writes fp64 cells; create the map with uph_map_create"); return UPH_ERR_INVALID; }
+    const GridDev& g = m->g;
+    if (g.nx_hold != g.nx) { setError("uph_map_update: a tile holds only part of the grid"); return UPH_ERR_INVALID; }
+    if (n < 0 || (n > 0 && !xyz)) { setError("uph_map_update: bad point arguments"); return UPH_ERR_INVALID; }
+    int32_t rect[4];
+    { const int r = uph_map_update_rect(&m->mp, box, rect); if (r != UPH_OK) return r; }
+    if (!m->resident || m->last_cloud <= 0) { setError("uph_map_update: no resident cloud (the cells must come from uph_map_build, uph_map_build_filtered or uph_map_update on the whole grid)"); return UPH_ERR_INVALID; }
+    if (n + m->last_cloud > (int64_t)INT32_MAX) { setError("uph_map_update: more than 2^31 points"); return UPH_ERR_LIMIT; }
+    HIPCHK(hipSetDevice(m->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto t_mark = t_begin;
+    auto lap = [&]() { const auto now = std::chrono::steady_clock::now(); const double ms = std::chrono::duration<double, std::milli>(now - t_mark).count(); t_mark = now; return ms; };
+    const int nW = (int)m->last_cloud, N = (int)n, cap_pts = nW + N;
+    const int ncol = g.nx_hold * g.ny;
+    BuildScratch b;
+    float* d_raw = N > 0 ? (float*)buildScr(m, 0, sizeof(float) * 3 * (size_t)N) : nullptr;
+    float *d_ax = (float*)buildScr(m, 16, 4 * (size_t)cap_pts), *d_ay = (float*)buildScr(m, 17, 4 * (size_t)cap_pts), *d_az = (float*)buildScr(m, 18, 4 * (size_t)cap_pts);
+    int *d_list = (int*)buildScr(m, 20, 4 * (size_t)ncol), *d_cflag = (int*)buildScr(m, 21, 4 * (size_t)ncol), *d_cscan = (int*)buildScr(m, 22, 4 * (size_t)ncol);
+    char* d_changed = (char*)buildScr(m, 23, (size_t)ncol);
+    if ((N > 0 && !d_raw) || !d_ax || !d_ay || !d_az || !d_list || !d_cflag || !d_cscan || !d_changed || buildScratch(m, cap_pts, ncol, b) != UPH_OK) return UPH_ERR_HIP;
+    unsigned* d_small = b.small;
+    const float *d_wx = (const float*)m->bscr[10], *d_wy = (const float*)m->bscr[11], *d_wz = (const float*)m->bscr[12];
+    if (N > 0) HIPCHK(hipMemcpy(d_raw, xyz, sizeof(float) * 3 * (size_t)N, hipMemcpyHostToDevice));
+    m->ustage_ms[0] = lap();
+    // ---- W' = (W without the points whose (x, y) lie in the box, order kept) ++ cropAndVoxel(new points that are finite and lie in the box)
+    size_t tb = b.tb;
+    const unsigned nbw = (unsigned)((nW + 255) / 256);
+    hipLaunchKernelGGL(uph_box_keep_flag_kernel, dim3(nbw), dim3(256), 0, 0, d_wx, d_wy, nW, box[0], box[1], box[2], box[3], b.flag);
+    hipcub::DeviceScan::ExclusiveSum(b.tmp, tb, b.flag, b.scan, nW, 0);
+    hipLaunchKernelGGL(uph_compact3_kernel, dim3(nbw), dim3(256), 0, 0, d_wx, d_wy, d_wz, nW, b.flag, b.scan, d_ax, d_ay, d_az);
+    int nkeep = 0, nadd = 0;
+    { const int r = flaggedCount(b, nW, &nkeep); if (r != UPH_OK) return r; }
+    if (N > 0) {
+        const unsigned nbn = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(uph_crop_box_flag_kernel, dim3(nbn), dim3(256), 0, 0, d_raw, N, box[0], box[1], box[2], box[3], b.flag);
+        hipcub::DeviceScan::ExclusiveSum(b.tmp, tb, b.flag, b.scan, N, 0);
+        hipLaunchKernelGGL(uph_compact_kernel, dim3(nbn), dim3(256), 0, 0, d_raw, N, b.flag, b.scan, b.cx, b.cy, b.cz);
+        int nc = 0;
+        { const int r = flaggedCount(b, N, &nc); if (r != UPH_OK) return r; }
+        if (nc > 0) { const int r = voxelStage(b, nc, true, d_ax + nkeep, d_ay + nkeep, d_az + nkeep, &nadd); if (r != UPH_OK) return r; }
+    }
+    HIPCHK(hipGetLastError());
+    const int np = nkeep + nadd;
+    if (np == 0) { setError("uph_map_update: the update would leave the cloud empty"); return UPH_ERR_INVALID; }
+    m->ustage_ms[1] = lap();
+    // ---- buckets of W' (whole); the same origin as the resident buckets = the disc walk of every other column visits the same points in the same order
+    CloudDev cd;
+    { const int r = bucketStage(m, b, d_ax, d_ay, d_az, np, 19, cd); if (r != UPH_OK) return r; }
+    const bool incremental = std::memcmp(&cd.bx0, &m->res_bx0, 4) == 0 && std::memcmp(&cd.by0, &m->res_by0, 4) == 0;
+    if (!incremental) { rect[0] = 0; rect[1] = g.nx; rect[2] = 0; rect[3] = g.ny; }
+    // ---- columns to refit: flag, scan, compact
+    int zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int cap = 64;
+    HIPCHK(hipMemcpy(d_small + 8, &cap, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_small + 9, zeros, 8, hipMemcpyHostToDevice));                 // [9] overflow, [10] far count
+    const unsigned nbcol = (unsigned)((ncol + 255) / 256);
+    hipLaunchKernelGGL(uph_col_flag_kernel, dim3(nbcol), dim3(256), 0, 0, ncol, g.ny, incremental ? 0 : 1, rect[0], rect[1], rect[2], rect[3], m->d_far, d_cflag, (int*)(d_small + 10));
+    hipcub::DeviceScan::ExclusiveSum(b.tmp, tb, d_cflag, d_cscan, ncol, 0);
+    hipLaunchKernelGGL(uph_col_compact_kernel, dim3(nbcol), dim3(256), 0, 0, ncol, d_cflag, d_cscan, d_list);
+    int last_flag = 0, last_pos = 0, n_far = 0;
+    HIPCHK(hipMemcpy(&last_flag, d_cflag + (ncol - 1), 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&last_pos, d_cscan + (ncol - 1), 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n_far, d_small + 10, 4, hipMemcpyDeviceToHost));
+    const int n_refit = last_pos + last_flag;
+    if (!incremental) n_far = 0;                                                      // (every column is listed as part of the whole grid)
+    if (n_refit > 0) {
+        hipLaunchKernelGGL(uph_disc_cap_list_kernel, dim3(n_refit), dim3(64), 0, 0, g, cd, d_list, m->mp.ellipsoid_x, m->mp.ellipsoid_y, m->mp.ellipsoid_z, (int*)(d_small + 8));
+        HIPCHK(hipMemcpy(&cap, d_small + 8, 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipGetLastError());
+    m->ustage_ms[2] = lap();
+    const size_t lds_bytes = (size_t)cap * sizeof(float4);
+    if (lds_bytes > 150 * 1024) { setError("uph_map_update: cloud too dense for the LDS staging window (" + std::to_string(cap) + " points within the staging radius of one cell centre; 9600 fit)"); return UPH_ERR_LIMIT; }
+    HIPCHK(hipFuncSetAttribute((const void*)uph_map_fit_list_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    if (!m->bev0) { HIPCHK(hipEventCreate(&m->bev0)); HIPCHK(hipEventCreate(&m->bev1)); }
+    const int big = 0x7fffffff;
+    const int info0[5] = {big, -1, big, -1, 0};
+    // from here on the cells change: a failure ends the residency (the grid then derives from neither cloud)
+    auto fail = [&](int code) { m->resident = false; return code; };
+    float ms = 0.f;
+    int got[5] = {big, -1, big, -1, 0};
+    if (n_refit > 0) {
+        if (hipMemcpy(d_small + 11, info0, sizeof(info0), hipMemcpyHostToDevice) != hipSuccess) { setError("uph_map_update: hipMemcpy failed"); return UPH_ERR_HIP; }
+        if (hipEventRecord(m->bev0, 0) != hipSuccess) { setError("uph_map_update: hipEventRecord failed"); return UPH_ERR_HIP; }
+        m->far_dirty = true;
+        hipLaunchKernelGGL(uph_map_fit_list_kernel, dim3(n_refit), dim3(64), lds_bytes, 0, g, cd, m->d_cells, d_list, (int)m->mp.iter_num, m->mp.ellipsoid_x, m->mp.ellipsoid_y,
+                           m->mp.ellipsoid_z, cap, (int*)(d_small + 9), m->d_far, d_changed);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(m->bev1, 0) != hipSuccess) { setError("uph_map_update: the fit kernel did not launch"); return fail(UPH_ERR_HIP); }
+        int ovf = 0;
+        if (hipMemcpy(&ovf, d_small + 9, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { setError("uph_map_update: the fit kernel failed"); return fail(UPH_ERR_HIP); }
+        if (ovf) { setError("uph_map_update: a staged neighbourhood exceeded the LDS window (internal sizing error)"); return fail(UPH_ERR_LIMIT); }
+        if (hipEventElapsedTime(&ms, m->bev0, m->bev1) != hipSuccess) ms = 0.f;
+        (void)lap();
+        // ---- windowed commit: c, occ, occ2 of the listed columns; changed columns reduced with integer min / max / count
+        hipLaunchKernelGGL(uph_map_commit_list_kernel, dim3((unsigned)((n_refit + 255) / 256)), dim3(256), 0, 0, g.ny, g.nyaw, m->d_cells, m->d_c, m->d_occ, m->d_occ2,
+                           m->mp.min_cnormal, m->mp.max_rho, d_list, n_refit, d_changed, (int*)(d_small + 11));
+        if (hipGetLastError() != hipSuccess || hipMemcpy(got, d_small + 11, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { setError("uph_map_update: the commit failed"); return fail(UPH_ERR_HIP); }
+    } else (void)lap();
+    m->ustage_ms[3] = ms;
+    m->ustage_ms[4] = lap();
+    // ---- W' becomes the resident cloud
+    for (int k = 0; k < 4; k++) { std::swap(m->bscr[10 + k], m->bscr[16 + k]); std::swap(m->bscr_cap[10 + k], m->bscr_cap[16 + k]); }
+    m->last_cloud = (int64_t)np;
+    m->res_bx0 = cd.bx0; m->res_by0 = cd.by0;
+    if (info) {
+        for (int k = 0; k < 4; k++) info->dirty[k] = rect[k];
+        if (got[4] > 0) { info->changed[0] = got[0]; info->changed[1] = got[1] + 1; info->changed[2] = got[2]; info->changed[3] = got[3] + 1; }
+        else info->changed[0] = info->changed[1] = info->changed[2] = info->changed[3] = 0;
+        info->n_refit = n_refit; info->n_far = n_far; info->n_changed = got[4]; info->full_refit = incremental ? 0 : 1;
+        info->n_removed = (int64_t)(nW - nkeep); info->n_added = (int64_t)nadd; info->n_cloud = (int64_t)np;
+    }
+    m->ustage_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return UPH_OK;
+}
+
+// stages of the last uph_map_update on this map, milliseconds: [0] upload of the new points, [1] cloud edit + filter, [2] bucketing + column list + LDS sizing,
+// [3] fit kernel (HIP events), [4] windowed commit, [5] the whole call (wall)
+int uph_map_update_stages(uph_map* m, double* out6) {
+    if (!m || !out6) return UPH_ERR_INVALID;
+    for (int k = 0; k < 6; k++) out6[k] = m->ustage_ms[k];
     return UPH_OK;
 }
 // the cloud the last uph_map_build fitted planes to, as the device filtered it (crop box + voxel grid): at most cap points into out_xyz, returns

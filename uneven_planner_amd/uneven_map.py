@@ -196,6 +196,48 @@ class UnevenMap:
         self.map_ready = True
         return self
 
+    def build_filtered(self, xyz, x0=0, x1=None, download=True):
+        """build() with the VoxelGrid stage skipped (uph_map_build_filtered): xyz passes the crop box and keeps its order -- for a cloud that is
+        filtered already (filter_cloud's or built_cloud's output)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        if x1 is None:
+            x1 = int(self.voxel_num[0])
+        _lib.check(self.L.uph_map_build_filtered(self.h, xyz.ctypes.data_as(C.POINTER(C.c_float)), xyz.shape[0], int(x0), int(x1)),
+                   "uph_map_build_filtered")
+        if download:
+            self.download()
+        self.map_ready = True
+        return self
+
+    def update(self, box, xyz=None, download=True):
+        """the world inside box = (x_min, x_max, y_min, y_max) is now the points of xyz (None: nothing -- remove only): uph_map_update on the resident
+        cloud of the last whole-grid build / update.  Returns the info fields (dirty and changed as (x0, x1, y0, y1) half-open column rects, n_refit,
+        n_far, n_changed, full_refit, n_removed, n_added, n_cloud) and stages_ms.  download=True refreshes the host mirrors map_buffer, c_buffer, occ_buffer and
+        occ_r2_buffer (a whole-grid download, as build's)."""
+        fp = C.POINTER(C.c_float)
+        bx = np.ascontiguousarray(box, dtype=np.float32).reshape(4)
+        n, ptr = 0, None
+        if xyz is not None:
+            xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            n, ptr = xyz.shape[0], (xyz.ctypes.data_as(fp) if xyz.shape[0] else None)
+        info = _lib.MapUpdateInfo()
+        _lib.check(self.L.uph_map_update(self.h, bx.ctypes.data_as(fp), ptr, n, C.byref(info)), "uph_map_update")
+        st = np.zeros(6)
+        _lib.check(self.L.uph_map_update_stages(self.h, _dp(st)), "uph_map_update_stages")
+        if download:
+            self.download()
+        out = {k: int(getattr(info, k)) for k in ("n_refit", "n_far", "n_changed", "full_refit", "n_removed", "n_added", "n_cloud")}
+        out.update(dirty=tuple(int(v) for v in info.dirty), changed=tuple(int(v) for v in info.changed),
+                   stages_ms=dict(upload=st[0], edit_filter=st[1], bucket_list=st[2], kernel=st[3], commit=st[4], call=st[5]))
+        return out
+
+    def update_rect(self, box):
+        """(x0, x1, y0, y1), half-open: the columns update(box) refits besides the far ones (uph_map_update_rect; host only)"""
+        bx = np.ascontiguousarray(box, dtype=np.float32).reshape(4)
+        r = (C.c_int32 * 4)()
+        _lib.check(self.L.uph_map_update_rect(C.byref(self._mp), bx.ctypes.data_as(C.POINTER(C.c_float)), r), "uph_map_update_rect")
+        return tuple(int(v) for v in r)
+
     @staticmethod
     def filter_cloud(xyz):
         """CropBox + 1 cm VoxelGrid of UnevenMap::init (uneven_map.cpp:133-143) as uph_map_build applies them; returns the (m,3) float32 cloud"""
