@@ -50,6 +50,9 @@
  *                              limits (alm_traj_opt.h:29-53) instead of printed
  *   uph_check_window        <- the part of their `for (t = 0; t < total; t += dt)` loop a time window holds
  *   uph_check_limits        <- the limits among ALMTrajOpt's parameter members  alm_traj_opt.h:33-38
+ *   uph_locate_batch        <- the time on a trajectory that traj_anal.hpp:490-491 takes from the wall clock (t_cur = now - start_time), here from the
+ *                              odometry pose PlanManager::rcvOdomCallBack holds (plan_manager.cpp:31-41), with the tracking error at that time
+ *   uph_within_batch        <- which resident trajectories enter a rect of the map (a changed region) and when
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -604,6 +607,38 @@ int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_
                     int32_t* counts /* [n][3]: samples, violating, occupied */, double* worst /* [n][7] */, double* worst_t /* [n][7] */);
 /* milliseconds of uph_check_kernel in the last uph_check_batch of c (events on the context's stream) */
 int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
+/* ---- locate poses on resident trajectories, and find where resident trajectories cross a rect.  Both reduce the STATE samples of (trajectory, time
+ * window) pairs of c's resident batch: query q names trajectory traj[q] and the window [t_from[q], t_to[q]] (t_to == NULL: to the end), and its samples
+ * tau_0 .. tau_{n-1} are, in table order, exactly the rows uph_rollout_batch(dt, with_end) has for that trajectory inside the window (uph_check_batch's
+ * rule, uph_check_window).  X, Y below are a STATE row's x, y: map coordinates.  No terrain is read.
+ *
+ * uph_locate_batch: poses [n][3] = x, y, yaw in map coordinates.
+ *   coarse stage (exact): d2 = ex ex + ey ey with ex = X - x, ey = Y - y and both products rounded before the add.  The smallest d2 wins, a NaN d2
+ *   counts as +inf, equal keys go to the smaller sample index j*.   near_t [n] = tau_j*,  near_d2 [n],  count [n] = samples in the window.
+ *   refinement (continuous): bracket lo = tau_max(j*-1, 0), hi = tau_min(j*+1, n-1).  With e = p(t) + shift - (x, y), g(t) = e . v and
+ *   h(t) = v . v + e . a: start at t = tau_j* with [a, b] = [lo, hi]; at most 8 iterations of -- evaluate at t; g > 0: b = t, g < 0: a = t, g == 0: stop;
+ *   the next t is t - g / h when h > 0 and that point lies in [a, b], else (a + b) / 2; stop when the next t equals t.  The state at the candidate and
+ *   its d2 (as above) are evaluated; !(d2 <= near_d2): the result is the coarse sample itself and refined = 0, otherwise the candidate and refined = 1.
+ *   t [n], refined [n], d2 [n];  state [n][10] in uph_traj_states' columns, equal to uph_traj_states(traj, t) bit for bit;
+ *   err [n][3] = e_lon, e_lat, e_yaw: with psi the raw yaw of the state (column 9) and r = (x, y) - (X, Y):  r . (cos psi, sin psi),
+ *   r . (-sin psi, cos psi),  normSO2(yaw - psi).
+ *   An empty window: count 0, near_t = t = NaN, near_d2 = d2 = +inf, refined 0, state and err NaN.
+ * uph_within_batch: rects [n][4] = x0, x1, y0, y1 in map coordinates, closed.  A sample is inside when x0 <= X && X <= x1 && y0 <= Y && Y <= y1 (a NaN
+ *   position is not inside; a reversed rect is empty, not an error).   enter_t [n] / leave_t [n] = t of the first / last sample inside (NaN: none),
+ *   counts [n][2] = samples in the window, samples inside.
+ * Any output may be NULL.  The same trajectory may be named by several queries.  Deterministic: selections under a total order, no floating-point
+ * atomics; the result does not depend on how lanes and waves are combined.  Blocking, on the context's stream.  Refused with UPH_ERR_INVALID, outputs
+ * untouched: bad arguments, dt <= 0 or not finite, no resident trajectory (uph_rollout_batch's rule), a traj[q] out of range or naming an
+ * UPH_RET_UNSUPPORTED slot, a non-finite t_from[q], a NaN t_to[q] (+-inf is allowed), a non-finite pose component, a NaN rect bound (+-inf is allowed),
+ * an asynchronous solve pending on c.  UPH_ERR_LIMIT as uph_rollout_plan. */
+int uph_locate_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* poses /* [n][3] */, const double* t_from, const double* t_to /* NULL: to the end */,
+                     double dt, int32_t with_end, double* near_t /* [n] */, double* near_d2 /* [n] */, int32_t* count /* [n] */, double* t /* [n] */,
+                     int32_t* refined /* [n] */, double* state /* [n][10] */, double* d2 /* [n] */, double* err /* [n][3]: e_lon, e_lat, e_yaw */);
+int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* rects /* [n][4] */, const double* t_from, const double* t_to /* NULL: to the end */,
+                     double dt, int32_t with_end, double* enter_t /* [n], NaN: none */, double* leave_t /* [n] */, int32_t* counts /* [n][2]: samples, inside */);
+/* milliseconds of the kernel(s) of the last uph_locate_batch or uph_within_batch of c, whichever came last (events on the context's stream) */
+int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
 // repository's image).  No Eigen header is included here.
 #pragma once
+#include <array>
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -554,6 +555,61 @@ public:
         if (uph_check_batch(ctx_, n, tr.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, lim7, out.first_t.data(),
                             out.first_mask.data(), out.counts.data(), out.worst.data(), out.worst_t.data()) != UPH_OK)
             throw std::runtime_error(std::string("uph_check_batch: ") + uph_last_error());
+        return out;
+    }
+    // where is each vehicle on its trajectory: pose poses[q] = (x, y, yaw) in map coordinates (odometry) located on trajectory traj[q] of this object's
+    // last batch among its samples with t in [t_from[q], t_to[q]] (t_to empty: to the end) -- the nearest sample, then the time refined between its
+    // neighbours, the state there and the tracking error (uph_locate_batch).  t is the t_now / t_switch of checkSE2TrajBatch / refineSE2TrajBatch /
+    // replanSE2TrajBatch; a large error says: plan again from the pose instead.
+    struct TrajLocate {
+        std::vector<double> near_t, near_d2;    // [n] the nearest sample and its squared distance
+        std::vector<int32_t> count;             // [n] samples in the window (0: t is NaN)
+        std::vector<double> t, d2;              // [n] the located time and the squared distance there
+        std::vector<int32_t> refined;           // [n] 0: the sample itself was kept
+        std::vector<double> state;              // [n][10] uph_traj_states' columns at t
+        std::vector<double> err;                // [n][3] e_lon, e_lat, e_yaw
+    };
+    TrajLocate locateSE2TrajBatch(const std::vector<int>& traj, const std::vector<std::array<double, 3>>& poses, const std::vector<double>& t_from,
+                                  const std::vector<double>& t_to = std::vector<double>(), double dt = 0.01, bool with_end = true) {
+        if (poses.size() != traj.size() || t_from.size() != traj.size() || (!t_to.empty() && t_to.size() != traj.size()))
+            throw std::runtime_error("locateSE2TrajBatch: traj, poses, t_from and t_to differ in number");
+        if (last_multi_) throw std::runtime_error("locateSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajLocate out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        std::vector<double> ps((size_t)3 * n);
+        for (int32_t q = 0; q < n; q++) for (int k = 0; k < 3; k++) ps[(size_t)3 * q + k] = poses[(size_t)q][k];
+        out.near_t.assign((size_t)n, 0.0); out.near_d2.assign((size_t)n, 0.0); out.count.assign((size_t)n, 0); out.t.assign((size_t)n, 0.0);
+        out.d2.assign((size_t)n, 0.0); out.refined.assign((size_t)n, 0); out.state.assign((size_t)10 * n, 0.0); out.err.assign((size_t)3 * n, 0.0);
+        if (uph_locate_batch(ctx_, n, tr.data(), ps.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, out.near_t.data(),
+                             out.near_d2.data(), out.count.data(), out.t.data(), out.refined.data(), out.state.data(), out.d2.data(), out.err.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_locate_batch: ") + uph_last_error());
+        return out;
+    }
+    // a region of the map changed (UnevenMapHandle's update: `changed`): which trajectories of the last batch have samples inside the closed rect
+    // rects[q] = (x0, x1, y0, y1) in map coordinates, with t in [t_from[q], t_to[q]], and when they enter and leave it (uph_within_batch).  Those are
+    // the ones to hand to checkSE2TrajBatch.
+    struct TrajWithin {
+        std::vector<double> enter_t, leave_t;   // [n] t of the first / last sample inside (NaN: none)
+        std::vector<int32_t> counts;            // [n][2] samples, inside
+        bool enters(size_t q) const { return counts[2 * q + 1] > 0; }
+    };
+    TrajWithin withinSE2TrajBatch(const std::vector<int>& traj, const std::vector<std::array<double, 4>>& rects, const std::vector<double>& t_from,
+                                  const std::vector<double>& t_to = std::vector<double>(), double dt = 0.01, bool with_end = true) {
+        if (rects.size() != traj.size() || t_from.size() != traj.size() || (!t_to.empty() && t_to.size() != traj.size()))
+            throw std::runtime_error("withinSE2TrajBatch: traj, rects, t_from and t_to differ in number");
+        if (last_multi_) throw std::runtime_error("withinSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajWithin out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        std::vector<double> rc((size_t)4 * n);
+        for (int32_t q = 0; q < n; q++) for (int k = 0; k < 4; k++) rc[(size_t)4 * q + k] = rects[(size_t)q][k];
+        out.enter_t.assign((size_t)n, 0.0); out.leave_t.assign((size_t)n, 0.0); out.counts.assign((size_t)2 * n, 0);
+        if (uph_within_batch(ctx_, n, tr.data(), rc.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, out.enter_t.data(),
+                             out.leave_t.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_within_batch: ") + uph_last_error());
         return out;
     }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)

@@ -1,0 +1,605 @@
+"""GPU tier of locating poses on resident trajectories and finding rect crossings (uph_locate_batch, uph_within_batch; uph_locate_kernel,
+uph_within_kernel).
+
+P1 (exact): near_t, near_d2, count, enter_t, leave_t, counts EQUAL (np.array_equal, NaN = NaN) the numpy mirrors locate_rows / within_rows applied to
+    the STATE rows the rollout writes for the same trajectory.
+P2 (exact): state equals traj_states(traj, t) bit for bit; lo <= t <= hi; d2 is the formula on state[:, :2] and the pose in numpy; d2 <= near_d2;
+    refined == 0 implies t == near_t.
+P3: where lo < t < hi, |g| <= G = 1e-9 max(1, |v|^2 + |e| |a|) in numpy from the state and the pose (1e-9: the per-evaluation bar of test_gpu_parity.py).
+P4: poses p(t0) + delta n(t0) are located at t0: |t - t0| h(t0) <= G(t0), where |v(t0)| >= 0.1 and h(t0) >= 0.5 |v(t0)|^2 (at most 25 % excluded).
+P5: err against its three formulas in numpy at 1e-9.
+P6: the loop -- locate feeds check and refine; within on update()'s changed rect selects the trajectories the rollout recipe selects.
+Source: 64 hill goals planned and solved by plan_goals (the fixture of test_gpu_check.py)."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_gpu_replan import _hill_map, _queries, _source
+from uneven_planner_amd import _lib
+from uneven_planner_amd.alm_traj_opt import locate_rows, norm_so2, within_rows
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INF = float("inf")
+LKEYS = ("near_t", "near_d2", "count")
+WKEYS = ("enter_t", "leave_t", "counts")
+ALLKEYS = LKEYS + ("t", "refined", "state", "d2", "err")
+MEASURED = {"g": 0.0, "t": 0.0, "err": 0.0}           # largest |g| / G, |t - t0| h / G and error difference seen (printed by the last test)
+
+
+def _valid(res):
+    return [j for j, r in enumerate(res) if r["ret"] != 4 and np.isfinite(r["c_xy"]).all() and np.isfinite([r["T_xy"], r["T_yaw"]]).all()]
+
+
+def _ref(opt, dt, with_end):
+    return opt.rollout(dt, 1, with_end=bool(with_end))
+
+
+def _bc(v, n, default):
+    return np.broadcast_to(default if v is None else np.asarray(v, dtype=np.float64), (n,))
+
+
+def _expect_locate(ref, traj, poses, t_from=None, t_to=None):
+    offs, rows = ref
+    n = len(traj)
+    poses = np.broadcast_to(np.asarray(poses, dtype=np.float64), (n, 3))
+    tf, tt = _bc(t_from, n, 0.0), _bc(t_to, n, INF)
+    per = [locate_rows(rows[int(offs[b]):int(offs[b + 1]), 0], rows[int(offs[b]):int(offs[b + 1]), 1:3], poses[q], tf[q], tt[q]) for q, b in enumerate(traj)]
+    out = {k: np.array([p[k] for p in per]) for k in LKEYS}
+    out["lo"] = np.array([p["times"][max(p["j"] - 1, 0)] if p["count"] else np.nan for p in per])
+    out["hi"] = np.array([p["times"][min(p["j"] + 1, p["count"] - 1)] if p["count"] else np.nan for p in per])
+    return out
+
+
+def _expect_within(ref, traj, rects, t_from=None, t_to=None):
+    offs, rows = ref
+    n = len(traj)
+    rects = np.broadcast_to(np.asarray(rects, dtype=np.float64), (n, 4))
+    tf, tt = _bc(t_from, n, 0.0), _bc(t_to, n, INF)
+    per = [within_rows(rows[int(offs[b]):int(offs[b + 1]), 0], rows[int(offs[b]):int(offs[b + 1]), 1:3], rects[q], tf[q], tt[q]) for q, b in enumerate(traj)]
+    return {k: np.array([p[k] for p in per]) for k in WKEYS}
+
+
+def _same(got, want, keys, tag=""):
+    for k in keys:
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape, (tag, k, g.shape, w.shape)
+        if not np.array_equal(g, w, equal_nan=g.dtype.kind == "f"):
+            bad = np.argwhere(~((g == w) | ((g != g) & (w != w))))
+            assert False, (tag, k, len(bad), bad[:4].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
+
+
+def _bar(v, e, a):
+    return 1e-9 * np.maximum(1.0, (v * v).sum(axis=1) + np.hypot(e[:, 0], e[:, 1]) * np.hypot(a[:, 0], a[:, 1]))
+
+
+def _properties(opt, got, want, traj, poses, tag=""):
+    """P2, P3 and P5 on the result `got` of a locate() whose coarse stage equals `want` (P1)"""
+    traj = np.asarray(traj, dtype=np.int32)
+    n = len(traj)
+    poses = np.broadcast_to(np.asarray(poses, dtype=np.float64), (n, 3))
+    some = got["count"] > 0
+    empty = ~some
+    assert np.isnan(got["t"][empty]).all() and np.isnan(got["near_t"][empty]).all() and (got["d2"][empty] == INF).all() and (got["near_d2"][empty] == INF).all()
+    assert (got["refined"][empty] == 0).all() and np.isnan(got["state"][empty]).all() and np.isnan(got["err"][empty]).all()
+    if not some.any():
+        return
+    t, st, ps = got["t"][some], got["state"][some], poses[some]
+    assert np.array_equal(st, opt.traj_states(traj[some], t), equal_nan=True), tag
+    assert (want["lo"][some] <= t).all() and (t <= want["hi"][some]).all(), tag
+    with np.errstate(over="ignore", invalid="ignore"):
+        ex, ey = st[:, 0] - ps[:, 0], st[:, 1] - ps[:, 1]
+        d2 = ex * ex + ey * ey
+    assert np.array_equal(got["d2"][some], d2, equal_nan=True), tag
+    assert (got["d2"][some] <= got["near_d2"][some]).all(), tag
+    kept = got["refined"][some] == 0
+    assert np.isin(got["refined"], (0, 1)).all() and np.array_equal(t[kept], got["near_t"][some][kept]), tag
+    e = np.stack([ex, ey], axis=1)
+    fin = np.isfinite(d2)
+    with np.errstate(over="ignore", invalid="ignore"):
+        g = np.abs(ex * st[:, 2] + ey * st[:, 3])
+        G = _bar(st[:, 2:4], e, st[:, 4:6])
+    inner = (want["lo"][some] < t) & (t < want["hi"][some]) & fin
+    if inner.any():
+        MEASURED["g"] = max(MEASURED["g"], float((g[inner] / G[inner]).max()))
+        print("P3 %s: %d interior, largest |g| / G = %.3g" % (tag, int(inner.sum()), (g[inner] / G[inner]).max()))
+        assert (g[inner] <= G[inner]).all(), (tag, float((g[inner] / G[inner]).max()))
+    psi = st[:, 9]
+    rx, ry = -ex, -ey
+    err = np.stack([rx * np.cos(psi) + ry * np.sin(psi), ry * np.cos(psi) - rx * np.sin(psi), np.array([norm_so2(v) for v in ps[:, 2] - psi])], axis=1)
+    if fin.any():
+        diff = float(np.abs(got["err"][some][fin] - err[fin]).max())
+        MEASURED["err"] = max(MEASURED["err"], diff)
+        print("P5 %s: largest error difference = %.3g" % (tag, diff))
+        assert diff <= 1e-9, (tag, diff)
+
+
+def _poses_near(ref, traj, rng, spread=0.1):
+    """one pose per query near a random row of the middle 80 % of its trajectory: odometry of a vehicle that tracks it to about `spread` metres"""
+    offs, rows = ref
+    out = []
+    for b in traj:
+        a, e = int(offs[b]), int(offs[b + 1])
+        r = rows[int(rng.integers(a + (e - a) // 10, e - (e - a) // 10))]
+        out.append([r[1] + rng.normal(0.0, spread), r[2] + rng.normal(0.0, spread), r[3] + rng.normal(0.0, 0.3)])
+    return np.array(out)
+
+
+def _rects_near(ref, traj, rng):
+    offs, rows = ref
+    out = []
+    for b in traj:
+        r = rows[int(rng.integers(int(offs[b]), int(offs[b + 1])))]
+        w = rng.uniform(0.05, 1.5, 2)
+        out.append([r[1] - w[0], r[1] + w[0], r[2] - w[1], r[2] + w[1]])
+    return np.array(out)
+
+
+def _both(opt, ref, traj, poses, rects, t_from=None, t_to=None, dt=0.01, with_end=1, tag=""):
+    """locate and within through the binding, held to P1, P2, P3 and P5"""
+    tf = 0.0 if t_from is None else t_from
+    got = opt.locate(traj, poses, tf, t_to, dt=dt, with_end=with_end)
+    want = _expect_locate(ref, traj, poses, t_from, t_to)
+    _same(got, want, LKEYS, tag)
+    _properties(opt, got, want, traj, poses, tag)
+    w = opt.within(traj, rects, tf, t_to, dt=dt, with_end=with_end)
+    _same(w, _expect_within(ref, traj, rects, t_from, t_to), WKEYS, tag)
+    return got, w
+
+
+@pytest.fixture(scope="module")
+def hill():
+    import uneven_planner_amd as U
+    m = _hill_map()
+    ka = U.KinoAstar(m)
+    S, G = _queries(m, 64, 14000)
+    src, res = _source(m, ka, S, G)
+    ok = np.array(_valid(res), dtype=np.int32)
+    assert len(ok) >= 40, len(ok)
+    refs = {(dt, we): _ref(src, dt, we) for dt in (0.01, 0.03) for we in (0, 1)}
+    return dict(m=m, ka=ka, S=S, G=G, src=src, res=res, ok=ok, refs=refs)
+
+
+@pytest.mark.parametrize("with_end", [0, 1])
+@pytest.mark.parametrize("dt", [0.01, 0.03])
+def test_full_windows_equal_the_rollout_bit_for_bit(hill, dt, with_end):
+    src, ok, ref = hill["src"], hill["ok"], hill["refs"][(dt, with_end)]
+    rng = np.random.default_rng(17)
+    got, w = _both(src, ref, ok, _poses_near(ref, ok, rng), _rects_near(ref, ok, rng), dt=dt, with_end=with_end, tag="full %g %d" % (dt, with_end))
+    assert (got["count"] == np.diff(ref[0])[ok]).all() and (got["count"] > 50).all() and (w["counts"][:, 0] == got["count"]).all()
+    assert (got["refined"] == 1).sum() >= len(ok) // 2 and (w["counts"][:, 1] > 0).all() and (w["counts"][:, 1] < w["counts"][:, 0]).any()
+    assert src.locate_kernel_ms() > 0.0
+
+
+@pytest.mark.parametrize("dt,with_end", [(0.01, 0), (0.03, 1)])
+def test_windows(hill, dt, with_end):
+    """t_from / t_to at 0, negative, exactly a row's t, between two rows, the total, beyond it, reversed, infinite: the literally selected rows"""
+    src, ok, ref = hill["src"], hill["ok"][:12], hill["refs"][(dt, with_end)]
+    offs, rows = ref
+    rng = np.random.default_rng(23)
+    tr, tf, tt, ps, rc = [], [], [], [], []
+    for b in ok:
+        blk = rows[int(offs[b]):int(offs[b + 1])]
+        t = blk[:, 0]
+        e1 = hill["refs"][(dt, 1)]
+        total = e1[1][int(e1[0][b + 1]) - 1, 0]
+        assert t.shape[0] > 40
+        h = lambda i: 0.5 * (t[i] + t[i + 1])
+        win = [(0.0, total), (0.0, 0.0), (-0.5, t[5]), (-2.0, -1.0), (t[3], t[10]), (t[7], t[7]), (np.nextafter(t[3], 9.0), np.nextafter(t[10], -9.0)),
+               (h(3), h(10)), (h(6), h(6)), (t[-2], total), (total, total), (np.nextafter(total, 0.0), total), (h(20), total + 5.0),
+               (total + 1.0, total + 2.0), (np.nextafter(total, 99.0), INF), (t[10], t[3]), (t[4], INF), (0.0, -INF), (-1e300, 1e300)]
+        for k, (a, e) in enumerate(win):
+            r = blk[[0, 4, 8, 20, t.shape[0] - 1][k % 5]]
+            tr.append(b), tf.append(a), tt.append(e)
+            ps.append([r[1] + rng.normal(0.0, 0.05), r[2] + rng.normal(0.0, 0.05), r[3]])
+            rc.append([r[1] - 0.3, r[1] + 0.3, r[2] - 0.3, r[2] + 0.3])
+    tr = np.array(tr, dtype=np.int32)
+    got, w = _both(src, ref, tr, ps, rc, tf, tt, dt=dt, with_end=with_end, tag="windows")
+    nw = len(tr) // len(ok)
+    c = got["count"][:nw].tolist()
+    assert c[1] == 1 and c[2] == 6 and c[3] == 0 and c[4] == 8 and c[5] == 1 and c[6] == 6 and c[7] == 7 and c[8] == 0 and c[10] == with_end
+    assert c[13] == 0 and c[14] == 0 and c[15] == 0 and c[17] == 0 and c[0] == c[18] == int(offs[ok[0] + 1] - offs[ok[0]])
+    assert (got["count"] == 0).sum() >= 5 * len(ok) and np.array_equal(w["counts"][:, 0], got["count"])
+    # t_to = None is "to the end"
+    g2 = src.locate(tr, ps, tf, None, dt=dt, with_end=with_end)
+    _same(g2, _expect_locate(ref, tr, ps, tf, None), LKEYS, "t_to None")
+    _same(src.within(tr, rc, tf, None, dt=dt, with_end=with_end), _expect_within(ref, tr, rc, tf, None), WKEYS, "t_to None")
+
+
+def test_lane_and_wave_tails(hill):
+    """windows of 1 .. 513 samples whose winner -- the pose sits exactly on that row -- or only inside sample (a rect that is that row's point) is first,
+    last, at index 64 or at index 256 of the window: the strided walk of 64 and of 256 lanes, both sides of the length at which the launch is split,
+    and the row / wave / workgroup levels of the reduction"""
+    src, ok, ref = hill["src"], hill["ok"], hill["refs"][(0.01, 0)]
+    offs, rows = ref
+    long = [int(b) for b in ok if offs[b + 1] - offs[b] >= 700]
+    assert len(long) >= 4
+    tr, tf, tt, ps, rc, at, ns = [], [], [], [], [], [], []
+    for n in (1, 2, 63, 64, 65, 191, 192, 193, 255, 256, 257, 513):
+        for p in sorted({0, n - 1, 64, 256}):
+            if p >= n:
+                continue
+            b = long[(n + p) % len(long)]
+            blk = rows[int(offs[b]):int(offs[b + 1])]
+            i0 = 90 + (n + p) % 7                                    # away from the start, where a vehicle at rest repeats its position
+            win = blk[i0:i0 + n]
+            r = win[p]
+            if ((win[:, 1] == r[1]) & (win[:, 2] == r[2])).sum() != 1:
+                continue
+            tr.append(b), tf.append(win[0, 0]), tt.append(win[-1, 0]), ps.append([r[1], r[2], r[3]]), rc.append([r[1], r[1], r[2], r[2]])
+            at.append(r[0]), ns.append(n)
+    assert len(tr) >= 28
+    got, w = _both(src, ref, np.array(tr, dtype=np.int32), ps, rc, tf, tt, dt=0.01, with_end=0, tag="tails")
+    at, ns = np.array(at), np.array(ns)
+    assert np.array_equal(got["count"], ns) and np.array_equal(got["near_t"], at) and (got["near_d2"] == 0.0).all()
+    assert np.array_equal(got["t"], at) and (got["d2"] == 0.0).all() and (got["refined"] == 1).all()
+    assert np.array_equal(w["enter_t"], at) and np.array_equal(w["leave_t"], at) and np.array_equal(w["counts"], np.stack([ns, np.ones_like(ns)], axis=1))
+    # one at a time answers the same (a launch of one kind of workgroup only)
+    for q in (0, len(tr) - 1):
+        one = src.locate([tr[q]], [ps[q]], tf[q], tt[q], dt=0.01, with_end=0)
+        for k in ALLKEYS:
+            assert np.array_equal(one[k][0], got[k][q], equal_nan=True), (q, k)
+
+
+def test_a_pose_at_1e200_ties_at_inf_and_sample_0_wins(hill):
+    src, ok, ref = hill["src"], hill["ok"][:16], hill["refs"][(0.01, 1)]
+    offs, rows = ref
+    poses = np.array([[1e200, 0.0, 0.0], [-1e200, 1e200, 1.0], [0.0, -1e200, -2.0], [1e200, 1e200, 0.0]])[np.arange(len(ok)) % 4]
+    tf = np.where(np.arange(len(ok)) % 2 == 0, 0.0, 1.2345)
+    got = src.locate(ok, poses, tf)
+    want = _expect_locate(ref, ok, poses, tf)
+    _same(got, want, LKEYS, "1e200")
+    _properties(src, got, want, ok, poses, "1e200")
+    first = np.array([rows[int(offs[b]):int(offs[b + 1]), 0][rows[int(offs[b]):int(offs[b + 1]), 0] >= tf[q]][0] for q, b in enumerate(ok)])
+    assert (got["near_d2"] == INF).all() and (got["d2"] == INF).all() and np.array_equal(got["near_t"], first) and (got["count"] > 100).all()
+
+
+def test_duplicates_and_query_order(hill):
+    src, ok, ref = hill["src"], hill["ok"], hill["refs"][(0.03, 1)]
+    rng = np.random.default_rng(3)
+    tr = np.concatenate([ok, ok[:9], np.repeat(ok[4], 5)]).astype(np.int32)
+    tf = rng.uniform(0.0, 2.0, tr.size)
+    tt = tf + rng.uniform(0.0, 6.0, tr.size)
+    ps, rc = _poses_near(ref, tr, rng), _rects_near(ref, tr, rng)
+    for a in (tf, tt, ps, rc):
+        a[-5:] = a[4]
+    got, w = _both(src, ref, tr, ps, rc, tf, tt, dt=0.03, tag="duplicates")
+    for k in ALLKEYS:
+        assert np.array_equal(got[k][-5:], np.repeat(got[k][4:5], 5, axis=0), equal_nan=True), k
+    perm = rng.permutation(tr.size)
+    sh = src.locate(tr[perm], ps[perm], tf[perm], tt[perm], dt=0.03)
+    for k in ALLKEYS:
+        assert np.array_equal(sh[k], got[k][perm], equal_nan=True), k
+    shw = src.within(tr[perm], rc[perm], tf[perm], tt[perm], dt=0.03)
+    for k in WKEYS:
+        assert np.array_equal(shw[k], w[k][perm], equal_nan=True), k
+
+
+def test_local_frames_and_fp32_cells():
+    """a grid beyond FRAME_EXTENT (every trajectory solved in its own local frame, poses and rects in map coordinates) and an fp32-cell map"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    big = U.UnevenMap(dict(map_size_x=160.0, map_size_y=160.0, xy_resolution=0.25)).fill_fbm()
+    nx, ny = int(big.voxel_num[0]), int(big.voxel_num[1])
+    far, seed = [], 7300
+    while len(far) < 6:
+        p = scenes.local_problems(1, seed0=seed, half=75.0, dmin=4.0, dmax=9.0, occ_r2=big.occ_r2_buffer, grid=(nx, ny, big.xy_resolution, big.map_origin[0], big.map_origin[1]))[0]
+        seed += 1
+        if max(abs(p["init_xy"][0, 0]), abs(p["init_xy"][1, 0])) > 45.0:
+            far.append(p)
+    m32 = U.UnevenMap(dict(map_size_x=32.0, map_size_y=32.0, xy_resolution=0.25), storage="f32").fill_fbm(dict(patch_lambda=5.0, rough_threshold=0.5))
+    nx, ny = int(m32.voxel_num[0]), int(m32.voxel_num[1])
+    p32 = scenes.local_problems(6, seed0=5000, half=14.0, dmin=4.0, dmax=12.0, occ_r2=m32.occ_r2_buffer,
+                                grid=(nx, ny, m32.xy_resolution, m32.map_origin[0], m32.map_origin[1]))
+    rng = np.random.default_rng(29)
+    for tag, m, probs in (("frames", big, far), ("f32", m32, p32)):
+        opt = U.ALMTrajOpt(m)
+        opt.set_rho(1.0)
+        opt.optimize_batch(probs)
+        tr = np.arange(len(probs), dtype=np.int32)
+        for dt, we in ((0.01, 0), (0.03, 1)):
+            ref = _ref(opt, dt, we)
+            if tag == "frames":
+                assert np.abs(ref[1][:, 1:3]).max() > 45.0
+            ps, rc = _poses_near(ref, tr, rng), _rects_near(ref, tr, rng)
+            got, w = _both(opt, ref, tr, ps, rc, dt=dt, with_end=we, tag=tag)
+            assert (got["count"] > 30).all() and (got["near_d2"] < 1.0).all() and (w["counts"][:, 1] > 0).all()
+            t1 = ref[1][ref[0][1:] - 1, 0]
+            _both(opt, ref, tr, ps, rc, 0.3 * t1, 0.7 * t1, dt=dt, with_end=we, tag=tag + " windows")
+
+
+def _known(src, ok, rng, per, deltas, lo=0.2, hi=0.8):
+    """queries of P4: per trajectory `per` times t0 uniform in [lo, hi] of its duration, each with the poses p(t0) + delta n(t0)"""
+    total = src.rollout(1.0, 1, with_end=True)
+    total = total[1][total[0][1:] - 1, 0][ok]
+    tr = np.repeat(ok, per)
+    t0 = rng.uniform(lo, hi, tr.size) * np.repeat(total, per)
+    s0 = src.traj_states(tr, t0)
+    v = s0[:, 2:4]
+    speed = np.hypot(v[:, 0], v[:, 1])
+    nrm = np.stack([-v[:, 1], v[:, 0]], axis=1) / np.maximum(speed, 1e-300)[:, None]
+    out = []
+    for d in deltas:
+        ps = np.concatenate([s0[:, :2] + d * nrm, s0[:, 9:10]], axis=1)
+        e0 = s0[:, :2] - ps[:, :2]
+        h0 = (v * v).sum(axis=1) + (e0 * s0[:, 4:6]).sum(axis=1)
+        use = (speed >= 0.1) & (h0 >= 0.5 * speed * speed)
+        out.append(dict(tr=tr, t0=t0, ps=ps, h0=h0, G0=_bar(v, e0, s0[:, 4:6]), use=use, delta=d))
+    return out
+
+
+def _held_to_t0(src, k, tag):
+    got = src.locate(k["tr"], k["ps"], k["t0"] - 0.5, k["t0"] + 0.5)
+    use = k["use"]
+    ratio = np.abs(got["t"] - k["t0"])[use] * k["h0"][use] / k["G0"][use]
+    MEASURED["t"] = max(MEASURED["t"], float(ratio.max()))
+    print("P4 %s: %d of %d compared, largest |t - t0| h / G = %.3g, refined %d" % (tag, int(use.sum()), use.size, ratio.max(), int(got["refined"][use].sum())))
+    assert (~use).sum() <= 0.25 * use.size, (tag, int((~use).sum()), use.size)
+    assert (ratio <= 1.0).all(), (tag, float(ratio.max()), int((ratio > 1.0).sum()))
+    return got
+
+
+def test_known_answers(hill):
+    """P4.  The windows t0 +- 0.5 s at dt = 0.01 hold 100 or 101 samples: the tracking workload"""
+    src, ok, ref = hill["src"], hill["ok"], hill["refs"][(0.01, 1)]
+    for k in _known(src, ok, np.random.default_rng(41), 3, (0.05, -0.05, 0.2, -0.2)):
+        got = _held_to_t0(src, k, "delta %+g" % k["delta"])
+        want = _expect_locate(ref, k["tr"], k["ps"], k["t0"] - 0.5, k["t0"] + 0.5)
+        _same(got, want, LKEYS, "known")
+        _properties(src, got, want, k["tr"], k["ps"], "known %+g" % k["delta"])
+        assert (got["count"] <= 102).all() and np.median(got["count"]) >= 100
+        # the tracking error of a pose on the normal: delta across (to the left of the velocity: positive), the heading as the trajectory's
+        u = k["use"]
+        assert np.abs(np.hypot(got["err"][u, 0], got["err"][u, 1]) - abs(k["delta"])).max() <= 1e-6
+        assert np.abs(got["err"][u, 2]).max() <= 1e-6
+
+
+def test_the_loop_from_odometry_and_a_scan(hill):
+    """P6: poses taken from the trajectories at known times are located at those times; t feeds check(t_from=) and refine.  Then a scan of a box:
+    within() on update()'s changed rect with two cells of margin selects exactly the trajectories the rollout recipe of INTEGRATION.md 3f selects"""
+    import uneven_planner_amd as U
+    from map_update_cases import scan
+    m, src, ok = hill["m"], hill["src"], hill["ok"]
+    k = _known(src, ok, np.random.default_rng(43), 1, (0.0,))[0]
+    got = _held_to_t0(src, k, "on the trajectory")
+    t_now = got["t"]
+    assert np.isfinite(t_now).all() and (got["d2"][k["use"]] <= 1e-12).all()
+    chk = src.check(k["tr"], t_from=t_now)
+    ref = src.check(k["tr"], t_from=k["t0"])
+    assert (np.abs(chk["counts"][:, 0] - ref["counts"][:, 0]) <= 1).all() and (chk["counts"][:, 0] > 0).all()
+    dst = U.ALMTrajOpt(m)
+    dst.set_rho(1.0)
+    up = dst.refine_upload(src, k["tr"], t_now)
+    assert (up["status"] == 0).all() and np.array_equal(up["switch_states"], got["state"])
+    # a scan with a mound under one trajectory
+    live = np.array([j for j, r in enumerate(hill["res"]) if r["ret"] != 4], dtype=np.int32)
+    offs, rows = src.rollout(0.05, channels=1)
+    mine = rows[int(offs[ok[0]]):int(offs[ok[0] + 1])]
+    p0 = mine[mine.shape[0] // 2, 1:3].copy()
+    box = (p0[0] - 0.5, p0[0] + 0.5, p0[1] - 0.5, p0[1] + 0.5)
+    info = m.update(box, scan(box, seed=14, n_side=50, mound=0.35, sigma=0.09, centre=(p0[0] + 0.07, p0[1] + 0.07), extras=False))
+    assert info["n_changed"] > 0
+    cx0, cx1, cy0, cy1 = info["changed"]
+    lo = m.map_origin[:2] + (np.array([cx0, cy0]) - 2) * m.xy_resolution
+    hi = m.map_origin[:2] + (np.array([cx1, cy1]) + 2) * m.xy_resolution
+    hit = [b for b in range(len(offs) - 1) if ((rows[offs[b]:offs[b + 1], 1:3] >= lo) & (rows[offs[b]:offs[b + 1], 1:3] <= hi)).all(axis=1).any()]
+    w = src.within(live, [lo[0], hi[0], lo[1], hi[1]], dt=0.05, with_end=False)
+    assert live[w["counts"][:, 1] > 0].tolist() == hit and int(ok[0]) in hit and len(hit) < len(live)
+    _same(w, _expect_within((offs, rows), live, [lo[0], hi[0], lo[1], hi[1]]), WKEYS, "changed rect")
+    sel = live[w["counts"][:, 1] > 0]
+    again = src.check(sel, t_from=w["enter_t"][w["counts"][:, 1] > 0] - 0.5)
+    assert (again["counts"][:, 0] > 0).all()
+    print("measured: largest |g| / G = %.3g, largest |t - t0| h / G = %.3g, largest error difference = %.3g" % (MEASURED["g"], MEASURED["t"], MEASURED["err"]))
+
+
+def _raw(c, fn, tr, rows, tf, tt=None, dt=0.01, with_end=1, n=None, null=()):
+    tr = np.ascontiguousarray(tr, dtype=np.int32)
+    tf = np.ascontiguousarray(tf, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    tt = None if tt is None else np.ascontiguousarray(tt, dtype=np.float64)
+    n = tr.size if n is None else n
+    m = max(1, tr.size)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    dp = lambda a: a.ctypes.data_as(_lib.DP)
+    head = (c.h if "ctx" not in null else None, n, None if "traj" in null else ip(tr), None if "rows" in null else dp(rows), None if "t_from" in null else dp(tf),
+            None if tt is None else dp(tt), dt, with_end)
+    if fn == "locate":
+        o = dict(near_t=np.full(m, -9.0), near_d2=np.full(m, -9.0), count=np.full(m, -9, dtype=np.int32), t=np.full(m, -9.0),
+                 refined=np.full(m, -9, dtype=np.int32), state=np.full((m, 10), -9.0), d2=np.full(m, -9.0), err=np.full((m, 3), -9.0))
+        rc = c.L.uph_locate_batch(*head, dp(o["near_t"]), dp(o["near_d2"]), ip(o["count"]), dp(o["t"]), ip(o["refined"]), dp(o["state"]), dp(o["d2"]), dp(o["err"]))
+    else:
+        o = dict(enter_t=np.full(m, -9.0), leave_t=np.full(m, -9.0), counts=np.full((m, 2), -9, dtype=np.int32))
+        rc = c.L.uph_within_batch(*head, dp(o["enter_t"]), dp(o["leave_t"]), ip(o["counts"]))
+    return rc, o
+
+
+def test_refusals(hill):
+    """each refusal of include/uneven_hip.h: UPH_ERR_INVALID (UPH_ERR_LIMIT for too many samples) with every output as it was pre-filled"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    m, ka, src, ok = hill["m"], hill["ka"], hill["src"], hill["ok"]
+    F = src.L.uph_batch_count(src.h)
+    untouched = lambda o: all((o[k] == -9).all() for k in o)
+    tr = ok[:4]
+    z4 = np.zeros(4)
+    nan = float("nan")
+    fresh = U.ALMTrajOpt(m)
+    fresh.plan_goals_upload(ka, hill["S"][:8], hill["G"][:8])                 # uploaded, not solved: no resident trajectory
+    probs = scenes.random_problems(3, seed0=2100)                              # an UPH_RET_UNSUPPORTED slot: a problem beyond UPH_MAX_PIECE_XY next to ordinary ones
+    big = dict(probs[0])
+    big["inner_xy"] = np.linspace([0.0, 0.0], [3.0, 0.5], 140).T.copy()
+    big["inner_yaw"] = np.zeros(140)
+    uns = U.ALMTrajOpt(m)
+    uns.set_rho(1.0)
+    assert uns.optimize_batch(probs + [big])[3]["ret"] == 4
+    src2, _ = _source(m, ka, hill["S"][:32], hill["G"][:32])
+    for fn, width in (("locate", 3), ("within", 4)):
+        good = np.tile(np.array([0.5, 1.5, 0.25, 1.25])[:width], (4, 1))
+
+        def refused(rc, o, what, code=-1):
+            assert rc == code and untouched(o), (fn, what, rc)
+
+        for null in (("ctx",), ("traj",), ("rows",), ("t_from",)):
+            refused(*_raw(src, fn, tr, good, z4, null=null), null)
+        refused(*_raw(src, fn, tr, good, z4, n=0), "n = 0")
+        refused(*_raw(src, fn, tr, good, z4, n=-3), "n < 0")
+        for dt in (0.0, -0.01, INF, nan):
+            refused(*_raw(src, fn, tr, good, z4, dt=dt), ("dt", dt))
+        refused(*_raw(fresh, fn, [0], good[:1], [0.0]), "not resident")
+        assert b"resident" in src.L.uph_last_error()
+        refused(*_raw(U.ALMTrajOpt(m), fn, [0], good[:1], [0.0]), "no batch")
+        for bad in ([F], [-1], [int(ok[0]), F + 7]):
+            refused(*_raw(src, fn, bad, good[:len(bad)], [0.5] * len(bad)), ("index", bad))
+        for t in (nan, INF, -INF):
+            refused(*_raw(src, fn, tr, good, [0.1, t, 0.2, 0.3]), ("t_from", t))
+        refused(*_raw(src, fn, tr, good, z4, [1.0, 2.0, nan, 3.0]), "NaN t_to")
+        for t in (INF, -INF):                                                   # an infinite t_to is a window
+            rc, o = _raw(src, fn, tr, good, z4, [1.0, t, 2.0, 3.0])
+            cnt = o["count"][1] if fn == "locate" else o["counts"][1, 0]
+            assert rc == 0 and not untouched(o) and cnt == (0 if t < 0 else np.diff(hill["refs"][(0.01, 1)][0])[tr[1]])
+        for col in range(width):                                                # a NaN anywhere in the pose / rect
+            bad = good.copy()
+            bad[2, col] = nan
+            refused(*_raw(src, fn, tr, bad, z4), ("NaN row", col))
+            assert (b"pose" if fn == "locate" else b"rect") in src.L.uph_last_error()
+        for v in (INF, -INF):                                                   # an infinite pose is refused, an infinite rect bound is a half plane
+            bad = good.copy()
+            bad[1, 1] = v
+            rc, o = _raw(src, fn, tr, bad, z4)
+            if fn == "locate":
+                refused(rc, o, ("pose", v))
+            else:
+                assert rc == 0 and (o["counts"][:, 0] > 0).all()
+        refused(*_raw(src, fn, tr, good, z4, dt=1e-6), "too many samples", code=_lib.UPH_ERR_LIMIT)
+        refused(*_raw(uns, fn, [0, 3], good[:2], [0.0, 0.0]), "unsupported slot")
+        assert b"UNSUPPORTED" in src.L.uph_last_error()
+        assert _raw(uns, fn, [0, 1, 2], good[:3], np.zeros(3))[0] == 0
+        src2.solve_async()                                                      # an asynchronous solve pending
+        rc, o = _raw(src2, fn, [0], good[:1], [0.0])
+        src2.wait()
+        refused(rc, o, "pending")
+        assert b"in flight" in src.L.uph_last_error()
+    # any output pointer may be NULL
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    one, ps = np.full(4, -9, dtype=np.int32), np.zeros((4, 3))
+    assert src.L.uph_locate_batch(src.h, 4, ip(tr), ps.ctypes.data_as(_lib.DP), z4.ctypes.data_as(_lib.DP), None, 0.01, 1, None, None, ip(one), None, None,
+                                  None, None, None) == 0
+    assert np.array_equal(one, src.locate(tr, ps)["count"])
+    rc4 = np.tile([-INF, INF, -INF, INF], (4, 1))
+    assert src.L.uph_within_batch(src.h, 4, ip(tr), rc4.ctypes.data_as(_lib.DP), z4.ctypes.data_as(_lib.DP), None, 0.01, 1, None, None, None) == 0
+    w = src.within(tr, rc4)
+    assert np.array_equal(w["counts"][:, 0], one) and np.array_equal(w["counts"][:, 1], one) and (w["enter_t"] == 0.0).all()
+
+
+CPP = r"""
+#include "uneven_hip_adapter.hpp"
+#include <array>
+#include <cstdio>
+using namespace uneven_hip;
+int main(int argc, char** argv) {
+    // in: {ncell, B}, cells, B x {start, goal, fractions of the planned duration the window starts and ends at}
+    FILE* f = std::fopen(argv[1], "rb");
+    long long hdr[2];
+    if (!f || fread(hdr, 8, 2, f) != 2) return 2;
+    std::vector<double> cells((size_t)hdr[0] * 4), sg((size_t)hdr[1] * 8);
+    if (fread(cells.data(), 8, cells.size(), f) != cells.size() || fread(sg.data(), 8, sg.size(), f) != sg.size()) return 2;
+    std::fclose(f);
+    uph_map_params mp = {2, 10.0, 10.0, 0.2, 0.1, 0.1, 0.05, 0.1, 0.8, 0.05, 9.81};
+    UnevenMapHandle map(mp, 0);
+    map.setCells(cells.data());
+    KinoAstar kino;
+    kino.setEnvironment(&map);
+    ALMTrajOpt opt;
+    opt.setEnvironment(&map);
+    std::vector<std::array<double, 3>> starts((size_t)hdr[1]), goals((size_t)hdr[1]);
+    for (long long b = 0; b < hdr[1]; b++) for (int k = 0; k < 3; k++) { starts[b][k] = sg[8 * b + k]; goals[b][k] = sg[8 * b + 3 + k]; }
+    uph_manager_params mgr{0.3, 0.5, 1.2, 2.0, 0.05, 0, 0.5};
+    ALMTrajOpt::GoalPlan p = opt.planSE2TrajBatch(kino, starts, goals, mgr);
+    std::vector<int> traj;
+    std::vector<double> tf, tt;
+    std::vector<std::array<double, 3>> poses;
+    std::vector<std::array<double, 4>> rects;
+    for (long long b = 0; b < hdr[1]; b++)
+        if (p.traj_of[b] >= 0 && p.ret[b] != UPH_RET_UNSUPPORTED) {
+            traj.push_back(p.traj_of[b]); tf.push_back(sg[8 * b + 6] * p.total_time[b]); tt.push_back(sg[8 * b + 7] * p.total_time[b]);
+            poses.push_back({goals[b][0] + 0.1, goals[b][1] - 0.05, goals[b][2] + 0.2});        // a pose near the goal, a rect around the start
+            rects.push_back({starts[b][0] - 1.0, starts[b][0] + 1.0, starts[b][1] - 1.0, starts[b][1] + 1.0});
+        }
+    const ALMTrajOpt::TrajLocate a = opt.locateSE2TrajBatch(traj, poses, tf, tt);                // every 0.01 s, with the end point
+    const ALMTrajOpt::TrajLocate c = opt.locateSE2TrajBatch(traj, poses, tf, {}, 0.03, false);
+    const ALMTrajOpt::TrajWithin w = opt.withinSE2TrajBatch(traj, rects, tf, tt);
+    const ALMTrajOpt::TrajWithin x = opt.withinSE2TrajBatch(traj, rects, tf, {}, 0.03, false);
+    // out: n, per query traj, t_from, t_to; the two locate results (19 doubles per query), the two within results (4 per query)
+    FILE* o = std::fopen(argv[2], "wb");
+    double n = (double)traj.size();
+    fwrite(&n, 8, 1, o);
+    for (size_t k = 0; k < traj.size(); k++) { double q[3] = {(double)traj[k], tf[k], tt[k]}; fwrite(q, 8, 3, o); }
+    for (const ALMTrajOpt::TrajLocate* r : {&a, &c})
+        for (size_t q = 0; q < traj.size(); q++) {
+            double h[6] = {r->near_t[q], r->near_d2[q], (double)r->count[q], r->t[q], (double)r->refined[q], r->d2[q]};
+            fwrite(h, 8, 6, o);
+            fwrite(r->state.data() + 10 * q, 8, 10, o);
+            fwrite(r->err.data() + 3 * q, 8, 3, o);
+        }
+    for (const ALMTrajOpt::TrajWithin* r : {&w, &x})
+        for (size_t q = 0; q < traj.size(); q++) {
+            double h[4] = {r->enter_t[q], r->leave_t[q], (double)r->counts[2 * q], (double)r->counts[2 * q + 1]};
+            fwrite(h, 8, 4, o);
+        }
+    std::fclose(o);
+    return 0;
+}
+"""
+
+
+def test_cpp_adapter_matches_ctypes_bit_for_bit(tmp_path, analytic_cells):
+    """ALMTrajOpt::locateSE2TrajBatch / withinSE2TrajBatch from a compiled C++ consumer (after planSE2TrajBatch) against plan_goals + locate / within
+    through ctypes"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    m = U.UnevenMap()
+    m.set_cells(analytic_cells)
+    ka = U.KinoAstar(m)
+    S, G = scenes.random_queries(24, seed0=9900)
+    f0 = np.array([[0.0, 0.3, 0.5, -0.2, 0.95, 0.6][b % 6] for b in range(S.shape[0])])
+    f1 = np.array([[1.0, 0.6, 2.0, 0.4, 1.0, 0.5][b % 6] for b in range(S.shape[0])])
+    mk = dict(piece_len=0.3, mean_vel=0.5, init_time_times=1.2, yaw_piece_times=2.0, init_sig_vel=0.05, test_mode=0, test_max_vel=0.5)
+    opt = U.ALMTrajOpt(m)
+    opt.set_rho(1.0)
+    plan = opt.plan_goals(ka, S, G, **mk)
+    src_ = tmp_path / "locate.cpp"
+    src_.write_text(CPP)
+    exe = str(tmp_path / "locate")
+    libdir = os.path.join(ROOT, "uneven_planner_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(src_), "-o", exe, "-L", libdir, "-lunevenhip",
+                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    cells = np.ascontiguousarray(analytic_cells, dtype=np.float64)
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<2q", cells.shape[0], S.shape[0]))
+        f.write(cells.tobytes())
+        f.write(np.ascontiguousarray(np.concatenate([S, G, f0[:, None], f1[:, None]], axis=1), dtype=np.float64).tobytes())
+    subprocess.check_call([exe, fin, fout])
+    raw = np.fromfile(fout, dtype=np.float64)
+    n = int(raw[0])
+    live = [b for b in range(S.shape[0]) if plan[b]["status"] == 0 and plan[b]["ret"] != 4]
+    want_tr = [plan[b]["traj_of"] for b in live]
+    assert n == len(want_tr) >= 10 and raw.size == 1 + 3 * n + 2 * 19 * n + 2 * 4 * n
+    q = raw[1:1 + 3 * n].reshape(n, 3)
+    assert q[:, 0].astype(int).tolist() == want_tr
+    loc = raw[1 + 3 * n:1 + 3 * n + 38 * n].reshape(2, n, 19)
+    wit = raw[1 + 41 * n:].reshape(2, n, 4)
+    poses = G[live] + np.array([0.1, -0.05, 0.2])
+    rects = np.stack([S[live, 0] - 1.0, S[live, 0] + 1.0, S[live, 1] - 1.0, S[live, 1] + 1.0], axis=1)
+    for got, want in ((loc[0], opt.locate(want_tr, poses, q[:, 1], q[:, 2])), (loc[1], opt.locate(want_tr, poses, q[:, 1], None, dt=0.03, with_end=False))):
+        cpp = dict(near_t=got[:, 0], near_d2=got[:, 1], count=got[:, 2].astype(np.int32), t=got[:, 3], refined=got[:, 4].astype(np.int32), d2=got[:, 5],
+                   state=got[:, 6:16], err=got[:, 16:19])
+        _same(cpp, want, ALLKEYS, "adapter locate")
+    for got, want in ((wit[0], opt.within(want_tr, rects, q[:, 1], q[:, 2])), (wit[1], opt.within(want_tr, rects, q[:, 1], None, dt=0.03, with_end=False))):
+        cpp = dict(enter_t=got[:, 0], leave_t=got[:, 1], counts=got[:, 2:4].astype(np.int32))
+        _same(cpp, want, WKEYS, "adapter within")
+    assert (loc[1][:, 2] > 0).any() and (loc[0][:, 2] == 0).any() and (wit[1][:, 3] > 0).any()

@@ -1,0 +1,36 @@
+"""Outputs of the existing calls that share code with uph_locate_batch / uph_within_batch, for bit-identity checks across library builds:
+python tools/locate_bitid.py OUT.npz [B = 1024] -- on B hill goals planned and solved by plan_goals: the check (full windows at dt 0.01 with the end
+point, and the middle third of every duration at dt 0.03), the STATE rollout at dt 0.01 with the end point and every channel at dt 0.05, and
+uph_traj_states at a third and two thirds of every duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
+python tools/check_bitid.py compare A.npz B.npz (np.array_equal, NaN equal to NaN)."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.getcwd())
+import uneven_planner_amd as U              # noqa: E402
+from uneven_planner_amd import scenes       # noqa: E402
+
+out = sys.argv[1]
+B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
+m = U.UnevenMap()
+m.build(scenes.make_hill_cloud())
+nx, ny = int(m.voxel_num[0]), int(m.voxel_num[1])
+S, G = scenes.random_queries(B, seed0=1000, occ_r2=m.occ_r2_buffer, grid=(nx, ny, m.xy_resolution, m.map_origin[0], m.map_origin[1]))
+ka = U.KinoAstar(m)
+opt = U.ALMTrajOpt(m)
+opt.set_rho(1.0)
+res = [r for r in opt.plan_goals(ka, S, G) if "c_xy" in r]
+arrs = {"c_xy": np.concatenate([r["c_xy"].ravel() for r in res]), "c_yaw": np.concatenate([r["c_yaw"].ravel() for r in res])}
+arrs["rollout_offsets_0.01"], arrs["rollout_state_0.01_end"] = opt.rollout(0.01, channels=1, with_end=True)
+arrs["rollout_offsets_0.05"], arrs["rollout_all_0.05_end"] = opt.rollout(0.05, channels=7, with_end=True)
+offs, rows = opt.rollout(1.0, channels=1, with_end=True)
+valid = np.nonzero(np.diff(offs) > 0)[0].astype(np.int32)
+total = rows[offs[valid + 1] - 1, 0]
+arrs["traj_states"] = opt.traj_states(np.concatenate([valid, valid]), np.concatenate([total / 3.0, 2.0 * total / 3.0]))
+for tag, c in (("full", opt.check(valid)), ("third", opt.check(valid, total / 3.0, 2.0 * total / 3.0, dt=0.03, with_end=False))):
+    for k, v in c.items():
+        arrs["check_%s_%s" % (tag, k)] = v
+np.savez(out, build=np.array(U._lib.build_id() or ""), **arrs)
+print("%s: build %s  goals %d  resident %d  rollout rows %d  checked %d" % (out, U._lib.build_id(), B, len(res), arrs["rollout_state_0.01_end"].shape[0], valid.size))

@@ -172,6 +172,9 @@ SYMBOLS = {
     "uph_check_window": (C.c_int, [C.c_double, _I32, C.c_double, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_check_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32), C.POINTER(_I32), DP, DP]),
     "uph_check_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_locate_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32), DP, C.POINTER(_I32), DP, DP, DP]),
+    "uph_within_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32)]),
+    "uph_locate_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None

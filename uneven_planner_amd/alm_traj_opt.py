@@ -234,6 +234,114 @@ def check_rows(t, terms, occ, lim, t_from=-np.inf, t_to=np.inf):
     return dict(first_t=first_t, first_mask=first_mask, counts=counts, worst=worst, worst_t=worst_t)
 
 
+# uph_locate_batch / uph_within_batch (include/uneven_hip.h): numpy mirrors written from the rule, not from the kernel
+LOCATE_NEWTON = 8
+
+
+def _window(t, t_from, t_to):
+    with np.errstate(invalid="ignore"):
+        return (t_from <= t) & (t <= t_to)
+
+
+def locate_rows(t, xy, pose, t_from=-np.inf, t_to=np.inf):
+    """Host mirror of the coarse stage of one uph_locate_batch query: among one trajectory's rollout rows -- t (n,), xy (n, 2) the STATE columns x, y --
+    whose t lies in [t_from, t_to], the one nearest to pose (x, y[, yaw]) by d2 = ex ex + ey ey (each product rounded, then the add).  A NaN d2 reads
+    +inf, a tie stays with the earlier row.  Returns near_t, near_d2, count, and for locate_refine j (the winner's index in the window, -1: empty
+    window) and times (the window's t)."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1)
+    sel = _window(t, t_from, t_to)
+    t, xy = t[sel], xy[sel]
+    if t.shape[0] == 0:
+        return dict(near_t=np.nan, near_d2=np.inf, count=0, j=-1, times=t)
+    with np.errstate(over="ignore", invalid="ignore"):
+        ex, ey = xy[:, 0] - pose[0], xy[:, 1] - pose[1]
+        d2 = ex * ex + ey * ey
+    key = np.where(np.isnan(d2), np.inf, d2)
+    j = int(np.argmin(key))                                         # the first occurrence of the minimum
+    return dict(near_t=t[j], near_d2=key[j], count=t.shape[0], j=j, times=t)
+
+
+def within_rows(t, xy, rect, t_from=-np.inf, t_to=np.inf):
+    """Host mirror of one uph_within_batch query: the rows of the window [t_from, t_to] inside the closed rect (x0, x1, y0, y1); a NaN position is
+    outside, a reversed rect is empty.  Returns enter_t / leave_t (t of the first / last row inside, NaN: none) and counts (2,): rows, rows inside."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    x0, x1, y0, y1 = (float(v) for v in np.asarray(rect, dtype=np.float64).reshape(4))
+    sel = _window(t, t_from, t_to)
+    t, xy = t[sel], xy[sel]
+    with np.errstate(invalid="ignore"):
+        inside = np.nonzero((x0 <= xy[:, 0]) & (xy[:, 0] <= x1) & (y0 <= xy[:, 1]) & (xy[:, 1] <= y1))[0]
+    return dict(enter_t=t[inside[0]] if inside.size else np.nan, leave_t=t[inside[-1]] if inside.size else np.nan,
+                counts=np.array([t.shape[0], inside.size], dtype=np.int32))
+
+
+def _state10(traj, shift, t):
+    """uph_traj_states' row of an SE2Traj at t (not clamped: the refinement stays inside the samples), the frame shift added to the position"""
+    ix, tl = traj._locate(list(traj.pos_durations), t)
+    iw, tw = traj._locate(list(traj.yaw_durations), t)
+    px, vx, ax = traj._derivs(traj.pos_coeffs[ix, 0], tl)
+    py, vy, ay = traj._derivs(traj.pos_coeffs[ix, 1], tl)
+    w, dw, ddw = traj._derivs(traj.yaw_coeffs[iw, 0], tw)
+    return np.array([px + shift[0], py + shift[1], vx, vy, ax, ay, norm_so2(w), dw, ddw, w])
+
+
+def locate_errors(state, pose):
+    """e_lon, e_lat, e_yaw of a pose (x, y, yaw) against a traj_states row: r = (x, y) - (X, Y) along and across the raw yaw psi (column 9), and
+    normSO2(yaw - psi)"""
+    psi = state[9]
+    rx, ry = pose[0] - state[0], pose[1] - state[1]
+    return np.array([rx * np.cos(psi) + ry * np.sin(psi), ry * np.cos(psi) - rx * np.sin(psi), norm_so2(pose[2] - psi)])
+
+
+def locate_refine(se2traj, shift, pose, times, j):
+    """Host mirror of the refinement of one uph_locate_batch query on a downloaded SE2Traj (`shift`: its frame's corner in map coordinates, (0, 0) for a
+    batch in the map's frame): `times` are the window's samples and j the coarse winner (locate_rows).  A safeguarded Newton iteration on
+    g(t) = e . v inside [times[max(j - 1, 0)], times[min(j + 1, n - 1)]], at most LOCATE_NEWTON iterations; the candidate is kept when its d2 is not
+    larger than the coarse one.  Returns t, refined, state (10,), d2, err (3,), lo, hi and iters (evaluations of g)."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    pose = np.asarray(pose, dtype=np.float64).reshape(3)
+    n = times.shape[0]
+    nan = np.nan
+    if n == 0 or j < 0:
+        return dict(t=nan, refined=0, state=np.full(10, nan), d2=np.inf, err=np.full(3, nan), lo=nan, hi=nan, iters=0)
+    lo, hi = times[max(j - 1, 0)], times[min(j + 1, n - 1)]
+
+    def at(t):
+        s = _state10(se2traj, shift, t)
+        ex, ey = s[0] - pose[0], s[1] - pose[1]
+        with np.errstate(over="ignore", invalid="ignore"):
+            return s, ex, ey, ex * ex + ey * ey
+
+    s0, _, _, d0 = at(times[j])
+    d0 = np.inf if np.isnan(d0) else d0
+    t, a, b, iters = times[j], lo, hi, 0
+    with np.errstate(all="ignore"):
+        for _ in range(LOCATE_NEWTON):
+            s, ex, ey, _ = at(t)
+            iters += 1
+            g = ex * s[2] + ey * s[3]
+            h = s[2] * s[2] + s[3] * s[3] + ex * s[4] + ey * s[5]
+            if g > 0:
+                b = t
+            elif g < 0:
+                a = t
+            elif g == 0:
+                break
+            tn = t - g / h if h > 0 else nan
+            if not (h > 0 and a <= tn <= b):
+                tn = 0.5 * (a + b)
+            if tn == t:
+                break
+            t = tn
+    s, _, _, d2 = at(t)
+    refined = bool(d2 <= d0)
+    if not refined:
+        t, s, d2 = times[j], s0, d0
+    return dict(t=t, refined=int(refined), state=s, d2=d2, err=locate_errors(s, pose), lo=lo, hi=hi, iters=iters)
+
+
 class ALMTrajOpt:
     def __init__(self, uneven_map=None, params=None):
         self.L = _lib.load()
@@ -712,6 +820,49 @@ class ALMTrajOpt:
         """milliseconds of uph_check_kernel in the last check() (events on the context's stream)"""
         ms = C.c_double(0)
         _lib.check(self.L.uph_check_kernel_ms(self.h, C.byref(ms)), "uph_check_kernel_ms")
+        return ms.value
+
+    # ---- poses located on resident trajectories, rects crossed by them (uph_locate_batch, uph_within_batch) ---------------------------------------
+    def _windows(self, traj, t_from, t_to, rows, width, who):
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        n = tr.shape[0]
+        if n == 0:
+            raise _lib.UnevenHipError(who + ": no query")
+        tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, dtype=np.float64), (n,)))
+        tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, dtype=np.float64), (n,)))
+        rw = np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=np.float64), (n, width)))
+        return tr, n, tf, tt, rw
+
+    def locate(self, traj, poses, t_from=0.0, t_to=None, dt=0.01, with_end=True):
+        """Locate, on the device, pose poses[q] = (x, y, yaw) in map coordinates on resident trajectory traj[q] among its rollout(dt, with_end) samples
+        with t in [t_from[q], t_to[q]] (scalars / one pose are broadcast; t_to = None: to the end): the nearest sample (near_t, near_d2, count), then the
+        time t refined between its neighbours where the pose's offset is normal to the velocity (refined = 0: the sample itself was kept), the state
+        there (n, 10: traj_states' columns), d2 and err (n, 3) = e_lon, e_lat, e_yaw of the pose against that state.  See locate_rows /
+        locate_refine for the rule."""
+        tr, n, tf, tt, ps = self._windows(traj, t_from, t_to, poses, 3, "locate")
+        out = dict(near_t=np.full(n, np.nan), near_d2=np.full(n, np.inf), count=np.zeros(n, dtype=np.int32), t=np.full(n, np.nan),
+                   refined=np.zeros(n, dtype=np.int32), state=np.full((n, _lib.TRAJ_STATE_COLS), np.nan), d2=np.full(n, np.inf), err=np.full((n, 3), np.nan))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_locate_batch(self.h, n, ip(tr), _dp(ps), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                           _dp(out["near_t"]), _dp(out["near_d2"]), ip(out["count"]), _dp(out["t"]), ip(out["refined"]), _dp(out["state"]),
+                                           _dp(out["d2"]), _dp(out["err"])), "uph_locate_batch")
+        return out
+
+    def within(self, traj, rects, t_from=0.0, t_to=None, dt=0.01, with_end=True):
+        """Which rollout(dt, with_end) samples of resident trajectory traj[q] with t in [t_from[q], t_to[q]] lie inside the closed rect rects[q] =
+        (x0, x1, y0, y1) in map coordinates (one rect is broadcast), on the device: enter_t / leave_t (t of the first / last sample inside, NaN: none)
+        and counts (n, 2: samples, inside); see within_rows."""
+        tr, n, tf, tt, rc = self._windows(traj, t_from, t_to, rects, 4, "within")
+        out = dict(enter_t=np.full(n, np.nan), leave_t=np.full(n, np.nan), counts=np.zeros((n, 2), dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_within_batch(self.h, n, ip(tr), _dp(rc), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                           _dp(out["enter_t"]), _dp(out["leave_t"]), ip(out["counts"])), "uph_within_batch")
+        return out
+
+    def locate_kernel_ms(self):
+        """milliseconds of the kernel(s) of the last locate() or within(), whichever came last (events on the context's stream)"""
+        ms = C.c_double(0)
+        _lib.check(self.L.uph_locate_kernel_ms(self.h, C.byref(ms)), "uph_locate_kernel_ms")
         return ms.value
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------

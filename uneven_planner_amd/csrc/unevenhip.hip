@@ -1058,6 +1058,199 @@ __global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __
     if (COLS > SWITCH_COLS) o[9] = s.yaw;
 }
 
+// ---- locate / within (uph_locate_batch, uph_within_batch): geometric reductions over the STATE samples of (trajectory, time window) pairs of the resident
+// batch, on uph_check_kernel's skeleton -- query records formed on the host in launch order, query-uniform data indexed by blockIdx only, lanes striding
+// over the window, a selection under a total order reduced by DPP row rotations, row leaders and LDS across the waves, lane 0 writes.  No terrain: a
+// sample is two quintics, about a tenth of the check's, so a query of the tracking workload (101 samples) gets one wave (NT = 64, no LDS, no
+// barrier) and only windows longer than LOC_SHORT samples get the check's 256 lanes; the host splits the sorted launch at that length.  The
+// selection makes the answer the same for either width.
+//   locate: the sample nearest to a pose (d2 = ex ex + ey ey with both products rounded, the smaller sample among equals, NaN as +inf), then, uniform
+//           work of lane 0, a safeguarded Newton iteration on g(t) = e . v inside the bracket of the neighbouring samples; state and tracking error there.
+//   within: first and last sample inside a closed rect, the number of samples inside.
+struct LocQuery {               // one query of a locate / within launch (formed on the host, in launch order)
+    int32_t b, out;             // resident trajectory; row of the output (the caller's query index)
+    int32_t q_lo, n_tab;        // as CheckQuery
+    int32_t end_row, pad;
+    double total;
+    double shift[2];
+    double p[4];                // locate: pose x, y, yaw (map coordinates);  within: rect x0, x1, y0, y1
+};
+struct LocateOut {              // one row per query
+    double near_t, near_d2;     // coarse stage
+    double t, d2;
+    double state[TRAJ_STATE_COLS];
+    double err[3];              // e_lon, e_lat, e_yaw
+    int32_t count, refined;
+};
+struct WithinOut {
+    double enter_t, leave_t;    // NaN: no sample inside
+    int32_t counts[2];          // samples, inside
+};
+struct LocArgs {
+    const TrajDesc* desc;
+    const TrajState* state;
+    const double* cxy;
+    const double* cyaw;
+    const LocQuery* qs;
+    const double* tt;           // the rollout's time table
+    void* out;                  // LocateOut / WithinOut rows
+    int framed, q0;             // the batch solves in local frames (add shift, as the rollout does); first query of this launch
+};
+constexpr int LOC_SHORT = 192;  // windows of at most this many samples run on one wave
+constexpr int LOC_NONE = 0x7fffffff;
+constexpr int LOC_NEWTON = 8;
+
+// the STATE row of query-uniform trajectory data at t: position in map coordinates as the rollout and uph_switch_state_kernel form it.  The values leave
+// trajectorySample as they leave it there (stored): nothing after this may be contracted into its arithmetic.
+struct LocTraj {
+    const double* cx;
+    const double* cy;
+    int Nxy, Nyaw;
+    double Tx, Ty, sx, sy;
+    bool framed;
+    __device__ __forceinline__ void sample(double t, TrajSample& s, double& X, double& Y) const {
+        double unused[7];
+        GridDev none;
+        trajectorySample<false, true>(cx, cy, Nxy, Nyaw, Tx, Ty, t, none, 0.0, s, unused);
+        X = framed ? s.p[0] + sx : s.p[0]; Y = framed ? s.p[1] + sy : s.p[1];
+        asm volatile("" : "+v"(X), "+v"(Y));
+    }
+};
+__device__ __forceinline__ LocTraj locTraj(const LocArgs& a, const LocQuery& lq) {
+    const TrajDesc& td = a.desc[lq.b];
+    LocTraj r;
+    r.cx = a.cxy + td.off_cxy; r.cy = a.cyaw + td.off_cyaw; r.Nxy = td.Nxy; r.Nyaw = td.Nyaw;
+    r.Tx = a.state[lq.b].T_xy; r.Ty = a.state[lq.b].T_yaw;
+    r.framed = a.framed != 0; r.sx = lq.shift[0]; r.sy = lq.shift[1];
+    return r;
+}
+// squared distance with both products rounded before the add
+__device__ __forceinline__ double locD2(double ex, double ey) {
+    double xx = ex * ex, yy = ey * ey;
+    asm volatile("" : "+v"(xx), "+v"(yy));
+    return xx + yy;
+}
+// (key, sample) pairs: the smaller key wins, equal keys go to the smaller sample (no NaN reaches here)
+__device__ __forceinline__ void locTake(double& v, int& i, double ov, int oi) {
+    const bool o = ov < v || (ov == v && oi < i);
+    v = o ? ov : v; i = o ? oi : i;
+}
+template <int CTRL>
+__device__ __forceinline__ void locStepNear(double& v, int& i) { const double ov = dppMov<CTRL>(v); const int oi = dppMovI<CTRL>(i); locTake(v, i, ov, oi); }
+template <int CTRL>
+__device__ __forceinline__ void locStepSpan(int& lo, int& hi, int& cnt) {
+    const int ol = dppMovI<CTRL>(lo), oh = dppMovI<CTRL>(hi);
+    lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; cnt += dppMovI<CTRL>(cnt);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
+    constexpr int NW = NT / 64;
+    __shared__ double s_v[NW];
+    __shared__ int s_i[NW];
+    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
+    const LocTraj tr = locTraj(a, lq);
+    const int n = lq.n_tab + (lq.end_row ? 1 : 0);
+    const double x = lq.p[0], y = lq.p[1];
+    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
+    double bv = inf;
+    int bi = LOC_NONE;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        const double t = j < lq.n_tab ? a.tt[lq.q_lo + j] : lq.total;
+        TrajSample s;
+        double X, Y;
+        tr.sample(t, s, X, Y);
+        const double d2 = locD2(X - x, Y - y);
+        locTake(bv, bi, d2 < inf ? d2 : inf, j);            // NaN: +inf
+    }
+    locStepNear<0x128>(bv, bi); locStepNear<0x124>(bv, bi); locStepNear<0x122>(bv, bi); locStepNear<0x121>(bv, bi);
+    double v = readLane(bv, 0);
+    int i = __builtin_amdgcn_readlane(bi, 0);
+#pragma unroll
+    for (int r = 16; r < 64; r += 16) locTake(v, i, readLane(bv, r), __builtin_amdgcn_readlane(bi, r));
+    if (NW > 1) {
+        if (((int)threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = v; s_i[threadIdx.x >> 6] = i; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < NW; w++) locTake(v, i, s_v[w], s_i[w]);
+    // sample k of the window (NaN outside it: an empty window answers NaN by this path, not by a special one)
+    auto tau = [&](int k) { return k < 0 || k >= n ? nan : (k < lq.n_tab ? a.tt[lq.q_lo + k] : lq.total); };
+    LocateOut o;
+    o.count = n; o.near_t = tau(i); o.near_d2 = v;
+    const double lo = tau(i - 1 > 0 ? i - 1 : 0), hi = tau((i < n - 2 ? i : n - 2) + 1);
+    double t = o.near_t, ta = lo, tb = hi;
+    TrajSample s, s0;
+    double X, Y, X0 = nan, Y0 = nan, d2 = nan;
+    for (int it = 0;; it++) {
+        tr.sample(t, s, X, Y);
+        const double ex = X - x, ey = Y - y;
+        d2 = locD2(ex, ey);
+        if (it == 0) { s0 = s; X0 = X; Y0 = Y; }
+        if (it == LOC_NEWTON) break;                        // the candidate left by the last iteration
+        const double g = ex * s.v[0] + ey * s.v[1];
+        const double h = s.v[0] * s.v[0] + s.v[1] * s.v[1] + ex * s.a[0] + ey * s.a[1];
+        if (g > 0.0) tb = t;
+        else if (g < 0.0) ta = t;
+        else if (g == 0.0) break;
+        double tn = t - g / h;
+        if (!(h > 0.0 && ta <= tn && tn <= tb)) tn = 0.5 * (ta + tb);
+        if (tn == t) break;
+        t = tn;
+    }
+    const bool refined = d2 <= v;
+    if (!refined) { s = s0; X = X0; Y = Y0; t = o.near_t; d2 = v; }
+    o.t = t; o.d2 = d2; o.refined = refined ? 1 : 0;
+    o.state[0] = X; o.state[1] = Y; o.state[2] = s.v[0]; o.state[3] = s.v[1]; o.state[4] = s.a[0]; o.state[5] = s.a[1];
+    o.state[6] = s.yawn; o.state[7] = s.dyaw; o.state[8] = s.ddyaw; o.state[9] = s.yaw;
+    const double rx = x - X, ry = y - Y;
+    double sw, cw;
+    sincos(s.yaw, &sw, &cw);
+    o.err[0] = rx * cw + ry * sw;
+    o.err[1] = ry * cw - rx * sw;
+    o.err[2] = normSO2(lq.p[2] - s.yaw);
+    ((LocateOut*)a.out)[lq.out] = o;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
+    constexpr int NW = NT / 64;
+    __shared__ int s_r[NW][3];
+    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
+    const LocTraj tr = locTraj(a, lq);
+    const int n = lq.n_tab + (lq.end_row ? 1 : 0);
+    const double x0 = lq.p[0], x1 = lq.p[1], y0 = lq.p[2], y1 = lq.p[3];
+    int first = LOC_NONE, last = -1, cnt = 0;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        const double t = j < lq.n_tab ? a.tt[lq.q_lo + j] : lq.total;
+        TrajSample s;
+        double X, Y;
+        tr.sample(t, s, X, Y);
+        if (x0 <= X && X <= x1 && y0 <= Y && Y <= y1) {     // (a NaN position is not inside)
+            first = first == LOC_NONE ? j : first; last = j; cnt++;
+        }
+    }
+    locStepSpan<0x128>(first, last, cnt); locStepSpan<0x124>(first, last, cnt); locStepSpan<0x122>(first, last, cnt); locStepSpan<0x121>(first, last, cnt);
+    int f = LOC_NONE, l = -1, c = 0;
+#pragma unroll
+    for (int r = 0; r < 64; r += 16) {
+        const int of = __builtin_amdgcn_readlane(first, r), ol = __builtin_amdgcn_readlane(last, r);
+        f = of < f ? of : f; l = ol > l ? ol : l; c += __builtin_amdgcn_readlane(cnt, r);
+    }
+    if (NW > 1) {
+        if (((int)threadIdx.x & 63) == 0) { s_r[threadIdx.x >> 6][0] = f; s_r[threadIdx.x >> 6][1] = l; s_r[threadIdx.x >> 6][2] = c; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < NW; w++) { f = s_r[w][0] < f ? s_r[w][0] : f; l = s_r[w][1] > l ? s_r[w][1] : l; c += s_r[w][2]; }
+    const double nan = __builtin_nan("");
+    WithinOut o;
+    o.enter_t = c == 0 ? nan : (f < lq.n_tab ? a.tt[lq.q_lo + f] : lq.total);
+    o.leave_t = c == 0 ? nan : (l < lq.n_tab ? a.tt[lq.q_lo + l] : lq.total);
+    o.counts[0] = n; o.counts[1] = c;
+    ((WithinOut*)a.out)[lq.out] = o;
+}
+
 // ---- refine (uph_refine_upload): the tail of a resident trajectory as a new problem, without a search.  uph_switch_state_kernel<TRAJ_STATE_COLS>
 // has evaluated the switch states (rows [0, B), one per query) and every way-point time of the batch into one table; one lane per uploaded query
 // copies its way-points into the plan staging (slot = query index) and forms its PlanHead in way-point order.  The bounding box and turn / kink
@@ -1216,6 +1409,8 @@ struct uph_ctx {
     DevBuf d_refine_rec;                   // uph_refine_upload: staging records
     DevBuf d_chk_q, d_chk_out;             // uph_check_batch: query records and result rows (allocated at the first call)
     double last_check_ms = 0.0;            // uph_check_kernel of the last uph_check_batch (events on the context's stream)
+    DevBuf d_loc_q, d_loc_out;             // uph_locate_batch / uph_within_batch: query records and result rows (allocated at the first call)
+    double last_locate_ms = 0.0;           // the kernel(s) of the last uph_locate_batch or uph_within_batch (events on the context's stream)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
@@ -1479,7 +1674,7 @@ void uph_ctx_destroy(uph_ctx* c) {
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
                       &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec, &c->d_chk_q,
-                      &c->d_chk_out};
+                      &c->d_chk_out, &c->d_loc_q, &c->d_loc_out};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -2885,6 +3080,120 @@ int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_
 int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
     if (!c || !kernel_ms) { setError("uph_check_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
     *kernel_ms = c->last_check_ms;
+    return UPH_OK;
+}
+
+// ---- locate / within (include/uneven_hip.h uph_locate_*, uph_within_batch) ---------------------------------------------------------------------------
+// what the two calls share: every refusal (outputs untouched), the windows as uph_check_batch forms them, the query records in launch order (longest
+// windows first, stable) with `extra` doubles of the caller's row (pose / rect) in each, the time table and the records on the device.  n_long: the
+// queries at the head of the launch whose window exceeds LOC_SHORT samples.
+static int locBegin(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* rows,
+                    int extra, const char* who, std::vector<LocQuery>& qs, int32_t& n_long) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(std::string(who) + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t_from, who);
+    if (r != UPH_OK) return r;
+    if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
+    for (int32_t q = 0; q < n; q++) for (int k = 0; k < extra; k++) {
+        const double v = rows[(size_t)extra * q + k];
+        if (extra == 3 ? !std::isfinite(v) : std::isnan(v)) {
+            setError(std::string(who) + ": query " + std::to_string(q) + (extra == 3 ? " has a non-finite pose component" : " has a NaN rect bound")); return UPH_ERR_INVALID;
+        }
+    }
+    RolloutSizes rs;
+    r = rolloutPlanCtx(c, dt, with_end, rs, who);
+    if (r != UPH_OK) return r;
+    qs.assign((size_t)n, LocQuery());
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t b = traj[q];
+        LocQuery& k = qs[(size_t)q];
+        int32_t q_hi = 0;
+        k.b = b; k.out = q; k.pad = 0;
+        checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
+        k.n_tab = q_hi - k.q_lo;
+        k.total = rs.total[(size_t)b];
+        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+        for (int d = 0; d < 4; d++) k.p[d] = d < extra ? rows[(size_t)extra * q + d] : 0.0;
+    }
+    std::stable_sort(qs.begin(), qs.end(), [](const LocQuery& x, const LocQuery& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
+    n_long = 0;
+    while (n_long < n && qs[(size_t)n_long].n_tab + qs[(size_t)n_long].end_row > LOC_SHORT) n_long++;
+    if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_loc_q.ensure(sizeof(LocQuery) * (size_t)n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_loc_q.p, qs.data(), sizeof(LocQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return UPH_OK;
+}
+
+// the launch (256 lanes for the first n_long queries, one wave for the rest) between the context's events, the result rows to the host, the wait
+extern "C++" template <class Out, class K256, class K64>
+static int locRun(uph_ctx* c, int32_t n, int32_t n_long, K256 k256, K64 k64, std::vector<Out>& out) {
+    if (c->d_loc_out.ensure(sizeof(Out) * (size_t)n)) return UPH_ERR_HIP;
+    LocArgs a;
+    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
+    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
+    a.qs = c->d_loc_q.as<LocQuery>(); a.tt = c->d_roll_tt.as<double>(); a.out = c->d_loc_out.p;
+    a.framed = c->frames.empty() ? 0 : 1; a.q0 = 0;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    hipError_t le = hipSuccess;
+    if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
+    if (n > n_long && le == hipSuccess) { a.q0 = n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    out.resize((size_t)n);
+    const hipError_t ce = hipMemcpyAsync(out.data(), c->d_loc_out.p, sizeof(Out) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
+    HIPCHK(le); HIPCHK(ce); HIPCHK(se);
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_locate_ms = ms;
+    return UPH_OK;
+}
+
+int uph_locate_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* poses, const double* t_from, const double* t_to, double dt, int32_t with_end,
+                     double* near_t, double* near_d2, int32_t* count, double* t, int32_t* refined, double* state, double* d2, double* err) {
+    if (!c || n <= 0 || !traj || !poses || !t_from) { setError("uph_locate_batch: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<LocQuery> qs;
+    int32_t n_long = 0;
+    int r = locBegin(c, n, traj, t_from, t_to, dt, with_end, poses, 3, "uph_locate_batch", qs, n_long);
+    if (r != UPH_OK) return r;
+    std::vector<LocateOut> out;
+    r = locRun(c, n, n_long, uph_locate_kernel<256>, uph_locate_kernel<64>, out);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const LocateOut& o = out[(size_t)q];
+        if (near_t) near_t[q] = o.near_t;
+        if (near_d2) near_d2[q] = o.near_d2;
+        if (count) count[q] = o.count;
+        if (t) t[q] = o.t;
+        if (refined) refined[q] = o.refined;
+        if (state) for (int k = 0; k < TRAJ_STATE_COLS; k++) state[(size_t)TRAJ_STATE_COLS * q + k] = o.state[k];
+        if (d2) d2[q] = o.d2;
+        if (err) for (int k = 0; k < 3; k++) err[3 * (size_t)q + k] = o.err[k];
+    }
+    return UPH_OK;
+}
+
+int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* rects, const double* t_from, const double* t_to, double dt, int32_t with_end,
+                     double* enter_t, double* leave_t, int32_t* counts) {
+    if (!c || n <= 0 || !traj || !rects || !t_from) { setError("uph_within_batch: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<LocQuery> qs;
+    int32_t n_long = 0;
+    int r = locBegin(c, n, traj, t_from, t_to, dt, with_end, rects, 4, "uph_within_batch", qs, n_long);
+    if (r != UPH_OK) return r;
+    std::vector<WithinOut> out;
+    r = locRun(c, n, n_long, uph_within_kernel<256>, uph_within_kernel<64>, out);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const WithinOut& o = out[(size_t)q];
+        if (enter_t) enter_t[q] = o.enter_t;
+        if (leave_t) leave_t[q] = o.leave_t;
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_locate_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_locate_ms;
     return UPH_OK;
 }
 
