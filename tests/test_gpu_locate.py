@@ -210,6 +210,47 @@ def test_windows(hill, dt, with_end):
     _same(src.within(tr, rc, tf, None, dt=dt, with_end=with_end), _expect_within(ref, tr, rc, tf, None), WKEYS, "t_to None")
 
 
+def test_check_locate_within_form_the_same_windows(hill):
+    """check, locate and within share one window former: on the same queries -- test_windows' list on two trajectories interleaved with windows of 192,
+    193 and 257 samples, so that one call holds both launch widths and the sort moves queries -- they count the same samples, and every time they
+    answer is the t of one of the literally selected rollout rows"""
+    src, ref = hill["src"], hill["refs"][(0.01, 1)]
+    offs, rows = ref
+    long = [int(b) for b in hill["ok"] if offs[b + 1] - offs[b] >= 700][:2]
+    assert len(long) == 2
+    tr, tf, tt, ps, rc = [], [], [], [], []
+    for b in long:
+        blk = rows[int(offs[b]):int(offs[b + 1])]
+        t, total = blk[:-1, 0], blk[-1, 0]
+        h = lambda i: 0.5 * (t[i] + t[i + 1])
+        win = [(0.0, total), (0.0, 0.0), (-0.5, t[5]), (-2.0, -1.0), (t[3], t[10]), (t[7], t[7]), (np.nextafter(t[3], 9.0), np.nextafter(t[10], -9.0)),
+               (h(3), h(10)), (h(6), h(6)), (t[-2], total), (total, total), (np.nextafter(total, 0.0), total), (h(20), total + 5.0),
+               (total + 1.0, total + 2.0), (np.nextafter(total, 99.0), INF), (t[10], t[3]), (t[4], INF), (0.0, -INF), (-1e300, 1e300)]
+        for k, n in enumerate((192, 193, 257)):
+            win.insert(5 * k + 2, (t[90 + k], t[90 + k + n - 1]))
+        for k, (a, e) in enumerate(win):
+            r = blk[[0, 4, 8, 20, 150][k % 5]]
+            tr.append(b), tf.append(a), tt.append(e)
+            ps.append([r[1] + 0.05, r[2] - 0.05, r[3]])
+            rc.append([r[1] - 0.3, r[1] + 0.3, r[2] - 0.3, r[2] + 0.3])
+    tr, tf, tt = np.array(tr, dtype=np.int32), np.array(tf), np.array(tt)
+    lim = src.check_limits()
+    lim[0] *= 0.5                                                      # so that some windows have a first violation
+    c = src.check(tr, tf, tt, dt=0.01, with_end=True, limits=lim)
+    g = src.locate(tr, ps, tf, tt, dt=0.01, with_end=True)
+    w = src.within(tr, rc, tf, tt, dt=0.01, with_end=True)
+    sel = [rows[int(offs[b]):int(offs[b + 1]), 0] for b in tr]
+    sel = [s[(s >= tf[q]) & (s <= tt[q])] for q, s in enumerate(sel)]
+    want = np.array([s.size for s in sel])
+    assert sorted(set(want.tolist()) & {192, 193, 257}) == [192, 193, 257] and (want == 0).sum() >= 10 and (want > 257).any()
+    assert np.array_equal(c["counts"][:, 0], want) and np.array_equal(g["count"], want) and np.array_equal(w["counts"][:, 0], want)
+    for q, s in enumerate(sel):
+        for v in [c["first_t"][q], g["near_t"][q], w["enter_t"][q], w["leave_t"][q]] + c["worst_t"][q].tolist():
+            assert np.isnan(v) or (s == v).any(), (q, v)
+        assert np.isnan(g["near_t"][q]) == (s.size == 0) and np.isnan(c["worst_t"][q]).all() == (s.size == 0)
+    assert np.isfinite(c["first_t"]).any() and np.isfinite(w["enter_t"]).any()
+
+
 def test_lane_and_wave_tails(hill):
     """windows of 1 .. 513 samples whose winner -- the pose sits exactly on that row -- or only inside sample (a rect that is that row's point) is first,
     last, at index 64 or at index 256 of the window: the strided walk of 64 and of 256 lanes, both sides of the length at which the launch is split,

@@ -1,5 +1,6 @@
 #!/bin/bash
 # disassemble the gfx950 code object of a library build: tools/isa_dump.sh [lib] [out.s]
+# (the first code object of the file: the library's is unevenhip.o's; for another unit pass its object file, build/obj/traj_query.o)
 LIB=${1:-uneven_planner_amd/libunevenhip.so}; OUT=${2:-build/isa/all.s}
 mkdir -p $(dirname $OUT); TMP=$(mktemp -d)
 /opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $LIB || exit 1

@@ -1,6 +1,7 @@
 #!/bin/bash
 # registers, scratch (spill) bytes and LDS of every kernel in the built library, from the code-object metadata
 # usage: tools/kernel_resources.sh [path/to/libunevenhip.so]
+# (the first code object of the file: the library's is unevenhip.o's; for another unit pass its object file, build/obj/traj_query.o)
 LIB=${1:-uneven_planner_amd/libunevenhip.so}
 TMP=$(mktemp -d)
 /opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $LIB || exit 1

@@ -1,7 +1,9 @@
-"""Outputs of the existing calls that share code with uph_locate_batch / uph_within_batch, for bit-identity checks across library builds:
+"""Outputs of uph_locate_batch / uph_within_batch and of the calls that share code with them, for bit-identity checks across library builds:
 python tools/locate_bitid.py OUT.npz [B = 1024] -- on B hill goals planned and solved by plan_goals: the check (full windows at dt 0.01 with the end
-point, and the middle third of every duration at dt 0.03), the STATE rollout at dt 0.01 with the end point and every channel at dt 0.05, and
-uph_traj_states at a third and two thirds of every duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
+point, and the middle third of every duration at dt 0.03), the STATE rollout at dt 0.01 with the end point and every channel at dt 0.05,
+uph_traj_states at a third and two thirds of every duration, locate (every output) for poses made from the recorded rollout rows plus seeded noise and
+within for rects around the same rows, both on the check's two kinds of windows, and the switch states replan_goals_upload returns at a third of every
+duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
 python tools/check_bitid.py compare A.npz B.npz (np.array_equal, NaN equal to NaN)."""
 import os
 import sys
@@ -32,5 +34,17 @@ arrs["traj_states"] = opt.traj_states(np.concatenate([valid, valid]), np.concate
 for tag, c in (("full", opt.check(valid)), ("third", opt.check(valid, total / 3.0, 2.0 * total / 3.0, dt=0.03, with_end=False))):
     for k, v in c.items():
         arrs["check_%s_%s" % (tag, k)] = v
+# one pose and one rect per trajectory around a recorded rollout row of its middle third
+ro, rr = arrs["rollout_offsets_0.01"], arrs["rollout_state_0.01_end"]
+rng = np.random.default_rng(5)
+row = rr[(ro[valid] + (ro[valid + 1] - ro[valid]) * rng.uniform(0.34, 0.66, valid.size)).astype(np.int64)]
+poses = row[:, 1:4] + rng.normal(0.0, [0.1, 0.1, 0.3], (valid.size, 3))
+half = rng.uniform(0.05, 1.5, (valid.size, 2))
+rects = np.stack([row[:, 1] - half[:, 0], row[:, 1] + half[:, 0], row[:, 2] - half[:, 1], row[:, 2] + half[:, 1]], axis=1)
+for tag, kw in (("full", dict()), ("third", dict(t_from=total / 3.0, t_to=2.0 * total / 3.0, dt=0.03, with_end=False))):
+    for name, res_ in (("locate", opt.locate(valid, poses, **kw)), ("within", opt.within(valid, rects, **kw))):
+        for k, v in res_.items():
+            arrs["%s_%s_%s" % (name, tag, k)] = v
+arrs["replan_switch_states"] = opt.replan_goals_upload(ka, opt, valid, total / 3.0)["switch_states"]
 np.savez(out, build=np.array(U._lib.build_id() or ""), **arrs)
 print("%s: build %s  goals %d  resident %d  rollout rows %d  checked %d" % (out, U._lib.build_id(), B, len(res), arrs["rollout_state_0.01_end"].shape[0], valid.size))

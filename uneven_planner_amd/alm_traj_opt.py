@@ -801,12 +801,7 @@ class ALMTrajOpt:
         [t_from[q], t_to[q]] (scalars are broadcast; t_to = None: to the end) against `limits` (7 values, None: check_limits()).  Returns a dict of
         arrays over the queries: first_t (NaN: no violation), first_mask (bit k: term k of CHECK_TERMS, bit CHECK_OCC_BIT: occupied or outside the
         map), counts (n, 3: samples, violating, occupied), worst and worst_t (n, 7); see check_rows for the rule."""
-        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
-        n = tr.shape[0]
-        if n == 0:
-            raise _lib.UnevenHipError("check: no query")
-        tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, dtype=np.float64), (n,)))
-        tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, dtype=np.float64), (n,)))
+        tr, n, tf, tt, _ = self._windows(traj, t_from, t_to, None, 0, "check")
         lim = None if limits is None else np.ascontiguousarray(limits, dtype=np.float64).reshape(7)
         out = dict(first_t=np.full(n, np.nan), first_mask=np.zeros(n, dtype=np.int32), counts=np.zeros((n, 3), dtype=np.int32),
                    worst=np.full((n, 7), -np.inf), worst_t=np.full((n, 7), np.nan))
@@ -824,13 +819,14 @@ class ALMTrajOpt:
 
     # ---- poses located on resident trajectories, rects crossed by them (uph_locate_batch, uph_within_batch) ---------------------------------------
     def _windows(self, traj, t_from, t_to, rows, width, who):
+        """the query arrays check / locate / within pass down: trajectories, broadcast window bounds and (rows not None) the n x width rows"""
         tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
         n = tr.shape[0]
         if n == 0:
             raise _lib.UnevenHipError(who + ": no query")
         tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, dtype=np.float64), (n,)))
         tt = None if t_to is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, dtype=np.float64), (n,)))
-        rw = np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=np.float64), (n, width)))
+        rw = None if rows is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=np.float64), (n, width)))
         return tr, n, tf, tt, rw
 
     def locate(self, traj, poses, t_from=0.0, t_to=None, dt=0.01, with_end=True):

@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "../../include/uneven_hip.h"
-#include "uph_internal.hpp"
+#include "uph_ctx.hpp"
 #include "terrain_dev.hpp"
 #include "rccl_dyn.hpp"
 
@@ -83,15 +83,6 @@ void* uphMapScratch(uph_map* m, int slot, size_t bytes) {
 }
 GridDev uphMapGrid(const uph_map* m) { return m->g; }
 void uphMapOcc(const uph_map* m, const char** occ, const char** occ_r2) { *occ = m->d_occ; *occ_r2 = m->d_occ2; }
-
-#define HIPCHK(call)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (call);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            setError(std::string(#call) + ": " + hipGetErrorString(_e));                           \
-            return UPH_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------ device code
 struct CloudDev {

@@ -250,7 +250,7 @@ UPH_HD void terrainVariables(const GridDev& g, double x, double y, double yaw, d
 
 // UnevenMap::getTerrainPos (uneven_map.h:203-218): SE(3) pose on the terrain at (x, y, w) from the value lookup there (tv = terrainValues of
 // locate(g, x, y, w)).  o[12] = R column-major (x_b, y_b, z_b), then p.  One definition for uph_terrain_pose_query (map_build.hip) and the pose
-// channel of the trajectory rollout (unevenhip.hip).
+// channel of the trajectory rollout (traj_query.hip).
 UPH_HD void terrainPoseFrom(double x, double y, double w, const double tv[4], double o[12]) {
     const double z = tv[3], zx = tv[1], zy = tv[2];
     const double zz = sqrt(1.0 - zx * zx - zy * zy);                 // RXS2::getC

@@ -1,0 +1,840 @@
+// libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within and the switch / trajectory states
+// (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states).  Kernels for gfx950 and their host side; the
+// context, its buffers and the solver live in unevenhip.hip (uph_ctx.hpp is what the two share).
+//
+// One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record (WinQuery: trajectory,
+// window of the rollout's time table, end point), lanes striding over the window, a selection or an integer sum reduced by wave_dev.hpp's rowReduce /
+// rowLeaders / acrossWaves, thread 0 writes the row.  Host: formWindowQueries (refusals, windows, launch order, uploads), runQueryLaunch (events, launch,
+// rows back, the wait).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/uneven_hip.h"
+#include "trajectory_dev.hpp"
+#include "uph_ctx.hpp"
+#include "wave_dev.hpp"
+
+// ------------------------------------------------------------------------------------------------ device side
+struct ResidentDev {            // the resident batch as the query kernels read it (residentDev)
+    const TrajDesc* desc;
+    const TrajState* state;
+    const double* cxy;
+    const double* cyaw;
+    const double* tt;           // t_q: q additions of dt to 0.0, shared by the batch
+};
+
+// One resident trajectory as a kernel samples it.  Everything here is uniform over a workgroup of the rollout, the check and locate / within (indexed by
+// blockIdx only: scalar loads).  sample is trajectorySample itself -- the rollout's statements -- so a state equals the rollout row of the same t bit for
+// bit; mapX / mapY add the frame's shift as the rollout does.
+struct TrajView {
+    const double* cx;
+    const double* cy;
+    int Nxy, Nyaw;
+    double Tx, Ty, sx, sy;
+    bool framed;                // the batch solves in local frames
+    template <bool TERMS, bool YAW2 = false>
+    __device__ __forceinline__ void sample(double t, const GridDev& g, double gravity, TrajSample& s, double* tm) const {
+        trajectorySample<TERMS, YAW2>(cx, cy, Nxy, Nyaw, Tx, Ty, t, g, gravity, s, tm);
+    }
+    __device__ __forceinline__ void state(double t, TrajSample& s) const {      // no terrain; with the raw yaw and the yaw acceleration
+        double unused[7];
+        GridDev none;
+        sample<false, true>(t, none, 0.0, s, unused);
+    }
+    __device__ __forceinline__ double mapX(double x) const { return framed ? x + sx : x; }
+    __device__ __forceinline__ double mapY(double y) const { return framed ? y + sy : y; }
+};
+__device__ __forceinline__ TrajView trajView(const TrajDesc* desc, const TrajState* state, const double* cxy, const double* cyaw, int b, bool framed, const double* shift) {
+    const TrajDesc& td = desc[b];
+    TrajView r;
+    r.cx = cxy + td.off_cxy; r.cy = cyaw + td.off_cyaw; r.Nxy = td.Nxy; r.Nyaw = td.Nyaw;
+    r.Tx = state[b].T_xy; r.Ty = state[b].T_yaw;
+    r.framed = framed; r.sx = shift[0]; r.sy = shift[1];
+    return r;
+}
+__device__ __forceinline__ TrajView trajView(const ResidentDev& r, int b, bool framed, const double* shift) {
+    return trajView(r.desc, r.state, r.cxy, r.cyaw, b, framed, shift);
+}
+
+// ---- trajectory rollout (uph_rollout_batch): every sample of the resident trajectories, one lane per sample, one 64-lane workgroup per
+// (trajectory, chunk of 64 samples).  Trajectory-uniform data -- descriptor, state (T_xy, T_yaw), launch record, grid descriptor -- is indexed
+// by blockIdx only (scalar loads); the coefficients come from L2.  The rows of a chunk are contiguous in the output: each lane writes its row
+// to LDS and the workgroup then streams the chunk out with consecutive lanes on consecutive doubles (a lane-per-row store of a 224-byte row
+// would touch a different cache line in every lane of every store).
+struct RolloutTraj {            // one trajectory of a rollout launch (formed on the host)
+    int64_t row0;               // its first row in the launch's output
+    int cnt, rows;              // samples of the t += dt loop; rows = cnt (+ 1 with the end point)
+    double total;               // getTotalDuration: t of the end point
+    double shift[2];            // map coordinate of the trajectory's frame corner (local frames, TrajFrame); unused in the map's own frame
+};
+struct RolloutArgs {
+    ResidentDev r;
+    const GridDev* grid_mem;    // per-trajectory (framed) grid descriptors, or nullptr: the map's own frame (the kernel's grid argument)
+    const RolloutTraj* traj;    // [trajectories of the launch]
+    double* out;                // [rows of the launch][ncol]
+    int b0, channels, ncol;
+};
+constexpr int ROLL_NT = 64;
+constexpr int ROLL_MAXCOL = 9 + 7 + 12;
+
+// the pose of one sample from its (x, y, yaw) in LDS: the statements of uph_pose_kernel (map_build.hip) on inputs the compiler cannot see
+// through, so that the two kernels contract the same arithmetic the same way (rows equal uph_terrain_pose_query bit for bit)
+__device__ __forceinline__ void rolloutPose(const GridDev& g, const double* in, double* o) {
+    const double x = in[0], y = in[1], w = in[2];
+    Corners c;
+    locate(g, x, y, w, c);
+    double tv[4];
+    terrainValues(g, c, tv);
+    terrainPoseFrom(x, y, w, tv, o);
+}
+
+__global__ __launch_bounds__(ROLL_NT) void uph_rollout_kernel(GridDev grid, RolloutArgs a) {
+    __shared__ double stage[ROLL_NT * ROLL_MAXCOL];
+    const RolloutTraj rt = a.traj[blockIdx.x];
+    const int q0 = (int)blockIdx.y * ROLL_NT;
+    if (q0 >= rt.rows) return;
+    const int nq = rt.rows - q0 < ROLL_NT ? rt.rows - q0 : ROLL_NT;
+    const int b = a.b0 + (int)blockIdx.x;
+    const int ncol = a.ncol;
+    const bool framed = a.grid_mem != nullptr;
+    const int pcol = ncol - 12;             // first pose column (when selected)
+    if ((int)threadIdx.x < nq) {
+        const int q = q0 + (int)threadIdx.x;
+        const TrajView tr = trajView(a.r, b, framed, rt.shift);
+        const GridDev g = framed ? a.grid_mem[b] : grid;
+        const double t = q < rt.cnt ? a.r.tt[q] : rt.total;
+        TrajSample s;
+        double tm[7];
+        if (a.channels & UPH_ROLLOUT_TERRAIN) tr.sample<true>(t, g, grid.gravity, s, tm);
+        else tr.sample<false>(t, g, grid.gravity, s, tm);
+        double* r = stage + threadIdx.x * ncol;
+        if (a.channels & UPH_ROLLOUT_STATE) {
+            r[0] = t; r[1] = tr.mapX(s.p[0]); r[2] = tr.mapY(s.p[1]); r[3] = s.yawn;
+            r[4] = s.v[0]; r[5] = s.v[1]; r[6] = s.a[0]; r[7] = s.a[1]; r[8] = s.dyaw;
+            r += 9;
+        }
+        if (a.channels & UPH_ROLLOUT_TERRAIN) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) r[k] = tm[k];
+            r += 7;
+        }
+        if (a.channels & UPH_ROLLOUT_POSE) { r[0] = s.p[0]; r[1] = s.p[1]; r[2] = s.yawn; }       // (the pose's input, in the trajectory's frame)
+    }
+    __syncthreads();
+    if ((a.channels & UPH_ROLLOUT_POSE) && (int)threadIdx.x < nq) {
+        double* r = stage + threadIdx.x * ncol + pcol;
+        double in[3] = {r[0], r[1], r[2]}, o[12];
+        if (framed) {
+            rolloutPose(a.grid_mem[b], in, o);
+            o[9] += rt.shift[0]; o[10] += rt.shift[1];
+        } else {
+            rolloutPose(grid, in, o);
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) r[k] = o[k];
+    }
+    __syncthreads();
+    double* o = a.out + (size_t)(rt.row0 + q0) * ncol;
+    for (int i = (int)threadIdx.x; i < nq * ncol; i += ROLL_NT) o[i] = stage[i];
+}
+
+// ---- window queries: (trajectory, time window) pairs of the resident batch, one workgroup per query.  Lane l takes samples l, l + NT, ... of the window, each
+// sample the rollout's (same time table, same trajectorySample, same grid descriptor).  Every reduction is a selection under a total order (value, then the
+// smaller sample index) or an integer sum, so the order in which lanes and waves are combined cannot change a bit.  Query-uniform data -- query record,
+// descriptor, T_xy / T_yaw, grid descriptor, limits -- is indexed by blockIdx only (scalar loads).
+struct WinQuery {               // one query of a launch (formed on the host, in launch order: formWindowQueries)
+    int32_t b, out;             // resident trajectory; row of the output (the caller's query index)
+    int32_t q_lo, n_tab;        // the window's first sample in the time table and the number of samples taken from it
+    int32_t end_row, pad;       // != 0: the end point (t = total) closes the window
+    double total;               // getTotalDuration: t of the end point
+    double shift[2];            // as RolloutTraj
+};
+__device__ __forceinline__ int winCount(const WinQuery& q) { return q.n_tab + (q.end_row ? 1 : 0); }
+__device__ __forceinline__ double winTime(const WinQuery& q, const double* tt, int j) { return j < q.n_tab ? tt[q.q_lo + j] : q.total; }     // t of sample j of the window
+constexpr int WIN_NONE = 0x7fffffff;    // no sample
+
+// (value, sample) pairs: the larger (LARGER) or the smaller value wins, equal values go to the smaller sample (no NaN reaches here: the callers make it +inf)
+template <bool LARGER>
+__device__ __forceinline__ void winTake(double& v, int& i, double ov, int oi) {
+    const bool o = (LARGER ? ov > v : ov < v) || (ov == v && oi < i);
+    v = o ? ov : v; i = o ? oi : i;
+}
+
+// ---- check (uph_check_batch): the window reduced against limits on the map as it is now.  A 256-lane workgroup; a lane keeps in registers the first sample with a
+// violation and its mask, per term the worst value and its sample, two counters (200 VGPRs at two waves per SIMD, no scratch).
+struct CheckOut {               // one row per query
+    double first_t;             // NaN: no sample violates
+    int32_t first_mask, counts[3];      // samples, violating, occupied
+    double worst[7], worst_t[7];
+};
+struct CheckArgs {
+    ResidentDev r;
+    const GridDev* grid_mem;    // as RolloutArgs
+    const WinQuery* qs;
+    const char* occ;            // the map's occupancy layer [nx_hold][ny][nyaw] (uph_frontend_query's)
+    CheckOut* out;
+    double lim[7];
+};
+constexpr int CHECK_NT = 256, CHECK_NW = CHECK_NT / 64;
+constexpr unsigned long long CHECK_NONE = ~0ull;
+
+__global__ __launch_bounds__(CHECK_NT, 2) void uph_check_kernel(GridDev grid, CheckArgs a) {
+    __shared__ double s_red[CHECK_NW * (7 * 12 + 8 + 2 * 4) / 8];       // per term a double and an int, the first violation, two counters
+    const WinQuery cq = a.qs[blockIdx.x];
+    const int b = cq.b;
+    const TrajView tr = trajView(a.r, b, a.grid_mem != nullptr, cq.shift);
+    const GridDev g = tr.framed ? a.grid_mem[b] : grid;
+    const int n = winCount(cq);
+    // first: (sample << 8) | mask of the first violating sample, so that one unsigned minimum carries both
+    unsigned long long first = CHECK_NONE;
+    double wv[7];
+    int wi[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) { wv[k] = -__builtin_huge_val(); wi[k] = WIN_NONE; }
+    int nviol = 0, nocc = 0;
+    for (int j = (int)threadIdx.x; j < n; j += CHECK_NT) {
+        const double t = winTime(cq, a.r.tt, j);
+        TrajSample s;
+        double tm[7];
+        tr.sample<true>(t, g, grid.gravity, s, tm);
+        // the sample's values leave trajectorySample as they leave it in the rollout (stored, there): nothing below may be contracted into its arithmetic
+        double px = s.p[0], py = s.p[1], w = s.yawn;
+        asm volatile("" : "+v"(px), "+v"(py), "+v"(w));
+#pragma unroll
+        for (int k = 0; k < 7; k++) asm volatile("" : "+v"(tm[k]));
+        // isOccupancy at the STATE row's (x, y, yaw), map coordinates, on the map's own grid: the statements of uph_frontend_kernel (map_build.hip)
+        const double x = tr.mapX(px), y = tr.mapY(py);
+        const int ix = (int)floor((x - grid.origin[0]) * grid.xy_inv), iy = (int)floor((y - grid.origin[1]) * grid.xy_inv), iw = (int)floor((w - grid.origin[2]) * grid.yaw_inv);
+        const int ixh = ix - grid.x_off;
+        const bool in = ix >= 0 && iy >= 0 && iw >= 0 && ix <= grid.nx - 1 && iy <= grid.ny - 1 && iw <= grid.nyaw - 1 && ixh >= 0 && ixh <= grid.nx_hold - 1;
+        const int occ = in ? (int)a.occ[((size_t)ixh * grid.ny + iy) * grid.nyaw + iw] : -1;
+        int mask = occ != 0 ? 1 << UPH_CHECK_OCC_BIT : 0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const double v = tm[k], m = k < 4 ? fabs(v) : v;
+            if (!(m <= a.lim[k])) mask |= 1 << k;
+            const double key = fabs(v) < __builtin_huge_val() ? m : __builtin_huge_val();      // non-finite (NaN included): +inf
+            if (key > wv[k]) { wv[k] = key; wi[k] = j; }
+        }
+        if (mask != 0) {
+            nviol++;
+            if (first == CHECK_NONE) first = ((unsigned long long)(unsigned)j << 8) | (unsigned)mask;
+        }
+        nocc += occ != 0 ? 1 : 0;
+    }
+    const auto worst = [](double& v, int& i, double ov, int oi) { winTake<true>(v, i, ov, oi); };
+    const auto least = [](unsigned long long& k, unsigned long long o) { k = o < k ? o : k; };
+    const auto sum2 = [](int& x, int& y, int ox, int oy) { x += ox; y += oy; };
+#pragma unroll
+    for (int k = 0; k < 7; k++) rowReduce(worst, wv[k], wi[k]);
+    rowReduce(least, first);
+    rowReduce(sum2, nviol, nocc);
+#pragma unroll
+    for (int k = 0; k < 7; k++) rowLeaders(worst, wv[k], wi[k]);
+    rowLeaders(least, first);
+    rowLeaders(sum2, nviol, nocc);
+    // the waves' slots are disjoint: one barrier for all of them
+#pragma unroll
+    for (int k = 0; k < 7; k++) wavesPut<CHECK_NW>(s_red + 6 * k, wv[k], wi[k]);
+    wavesPut<CHECK_NW>(s_red + 42, first);
+    wavesPut<CHECK_NW>(s_red + 46, nviol, nocc);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 7; k++) wavesFold<CHECK_NW>(worst, s_red + 6 * k, wv[k], wi[k]);
+    wavesFold<CHECK_NW>(least, s_red + 42, first);
+    if (!wavesFold<CHECK_NW>(sum2, s_red + 46, nviol, nocc)) return;
+    const double nan = __builtin_nan("");
+    CheckOut o;
+    o.first_t = first == CHECK_NONE ? nan : winTime(cq, a.r.tt, (int)(first >> 8));
+    o.first_mask = first == CHECK_NONE ? 0 : (int)(first & 0xff);
+    o.counts[0] = n; o.counts[1] = nviol; o.counts[2] = nocc;
+    for (int k = 0; k < 7; k++) {
+        o.worst[k] = wv[k];
+        o.worst_t[k] = wi[k] == WIN_NONE ? nan : winTime(cq, a.r.tt, wi[k]);
+    }
+    a.out[cq.out] = o;
+}
+
+// ---- switch states (uph_replan_upload, uph_traj_states, uph_refine_upload): trajectory b of the resident batch at its clamped time, one lane per query.  The
+// sample is the rollout's, so at a rollout row's t the state equals that row bit for bit; the duration is the rollout's too (trajTotal).  Row q: x, y (map
+// coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw; COLS = TRAJ_STATE_COLS adds the raw yaw as column 9.  The 9-column instantiation is uph_replan_upload's.
+template <int COLS>
+__global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __restrict__ desc, const TrajState* __restrict__ state, const double* __restrict__ cxy,
+                                                              const double* __restrict__ cyaw, const SwitchQuery* __restrict__ qs, int nq, double* __restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const SwitchQuery sq = qs[q];
+    const TrajView tr = trajView(desc, state, cxy, cyaw, sq.b, sq.framed != 0, sq.shift);
+    const double total = trajTotal(tr.Nxy, tr.Tx, tr.Nyaw, tr.Ty);
+    const double t = sq.t <= 0.0 ? 0.0 : (sq.t >= total ? total : sq.t);
+    TrajSample s;
+    tr.state(t, s);
+    double* o = out + (size_t)q * COLS;
+    o[0] = tr.mapX(s.p[0]); o[1] = tr.mapY(s.p[1]);
+    o[2] = s.v[0]; o[3] = s.v[1]; o[4] = s.a[0]; o[5] = s.a[1];
+    o[6] = s.yawn; o[7] = s.dyaw; o[8] = s.ddyaw;
+    if (COLS > SWITCH_COLS) o[9] = s.yaw;
+}
+
+// ---- locate / within (uph_locate_batch, uph_within_batch): geometric reductions over the STATE samples of a window.  No terrain: a sample is two quintics,
+// about a tenth of the check's, so a query of the tracking workload (101 samples) gets one wave (NT = 64, no LDS, no barrier) and only windows longer than
+// LOC_SHORT samples get the check's 256 lanes; the host splits the sorted launch at that length.  The selection makes the answer the same for either width.
+//   locate: the sample nearest to a pose (d2 = ex ex + ey ey with both products rounded, the smaller sample among equals, NaN as +inf), then, uniform
+//           work of thread 0, a safeguarded Newton iteration on g(t) = e . v inside the bracket of the neighbouring samples; state and tracking error there.
+//   within: first and last sample inside a closed rect, the number of samples inside.
+struct LocQuery : WinQuery {
+    double p[4];                // locate: pose x, y, yaw (map coordinates);  within: rect x0, x1, y0, y1
+};
+struct LocateOut {              // one row per query
+    double near_t, near_d2;     // coarse stage
+    double t, d2;
+    double state[TRAJ_STATE_COLS];
+    double err[3];              // e_lon, e_lat, e_yaw
+    int32_t count, refined;
+};
+struct WithinOut {
+    double enter_t, leave_t;    // NaN: no sample inside
+    int32_t counts[2];          // samples, inside
+};
+struct LocArgs {
+    ResidentDev r;
+    const LocQuery* qs;
+    void* out;                  // LocateOut / WithinOut rows
+    int framed, q0;             // the batch solves in local frames (add shift, as the rollout does); first query of this launch
+};
+constexpr int LOC_SHORT = 192;  // windows of at most this many samples run on one wave
+constexpr int LOC_NEWTON = 8;
+
+// the STATE row at t: position in map coordinates as the rollout and uph_switch_state_kernel form it.  The values leave trajectorySample as they leave it
+// there (stored): nothing after this may be contracted into its arithmetic.
+__device__ __forceinline__ void locSample(const TrajView& tr, double t, TrajSample& s, double& X, double& Y) {
+    tr.state(t, s);
+    X = tr.mapX(s.p[0]); Y = tr.mapY(s.p[1]);
+    asm volatile("" : "+v"(X), "+v"(Y));
+}
+// squared distance with both products rounded before the add
+__device__ __forceinline__ double locD2(double ex, double ey) {
+    double xx = ex * ex, yy = ey * ey;
+    asm volatile("" : "+v"(xx), "+v"(yy));
+    return xx + yy;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
+    __shared__ double s_red[NT / 64 * 12 / 8];
+    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
+    const TrajView tr = trajView(a.r, lq.b, a.framed != 0, lq.shift);
+    const int n = winCount(lq);
+    const double x = lq.p[0], y = lq.p[1];
+    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
+    double v = inf;
+    int i = WIN_NONE;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        TrajSample s;
+        double X, Y;
+        locSample(tr, winTime(lq, a.r.tt, j), s, X, Y);
+        const double d2 = locD2(X - x, Y - y);
+        winTake<false>(v, i, d2 < inf ? d2 : inf, j);       // NaN: +inf
+    }
+    const auto nearest = [](double& v, int& i, double ov, int oi) { winTake<false>(v, i, ov, oi); };
+    rowReduce(nearest, v, i);
+    rowLeaders(nearest, v, i);
+    if (!acrossWaves<NT / 64>(nearest, s_red, v, i)) return;
+    // sample k of the window (NaN outside it: an empty window answers NaN by this path, not by a special one)
+    auto tau = [&](int k) { return k < 0 || k >= n ? nan : winTime(lq, a.r.tt, k); };
+    LocateOut o;
+    o.count = n; o.near_t = tau(i); o.near_d2 = v;
+    const double lo = tau(i - 1 > 0 ? i - 1 : 0), hi = tau((i < n - 2 ? i : n - 2) + 1);
+    double t = o.near_t, ta = lo, tb = hi;
+    TrajSample s, s0;
+    double X, Y, X0 = nan, Y0 = nan, d2 = nan;
+    for (int it = 0;; it++) {
+        locSample(tr, t, s, X, Y);
+        const double ex = X - x, ey = Y - y;
+        d2 = locD2(ex, ey);
+        if (it == 0) { s0 = s; X0 = X; Y0 = Y; }
+        if (it == LOC_NEWTON) break;                        // the candidate left by the last iteration
+        const double g = ex * s.v[0] + ey * s.v[1];
+        const double h = s.v[0] * s.v[0] + s.v[1] * s.v[1] + ex * s.a[0] + ey * s.a[1];
+        if (g > 0.0) tb = t;
+        else if (g < 0.0) ta = t;
+        else if (g == 0.0) break;
+        double tn = t - g / h;
+        if (!(h > 0.0 && ta <= tn && tn <= tb)) tn = 0.5 * (ta + tb);
+        if (tn == t) break;
+        t = tn;
+    }
+    const bool refined = d2 <= v;
+    if (!refined) { s = s0; X = X0; Y = Y0; t = o.near_t; d2 = v; }
+    o.t = t; o.d2 = d2; o.refined = refined ? 1 : 0;
+    o.state[0] = X; o.state[1] = Y; o.state[2] = s.v[0]; o.state[3] = s.v[1]; o.state[4] = s.a[0]; o.state[5] = s.a[1];
+    o.state[6] = s.yawn; o.state[7] = s.dyaw; o.state[8] = s.ddyaw; o.state[9] = s.yaw;
+    const double rx = x - X, ry = y - Y;
+    double sw, cw;
+    sincos(s.yaw, &sw, &cw);
+    o.err[0] = rx * cw + ry * sw;
+    o.err[1] = ry * cw - rx * sw;
+    o.err[2] = normSO2(lq.p[2] - s.yaw);
+    ((LocateOut*)a.out)[lq.out] = o;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
+    __shared__ double s_red[NT / 64 * 12 / 8];
+    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
+    const TrajView tr = trajView(a.r, lq.b, a.framed != 0, lq.shift);
+    const int n = winCount(lq);
+    const double x0 = lq.p[0], x1 = lq.p[1], y0 = lq.p[2], y1 = lq.p[3];
+    int first = WIN_NONE, last = -1, cnt = 0;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        TrajSample s;
+        double X, Y;
+        locSample(tr, winTime(lq, a.r.tt, j), s, X, Y);
+        if (x0 <= X && X <= x1 && y0 <= Y && Y <= y1) {     // (a NaN position is not inside)
+            first = first == WIN_NONE ? j : first; last = j; cnt++;
+        }
+    }
+    const auto span = [](int& lo, int& hi, int& c, int ol, int oh, int oc) { lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; c += oc; };
+    rowReduce(span, first, last, cnt);
+    rowLeaders(span, first, last, cnt);
+    if (!acrossWaves<NT / 64>(span, s_red, first, last, cnt)) return;
+    const double nan = __builtin_nan("");
+    WithinOut o;
+    o.enter_t = cnt == 0 ? nan : winTime(lq, a.r.tt, first);
+    o.leave_t = cnt == 0 ? nan : winTime(lq, a.r.tt, last);
+    o.counts[0] = n; o.counts[1] = cnt;
+    ((WithinOut*)a.out)[lq.out] = o;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+static ResidentDev residentDev(uph_ctx* c) {
+    ResidentDev r;
+    r.desc = c->d_desc.as<TrajDesc>(); r.state = c->d_state.as<TrajState>();
+    r.cxy = c->d_cxy.as<double>(); r.cyaw = c->d_cyaw.as<double>();
+    r.tt = c->d_roll_tt.as<double>();
+    return r;
+}
+
+// uph_traj_states / uph_replan_upload / uph_refine_upload and the window queries: c holds resident trajectories and every query names one of them at a finite time
+int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t, const char* who) {
+    if (c->B <= 0 || !c->traj_resident) {
+        setError(std::string(who) + ": no trajectory is resident (uph_batch_solve / uph_eval_batch after the upload first)"); return UPH_ERR_INVALID;
+    }
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t b = traj[q];
+        if (b < 0 || b >= c->B) { setError(std::string(who) + ": query " + std::to_string(q) + " names no trajectory of the resident batch"); return UPH_ERR_INVALID; }
+        if (!c->rejected.empty() && c->rejected[(size_t)b]) {
+            setError(std::string(who) + ": query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
+        }
+        if (!std::isfinite(t[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a non-finite time"); return UPH_ERR_INVALID; }
+    }
+    return UPH_OK;
+}
+
+// the states of queries sq on c's resident trajectories into c->d_sw_out [n][cols] (enqueued on c's stream, not waited for)
+int launchTrajStates(uph_ctx* c, const std::vector<SwitchQuery>& sq, int cols) {
+    const size_t n = sq.size();
+    if (c->d_sw_q.ensure(sizeof(SwitchQuery) * n) || c->d_sw_out.ensure(sizeof(double) * cols * n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * n, hipMemcpyHostToDevice, c->stream));
+    const auto kernel = cols == SWITCH_COLS ? uph_switch_state_kernel<SWITCH_COLS> : uph_switch_state_kernel<TRAJ_STATE_COLS>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->d_desc.as<TrajDesc>(), c->d_state.as<TrajState>(), c->d_cxy.as<double>(),
+                       c->d_cyaw.as<double>(), c->d_sw_q.as<SwitchQuery>(), (int)n, c->d_sw_out.as<double>());
+    HIPCHK(hipGetLastError());
+    return UPH_OK;
+}
+
+SwitchQuery trajQuery(const uph_ctx* c, int32_t b, double t) {
+    SwitchQuery r;
+    r.b = b; r.framed = c->frames.empty() ? 0 : 1; r.t = t;
+    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    return r;
+}
+
+// ---- trajectory rollout (include/uneven_hip.h uph_rollout_*) -------------------------------------------------------------------------------
+// Sample times: t_q = the value after q additions of dt to 0.0 -- the running sum of the reference's `for (t = 0; t < total; t += dt)` loops
+// (alm_traj_opt.h:182, alm_traj_opt.cpp:1109) and of Solver::report -- built ONCE per call, serially in fp64, up to the longest trajectory and
+// shared by the batch; a trajectory's count is the first q with t_q >= total (binary search).  A NaN duration has no samples, as in the loop.
+static int rolloutTimes(double dt, double tmax, std::vector<double>& tab) {
+    tab.assign(1, 0.0);
+    double t = 0.0;
+    while (t < tmax && (int64_t)tab.size() <= UPH_ROLLOUT_MAX_SAMPLES) {
+        const double tn = t + dt;
+        if (!(tn > t)) { setError("uph_rollout: the running sum t += dt stops growing before it reaches the trajectory's duration"); return UPH_ERR_LIMIT; }
+        t = tn;
+        tab.push_back(t);
+    }
+    return UPH_OK;
+}
+
+struct RolloutSizes {
+    std::vector<double> tab;        // t_q
+    std::vector<int32_t> cnt;       // samples of the loop per trajectory
+    std::vector<double> total;      // durations
+    std::vector<int64_t> offs;      // [B + 1] row offsets
+};
+
+// durations as Solver::report forms them (trajTotal); skip[b] != 0: no rows
+static int rolloutSizes(int B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, const int* skip, double dt, int with_end,
+                        RolloutSizes& rs) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_rollout: dt must be positive and finite"); return UPH_ERR_INVALID; }
+    rs.cnt.assign(B, 0); rs.total.assign(B, 0.0); rs.offs.assign((size_t)B + 1, 0);
+    double tmax = 0.0;
+    for (int b = 0; b < B; b++) {
+        if (n_xy[b] < 0 || n_yaw[b] < 0) { setError("uph_rollout_sizes: negative piece count"); return UPH_ERR_INVALID; }
+        if (skip && skip[b]) continue;
+        rs.total[b] = trajTotal(n_xy[b], T_xy[b], n_yaw[b], T_yaw[b]);
+        if (rs.total[b] > tmax) tmax = rs.total[b];
+    }
+    const int r = rolloutTimes(dt, tmax, rs.tab);
+    if (r != UPH_OK) return r;
+    for (int b = 0; b < B; b++) {
+        int64_t rows = 0;
+        if (!(skip && skip[b])) {
+            const int64_t q = std::lower_bound(rs.tab.begin(), rs.tab.end(), rs.total[b]) - rs.tab.begin();
+            if (q >= (int64_t)rs.tab.size()) {
+                setError("uph_rollout: trajectory " + std::to_string(b) + " needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt");
+                return UPH_ERR_LIMIT;
+            }
+            rs.cnt[b] = (int32_t)q;
+            rows = q + (with_end ? 1 : 0);
+        }
+        rs.offs[b + 1] = rs.offs[b] + rows;
+    }
+    return UPH_OK;
+}
+
+static int rolloutColumns(int channels) {
+    return (channels & UPH_ROLLOUT_STATE ? 9 : 0) + (channels & UPH_ROLLOUT_TERRAIN ? 7 : 0) + (channels & UPH_ROLLOUT_POSE ? 12 : 0);
+}
+
+// the resident batch of c: checks + sizes
+static int rolloutPlanCtx(uph_ctx* c, double dt, int with_end, RolloutSizes& rs, const char* who) {
+    if (!c || c->B <= 0) { setError(std::string(who) + ": no batch uploaded"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    if (!c->traj_resident) {
+        setError(std::string(who) + ": no trajectory is resident -- the batch was uploaded but not solved or evaluated since (uph_batch_solve / uph_eval_batch first)");
+        return UPH_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    const int r = refreshStates(c);
+    if (r != UPH_OK) return r;
+    const int B = c->B;
+    std::vector<int32_t> nx(B), ny(B);
+    std::vector<double> tx(B), ty(B);
+    for (int b = 0; b < B; b++) { nx[b] = c->desc[b].Nxy; ny[b] = c->desc[b].Nyaw; tx[b] = c->state_host[b].T_xy; ty[b] = c->state_host[b].T_yaw; }
+    return rolloutSizes(B, nx.data(), tx.data(), ny.data(), ty.data(), c->rejected.data(), dt, with_end, rs);
+}
+
+// enqueue the kernel for trajectories [b0, b1) writing rows offs[b0] .. offs[b1] to out_dev (row offs[b0] first); the time table is resident
+static int rolloutLaunch(uph_ctx* c, const GridDev& grid, const RolloutSizes& rs, int channels, int b0, int b1, double* out_dev, std::vector<RolloutTraj>& rec) {
+    const int n = b1 - b0;
+    if (n <= 0 || rs.offs[b1] == rs.offs[b0]) return UPH_OK;
+    rec.assign(n, RolloutTraj());
+    int ychunks = 0;
+    for (int k = 0; k < n; k++) {
+        const int b = b0 + k;
+        RolloutTraj& t = rec[k];
+        t.row0 = rs.offs[b] - rs.offs[b0];
+        t.cnt = rs.cnt[b];
+        t.rows = (int)(rs.offs[b + 1] - rs.offs[b]);
+        t.total = rs.total[b];
+        t.shift[0] = c->frames.empty() ? 0.0 : c->frames[b].shift[0];
+        t.shift[1] = c->frames.empty() ? 0.0 : c->frames[b].shift[1];
+        ychunks = std::max(ychunks, (t.rows + ROLL_NT - 1) / ROLL_NT);
+    }
+    if (c->d_roll_traj.ensure(sizeof(RolloutTraj) * n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_traj.p, rec.data(), sizeof(RolloutTraj) * n, hipMemcpyHostToDevice, c->stream));
+    RolloutArgs a;
+    a.r = residentDev(c);
+    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
+    a.traj = c->d_roll_traj.as<RolloutTraj>(); a.out = out_dev;
+    a.b0 = b0; a.channels = channels; a.ncol = rolloutColumns(channels);
+    hipLaunchKernelGGL(uph_rollout_kernel, dim3(n, ychunks), dim3(ROLL_NT), 0, c->stream, grid, a);
+    HIPCHK(hipGetLastError());
+    return UPH_OK;
+}
+
+// common part of the two variants: arguments, sizes, grid descriptors, time table
+static int rolloutBegin(uph_ctx* c, double dt, int with_end, int channels, int b0, int b1, const void* out, RolloutSizes& rs, GridDev& grid, const char* who) {
+    if (!c || !out || (channels & ~UPH_ROLLOUT_ALL) || !(channels & UPH_ROLLOUT_ALL)) { setError(std::string(who) + ": bad arguments (null pointer or channel mask)"); return UPH_ERR_INVALID; }
+    if (b0 < 0 || b1 < b0 || b1 > c->B) { setError(std::string(who) + ": trajectory range [b0, b1) outside the batch"); return UPH_ERR_INVALID; }
+    int r = rolloutPlanCtx(c, dt, with_end, rs, who);
+    if (r != UPH_OK) return r;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    if (c->d_roll_tt.ensure(8 * rs.tab.size())) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
+    return UPH_OK;
+}
+
+// the host variant stages chunks of whole trajectories through a device buffer of at most this size (one trajectory at the sample cap: 59 MB)
+static const size_t ROLL_STAGE_BYTES = (size_t)256 << 20;
+
+// ---- check (include/uneven_hip.h uph_check_*) ------------------------------------------------------------------------------------------------
+// the window [t_from, t_to] in the first cnt entries of the time table (strictly increasing): samples [q_lo, q_hi) have t_from <= t_q and t_q <= t_to
+static void checkWindow(const std::vector<double>& tab, int64_t cnt, int with_end, double total, double t_from, double t_to, int32_t& q_lo, int32_t& q_hi,
+                        int32_t& end_row) {
+    const auto b = tab.begin(), e = tab.begin() + cnt;
+    const int64_t lo = std::lower_bound(b, e, t_from) - b;            // the first q with t_from <= t_q
+    const int64_t hi = std::upper_bound(b, e, t_to) - b;              // the first q with t_to < t_q
+    q_lo = (int32_t)lo; q_hi = (int32_t)(hi < lo ? lo : hi);
+    end_row = (with_end && t_from <= total && total <= t_to) ? 1 : 0;
+}
+
+// what the window queries share: every refusal (outputs untouched), the caller's own check of each query's row, which also stores it in the record (own(q, record)),
+// the windows in the rollout's time table, the query records in launch order -- the longest windows first (as the uploads order the solves by predicted cost: the
+// tail of the launch is made of short workgroups), stable -- and the time table and the records on the device (d_roll_tt, d_win_q)
+template <class Q, class Own>
+static int formWindowQueries(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const char* who,
+                             std::vector<Q>& qs, Own own) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(std::string(who) + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t_from, who);
+    if (r != UPH_OK) return r;
+    if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
+    qs.assign((size_t)n, Q());
+    for (int32_t q = 0; q < n; q++) if ((r = own(q, qs[(size_t)q])) != UPH_OK) return r;
+    RolloutSizes rs;
+    r = rolloutPlanCtx(c, dt, with_end, rs, who);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const int32_t b = traj[q];
+        Q& k = qs[(size_t)q];
+        int32_t q_hi = 0;
+        k.b = b; k.out = q; k.pad = 0;
+        checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
+        k.n_tab = q_hi - k.q_lo;
+        k.total = rs.total[(size_t)b];
+        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    }
+    std::stable_sort(qs.begin(), qs.end(), [](const Q& x, const Q& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
+    if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_win_q.ensure(sizeof(Q) * (size_t)n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_win_q.p, qs.data(), sizeof(Q) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return UPH_OK;
+}
+
+// the launch(es) of a window query between the context's events -- launch() enqueues on the context's stream and returns hipGetLastError() --, the rows of
+// d_win_out to the host, the wait (also after a failed launch: nothing of this call stays queued, and the host copies outlive it), the time between the events
+template <class Out, class Launch>
+static int runQueryLaunch(uph_ctx* c, Launch launch, std::vector<Out>& out, double& ms_out) {
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    const hipError_t le = launch();
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    const hipError_t ce = hipMemcpyAsync(out.data(), c->d_win_out.p, sizeof(Out) * out.size(), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    HIPCHK(le); HIPCHK(ce); HIPCHK(se);
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    ms_out = ms;
+    return UPH_OK;
+}
+
+// locate / within: the records in launch order with the caller's `extra` doubles per query (pose / rect) in each, then 256 lanes for the queries at the head of
+// the launch whose window exceeds LOC_SHORT samples and one wave for the rest
+template <class Out, class K256, class K64>
+static int locRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* rows, int extra,
+                  const char* who, K256 k256, K64 k64, std::vector<Out>& out) {
+    std::vector<LocQuery> qs;
+    int r = formWindowQueries(c, n, traj, t_from, t_to, dt, with_end, who, qs, [&](int32_t q, LocQuery& k) {
+        for (int d = 0; d < 4; d++) k.p[d] = d < extra ? rows[(size_t)extra * q + d] : 0.0;
+        for (int d = 0; d < extra; d++) if (extra == 3 ? !std::isfinite(k.p[d]) : std::isnan(k.p[d])) {
+            setError(std::string(who) + ": query " + std::to_string(q) + (extra == 3 ? " has a non-finite pose component" : " has a NaN rect bound")); return (int)UPH_ERR_INVALID;
+        }
+        return (int)UPH_OK;
+    });
+    if (r != UPH_OK) return r;
+    int32_t n_long = 0;
+    while (n_long < n && qs[(size_t)n_long].n_tab + qs[(size_t)n_long].end_row > LOC_SHORT) n_long++;
+    if (c->d_win_out.ensure(sizeof(Out) * (size_t)n)) return UPH_ERR_HIP;
+    LocArgs a;
+    a.r = residentDev(c); a.qs = c->d_win_q.as<LocQuery>(); a.out = c->d_win_out.p; a.framed = c->frames.empty() ? 0 : 1; a.q0 = 0;
+    out.resize((size_t)n);
+    return runQueryLaunch(c, [&]() {
+        hipError_t le = hipSuccess;
+        if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
+        if (n > n_long && le == hipSuccess) { a.q0 = n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
+        return le;
+    }, out, c->last_locate_ms);
+}
+
+extern "C" {
+
+int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
+    if (!c || n <= 0 || !traj || !t || !out10) { setError("uph_traj_states: bad arguments"); return UPH_ERR_INVALID; }
+    if (c->pending) { setError("uph_traj_states: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t, "uph_traj_states");
+    if (r != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    std::vector<SwitchQuery> sq((size_t)n);
+    for (int32_t q = 0; q < n; q++) sq[(size_t)q] = trajQuery(c, traj[q], t[q]);
+    r = launchTrajStates(c, sq);
+    if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
+    HIPCHK(hipMemcpyAsync(out10, c->d_sw_out.p, sizeof(double) * TRAJ_STATE_COLS * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return UPH_OK;
+}
+
+int uph_rollout_sizes(int32_t B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, double dt, int32_t with_end,
+                      int64_t* offsets) {
+    if (B < 0 || !offsets || (B > 0 && (!n_xy || !T_xy || !n_yaw || !T_yaw))) { setError("uph_rollout_sizes: bad arguments"); return UPH_ERR_INVALID; }
+    RolloutSizes rs;
+    const int r = rolloutSizes(B, n_xy, T_xy, n_yaw, T_yaw, nullptr, dt, with_end, rs);
+    if (r != UPH_OK) return r;
+    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)B + 1));
+    return UPH_OK;
+}
+
+int uph_rollout_plan(uph_ctx* c, double dt, int32_t with_end, int64_t* offsets) {
+    if (!offsets) { setError("uph_rollout_plan: bad arguments"); return UPH_ERR_INVALID; }
+    RolloutSizes rs;
+    const int r = rolloutPlanCtx(c, dt, with_end, rs, "uph_rollout_plan");
+    if (r != UPH_OK) return r;
+    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)c->B + 1));
+    return UPH_OK;
+}
+
+int uph_rollout_batch(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, double* out) {
+    RolloutSizes rs;
+    GridDev grid;
+    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out, rs, grid, "uph_rollout_batch");
+    if (r != UPH_OK) return r;
+    const size_t row_bytes = 8 * (size_t)rolloutColumns(channels);
+    const size_t need = row_bytes * (size_t)(rs.offs[b1] - rs.offs[b0]);
+    if (need > 0 && c->d_roll_stage.ensure(std::min(need, ROLL_STAGE_BYTES))) return UPH_ERR_HIP;
+    std::vector<RolloutTraj> rec;
+    for (int k0 = b0; k0 < b1;) {
+        int k1 = k0 + 1;           // whole trajectories while they fit the staging buffer (one always does)
+        while (k1 < b1 && row_bytes * (size_t)(rs.offs[k1 + 1] - rs.offs[k0]) <= ROLL_STAGE_BYTES) k1++;
+        const size_t bytes = row_bytes * (size_t)(rs.offs[k1] - rs.offs[k0]);
+        if (bytes > 0) {
+            r = rolloutLaunch(c, grid, rs, channels, k0, k1, c->d_roll_stage.as<double>(), rec);
+            if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
+            HIPCHK(hipMemcpyAsync((char*)out + row_bytes * (size_t)(rs.offs[k0] - rs.offs[b0]), c->d_roll_stage.p, bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        k0 = k1;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return UPH_OK;
+}
+
+int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, void* out_dev) {
+    RolloutSizes rs;
+    GridDev grid;
+    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out_dev, rs, grid, "uph_rollout_batch_dev");
+    if (r != UPH_OK) return r;
+    std::vector<RolloutTraj> rec;
+    r = rolloutLaunch(c, grid, rs, channels, b0, b1, (double*)out_dev, rec);
+    const hipError_t e = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
+    if (r != UPH_OK) return r;
+    if (e != hipSuccess) { setError(std::string("uph_rollout_batch_dev: ") + hipGetErrorString(e)); return UPH_ERR_HIP; }
+    return UPH_OK;
+}
+
+int uph_check_limits(const uph_ctx* c, double* lim7) {
+    if (!c || !lim7) { setError("uph_check_limits: bad arguments"); return UPH_ERR_INVALID; }
+    const OptParams& P = c->P;
+    const double l[7] = {P.max_vel, P.max_acc_lon, P.max_acc_lat, P.max_kap, -P.min_cxi, P.max_sig, __builtin_huge_val()};
+    std::memcpy(lim7, l, sizeof(l));
+    return UPH_OK;
+}
+
+int uph_check_window(double dt, int32_t with_end, double total, double t_from, double t_to, int32_t* q_lo, int32_t* q_hi, int32_t* end_row) {
+    if (!q_lo || !q_hi || !end_row) { setError("uph_check_window: bad arguments"); return UPH_ERR_INVALID; }
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_check_window: dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (std::isnan(t_from) || std::isnan(t_to)) { setError("uph_check_window: a window bound is NaN"); return UPH_ERR_INVALID; }
+    std::vector<double> tab;
+    const int r = rolloutTimes(dt, total, tab);
+    if (r != UPH_OK) return r;
+    const int64_t cnt = std::lower_bound(tab.begin(), tab.end(), total) - tab.begin();       // (a NaN total: no samples, as in the loop)
+    if (cnt >= (int64_t)tab.size()) { setError("uph_check_window: the trajectory needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt"); return UPH_ERR_LIMIT; }
+    checkWindow(tab, cnt, with_end, total, t_from, t_to, *q_lo, *q_hi, *end_row);
+    return UPH_OK;
+}
+
+int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* lim7,
+                    double* first_t, int32_t* first_mask, int32_t* counts, double* worst, double* worst_t) {
+    if (!c || n <= 0 || !traj || !t_from) { setError("uph_check_batch: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<WinQuery> qs;
+    int r = formWindowQueries(c, n, traj, t_from, t_to, dt, with_end, "uph_check_batch", qs, [](int32_t, WinQuery&) { return (int)UPH_OK; });
+    if (r != UPH_OK) return r;
+    GridDev grid;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    if (c->d_win_out.ensure(sizeof(CheckOut) * (size_t)n)) return UPH_ERR_HIP;
+    CheckArgs a;
+    a.r = residentDev(c); a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>(); a.qs = c->d_win_q.as<WinQuery>(); a.out = c->d_win_out.as<CheckOut>();
+    const char* occ_r2 = nullptr;
+    uphMapOcc(c->map, &a.occ, &occ_r2);
+    if (lim7) std::memcpy(a.lim, lim7, sizeof(a.lim));
+    else uph_check_limits(c, a.lim);
+    std::vector<CheckOut> out((size_t)n);
+    r = runQueryLaunch(c, [&]() { hipLaunchKernelGGL(uph_check_kernel, dim3((unsigned)n), dim3(CHECK_NT), 0, c->stream, grid, a); return hipGetLastError(); }, out, c->last_check_ms);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const CheckOut& o = out[(size_t)q];
+        if (first_t) first_t[q] = o.first_t;
+        if (first_mask) first_mask[q] = o.first_mask;
+        if (counts) for (int k = 0; k < 3; k++) counts[3 * (size_t)q + k] = o.counts[k];
+        if (worst) for (int k = 0; k < 7; k++) worst[7 * (size_t)q + k] = o.worst[k];
+        if (worst_t) for (int k = 0; k < 7; k++) worst_t[7 * (size_t)q + k] = o.worst_t[k];
+    }
+    return UPH_OK;
+}
+
+int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_check_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_check_ms;
+    return UPH_OK;
+}
+
+
+// ---- locate / within (include/uneven_hip.h uph_locate_*, uph_within_batch) ---------------------------------------------------------------------------
+int uph_locate_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* poses, const double* t_from, const double* t_to, double dt, int32_t with_end,
+                     double* near_t, double* near_d2, int32_t* count, double* t, int32_t* refined, double* state, double* d2, double* err) {
+    if (!c || n <= 0 || !traj || !poses || !t_from) { setError("uph_locate_batch: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<LocateOut> out;
+    const int r = locRun(c, n, traj, t_from, t_to, dt, with_end, poses, 3, "uph_locate_batch", uph_locate_kernel<256>, uph_locate_kernel<64>, out);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const LocateOut& o = out[(size_t)q];
+        if (near_t) near_t[q] = o.near_t;
+        if (near_d2) near_d2[q] = o.near_d2;
+        if (count) count[q] = o.count;
+        if (t) t[q] = o.t;
+        if (refined) refined[q] = o.refined;
+        if (state) for (int k = 0; k < TRAJ_STATE_COLS; k++) state[(size_t)TRAJ_STATE_COLS * q + k] = o.state[k];
+        if (d2) d2[q] = o.d2;
+        if (err) for (int k = 0; k < 3; k++) err[3 * (size_t)q + k] = o.err[k];
+    }
+    return UPH_OK;
+}
+
+int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* rects, const double* t_from, const double* t_to, double dt, int32_t with_end,
+                     double* enter_t, double* leave_t, int32_t* counts) {
+    if (!c || n <= 0 || !traj || !rects || !t_from) { setError("uph_within_batch: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<WithinOut> out;
+    const int r = locRun(c, n, traj, t_from, t_to, dt, with_end, rects, 4, "uph_within_batch", uph_within_kernel<256>, uph_within_kernel<64>, out);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const WithinOut& o = out[(size_t)q];
+        if (enter_t) enter_t[q] = o.enter_t;
+        if (leave_t) leave_t[q] = o.leave_t;
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_locate_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_locate_ms;
+    return UPH_OK;
+}
+
+}  // extern "C"

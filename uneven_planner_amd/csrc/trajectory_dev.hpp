@@ -1,5 +1,5 @@
 // One sample of a solved trajectory: the evaluation that the post-solve report (Solver::report, solver_program.hpp) reduces and the
-// trajectory rollout (uph_rollout_batch, unevenhip.hip) writes out row by row.  One definition, so that the two cannot drift apart.
+// trajectory rollout (uph_rollout_batch, traj_query.hip) writes out row by row.  One definition, so that the two cannot drift apart.
 //   getNormSE2Pos / getVel / getAcc of SE2Trajectory (se2traj.hpp:343-361 locatePieceIdx, :106-140 Piece value and derivatives)
 //   + the terms of getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229) and getNonHolError (se2traj.hpp:551-561) at that sample.
 #pragma once
@@ -70,6 +70,14 @@ UPH_HD void trajectorySample(const double* cxy, const double* cyaw, int Nxy, int
     out[4] = -1.0 / tv[5];
     out[5] = tv[6];
     out[6] = fabs(v[0] * sy_ + v[1] * (-cy_));
+}
+
+// getTotalDuration of that trajectory as Solver::report forms it: running sums of the piece durations, the smaller of the two
+UPH_HD double trajTotal(int Nxy, double Tx, int Nyaw, double Ty) {
+    double durx = 0.0, dury = 0.0;
+    for (int i = 0; i < Nxy; i++) durx += Tx;
+    for (int i = 0; i < Nyaw; i++) dury += Ty;
+    return durx < dury ? durx : dury;
 }
 
 }  // namespace uph

@@ -1,6 +1,6 @@
 // libunevenhip.so -- optimiser half: gfx950 kernels + the C-ABI declared in include/uneven_hip.h.
 // One persistent workgroup (64, 128 or 256 lanes) per trajectory runs the whole ALM / L-BFGS / MINCO solve (solver_program.hpp).
-// The map half (plane-fit build) lives in map_build.hip.
+// The map half (plane-fit build) lives in map_build.hip, the queries on resident trajectories (rollout, check, locate / within, states) in traj_query.hip.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -20,7 +20,8 @@
 #include "minco_op_host.hpp"
 #include "resample_walk.hpp"
 #include "solver_program.hpp"
-#include "uph_internal.hpp"
+#include "uph_ctx.hpp"
+#include "wave_dev.hpp"
 
 using namespace uph;
 
@@ -35,59 +36,6 @@ using namespace uph;
 #endif
 
 // ------------------------------------------------------------------------------------------------ device workgroup object
-// wave64 sum with DPP row rotations (no LDS traffic, no barrier): rotate-and-add inside each row of 16 lanes, then the four
-// row totals are read from lanes 0/16/32/48 and added in a fixed order, so every lane gets the same bits.
-template <int CTRL>
-__device__ __forceinline__ double dppMov(double v) {
-    // a row rotation writes every lane, so no "old" value has to be preserved: mov_dpp (undefined old) spares the two copies
-    // per step that update_dpp(old = src) costs on the dependency chain of every reduction
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readLane(double v, int l) {      // l must be wave-uniform
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-// wave-uniform values (block reduction results, ring positions, ...) are moved to SGPRs explicitly: the compiler cannot prove
-// uniformity of anything that passed through LDS, and would otherwise keep loop bounds in VGPRs, branch through exec masks and
-// -- worst -- park them in scratch, whose reload forces s_waitcnt vmcnt(0) and drains every prefetch in flight.
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double uni(double v) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-typedef const __attribute__((address_space(1))) double* gcptr;       // read-only global pointer
-__device__ __forceinline__ gcptr uniG(const double* p) {             // wave-uniform global pointer held in an SGPR pair
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return (gcptr)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double writeLane(double v /*wave-uniform*/, int l /*wave-uniform*/, double old) {   // old with lane l replaced by v
-    int hi = __double2hiint(old), lo = __double2loint(old);
-    const int vh = __builtin_amdgcn_readfirstlane(__double2hiint(v)), vl = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    const int ls = __builtin_amdgcn_readfirstlane(l);
-    asm volatile("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(hi) : "s"(vh), "s"(ls) : "m0");
-    asm volatile("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(lo) : "s"(vl), "s"(ls) : "m0");
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double waveSum(double v) {
-    v += dppMov<0x128>(v);   // row_ror:8
-    v += dppMov<0x124>(v);   // row_ror:4
-    v += dppMov<0x122>(v);   // row_ror:2
-    v += dppMov<0x121>(v);   // row_ror:1
-    return ((readLane(v, 0) + readLane(v, 16)) + readLane(v, 32)) + readLane(v, 48);
-}
-
-__device__ __forceinline__ double waveMax(double v) {
-    double o;
-    o = dppMov<0x128>(v); v = o > v ? o : v;
-    o = dppMov<0x124>(v); v = o > v ? o : v;
-    o = dppMov<0x122>(v); v = o > v ? o : v;
-    o = dppMov<0x121>(v); v = o > v ? o : v;
-    const double a = readLane(v, 0), b = readLane(v, 16), c = readLane(v, 32), d = readLane(v, 48);
-    const double ab = a > b ? a : b, cd = c > d ? c : d;
-    return ab > cd ? ab : cd;
-}
-
 // NT lanes cooperate on one trajectory: NT = 64 (one wave, no cross-wave barrier; throughput mode, many trajectories per CU)
 // or NT = 256 (four waves; lower latency for small batches).
 template <int NT>
@@ -663,269 +611,6 @@ __global__ void uph_terrain_kernel(GridDev grid, const double* __restrict__ pos,
     }
 }
 
-// ---- trajectory rollout (uph_rollout_batch): every sample of the resident trajectories, one lane per sample, one 64-lane workgroup per
-// (trajectory, chunk of 64 samples).  Trajectory-uniform data -- descriptor, state (T_xy, T_yaw), launch record, grid descriptor -- is indexed
-// by blockIdx only (scalar loads); the coefficients come from L2.  The rows of a chunk are contiguous in the output: each lane writes its row
-// to LDS and the workgroup then streams the chunk out with consecutive lanes on consecutive doubles (a lane-per-row store of a 224-byte row
-// would touch a different cache line in every lane of every store).
-struct RolloutTraj {            // one trajectory of a rollout launch (formed on the host)
-    int64_t row0;               // its first row in the launch's output
-    int cnt, rows;              // samples of the t += dt loop; rows = cnt (+ 1 with the end point)
-    double total;               // getTotalDuration: t of the end point
-    double shift[2];            // map coordinate of the trajectory's frame corner (local frames, TrajFrame); unused in the map's own frame
-};
-struct RolloutArgs {
-    const TrajDesc* desc;
-    const TrajState* state;
-    const double* cxy;
-    const double* cyaw;
-    const GridDev* grid_mem;    // per-trajectory (framed) grid descriptors, or nullptr: the map's own frame (the kernel's grid argument)
-    const RolloutTraj* traj;    // [trajectories of the launch]
-    const double* tt;           // t_q: q additions of dt to 0.0, shared by the batch
-    double* out;                // [rows of the launch][ncol]
-    int b0, channels, ncol;
-};
-constexpr int ROLL_NT = 64;
-constexpr int ROLL_MAXCOL = 9 + 7 + 12;
-
-// the pose of one sample from its (x, y, yaw) in LDS: the statements of uph_pose_kernel (map_build.hip) on inputs the compiler cannot see
-// through, so that the two kernels contract the same arithmetic the same way (rows equal uph_terrain_pose_query bit for bit)
-__device__ __forceinline__ void rolloutPose(const GridDev& g, const double* in, double* o) {
-    const double x = in[0], y = in[1], w = in[2];
-    Corners c;
-    locate(g, x, y, w, c);
-    double tv[4];
-    terrainValues(g, c, tv);
-    terrainPoseFrom(x, y, w, tv, o);
-}
-
-__global__ __launch_bounds__(ROLL_NT) void uph_rollout_kernel(GridDev grid, RolloutArgs a) {
-    __shared__ double stage[ROLL_NT * ROLL_MAXCOL];
-    const RolloutTraj rt = a.traj[blockIdx.x];
-    const int q0 = (int)blockIdx.y * ROLL_NT;
-    if (q0 >= rt.rows) return;
-    const int nq = rt.rows - q0 < ROLL_NT ? rt.rows - q0 : ROLL_NT;
-    const int b = a.b0 + (int)blockIdx.x;
-    const int ncol = a.ncol;
-    const bool framed = a.grid_mem != nullptr;
-    const int pcol = ncol - 12;             // first pose column (when selected)
-    if ((int)threadIdx.x < nq) {
-        const int q = q0 + (int)threadIdx.x;
-        const TrajDesc& td = a.desc[b];
-        const double Tx = a.state[b].T_xy, Ty = a.state[b].T_yaw;
-        const GridDev g = framed ? a.grid_mem[b] : grid;
-        const double sx = framed ? rt.shift[0] : 0.0, sy = framed ? rt.shift[1] : 0.0;
-        const double t = q < rt.cnt ? a.tt[q] : rt.total;
-        const double* cx = a.cxy + td.off_cxy;
-        const double* cy = a.cyaw + td.off_cyaw;
-        TrajSample s;
-        double tm[7];
-        if (a.channels & UPH_ROLLOUT_TERRAIN) trajectorySample<true>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
-        else trajectorySample<false>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
-        double* r = stage + threadIdx.x * ncol;
-        if (a.channels & UPH_ROLLOUT_STATE) {
-            r[0] = t; r[1] = framed ? s.p[0] + sx : s.p[0]; r[2] = framed ? s.p[1] + sy : s.p[1]; r[3] = s.yawn;
-            r[4] = s.v[0]; r[5] = s.v[1]; r[6] = s.a[0]; r[7] = s.a[1]; r[8] = s.dyaw;
-            r += 9;
-        }
-        if (a.channels & UPH_ROLLOUT_TERRAIN) {
-#pragma unroll
-            for (int k = 0; k < 7; k++) r[k] = tm[k];
-            r += 7;
-        }
-        if (a.channels & UPH_ROLLOUT_POSE) { r[0] = s.p[0]; r[1] = s.p[1]; r[2] = s.yawn; }       // (the pose's input, in the trajectory's frame)
-    }
-    __syncthreads();
-    if ((a.channels & UPH_ROLLOUT_POSE) && (int)threadIdx.x < nq) {
-        double* r = stage + threadIdx.x * ncol + pcol;
-        double in[3] = {r[0], r[1], r[2]}, o[12];
-        if (framed) {
-            rolloutPose(a.grid_mem[b], in, o);
-            o[9] += rt.shift[0]; o[10] += rt.shift[1];
-        } else {
-            rolloutPose(grid, in, o);
-        }
-#pragma unroll
-        for (int k = 0; k < 12; k++) r[k] = o[k];
-    }
-    __syncthreads();
-    double* o = a.out + (size_t)(rt.row0 + q0) * ncol;
-    for (int i = (int)threadIdx.x; i < nq * ncol; i += ROLL_NT) o[i] = stage[i];
-}
-
-// ---- check (uph_check_batch): (trajectory, time window) pairs of the resident batch reduced against limits on the map as it is now.  One 256-lane
-// workgroup per query; lane l takes samples l, l + 256, ... of the window, each sample the rollout's (same time table, trajectorySample<true>, same
-// grid descriptor), and keeps in registers: the first sample with a violation and its mask, per term the worst value and its sample, two counters.
-// The reduction is a selection under a total order (value, then the smaller sample index), so the order in which lanes and waves are combined
-// cannot change a bit: DPP row rotations inside a wave, LDS across the four waves, lane 0 writes.  Query-uniform data -- query record, descriptor,
-// T_xy / T_yaw, grid descriptor, limits -- is indexed by blockIdx only (scalar loads).
-struct CheckQuery {             // one query of a check launch (formed on the host, in launch order)
-    int32_t b, out;             // resident trajectory; row of the output (the caller's query index)
-    int32_t q_lo, n_tab;        // the window's first sample in the time table and the number of samples taken from it
-    int32_t end_row, pad;       // != 0: the end point (t = total) closes the window
-    double total;               // getTotalDuration: t of the end point
-    double shift[2];            // as RolloutTraj
-};
-struct CheckOut {               // one row per query
-    double first_t;             // NaN: no sample violates
-    int32_t first_mask, counts[3];      // samples, violating, occupied
-    double worst[7], worst_t[7];
-};
-struct CheckArgs {
-    const TrajDesc* desc;
-    const TrajState* state;
-    const double* cxy;
-    const double* cyaw;
-    const GridDev* grid_mem;    // as RolloutArgs
-    const CheckQuery* qs;
-    const double* tt;           // the rollout's time table
-    const char* occ;            // the map's occupancy layer [nx_hold][ny][nyaw] (uph_frontend_query's)
-    CheckOut* out;
-    double lim[7];
-};
-constexpr int CHECK_NT = 256, CHECK_NW = CHECK_NT / 64;
-constexpr unsigned long long CHECK_NONE = ~0ull;
-
-template <int CTRL>
-__device__ __forceinline__ int dppMovI(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false); }
-// (value, sample) pairs: the larger value wins, equal values go to the smaller sample (no NaN reaches here: a non-finite term is +inf)
-__device__ __forceinline__ void checkTake(double& v, int& i, double ov, int oi) {
-    const bool o = ov > v || (ov == v && oi < i);
-    v = o ? ov : v; i = o ? oi : i;
-}
-template <int CTRL>
-__device__ __forceinline__ void checkStepWorst(double& v, int& i) { const double ov = dppMov<CTRL>(v); const int oi = dppMovI<CTRL>(i); checkTake(v, i, ov, oi); }
-template <int CTRL>
-__device__ __forceinline__ void checkStepFirst(unsigned long long& k) {
-    const unsigned lo = (unsigned)dppMovI<CTRL>((int)(unsigned)k), hi = (unsigned)dppMovI<CTRL>((int)(unsigned)(k >> 32));
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    k = o < k ? o : k;
-}
-template <int CTRL>
-__device__ __forceinline__ void checkStepSum(int& a, int& b) { a += dppMovI<CTRL>(a); b += dppMovI<CTRL>(b); }
-
-// build knobs of the measurements in DESIGN.md 7i (tools/build_variants.sh): UPH_CHECK_WPE = waves per SIMD the kernel is compiled for (2: 200 VGPRs, no
-// scratch; 3 caps it at 168 and spills), UPH_CHECK_LDS_STATE keeps the per-lane worst values in LDS instead of registers.  Neither variant was faster.
-#ifndef UPH_CHECK_WPE
-#define UPH_CHECK_WPE 2
-#endif
-__global__ __launch_bounds__(CHECK_NT, UPH_CHECK_WPE) void uph_check_kernel(GridDev grid, CheckArgs a) {
-    __shared__ double s_wv[CHECK_NW][7];
-    __shared__ int s_wi[CHECK_NW][7];
-    __shared__ unsigned long long s_first[CHECK_NW];
-    __shared__ int s_cnt[CHECK_NW][2];
-    const CheckQuery cq = a.qs[blockIdx.x];
-    const int b = cq.b;
-    const TrajDesc& td = a.desc[b];
-    const double Tx = a.state[b].T_xy, Ty = a.state[b].T_yaw;
-    const bool framed = a.grid_mem != nullptr;
-    const GridDev g = framed ? a.grid_mem[b] : grid;
-    const double sx = framed ? cq.shift[0] : 0.0, sy = framed ? cq.shift[1] : 0.0;
-    const double* cx = a.cxy + td.off_cxy;
-    const double* cy = a.cyaw + td.off_cyaw;
-    const int n = cq.n_tab + (cq.end_row ? 1 : 0);
-    // first: (sample << 8) | mask of the first violating sample, so that one unsigned minimum carries both
-    unsigned long long first = CHECK_NONE;
-    double wv[7];
-    int wi[7];
-#ifdef UPH_CHECK_LDS_STATE
-    __shared__ double l_wv[7][CHECK_NT];
-    __shared__ int l_wi[7][CHECK_NT];
-#pragma unroll
-    for (int k = 0; k < 7; k++) { l_wv[k][threadIdx.x] = -__builtin_huge_val(); l_wi[k][threadIdx.x] = 0x7fffffff; }
-#else
-#pragma unroll
-    for (int k = 0; k < 7; k++) { wv[k] = -__builtin_huge_val(); wi[k] = 0x7fffffff; }
-#endif
-    int nviol = 0, nocc = 0;
-    for (int j = (int)threadIdx.x; j < n; j += CHECK_NT) {
-        const double t = j < cq.n_tab ? a.tt[cq.q_lo + j] : cq.total;
-        TrajSample s;
-        double tm[7];
-        trajectorySample<true>(cx, cy, td.Nxy, td.Nyaw, Tx, Ty, t, g, grid.gravity, s, tm);
-        // the sample's values leave trajectorySample as they leave it in the rollout (stored, there): nothing below may be contracted into its arithmetic
-        double px = s.p[0], py = s.p[1], w = s.yawn;
-        asm volatile("" : "+v"(px), "+v"(py), "+v"(w));
-#pragma unroll
-        for (int k = 0; k < 7; k++) asm volatile("" : "+v"(tm[k]));
-        // isOccupancy at the STATE row's (x, y, yaw), map coordinates, on the map's own grid: the statements of uph_frontend_kernel (map_build.hip)
-        const double x = framed ? px + sx : px, y = framed ? py + sy : py;
-        const int ix = (int)floor((x - grid.origin[0]) * grid.xy_inv), iy = (int)floor((y - grid.origin[1]) * grid.xy_inv), iw = (int)floor((w - grid.origin[2]) * grid.yaw_inv);
-        const int ixh = ix - grid.x_off;
-        const bool in = ix >= 0 && iy >= 0 && iw >= 0 && ix <= grid.nx - 1 && iy <= grid.ny - 1 && iw <= grid.nyaw - 1 && ixh >= 0 && ixh <= grid.nx_hold - 1;
-        const int occ = in ? (int)a.occ[((size_t)ixh * grid.ny + iy) * grid.nyaw + iw] : -1;
-        int mask = occ != 0 ? 1 << UPH_CHECK_OCC_BIT : 0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-            const double v = tm[k], m = k < 4 ? fabs(v) : v;
-            if (!(m <= a.lim[k])) mask |= 1 << k;
-            const double key = fabs(v) < __builtin_huge_val() ? m : __builtin_huge_val();      // non-finite (NaN included): +inf
-#ifdef UPH_CHECK_LDS_STATE
-            if (key > l_wv[k][threadIdx.x]) { l_wv[k][threadIdx.x] = key; l_wi[k][threadIdx.x] = j; }
-#else
-            if (key > wv[k]) { wv[k] = key; wi[k] = j; }
-#endif
-        }
-        if (mask != 0) {
-            nviol++;
-            if (first == CHECK_NONE) first = ((unsigned long long)(unsigned)j << 8) | (unsigned)mask;
-        }
-        nocc += occ != 0 ? 1 : 0;
-    }
-#ifdef UPH_CHECK_LDS_STATE
-#pragma unroll
-    for (int k = 0; k < 7; k++) { wv[k] = l_wv[k][threadIdx.x]; wi[k] = l_wi[k][threadIdx.x]; }
-#endif
-    // inside each row of 16 lanes, then the four rows of the wave
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        checkStepWorst<0x128>(wv[k], wi[k]); checkStepWorst<0x124>(wv[k], wi[k]); checkStepWorst<0x122>(wv[k], wi[k]); checkStepWorst<0x121>(wv[k], wi[k]);
-    }
-    checkStepFirst<0x128>(first); checkStepFirst<0x124>(first); checkStepFirst<0x122>(first); checkStepFirst<0x121>(first);
-    checkStepSum<0x128>(nviol, nocc); checkStepSum<0x124>(nviol, nocc); checkStepSum<0x122>(nviol, nocc); checkStepSum<0x121>(nviol, nocc);
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        double v = readLane(wv[k], 0);
-        int i = __builtin_amdgcn_readlane(wi[k], 0);
-#pragma unroll
-        for (int r = 16; r < 64; r += 16) checkTake(v, i, readLane(wv[k], r), __builtin_amdgcn_readlane(wi[k], r));
-        if (lane == 0) { s_wv[wave][k] = v; s_wi[wave][k] = i; }
-    }
-    {
-        unsigned long long f = CHECK_NONE;
-        int cv = 0, co = 0;
-#pragma unroll
-        for (int r = 0; r < 64; r += 16) {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)first, r), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(first >> 32), r);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            f = o < f ? o : f;
-            cv += __builtin_amdgcn_readlane(nviol, r); co += __builtin_amdgcn_readlane(nocc, r);
-        }
-        if (lane == 0) { s_first[wave] = f; s_cnt[wave][0] = cv; s_cnt[wave][1] = co; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CheckOut o;
-        unsigned long long f = s_first[0];
-        int cv = s_cnt[0][0], co = s_cnt[0][1];
-        for (int wq = 1; wq < CHECK_NW; wq++) { f = s_first[wq] < f ? s_first[wq] : f; cv += s_cnt[wq][0]; co += s_cnt[wq][1]; }
-        const double nan = __builtin_nan("");
-        const int fj = (int)(f >> 8);
-        o.first_t = f == CHECK_NONE ? nan : (fj < cq.n_tab ? a.tt[cq.q_lo + fj] : cq.total);
-        o.first_mask = f == CHECK_NONE ? 0 : (int)(f & 0xff);
-        o.counts[0] = n; o.counts[1] = cv; o.counts[2] = co;
-        for (int k = 0; k < 7; k++) {
-            double v = s_wv[0][k];
-            int i = s_wi[0][k];
-            for (int wq = 1; wq < CHECK_NW; wq++) checkTake(v, i, s_wv[wq][k], s_wi[wq][k]);
-            o.worst[k] = v;
-            o.worst_t[k] = i == 0x7fffffff ? nan : (i < cq.n_tab ? a.tt[cq.q_lo + i] : cq.total);
-        }
-        a.out[cq.out] = o;
-    }
-}
-
 // ---- goals -> resident batch (uph_plan_upload): PlanManager's initial-guess stage (plan_manager.cpp:62-132; with mp.test_mode the test node's,
 // alm_traj_opt.cpp:73-144) over the paths the front-end search left in HBM, then x0 scattered from the staging into the resident batch.
 // Staging (owned by the context, indexed by GOAL): way-points [goal][PLAN_SX][2] and [goal][PLAN_SY], and one PlanHead per goal -- the only
@@ -1024,233 +709,6 @@ __global__ __launch_bounds__(64) void uph_plan_scatter_kernel(const PlanScatter*
     }
 }
 
-// ---- switch states (uph_replan_upload): trajectory b of the resident batch at its clamped time, one lane per query.  The sample is the rollout's
-// (trajectorySample, same piece location, same statements), so at a rollout row's t the state equals that row bit for bit; the duration is the
-// rollout's too (running sums of the piece durations, the smaller of the two).  Row q: x, y (map coordinates), dx, dy, ddx, ddy, normSO2(yaw), dyaw, ddyaw;
-// COLS = TRAJ_STATE_COLS (uph_traj_states, uph_refine_upload) adds the raw yaw as column 9.  The 9-column instantiation is uph_replan_upload's.
-struct SwitchQuery {            // formed on the host
-    int32_t b, framed;          // resident trajectory; framed: the batch solves in local frames (add shift, as the rollout does)
-    double t;                   // switch time (finite)
-    double shift[2];
-};
-constexpr int SWITCH_COLS = 9, TRAJ_STATE_COLS = 10;
-template <int COLS>
-__global__ __launch_bounds__(64) void uph_switch_state_kernel(const TrajDesc* __restrict__ desc, const TrajState* __restrict__ state, const double* __restrict__ cxy,
-                                                              const double* __restrict__ cyaw, const SwitchQuery* __restrict__ qs, int nq, double* __restrict__ out) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    const SwitchQuery sq = qs[q];
-    const TrajDesc& td = desc[sq.b];
-    const double Tx = state[sq.b].T_xy, Ty = state[sq.b].T_yaw;
-    double durx = 0.0, dury = 0.0;
-    for (int i = 0; i < td.Nxy; i++) durx += Tx;
-    for (int i = 0; i < td.Nyaw; i++) dury += Ty;
-    const double total = durx < dury ? durx : dury;
-    const double t = sq.t <= 0.0 ? 0.0 : (sq.t >= total ? total : sq.t);
-    TrajSample s;
-    double unused[7];
-    GridDev none;
-    trajectorySample<false, true>(cxy + td.off_cxy, cyaw + td.off_cyaw, td.Nxy, td.Nyaw, Tx, Ty, t, none, 0.0, s, unused);
-    double* o = out + (size_t)q * COLS;
-    o[0] = sq.framed ? s.p[0] + sq.shift[0] : s.p[0]; o[1] = sq.framed ? s.p[1] + sq.shift[1] : s.p[1];
-    o[2] = s.v[0]; o[3] = s.v[1]; o[4] = s.a[0]; o[5] = s.a[1];
-    o[6] = s.yawn; o[7] = s.dyaw; o[8] = s.ddyaw;
-    if (COLS > SWITCH_COLS) o[9] = s.yaw;
-}
-
-// ---- locate / within (uph_locate_batch, uph_within_batch): geometric reductions over the STATE samples of (trajectory, time window) pairs of the resident
-// batch, on uph_check_kernel's skeleton -- query records formed on the host in launch order, query-uniform data indexed by blockIdx only, lanes striding
-// over the window, a selection under a total order reduced by DPP row rotations, row leaders and LDS across the waves, lane 0 writes.  No terrain: a
-// sample is two quintics, about a tenth of the check's, so a query of the tracking workload (101 samples) gets one wave (NT = 64, no LDS, no
-// barrier) and only windows longer than LOC_SHORT samples get the check's 256 lanes; the host splits the sorted launch at that length.  The
-// selection makes the answer the same for either width.
-//   locate: the sample nearest to a pose (d2 = ex ex + ey ey with both products rounded, the smaller sample among equals, NaN as +inf), then, uniform
-//           work of lane 0, a safeguarded Newton iteration on g(t) = e . v inside the bracket of the neighbouring samples; state and tracking error there.
-//   within: first and last sample inside a closed rect, the number of samples inside.
-struct LocQuery {               // one query of a locate / within launch (formed on the host, in launch order)
-    int32_t b, out;             // resident trajectory; row of the output (the caller's query index)
-    int32_t q_lo, n_tab;        // as CheckQuery
-    int32_t end_row, pad;
-    double total;
-    double shift[2];
-    double p[4];                // locate: pose x, y, yaw (map coordinates);  within: rect x0, x1, y0, y1
-};
-struct LocateOut {              // one row per query
-    double near_t, near_d2;     // coarse stage
-    double t, d2;
-    double state[TRAJ_STATE_COLS];
-    double err[3];              // e_lon, e_lat, e_yaw
-    int32_t count, refined;
-};
-struct WithinOut {
-    double enter_t, leave_t;    // NaN: no sample inside
-    int32_t counts[2];          // samples, inside
-};
-struct LocArgs {
-    const TrajDesc* desc;
-    const TrajState* state;
-    const double* cxy;
-    const double* cyaw;
-    const LocQuery* qs;
-    const double* tt;           // the rollout's time table
-    void* out;                  // LocateOut / WithinOut rows
-    int framed, q0;             // the batch solves in local frames (add shift, as the rollout does); first query of this launch
-};
-constexpr int LOC_SHORT = 192;  // windows of at most this many samples run on one wave
-constexpr int LOC_NONE = 0x7fffffff;
-constexpr int LOC_NEWTON = 8;
-
-// the STATE row of query-uniform trajectory data at t: position in map coordinates as the rollout and uph_switch_state_kernel form it.  The values leave
-// trajectorySample as they leave it there (stored): nothing after this may be contracted into its arithmetic.
-struct LocTraj {
-    const double* cx;
-    const double* cy;
-    int Nxy, Nyaw;
-    double Tx, Ty, sx, sy;
-    bool framed;
-    __device__ __forceinline__ void sample(double t, TrajSample& s, double& X, double& Y) const {
-        double unused[7];
-        GridDev none;
-        trajectorySample<false, true>(cx, cy, Nxy, Nyaw, Tx, Ty, t, none, 0.0, s, unused);
-        X = framed ? s.p[0] + sx : s.p[0]; Y = framed ? s.p[1] + sy : s.p[1];
-        asm volatile("" : "+v"(X), "+v"(Y));
-    }
-};
-__device__ __forceinline__ LocTraj locTraj(const LocArgs& a, const LocQuery& lq) {
-    const TrajDesc& td = a.desc[lq.b];
-    LocTraj r;
-    r.cx = a.cxy + td.off_cxy; r.cy = a.cyaw + td.off_cyaw; r.Nxy = td.Nxy; r.Nyaw = td.Nyaw;
-    r.Tx = a.state[lq.b].T_xy; r.Ty = a.state[lq.b].T_yaw;
-    r.framed = a.framed != 0; r.sx = lq.shift[0]; r.sy = lq.shift[1];
-    return r;
-}
-// squared distance with both products rounded before the add
-__device__ __forceinline__ double locD2(double ex, double ey) {
-    double xx = ex * ex, yy = ey * ey;
-    asm volatile("" : "+v"(xx), "+v"(yy));
-    return xx + yy;
-}
-// (key, sample) pairs: the smaller key wins, equal keys go to the smaller sample (no NaN reaches here)
-__device__ __forceinline__ void locTake(double& v, int& i, double ov, int oi) {
-    const bool o = ov < v || (ov == v && oi < i);
-    v = o ? ov : v; i = o ? oi : i;
-}
-template <int CTRL>
-__device__ __forceinline__ void locStepNear(double& v, int& i) { const double ov = dppMov<CTRL>(v); const int oi = dppMovI<CTRL>(i); locTake(v, i, ov, oi); }
-template <int CTRL>
-__device__ __forceinline__ void locStepSpan(int& lo, int& hi, int& cnt) {
-    const int ol = dppMovI<CTRL>(lo), oh = dppMovI<CTRL>(hi);
-    lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; cnt += dppMovI<CTRL>(cnt);
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
-    constexpr int NW = NT / 64;
-    __shared__ double s_v[NW];
-    __shared__ int s_i[NW];
-    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
-    const LocTraj tr = locTraj(a, lq);
-    const int n = lq.n_tab + (lq.end_row ? 1 : 0);
-    const double x = lq.p[0], y = lq.p[1];
-    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
-    double bv = inf;
-    int bi = LOC_NONE;
-    for (int j = (int)threadIdx.x; j < n; j += NT) {
-        const double t = j < lq.n_tab ? a.tt[lq.q_lo + j] : lq.total;
-        TrajSample s;
-        double X, Y;
-        tr.sample(t, s, X, Y);
-        const double d2 = locD2(X - x, Y - y);
-        locTake(bv, bi, d2 < inf ? d2 : inf, j);            // NaN: +inf
-    }
-    locStepNear<0x128>(bv, bi); locStepNear<0x124>(bv, bi); locStepNear<0x122>(bv, bi); locStepNear<0x121>(bv, bi);
-    double v = readLane(bv, 0);
-    int i = __builtin_amdgcn_readlane(bi, 0);
-#pragma unroll
-    for (int r = 16; r < 64; r += 16) locTake(v, i, readLane(bv, r), __builtin_amdgcn_readlane(bi, r));
-    if (NW > 1) {
-        if (((int)threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = v; s_i[threadIdx.x >> 6] = i; }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    for (int w = 1; w < NW; w++) locTake(v, i, s_v[w], s_i[w]);
-    // sample k of the window (NaN outside it: an empty window answers NaN by this path, not by a special one)
-    auto tau = [&](int k) { return k < 0 || k >= n ? nan : (k < lq.n_tab ? a.tt[lq.q_lo + k] : lq.total); };
-    LocateOut o;
-    o.count = n; o.near_t = tau(i); o.near_d2 = v;
-    const double lo = tau(i - 1 > 0 ? i - 1 : 0), hi = tau((i < n - 2 ? i : n - 2) + 1);
-    double t = o.near_t, ta = lo, tb = hi;
-    TrajSample s, s0;
-    double X, Y, X0 = nan, Y0 = nan, d2 = nan;
-    for (int it = 0;; it++) {
-        tr.sample(t, s, X, Y);
-        const double ex = X - x, ey = Y - y;
-        d2 = locD2(ex, ey);
-        if (it == 0) { s0 = s; X0 = X; Y0 = Y; }
-        if (it == LOC_NEWTON) break;                        // the candidate left by the last iteration
-        const double g = ex * s.v[0] + ey * s.v[1];
-        const double h = s.v[0] * s.v[0] + s.v[1] * s.v[1] + ex * s.a[0] + ey * s.a[1];
-        if (g > 0.0) tb = t;
-        else if (g < 0.0) ta = t;
-        else if (g == 0.0) break;
-        double tn = t - g / h;
-        if (!(h > 0.0 && ta <= tn && tn <= tb)) tn = 0.5 * (ta + tb);
-        if (tn == t) break;
-        t = tn;
-    }
-    const bool refined = d2 <= v;
-    if (!refined) { s = s0; X = X0; Y = Y0; t = o.near_t; d2 = v; }
-    o.t = t; o.d2 = d2; o.refined = refined ? 1 : 0;
-    o.state[0] = X; o.state[1] = Y; o.state[2] = s.v[0]; o.state[3] = s.v[1]; o.state[4] = s.a[0]; o.state[5] = s.a[1];
-    o.state[6] = s.yawn; o.state[7] = s.dyaw; o.state[8] = s.ddyaw; o.state[9] = s.yaw;
-    const double rx = x - X, ry = y - Y;
-    double sw, cw;
-    sincos(s.yaw, &sw, &cw);
-    o.err[0] = rx * cw + ry * sw;
-    o.err[1] = ry * cw - rx * sw;
-    o.err[2] = normSO2(lq.p[2] - s.yaw);
-    ((LocateOut*)a.out)[lq.out] = o;
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
-    constexpr int NW = NT / 64;
-    __shared__ int s_r[NW][3];
-    const LocQuery lq = a.qs[a.q0 + blockIdx.x];
-    const LocTraj tr = locTraj(a, lq);
-    const int n = lq.n_tab + (lq.end_row ? 1 : 0);
-    const double x0 = lq.p[0], x1 = lq.p[1], y0 = lq.p[2], y1 = lq.p[3];
-    int first = LOC_NONE, last = -1, cnt = 0;
-    for (int j = (int)threadIdx.x; j < n; j += NT) {
-        const double t = j < lq.n_tab ? a.tt[lq.q_lo + j] : lq.total;
-        TrajSample s;
-        double X, Y;
-        tr.sample(t, s, X, Y);
-        if (x0 <= X && X <= x1 && y0 <= Y && Y <= y1) {     // (a NaN position is not inside)
-            first = first == LOC_NONE ? j : first; last = j; cnt++;
-        }
-    }
-    locStepSpan<0x128>(first, last, cnt); locStepSpan<0x124>(first, last, cnt); locStepSpan<0x122>(first, last, cnt); locStepSpan<0x121>(first, last, cnt);
-    int f = LOC_NONE, l = -1, c = 0;
-#pragma unroll
-    for (int r = 0; r < 64; r += 16) {
-        const int of = __builtin_amdgcn_readlane(first, r), ol = __builtin_amdgcn_readlane(last, r);
-        f = of < f ? of : f; l = ol > l ? ol : l; c += __builtin_amdgcn_readlane(cnt, r);
-    }
-    if (NW > 1) {
-        if (((int)threadIdx.x & 63) == 0) { s_r[threadIdx.x >> 6][0] = f; s_r[threadIdx.x >> 6][1] = l; s_r[threadIdx.x >> 6][2] = c; }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    for (int w = 1; w < NW; w++) { f = s_r[w][0] < f ? s_r[w][0] : f; l = s_r[w][1] > l ? s_r[w][1] : l; c += s_r[w][2]; }
-    const double nan = __builtin_nan("");
-    WithinOut o;
-    o.enter_t = c == 0 ? nan : (f < lq.n_tab ? a.tt[lq.q_lo + f] : lq.total);
-    o.leave_t = c == 0 ? nan : (l < lq.n_tab ? a.tt[lq.q_lo + l] : lq.total);
-    o.counts[0] = n; o.counts[1] = c;
-    ((WithinOut*)a.out)[lq.out] = o;
-}
-
 // ---- refine (uph_refine_upload): the tail of a resident trajectory as a new problem, without a search.  uph_switch_state_kernel<TRAJ_STATE_COLS>
 // has evaluated the switch states (rows [0, B), one per query) and every way-point time of the batch into one table; one lane per uploaded query
 // copies its way-points into the plan staging (slot = query index) and forms its PlanHead in way-point order.  The bounding box and turn / kink
@@ -1309,126 +767,6 @@ thread_local std::string g_last_error;
 void setError(const std::string& s) { g_last_error = s; }
 }  // namespace uph
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        if (hipMalloc(&p, want) != hipSuccess) { setError("hipMalloc failed"); return -1; }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() { return (T*)p; }
-};
-
-// grow-only pinned host staging (downloads run at the PCIe rate instead of the pageable-copy rate)
-struct HostBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { setError("hipHostMalloc failed"); return -1; }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() { return (T*)p; }
-};
-
-// What the admission of a batch reads of a problem: its scalars, the bounding box of its initial path and the heading changes of its yaw way-points --
-// not the way-points themselves.  uph_batch_upload forms it from the caller's uph_problem, uph_plan_upload from the headers the device staged.
-struct ProblemHead {
-    int32_t n_inner_xy = 0, n_inner_yaw = 0;
-    int refused = 0;                // != 0: refused before the limit checks (that UPH_ERR_* reason, message `why`)
-    const char* why = nullptr;
-    double init_xy[6], end_xy[6], init_yaw[3], end_yaw[3], total_time = 0.0;
-    double lo[2], hi[2];            // bounding box of the inner way-points together with the init / end positions
-    double turn = 0.0, kink = 0.0;  // yawTurnKink
-};
-struct uph_ctx {
-    uph_map* map = nullptr;
-    int device = 0;                         // copied at creation: the context must never dereference the map during teardown
-    OptParams P;
-    double rho = 1.0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // MINCO operator cache
-    std::map<int, int> op_index;            // N -> index
-    std::vector<MincoOp> ops_host;          // device pointers inside
-    std::vector<void*> op_allocs;
-    DevBuf d_ops;
-    bool ops_dirty = false;
-    // batch
-    int B = 0;
-    std::vector<TrajDesc> desc;
-    std::vector<int> order;
-    int64_t sum_n = 0, sum_S = 0, sum_cxy = 0, sum_cyaw = 0, sum_hist = 0;
-    size_t lds_bytes = 0;                   // dynamic LDS of the main launch (largest footprint among the trajectories below the residency limit)
-    size_t lds_big = 0;                     // ... and of the oversize class, launched concurrently on stream2 (0 = no such class)
-    int n_main = 0;                         // order[0, n_main) main class, order[n_main, B) oversize class
-    std::vector<int> rejected;              // per problem: 0, or the status code that made it unsupported (solved as a placeholder, reported as UPH_RET_UNSUPPORTED)
-    int n_rejected = 0;
-    bool all_rejected = false;              // the last upload failed because EVERY problem was unsupported (not because of a misuse or a resource limit)
-    std::vector<TrajFrame> frames;          // per-trajectory local frames of the uploaded batch (empty: the map's own frame, uph_common.hpp TrajFrame)
-    std::vector<GridDev> grid_host_framed;  // ... and the per-trajectory grid descriptors made from them (source of the asynchronous copy)
-    GridDev frames_grid;                    // the map's descriptor the frames were formed from (geometry check at launch)
-    GridDev framed_from;                    // the map's descriptor the resident per-trajectory descriptors were made from
-    bool framed_valid = false;              // d_gridmem holds the framed descriptors of the current batch
-    std::vector<int> origin;                // batch loaded by uph_optimize_batch_multi: the caller's index of each problem of this context's share (empty: identity)
-    bool sample_f32 = false;                // fp32 sample arithmetic (uph_ctx_set_sample_precision)
-    int xcd_group = 0;                      // experiment knob (uph_ctx_set_xcd_locality): > 0 = permute the launch order inside groups of that many workgroups for per-XCD L2 locality
-    hipStream_t stream2 = nullptr;
-    hipEvent_t evp0 = nullptr, evp1 = nullptr;      // prepare launch of an asynchronous solve
-    bool pending = false;                   // uph_batch_solve_async issued, uph_batch_wait not yet called
-    hipEvent_t ev2 = nullptr;
-    std::vector<size_t> fp_bytes;           // per-trajectory LDS footprint
-    int lanes = 64;                         // lanes per trajectory of the current batch (64 or 256)
-    int lanes_forced = 0;                   // 0 = choose from the batch size
-    int wps = 1;                            // workgroups of 256 lanes per CU the kernel is compiled for (1 or 2)
-    int wps_forced = 0;                     // experiment knob: register-capped (2) or uncapped (1) build regardless of batch size
-    DevBuf d_thomas, d_rsd, d_rs, d_gridmem, d_parammem;
-    GridDev grid_host;                      // source of the descriptor copy (outlives the asynchronous copy)
-    DevBuf d_desc, d_state, d_x, d_x0, d_gout, d_dual, d_res, d_scl, d_cxy, d_cyaw, d_hist, d_report, d_order, d_trace;
-    DevBuf d_pen_gxy, d_pen_gyaw, d_pen_out;      // uph_penalty_batch outputs (allocated at its first call)
-    DevBuf d_roll_tt, d_roll_traj, d_roll_stage;  // uph_rollout_*: time table, launch records, staging of the host variant (allocated at the first call)
-    bool traj_resident = false;             // the resident coefficients / durations are those of a solve or evaluation of the current batch (rollout input)
-    // uph_plan_upload: staging indexed by goal (PlanHead, way-points), re-searched goals' indices, scatter records; the resident problems as staged
-    DevBuf d_plan_head, d_plan_xy, d_plan_yaw, d_plan_goal, d_plan_rec;
-    bool planned = false;                   // the resident batch came from uph_plan_upload (uph_plan_staged may read the staging)
-    std::vector<ProblemHead> plan_probs;   // [B] the staged problems in resident order, boundary velocities formed on the host
-    std::vector<double> end_pose;          // [B][3] each problem's end position (map coordinates) and end yaw as uploaded (uph_replan_upload, goals == NULL)
-    std::vector<double> end_bnd;           // [B][9] each problem's whole end boundary as uploaded: end_xy {P, V, A} (map coordinates), end_yaw (uph_refine_upload)
-    DevBuf d_sw_q, d_sw_out;               // uph_replan_upload / uph_traj_states / uph_refine_upload: state queries and states (allocated at the first call)
-    DevBuf d_refine_rec;                   // uph_refine_upload: staging records
-    DevBuf d_chk_q, d_chk_out;             // uph_check_batch: query records and result rows (allocated at the first call)
-    double last_check_ms = 0.0;            // uph_check_kernel of the last uph_check_batch (events on the context's stream)
-    DevBuf d_loc_q, d_loc_out;             // uph_locate_batch / uph_within_batch: query records and result rows (allocated at the first call)
-    double last_locate_ms = 0.0;           // the kernel(s) of the last uph_locate_batch or uph_within_batch (events on the context's stream)
-    int trace_cap = 0;                      // requested for the next upload
-    int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
-    std::vector<TrajState> state_host;
-    HostBuf h_x, h_cxy, h_cyaw, h_dual, h_res, h_scl;      // download staging
-    // stats of the last solve
-    double last_ms = 0.0, last_prepare_ms = 0.0;
-    int64_t last_evals = 0, last_sample_evals = 0, last_iters = 0, last_hist_bytes = 0;
-};
-
-#define HIPCHK(call)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (call);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            setError(std::string(#call) + ": " + hipGetErrorString(_e));                           \
-            return UPH_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
-
 static BatchDev makeBatchDev(uph_ctx* c) {
     BatchDev bd;
     std::memset(&bd, 0, sizeof(bd));
@@ -1475,7 +813,7 @@ static int ensureOp(uph_ctx* c, int N) {
 }
 
 // the map's grid descriptor -> grid, and the descriptors the kernels read from memory (BatchDev::grid_mem) brought up to date on the context's stream
-static int syncGridMem(uph_ctx* c, GridDev& grid) {
+int syncGridMem(uph_ctx* c, GridDev& grid) {
     grid = uphMapGrid(c->map);
     c->grid_host = grid;
     if (c->frames.empty()) {
@@ -1502,6 +840,11 @@ static int syncGridMem(uph_ctx* c, GridDev& grid) {
             c->framed_valid = true;
         }
     }
+    return UPH_OK;
+}
+
+int refreshStates(uph_ctx* c) {
+    HIPCHK(hipMemcpy(c->state_host.data(), c->d_state.p, sizeof(TrajState) * c->B, hipMemcpyDeviceToHost));
     return UPH_OK;
 }
 
@@ -1673,8 +1016,8 @@ void uph_ctx_destroy(uph_ctx* c) {
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
-                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec, &c->d_chk_q,
-                      &c->d_chk_out, &c->d_loc_q, &c->d_loc_out};
+                      &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec, &c->d_win_q,
+                      &c->d_win_out};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -2110,29 +1453,13 @@ int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager
     }
     if (uphKinoMap(k) != src->map || dst->map != src->map) { setError("uph_replan_upload: the search context and the optimiser contexts are bound to different maps"); return UPH_ERR_INVALID; }
     if (src->pending || dst->pending) { setError("uph_replan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    if (src->B <= 0 || !src->traj_resident) {
-        setError("uph_replan_upload: the source holds no resident trajectory (uph_batch_solve / uph_eval_batch after its upload first)"); return UPH_ERR_INVALID;
-    }
-    for (int32_t q = 0; q < B; q++) {
-        const int32_t b = src_traj[q];
-        if (b < 0 || b >= src->B) { setError("uph_replan_upload: query " + std::to_string(q) + " names no trajectory of the source batch"); return UPH_ERR_INVALID; }
-        if (!src->rejected.empty() && src->rejected[(size_t)b]) {
-            setError("uph_replan_upload: query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
-        }
-        if (!std::isfinite(t_switch[q])) { setError("uph_replan_upload: query " + std::to_string(q) + " has a non-finite switch time"); return UPH_ERR_INVALID; }
-    }
+    int r = checkTrajQueries(src, B, src_traj, t_switch, "uph_replan_upload");
+    if (r != UPH_OK) return r;
     HIPCHK(hipSetDevice(uphMapDevice(src->map)));
     std::vector<SwitchQuery> sq((size_t)B);
-    for (int32_t q = 0; q < B; q++) {
-        SwitchQuery& r = sq[(size_t)q];
-        r.b = src_traj[q]; r.framed = src->frames.empty() ? 0 : 1; r.t = t_switch[q];
-        for (int d = 0; d < 2; d++) r.shift[d] = src->frames.empty() ? 0.0 : src->frames[(size_t)r.b].shift[d];
-    }
-    if (src->d_sw_q.ensure(sizeof(SwitchQuery) * (size_t)B) || src->d_sw_out.ensure(sizeof(double) * SWITCH_COLS * (size_t)B)) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(src->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * (size_t)B, hipMemcpyHostToDevice, src->stream));
-    hipLaunchKernelGGL(uph_switch_state_kernel<SWITCH_COLS>, dim3((B + 63) / 64), dim3(64), 0, src->stream, src->d_desc.as<TrajDesc>(), src->d_state.as<TrajState>(),
-                       src->d_cxy.as<double>(), src->d_cyaw.as<double>(), src->d_sw_q.as<SwitchQuery>(), (int)B, src->d_sw_out.as<double>());
-    HIPCHK(hipGetLastError());
+    for (int32_t q = 0; q < B; q++) sq[(size_t)q] = trajQuery(src, src_traj[q], t_switch[q]);
+    r = launchTrajStates(src, sq, SWITCH_COLS);
+    if (r != UPH_OK) { hipStreamSynchronize(src->stream); return r; }
     std::vector<double> zs((size_t)SWITCH_COLS * B);
     HIPCHK(hipMemcpyAsync(zs.data(), src->d_sw_out.p, sizeof(double) * SWITCH_COLS * (size_t)B, hipMemcpyDeviceToHost, src->stream));
     HIPCHK(hipStreamSynchronize(src->stream));
@@ -2151,60 +1478,10 @@ int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager
                       n_inner_yaw);
 }
 
-// uph_traj_states / uph_refine_upload: c holds resident trajectories and every query names one of them at a finite time (uph_replan_upload's rules)
-static int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t, const char* who) {
-    if (c->B <= 0 || !c->traj_resident) {
-        setError(std::string(who) + ": no trajectory is resident (uph_batch_solve / uph_eval_batch after the upload first)"); return UPH_ERR_INVALID;
-    }
-    for (int32_t q = 0; q < n; q++) {
-        const int32_t b = traj[q];
-        if (b < 0 || b >= c->B) { setError(std::string(who) + ": query " + std::to_string(q) + " names no trajectory of the resident batch"); return UPH_ERR_INVALID; }
-        if (!c->rejected.empty() && c->rejected[(size_t)b]) {
-            setError(std::string(who) + ": query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
-        }
-        if (!std::isfinite(t[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a non-finite time"); return UPH_ERR_INVALID; }
-    }
-    return UPH_OK;
-}
-
-// the states of queries sq on c's resident trajectories into c->d_sw_out [n][TRAJ_STATE_COLS] (enqueued on c's stream, not waited for)
-static int launchTrajStates(uph_ctx* c, const std::vector<SwitchQuery>& sq) {
-    const size_t n = sq.size();
-    if (c->d_sw_q.ensure(sizeof(SwitchQuery) * n) || c->d_sw_out.ensure(sizeof(double) * TRAJ_STATE_COLS * n)) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_sw_q.p, sq.data(), sizeof(SwitchQuery) * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(uph_switch_state_kernel<TRAJ_STATE_COLS>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->d_desc.as<TrajDesc>(),
-                       c->d_state.as<TrajState>(), c->d_cxy.as<double>(), c->d_cyaw.as<double>(), c->d_sw_q.as<SwitchQuery>(), (int)n, c->d_sw_out.as<double>());
-    HIPCHK(hipGetLastError());
-    return UPH_OK;
-}
-
-static SwitchQuery trajQuery(const uph_ctx* c, int32_t b, double t) {
-    SwitchQuery r;
-    r.b = b; r.framed = c->frames.empty() ? 0 : 1; r.t = t;
-    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
-    return r;
-}
-
-int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
-    if (!c || n <= 0 || !traj || !t || !out10) { setError("uph_traj_states: bad arguments"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError("uph_traj_states: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    int r = checkTrajQueries(c, n, traj, t, "uph_traj_states");
-    if (r != UPH_OK) return r;
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    std::vector<SwitchQuery> sq((size_t)n);
-    for (int32_t q = 0; q < n; q++) sq[(size_t)q] = trajQuery(c, traj[q], t[q]);
-    r = launchTrajStates(c, sq);
-    if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
-    HIPCHK(hipMemcpyAsync(out10, c->d_sw_out.p, sizeof(double) * TRAJ_STATE_COLS * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return UPH_OK;
-}
-
 // refine resident trajectories from a switch time without a search: every refusal first (dst untouched) -> the source's piece durations (one
 // download) -> remaining time and piece counts on the host -> the switch states and every way-point state of the batch on the device (one launch of
 // uph_switch_state_kernel<TRAJ_STATE_COLS> over src's coefficients) -> uph_refine_stage_kernel writes dst's plan staging and heads -> uploadStaged, as
 // planUpload.  Everything read from src is on the host or in src's state table before dst is reset, so dst == src works.
-static int refreshStates(uph_ctx* c);
 int uph_refine_upload(uph_ctx* src, uph_ctx* dst, int32_t B, const int32_t* src_traj, const double* t_switch, double* switch_states, int32_t* status,
                       int32_t* traj_of, int32_t* n_inner_xy, int32_t* n_inner_yaw) {
 #pragma clang fp contract(off)
@@ -2227,10 +1504,7 @@ int uph_refine_upload(uph_ctx* src, uph_ctx* dst, int32_t B, const int32_t* src_
         if (!std::isfinite(Tx) || !std::isfinite(Ty)) {
             setError("uph_refine_upload: query " + std::to_string(q) + " names a trajectory with non-finite piece durations"); return UPH_ERR_INVALID;
         }
-        double durx = 0.0, dury = 0.0;                 // the duration as uph_switch_state_kernel and the rollout form it
-        for (int i = 0; i < src->desc[(size_t)b].Nxy; i++) durx += Tx;
-        for (int i = 0; i < src->desc[(size_t)b].Nyaw; i++) dury += Ty;
-        const double D = durx < dury ? durx : dury;
+        const double D = trajTotal(src->desc[(size_t)b].Nxy, Tx, src->desc[(size_t)b].Nyaw, Ty);           // the duration as uph_switch_state_kernel and the rollout form it
         const double tc = t_switch[q] <= 0.0 ? 0.0 : (t_switch[q] >= D ? D : t_switch[q]);
         const double R = D - tc;
         tcs[(size_t)q] = tc; rem[(size_t)q] = R;
@@ -2338,11 +1612,6 @@ int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy
     }
     if (status == UPH_ERR_LIMIT) setError("uph_plan_staged: a problem has more way-points than the caller's capacity or the staging's");
     return status;
-}
-
-static int refreshStates(uph_ctx* c) {
-    HIPCHK(hipMemcpy(c->state_host.data(), c->d_state.p, sizeof(TrajState) * c->B, hipMemcpyDeviceToHost));
-    return UPH_OK;
 }
 
 // enqueue one solve of the uploaded batch on the context's stream and return: reset + initScaling kernel, then the ALM kernel.  Two
@@ -2799,401 +2068,6 @@ int uph_terrain_query(uph_map* m, const double* pos, int32_t n, double* values7,
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(values7, tv.p, 8 * 7 * (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(grads21, tg.p, 8 * 21 * (size_t)n, hipMemcpyDeviceToHost));
-    return UPH_OK;
-}
-
-
-// ---- trajectory rollout (include/uneven_hip.h uph_rollout_*) -------------------------------------------------------------------------------
-// Sample times: t_q = the value after q additions of dt to 0.0 -- the running sum of the reference's `for (t = 0; t < total; t += dt)` loops
-// (alm_traj_opt.h:182, alm_traj_opt.cpp:1109) and of Solver::report -- built ONCE per call, serially in fp64, up to the longest trajectory and
-// shared by the batch; a trajectory's count is the first q with t_q >= total (binary search).  A NaN duration has no samples, as in the loop.
-static int rolloutTimes(double dt, double tmax, std::vector<double>& tab) {
-    tab.assign(1, 0.0);
-    double t = 0.0;
-    while (t < tmax && (int64_t)tab.size() <= UPH_ROLLOUT_MAX_SAMPLES) {
-        const double tn = t + dt;
-        if (!(tn > t)) { setError("uph_rollout: the running sum t += dt stops growing before it reaches the trajectory's duration"); return UPH_ERR_LIMIT; }
-        t = tn;
-        tab.push_back(t);
-    }
-    return UPH_OK;
-}
-
-struct RolloutSizes {
-    std::vector<double> tab;        // t_q
-    std::vector<int32_t> cnt;       // samples of the loop per trajectory
-    std::vector<double> total;      // durations
-    std::vector<int64_t> offs;      // [B + 1] row offsets
-};
-
-// durations piece by piece as Solver::report forms them; skip[b] != 0: no rows
-static int rolloutSizes(int B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, const int* skip, double dt, int with_end,
-                        RolloutSizes& rs) {
-    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_rollout: dt must be positive and finite"); return UPH_ERR_INVALID; }
-    rs.cnt.assign(B, 0); rs.total.assign(B, 0.0); rs.offs.assign((size_t)B + 1, 0);
-    double tmax = 0.0;
-    for (int b = 0; b < B; b++) {
-        if (n_xy[b] < 0 || n_yaw[b] < 0) { setError("uph_rollout_sizes: negative piece count"); return UPH_ERR_INVALID; }
-        if (skip && skip[b]) continue;
-        double durx = 0.0, dury = 0.0;
-        for (int i = 0; i < n_xy[b]; i++) durx += T_xy[b];
-        for (int i = 0; i < n_yaw[b]; i++) dury += T_yaw[b];
-        rs.total[b] = durx < dury ? durx : dury;          // (dmin, as Solver::report)
-        if (rs.total[b] > tmax) tmax = rs.total[b];
-    }
-    const int r = rolloutTimes(dt, tmax, rs.tab);
-    if (r != UPH_OK) return r;
-    for (int b = 0; b < B; b++) {
-        int64_t rows = 0;
-        if (!(skip && skip[b])) {
-            const int64_t q = std::lower_bound(rs.tab.begin(), rs.tab.end(), rs.total[b]) - rs.tab.begin();
-            if (q >= (int64_t)rs.tab.size()) {
-                setError("uph_rollout: trajectory " + std::to_string(b) + " needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt");
-                return UPH_ERR_LIMIT;
-            }
-            rs.cnt[b] = (int32_t)q;
-            rows = q + (with_end ? 1 : 0);
-        }
-        rs.offs[b + 1] = rs.offs[b] + rows;
-    }
-    return UPH_OK;
-}
-
-static int rolloutColumns(int channels) {
-    return (channels & UPH_ROLLOUT_STATE ? 9 : 0) + (channels & UPH_ROLLOUT_TERRAIN ? 7 : 0) + (channels & UPH_ROLLOUT_POSE ? 12 : 0);
-}
-
-// the resident batch of c: checks + sizes
-static int rolloutPlanCtx(uph_ctx* c, double dt, int with_end, RolloutSizes& rs, const char* who) {
-    if (!c || c->B <= 0) { setError(std::string(who) + ": no batch uploaded"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    if (!c->traj_resident) {
-        setError(std::string(who) + ": no trajectory is resident -- the batch was uploaded but not solved or evaluated since (uph_batch_solve / uph_eval_batch first)");
-        return UPH_ERR_INVALID;
-    }
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    const int r = refreshStates(c);
-    if (r != UPH_OK) return r;
-    const int B = c->B;
-    std::vector<int32_t> nx(B), ny(B);
-    std::vector<double> tx(B), ty(B);
-    for (int b = 0; b < B; b++) { nx[b] = c->desc[b].Nxy; ny[b] = c->desc[b].Nyaw; tx[b] = c->state_host[b].T_xy; ty[b] = c->state_host[b].T_yaw; }
-    return rolloutSizes(B, nx.data(), tx.data(), ny.data(), ty.data(), c->rejected.data(), dt, with_end, rs);
-}
-
-// enqueue the kernel for trajectories [b0, b1) writing rows offs[b0] .. offs[b1] to out_dev (row offs[b0] first); the time table is resident
-static int rolloutLaunch(uph_ctx* c, const GridDev& grid, const RolloutSizes& rs, int channels, int b0, int b1, double* out_dev, std::vector<RolloutTraj>& rec) {
-    const int n = b1 - b0;
-    if (n <= 0 || rs.offs[b1] == rs.offs[b0]) return UPH_OK;
-    rec.assign(n, RolloutTraj());
-    int ychunks = 0;
-    for (int k = 0; k < n; k++) {
-        const int b = b0 + k;
-        RolloutTraj& t = rec[k];
-        t.row0 = rs.offs[b] - rs.offs[b0];
-        t.cnt = rs.cnt[b];
-        t.rows = (int)(rs.offs[b + 1] - rs.offs[b]);
-        t.total = rs.total[b];
-        t.shift[0] = c->frames.empty() ? 0.0 : c->frames[b].shift[0];
-        t.shift[1] = c->frames.empty() ? 0.0 : c->frames[b].shift[1];
-        ychunks = std::max(ychunks, (t.rows + ROLL_NT - 1) / ROLL_NT);
-    }
-    if (c->d_roll_traj.ensure(sizeof(RolloutTraj) * n)) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_roll_traj.p, rec.data(), sizeof(RolloutTraj) * n, hipMemcpyHostToDevice, c->stream));
-    RolloutArgs a;
-    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
-    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
-    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
-    a.traj = c->d_roll_traj.as<RolloutTraj>(); a.tt = c->d_roll_tt.as<double>(); a.out = out_dev;
-    a.b0 = b0; a.channels = channels; a.ncol = rolloutColumns(channels);
-    hipLaunchKernelGGL(uph_rollout_kernel, dim3(n, ychunks), dim3(ROLL_NT), 0, c->stream, grid, a);
-    HIPCHK(hipGetLastError());
-    return UPH_OK;
-}
-
-// common part of the two variants: arguments, sizes, grid descriptors, time table
-static int rolloutBegin(uph_ctx* c, double dt, int with_end, int channels, int b0, int b1, const void* out, RolloutSizes& rs, GridDev& grid, const char* who) {
-    if (!c || !out || (channels & ~UPH_ROLLOUT_ALL) || !(channels & UPH_ROLLOUT_ALL)) { setError(std::string(who) + ": bad arguments (null pointer or channel mask)"); return UPH_ERR_INVALID; }
-    if (b0 < 0 || b1 < b0 || b1 > c->B) { setError(std::string(who) + ": trajectory range [b0, b1) outside the batch"); return UPH_ERR_INVALID; }
-    int r = rolloutPlanCtx(c, dt, with_end, rs, who);
-    if (r != UPH_OK) return r;
-    r = syncGridMem(c, grid);
-    if (r != UPH_OK) return r;
-    if (c->d_roll_tt.ensure(8 * rs.tab.size())) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
-    return UPH_OK;
-}
-
-int uph_rollout_sizes(int32_t B, const int32_t* n_xy, const double* T_xy, const int32_t* n_yaw, const double* T_yaw, double dt, int32_t with_end,
-                      int64_t* offsets) {
-    if (B < 0 || !offsets || (B > 0 && (!n_xy || !T_xy || !n_yaw || !T_yaw))) { setError("uph_rollout_sizes: bad arguments"); return UPH_ERR_INVALID; }
-    RolloutSizes rs;
-    const int r = rolloutSizes(B, n_xy, T_xy, n_yaw, T_yaw, nullptr, dt, with_end, rs);
-    if (r != UPH_OK) return r;
-    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)B + 1));
-    return UPH_OK;
-}
-
-int uph_rollout_plan(uph_ctx* c, double dt, int32_t with_end, int64_t* offsets) {
-    if (!offsets) { setError("uph_rollout_plan: bad arguments"); return UPH_ERR_INVALID; }
-    RolloutSizes rs;
-    const int r = rolloutPlanCtx(c, dt, with_end, rs, "uph_rollout_plan");
-    if (r != UPH_OK) return r;
-    std::memcpy(offsets, rs.offs.data(), 8 * ((size_t)c->B + 1));
-    return UPH_OK;
-}
-
-// the host variant stages chunks of whole trajectories through a device buffer of at most this size (one trajectory at the sample cap: 59 MB)
-static const size_t ROLL_STAGE_BYTES = (size_t)256 << 20;
-
-int uph_rollout_batch(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, double* out) {
-    RolloutSizes rs;
-    GridDev grid;
-    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out, rs, grid, "uph_rollout_batch");
-    if (r != UPH_OK) return r;
-    const size_t row_bytes = 8 * (size_t)rolloutColumns(channels);
-    const size_t need = row_bytes * (size_t)(rs.offs[b1] - rs.offs[b0]);
-    if (need > 0 && c->d_roll_stage.ensure(std::min(need, ROLL_STAGE_BYTES))) return UPH_ERR_HIP;
-    std::vector<RolloutTraj> rec;
-    for (int k0 = b0; k0 < b1;) {
-        int k1 = k0 + 1;           // whole trajectories while they fit the staging buffer (one always does)
-        while (k1 < b1 && row_bytes * (size_t)(rs.offs[k1 + 1] - rs.offs[k0]) <= ROLL_STAGE_BYTES) k1++;
-        const size_t bytes = row_bytes * (size_t)(rs.offs[k1] - rs.offs[k0]);
-        if (bytes > 0) {
-            r = rolloutLaunch(c, grid, rs, channels, k0, k1, c->d_roll_stage.as<double>(), rec);
-            if (r != UPH_OK) { hipStreamSynchronize(c->stream); return r; }
-            HIPCHK(hipMemcpyAsync((char*)out + row_bytes * (size_t)(rs.offs[k0] - rs.offs[b0]), c->d_roll_stage.p, bytes, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-        k0 = k1;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return UPH_OK;
-}
-
-int uph_rollout_batch_dev(uph_ctx* c, double dt, int32_t with_end, int32_t channels, int32_t b0, int32_t b1, void* out_dev) {
-    RolloutSizes rs;
-    GridDev grid;
-    int r = rolloutBegin(c, dt, with_end, channels, b0, b1, out_dev, rs, grid, "uph_rollout_batch_dev");
-    if (r != UPH_OK) return r;
-    std::vector<RolloutTraj> rec;
-    r = rolloutLaunch(c, grid, rs, channels, b0, b1, (double*)out_dev, rec);
-    const hipError_t e = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
-    if (r != UPH_OK) return r;
-    if (e != hipSuccess) { setError(std::string("uph_rollout_batch_dev: ") + hipGetErrorString(e)); return UPH_ERR_HIP; }
-    return UPH_OK;
-}
-
-// ---- check (include/uneven_hip.h uph_check_*) ------------------------------------------------------------------------------------------------
-// the window [t_from, t_to] in the first cnt entries of the time table (strictly increasing): samples [q_lo, q_hi) have t_from <= t_q and t_q <= t_to
-static void checkWindow(const std::vector<double>& tab, int64_t cnt, int with_end, double total, double t_from, double t_to, int32_t& q_lo, int32_t& q_hi,
-                        int32_t& end_row) {
-    const auto b = tab.begin(), e = tab.begin() + cnt;
-    const int64_t lo = std::lower_bound(b, e, t_from) - b;            // the first q with t_from <= t_q
-    const int64_t hi = std::upper_bound(b, e, t_to) - b;              // the first q with t_to < t_q
-    q_lo = (int32_t)lo; q_hi = (int32_t)(hi < lo ? lo : hi);
-    end_row = (with_end && t_from <= total && total <= t_to) ? 1 : 0;
-}
-
-int uph_check_limits(const uph_ctx* c, double* lim7) {
-    if (!c || !lim7) { setError("uph_check_limits: bad arguments"); return UPH_ERR_INVALID; }
-    const OptParams& P = c->P;
-    const double l[7] = {P.max_vel, P.max_acc_lon, P.max_acc_lat, P.max_kap, -P.min_cxi, P.max_sig, __builtin_huge_val()};
-    std::memcpy(lim7, l, sizeof(l));
-    return UPH_OK;
-}
-
-int uph_check_window(double dt, int32_t with_end, double total, double t_from, double t_to, int32_t* q_lo, int32_t* q_hi, int32_t* end_row) {
-    if (!q_lo || !q_hi || !end_row) { setError("uph_check_window: bad arguments"); return UPH_ERR_INVALID; }
-    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_check_window: dt must be positive and finite"); return UPH_ERR_INVALID; }
-    if (std::isnan(t_from) || std::isnan(t_to)) { setError("uph_check_window: a window bound is NaN"); return UPH_ERR_INVALID; }
-    std::vector<double> tab;
-    const int r = rolloutTimes(dt, total, tab);
-    if (r != UPH_OK) return r;
-    const int64_t cnt = std::lower_bound(tab.begin(), tab.end(), total) - tab.begin();       // (a NaN total: no samples, as in the loop)
-    if (cnt >= (int64_t)tab.size()) { setError("uph_check_window: the trajectory needs more than UPH_ROLLOUT_MAX_SAMPLES samples at this dt"); return UPH_ERR_LIMIT; }
-    checkWindow(tab, cnt, with_end, total, t_from, t_to, *q_lo, *q_hi, *end_row);
-    return UPH_OK;
-}
-
-int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* lim7,
-                    double* first_t, int32_t* first_mask, int32_t* counts, double* worst, double* worst_t) {
-    if (!c || n <= 0 || !traj || !t_from) { setError("uph_check_batch: bad arguments"); return UPH_ERR_INVALID; }
-    if (!(dt > 0.0) || !std::isfinite(dt)) { setError("uph_check_batch: dt must be positive and finite"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError("uph_check_batch: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    int r = checkTrajQueries(c, n, traj, t_from, "uph_check_batch");
-    if (r != UPH_OK) return r;
-    if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError("uph_check_batch: query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
-    RolloutSizes rs;
-    r = rolloutPlanCtx(c, dt, with_end, rs, "uph_check_batch");
-    if (r != UPH_OK) return r;
-    GridDev grid;
-    r = syncGridMem(c, grid);
-    if (r != UPH_OK) return r;
-    std::vector<CheckQuery> qs((size_t)n);
-    for (int32_t q = 0; q < n; q++) {
-        const int32_t b = traj[q];
-        CheckQuery& k = qs[(size_t)q];
-        int32_t q_hi = 0;
-        k.b = b; k.out = q; k.pad = 0;
-        checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
-        k.n_tab = q_hi - k.q_lo;
-        k.total = rs.total[(size_t)b];
-        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
-    }
-    // the longest windows first (as the uploads order the solves by predicted cost): the tail of the launch is made of short workgroups
-    std::stable_sort(qs.begin(), qs.end(), [](const CheckQuery& x, const CheckQuery& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
-    if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_chk_q.ensure(sizeof(CheckQuery) * (size_t)n) || c->d_chk_out.ensure(sizeof(CheckOut) * (size_t)n)) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_chk_q.p, qs.data(), sizeof(CheckQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    CheckArgs a;
-    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
-    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
-    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
-    a.qs = c->d_chk_q.as<CheckQuery>(); a.tt = c->d_roll_tt.as<double>(); a.out = c->d_chk_out.as<CheckOut>();
-    const char* occ_r2 = nullptr;
-    uphMapOcc(c->map, &a.occ, &occ_r2);
-    if (lim7) std::memcpy(a.lim, lim7, sizeof(a.lim));
-    else uph_check_limits(c, a.lim);
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(uph_check_kernel, dim3((unsigned)n), dim3(CHECK_NT), 0, c->stream, grid, a);
-    const hipError_t le = hipGetLastError();
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    std::vector<CheckOut> out((size_t)n);
-    const hipError_t ce = hipMemcpyAsync(out.data(), c->d_chk_out.p, sizeof(CheckOut) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued, and the host copies above outlive it)
-    HIPCHK(le); HIPCHK(ce); HIPCHK(se);
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_check_ms = ms;
-    for (int32_t q = 0; q < n; q++) {
-        const CheckOut& o = out[(size_t)q];
-        if (first_t) first_t[q] = o.first_t;
-        if (first_mask) first_mask[q] = o.first_mask;
-        if (counts) for (int k = 0; k < 3; k++) counts[3 * (size_t)q + k] = o.counts[k];
-        if (worst) for (int k = 0; k < 7; k++) worst[7 * (size_t)q + k] = o.worst[k];
-        if (worst_t) for (int k = 0; k < 7; k++) worst_t[7 * (size_t)q + k] = o.worst_t[k];
-    }
-    return UPH_OK;
-}
-
-int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_check_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_check_ms;
-    return UPH_OK;
-}
-
-// ---- locate / within (include/uneven_hip.h uph_locate_*, uph_within_batch) ---------------------------------------------------------------------------
-// what the two calls share: every refusal (outputs untouched), the windows as uph_check_batch forms them, the query records in launch order (longest
-// windows first, stable) with `extra` doubles of the caller's row (pose / rect) in each, the time table and the records on the device.  n_long: the
-// queries at the head of the launch whose window exceeds LOC_SHORT samples.
-static int locBegin(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* rows,
-                    int extra, const char* who, std::vector<LocQuery>& qs, int32_t& n_long) {
-    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(std::string(who) + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    int r = checkTrajQueries(c, n, traj, t_from, who);
-    if (r != UPH_OK) return r;
-    if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
-    for (int32_t q = 0; q < n; q++) for (int k = 0; k < extra; k++) {
-        const double v = rows[(size_t)extra * q + k];
-        if (extra == 3 ? !std::isfinite(v) : std::isnan(v)) {
-            setError(std::string(who) + ": query " + std::to_string(q) + (extra == 3 ? " has a non-finite pose component" : " has a NaN rect bound")); return UPH_ERR_INVALID;
-        }
-    }
-    RolloutSizes rs;
-    r = rolloutPlanCtx(c, dt, with_end, rs, who);
-    if (r != UPH_OK) return r;
-    qs.assign((size_t)n, LocQuery());
-    for (int32_t q = 0; q < n; q++) {
-        const int32_t b = traj[q];
-        LocQuery& k = qs[(size_t)q];
-        int32_t q_hi = 0;
-        k.b = b; k.out = q; k.pad = 0;
-        checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
-        k.n_tab = q_hi - k.q_lo;
-        k.total = rs.total[(size_t)b];
-        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
-        for (int d = 0; d < 4; d++) k.p[d] = d < extra ? rows[(size_t)extra * q + d] : 0.0;
-    }
-    std::stable_sort(qs.begin(), qs.end(), [](const LocQuery& x, const LocQuery& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
-    n_long = 0;
-    while (n_long < n && qs[(size_t)n_long].n_tab + qs[(size_t)n_long].end_row > LOC_SHORT) n_long++;
-    if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_loc_q.ensure(sizeof(LocQuery) * (size_t)n)) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_roll_tt.p, rs.tab.data(), 8 * rs.tab.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_loc_q.p, qs.data(), sizeof(LocQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    return UPH_OK;
-}
-
-// the launch (256 lanes for the first n_long queries, one wave for the rest) between the context's events, the result rows to the host, the wait
-extern "C++" template <class Out, class K256, class K64>
-static int locRun(uph_ctx* c, int32_t n, int32_t n_long, K256 k256, K64 k64, std::vector<Out>& out) {
-    if (c->d_loc_out.ensure(sizeof(Out) * (size_t)n)) return UPH_ERR_HIP;
-    LocArgs a;
-    a.desc = c->d_desc.as<TrajDesc>(); a.state = c->d_state.as<TrajState>();
-    a.cxy = c->d_cxy.as<double>(); a.cyaw = c->d_cyaw.as<double>();
-    a.qs = c->d_loc_q.as<LocQuery>(); a.tt = c->d_roll_tt.as<double>(); a.out = c->d_loc_out.p;
-    a.framed = c->frames.empty() ? 0 : 1; a.q0 = 0;
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    hipError_t le = hipSuccess;
-    if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
-    if (n > n_long && le == hipSuccess) { a.q0 = n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    out.resize((size_t)n);
-    const hipError_t ce = hipMemcpyAsync(out.data(), c->d_loc_out.p, sizeof(Out) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);      // (also after a failed launch: nothing of this call stays queued)
-    HIPCHK(le); HIPCHK(ce); HIPCHK(se);
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_locate_ms = ms;
-    return UPH_OK;
-}
-
-int uph_locate_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* poses, const double* t_from, const double* t_to, double dt, int32_t with_end,
-                     double* near_t, double* near_d2, int32_t* count, double* t, int32_t* refined, double* state, double* d2, double* err) {
-    if (!c || n <= 0 || !traj || !poses || !t_from) { setError("uph_locate_batch: bad arguments"); return UPH_ERR_INVALID; }
-    std::vector<LocQuery> qs;
-    int32_t n_long = 0;
-    int r = locBegin(c, n, traj, t_from, t_to, dt, with_end, poses, 3, "uph_locate_batch", qs, n_long);
-    if (r != UPH_OK) return r;
-    std::vector<LocateOut> out;
-    r = locRun(c, n, n_long, uph_locate_kernel<256>, uph_locate_kernel<64>, out);
-    if (r != UPH_OK) return r;
-    for (int32_t q = 0; q < n; q++) {
-        const LocateOut& o = out[(size_t)q];
-        if (near_t) near_t[q] = o.near_t;
-        if (near_d2) near_d2[q] = o.near_d2;
-        if (count) count[q] = o.count;
-        if (t) t[q] = o.t;
-        if (refined) refined[q] = o.refined;
-        if (state) for (int k = 0; k < TRAJ_STATE_COLS; k++) state[(size_t)TRAJ_STATE_COLS * q + k] = o.state[k];
-        if (d2) d2[q] = o.d2;
-        if (err) for (int k = 0; k < 3; k++) err[3 * (size_t)q + k] = o.err[k];
-    }
-    return UPH_OK;
-}
-
-int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* rects, const double* t_from, const double* t_to, double dt, int32_t with_end,
-                     double* enter_t, double* leave_t, int32_t* counts) {
-    if (!c || n <= 0 || !traj || !rects || !t_from) { setError("uph_within_batch: bad arguments"); return UPH_ERR_INVALID; }
-    std::vector<LocQuery> qs;
-    int32_t n_long = 0;
-    int r = locBegin(c, n, traj, t_from, t_to, dt, with_end, rects, 4, "uph_within_batch", qs, n_long);
-    if (r != UPH_OK) return r;
-    std::vector<WithinOut> out;
-    r = locRun(c, n, n_long, uph_within_kernel<256>, uph_within_kernel<64>, out);
-    if (r != UPH_OK) return r;
-    for (int32_t q = 0; q < n; q++) {
-        const WithinOut& o = out[(size_t)q];
-        if (enter_t) enter_t[q] = o.enter_t;
-        if (leave_t) leave_t[q] = o.leave_t;
-        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
-    }
-    return UPH_OK;
-}
-
-int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_locate_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_locate_ms;
     return UPH_OK;
 }
 

@@ -1,4 +1,4 @@
-// Internal glue between the two translation units of libunevenhip.so (unevenhip.hip, map_build.hip).
+// Internal glue between the optimiser, query, map and search translation units of libunevenhip.so (unevenhip.hip, traj_query.hip, map_build.hip, kino_search.hip).
 #pragma once
 #include <string>
 
