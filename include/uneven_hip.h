@@ -53,6 +53,8 @@
  *   uph_locate_batch        <- the time on a trajectory that traj_anal.hpp:490-491 takes from the wall clock (t_cur = now - start_time), here from the
  *                              odometry pose PlanManager::rcvOdomCallBack holds (plan_manager.cpp:31-41), with the tracking error at that time
  *   uph_within_batch        <- which resident trajectories enter a rect of the map (a changed region) and when
+ *   uph_separation_batch    <- how close two resident trajectories come at the same moment of a clock they share (each starts at its own t0 on it)
+ *   uph_conflicts_batch     <- the pairs of a fleet on one map that come closer than their radii allow: extents, a host broad phase, separation
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -639,6 +641,49 @@ int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* r
                      double dt, int32_t with_end, double* enter_t /* [n], NaN: none */, double* leave_t /* [n] */, int32_t* counts /* [n][2]: samples, inside */);
 /* milliseconds of the kernel(s) of the last uph_locate_batch or uph_within_batch of c, whichever came last (events on the context's stream) */
 int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
+/* ---- resident trajectories against each other on a common clock.  Every resident trajectory counts time from its own start; a vehicle here is a trajectory
+ * and the time t0 on the common clock at which it starts.
+ *   sample times   a query has a window [t_from, t_to] on the common clock (both finite) and a step dt > 0 (finite).  Sample k sits at
+ *                  tau_k = t_from + k * dt -- the product rounded, then the sum rounded, never one fused operation.  K = the number of k >= 0 with tau_k <= t_to
+ *                  (0 when t_to < t_from).  The rollout's additive time table is not used.  A query with K > 2^22 is refused with UPH_ERR_LIMIT.
+ *   a vehicle at tau   its own time is u = tau - t0 (one rounded subtraction), clamped as uph_traj_states clamps it (u <= 0: 0, u >= total: total); its position
+ *                  X, Y is columns 0 and 1 of uph_traj_states(traj, u), bit for bit.  Before t0 it stands at its start, after its end at its goal.
+ *   separation     d2 = ex ex + ey ey with ex = X_a - X_b, ey = Y_a - Y_b and both products rounded before the add (uph_locate_batch's d2).  A sample is
+ *                  BELOW when d2 < R2, strictly, R2 = R * R rounded; a NaN d2 is never below.  For the minimum a NaN d2 reads +inf and the smaller k wins
+ *                  among equals.
+ *   extent         (xmin, xmax, ymin, ymax) over the samples whose X and Y are both not NaN; (+inf, -inf, +inf, -inf) when there is none.
+ *   candidates     the pair (i, j), i < j, of boxes box_i, box_j with radii r_i, r_j has R = r_i + r_j (one rounded add) and is DROPPED iff
+ *                  xmin_i - xmax_j > R || xmin_j - xmax_i > R || ymin_i - ymax_j > R || ymin_j - ymax_i > R.  Rounding is monotone and `below` is strict, so a
+ *                  dropped pair has d2 >= R2 at every sample of the window its boxes were taken over: the pruning loses nothing and needs no epsilon.
+ * Deterministic as uph_locate_batch: selections under a total order and integer sums.  The device calls are blocking, on the (first) context's stream; any
+ * output may be NULL; every refusal leaves the outputs untouched: UPH_ERR_INVALID for bad arguments, dt <= 0 or not finite, a non-finite window bound or start
+ * time, a negative or non-finite radius, no resident trajectory, a trajectory index out of range or naming an UPH_RET_UNSUPPORTED slot, an asynchronous solve
+ * pending; UPH_ERR_LIMIT for K > 2^22. */
+/* host only, no device needed: K of the window by the rule above */
+int uph_separation_times(double t_from, double t_to, double dt, int64_t* K);
+/* query q: the extent of vehicle (traj[q], t0[q]) of c's resident batch over the window [t_from[q], t_to[q]] */
+int uph_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt,
+                     double* box /* [n][4]: xmin, xmax, ymin, ymax */, int32_t* counts /* [n][2]: samples, NaN samples */);
+/* query q: vehicle (traj_a[q], t0_a[q]) of ca against vehicle (traj_b[q], t0_b[q]) of cb over [t_from[q], t_to[q]], radius[q] = R itself.  min_t, first_t and
+ * last_t are tau on the common clock: of the minimum, of the first and of the last sample below (NaN: no such sample); min_d2 is +inf for K = 0.  The two
+ * contexts may differ (a refined batch against the fleet it came from): both on the same device, both with solved trajectories and no solve in flight; cb's
+ * stream is waited for before the launch on ca's stream, and each side applies its own context's frame shift.  The kernel time is kept on ca. */
+int uph_separation_batch(uph_ctx* ca, uph_ctx* cb /* NULL: ca */, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
+                         const double* t_from, const double* t_to, double dt, const double* radius, double* min_d2 /* [n] */, double* min_t /* [n] */,
+                         double* first_t /* [n], NaN: none */, double* last_t /* [n] */, int32_t* counts /* [n][2]: samples, below */);
+/* host only, no device needed: the pairs of n boxes (uph_extent_batch's rows; +-inf allowed, NaN refused) with per-box radii that the rule does not drop, by a
+ * sort on xmin and a sweep.  pairs holds the first cap of them in (i, j) order, *n_pairs is their full number. */
+int uph_conflict_candidates(int32_t n, const double* box /* [n][4] */, const double* radius /* [n] */, int64_t cap, int32_t* pairs /* [cap][2] */, int64_t* n_pairs);
+/* the fleet: vehicles (traj[i], t0[i]) of c's resident batch with radius[i] each, one window for all.  Extents on the device, candidates on the host, then the
+ * separation of every candidate (a = i, b = j, R = radius[i] + radius[j]) on the device in launches of bounded size.  The pairs with below > 0 -- indices into
+ * the vehicle list, in (i, j) order, the first cap of them -- with rows = min_d2, min_t, first_t, last_t and below = their number of samples below;
+ * *n_conflicts is the full number of such pairs, *n_candidates the number of pairs the broad phase kept. */
+int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius /* [n]: per vehicle */, double t_from, double t_to, double dt,
+                        int64_t cap, int32_t* pairs /* [cap][2] */, double* rows /* [cap][4]: min_d2, min_t, first_t, last_t */, int32_t* below /* [cap] */,
+                        int64_t* n_conflicts, int64_t* n_candidates);
+/* milliseconds of the kernels of the last uph_extent_batch, uph_separation_batch or uph_conflicts_batch of c (events on the context's stream) */
+int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
 // repository's image).  No Eigen header is included here.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <stdexcept>
@@ -610,6 +611,88 @@ public:
         if (uph_within_batch(ctx_, n, tr.data(), rc.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, out.enter_t.data(),
                              out.leave_t.data(), out.counts.data()) != UPH_OK)
             throw std::runtime_error(std::string("uph_within_batch: ") + uph_last_error());
+        return out;
+    }
+    // ---- the trajectories of a fleet against each other.  Every trajectory counts time from its own start; on the clock the fleet shares, vehicle q starts
+    // at t0[q].  A window [t_from, t_to] of that clock is sampled at tau_k = t_from + k dt; a vehicle stands at its start before t0 and at its goal after its
+    // end.  The bounding box of each vehicle's positions over its window (uph_extent_batch): the input of a broad phase.
+    struct TrajExtent {
+        std::vector<double> box;                // [n][4] xmin, xmax, ymin, ymax in map coordinates ((+inf, -inf, +inf, -inf): no sample)
+        std::vector<int32_t> counts;            // [n][2] samples, NaN samples
+    };
+    TrajExtent extentSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                  double dt = 0.01) {
+        if (t0.size() != traj.size() || t_from.size() != traj.size() || t_to.size() != traj.size())
+            throw std::runtime_error("extentSE2TrajBatch: traj, t0, t_from and t_to differ in number");
+        if (last_multi_) throw std::runtime_error("extentSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajExtent out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        out.box.assign((size_t)4 * n, 0.0); out.counts.assign((size_t)2 * n, 0);
+        if (uph_extent_batch(ctx_, n, tr.data(), t0.data(), t_from.data(), t_to.data(), dt, out.box.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_extent_batch: ") + uph_last_error());
+        return out;
+    }
+    // how close vehicle a = (traj_a[q], t0_a[q]) of this object's last batch and vehicle b = (traj_b[q], t0_b[q]) of `other`'s last batch (nullptr: this
+    // object's; a refined batch against the fleet it came from is the main use) come over [t_from[q], t_to[q]], and when they are closer than radius[q]
+    // (uph_separation_batch).  Before a refined or re-planned trajectory is handed to its vehicle.
+    struct TrajSeparation {
+        std::vector<double> min_d2, min_t;      // [n] the smallest squared distance and its time on the common clock (+inf, NaN: no sample)
+        std::vector<double> first_t, last_t;    // [n] the first / last sample with d2 < radius^2 (NaN: none)
+        std::vector<int32_t> counts;            // [n][2] samples, below
+        bool conflicts(size_t q) const { return counts[2 * q + 1] > 0; }
+    };
+    TrajSeparation separationSE2TrajBatch(const std::vector<int>& traj_a, const std::vector<int>& traj_b, const std::vector<double>& t0_a, const std::vector<double>& t0_b,
+                                          const std::vector<double>& t_from, const std::vector<double>& t_to, const std::vector<double>& radius, double dt = 0.01,
+                                          const ALMTrajOpt* other = nullptr) {
+        const size_t m = traj_a.size();
+        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || radius.size() != m)
+            throw std::runtime_error("separationSE2TrajBatch: the query arrays differ in number");
+        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("separationSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)m;
+        TrajSeparation out;
+        if (n == 0) return out;
+        std::vector<int32_t> ta(traj_a.begin(), traj_a.end()), tb(traj_b.begin(), traj_b.end());
+        out.min_d2.assign(m, 0.0); out.min_t.assign(m, 0.0); out.first_t.assign(m, 0.0); out.last_t.assign(m, 0.0); out.counts.assign(2 * m, 0);
+        if (uph_separation_batch(ctx_, other ? other->ctx_ : nullptr, n, ta.data(), tb.data(), t0_a.data(), t0_b.data(), t_from.data(), t_to.data(), dt, radius.data(),
+                                 out.min_d2.data(), out.min_t.data(), out.first_t.data(), out.last_t.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_separation_batch: ") + uph_last_error());
+        return out;
+    }
+    // the whole fleet at once: vehicles (traj[i], t0[i]) of this object's last batch, each a disc of radius[i], one window.  Every pair (i < j, indices into
+    // traj) with a sample closer than radius[i] + radius[j], in (i, j) order (uph_conflicts_batch: extents, a host broad phase, separation of its candidates).
+    struct TrajConflicts {
+        std::vector<std::array<int32_t, 2>> pairs;      // [m]
+        std::vector<double> min_d2, min_t, first_t, last_t;
+        std::vector<int32_t> below;                     // [m] samples below
+        int64_t n_conflicts = 0, n_candidates = 0;      // all conflicts (m of them are listed); pairs the broad phase kept
+    };
+    TrajConflicts conflictsSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<double>& radius, double t_from, double t_to,
+                                        double dt = 0.05, int64_t cap = -1) {
+        if (t0.size() != traj.size() || radius.size() != traj.size()) throw std::runtime_error("conflictsSE2TrajBatch: traj, t0 and radius differ in number");
+        if (last_multi_) throw std::runtime_error("conflictsSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajConflicts out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        int64_t room = cap >= 0 ? cap : std::max<int64_t>(1024, 4 * (int64_t)n);
+        std::vector<int32_t> pairs, below;
+        std::vector<double> rows;
+        for (;;) {                                                    // cap < 0: every conflict (repeated once with room for all of them)
+            pairs.assign((size_t)2 * room + 2, 0); rows.assign((size_t)4 * room + 4, 0.0); below.assign((size_t)room + 1, 0);
+            if (uph_conflicts_batch(ctx_, n, tr.data(), t0.data(), radius.data(), t_from, t_to, dt, room, pairs.data(), rows.data(), below.data(), &out.n_conflicts,
+                                    &out.n_candidates) != UPH_OK)
+                throw std::runtime_error(std::string("uph_conflicts_batch: ") + uph_last_error());
+            if (cap >= 0 || out.n_conflicts <= room) break;
+            room = out.n_conflicts;
+        }
+        const size_t m = (size_t)std::min<int64_t>(room, out.n_conflicts);
+        for (size_t k = 0; k < m; k++) {
+            out.pairs.push_back({pairs[2 * k], pairs[2 * k + 1]});
+            out.min_d2.push_back(rows[4 * k]); out.min_t.push_back(rows[4 * k + 1]); out.first_t.push_back(rows[4 * k + 2]); out.last_t.push_back(rows[4 * k + 3]);
+            out.below.push_back(below[k]);
+        }
         return out;
     }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)

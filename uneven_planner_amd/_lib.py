@@ -175,6 +175,13 @@ SYMBOLS = {
     "uph_locate_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32), DP, C.POINTER(_I32), DP, DP, DP]),
     "uph_within_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, _I32, DP, DP, C.POINTER(_I32)]),
     "uph_locate_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_separation_times": (C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(_I64)]),
+    "uph_extent_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, DP, C.POINTER(_I32)]),
+    "uph_separation_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, DP, DP, DP, DP, C.POINTER(_I32)]),
+    "uph_conflict_candidates": (C.c_int, [_I32, DP, DP, _I64, C.POINTER(_I32), C.POINTER(_I64)]),
+    "uph_conflicts_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, C.c_double, C.c_double, _I64, C.POINTER(_I32), DP, C.POINTER(_I32),
+                                      C.POINTER(_I64), C.POINTER(_I64)]),
+    "uph_separation_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None
@@ -189,6 +196,7 @@ UPH_ERR_INVALID, UPH_ERR_LIMIT = -1, -4
 UPH_KINO_OK = 0
 UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
 UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
+SEPARATION_MAX_SAMPLES = 1 << 22     # include/uneven_hip.h: samples of one query on the common clock
 TRAJ_STATE_COLS = 10       # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
 
 

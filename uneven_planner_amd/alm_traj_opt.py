@@ -342,6 +342,76 @@ def locate_refine(se2traj, shift, pose, times, j):
     return dict(t=t, refined=int(refined), state=s, d2=d2, err=locate_errors(s, pose), lo=lo, hi=hi, iters=iters)
 
 
+# uph_separation_batch / uph_extent_batch / uph_conflict_candidates (include/uneven_hip.h): numpy mirrors written from the rule, not from the kernels
+def separation_times(t_from, t_to, dt):
+    """Host mirror of the sample times of a window on the common clock: tau_k = t_from + k * dt (the product rounded, then the sum) for every k >= 0
+    with tau_k <= t_to, as an array (empty when t_to < t_from).  Raises for bounds or a dt the library refuses and for more than 2^22 samples."""
+    t_from, t_to, dt = float(t_from), float(t_to), float(dt)
+    if not (np.isfinite(t_from) and np.isfinite(t_to) and np.isfinite(dt) and dt > 0.0):
+        raise _lib.UnevenHipError("separation_times: the bounds must be finite and dt positive and finite")
+    if t_to < t_from:
+        return np.zeros(0)
+    cap = _lib.SEPARATION_MAX_SAMPLES + 1
+    n = int(min((t_to - t_from) / dt, float(cap))) + 2
+    while True:                                                     # tau does not decrease with k: grow until the last one is beyond t_to
+        n = min(n, cap)
+        with np.errstate(over="ignore"):
+            p = np.arange(n, dtype=np.float64) * dt
+            tau = t_from + p
+        if tau[-1] > t_to or n == cap:
+            break
+        n *= 2
+    K = int(np.count_nonzero(tau <= t_to))
+    if K > _lib.SEPARATION_MAX_SAMPLES:
+        raise _lib.UnevenHipError("separation_times: the window holds more than 2^22 samples at this dt")
+    return tau[:K]
+
+
+def separation_rows(tau, xy_a, xy_b, radius):
+    """Host mirror of one uph_separation_batch query: tau (K,) the sample times, xy_a / xy_b (K, 2) the two vehicles' positions at them, radius = R.
+    d2 = ex ex + ey ey (each product rounded, then the add); a sample is below when d2 < R * R, strictly (a NaN d2 never is); for the minimum a NaN d2
+    reads +inf and a tie stays with the earlier sample.  Returns min_d2, min_t, first_t, last_t (NaN: no such sample) and counts (2,): samples, below."""
+    tau = np.asarray(tau, dtype=np.float64).reshape(-1)
+    a = np.asarray(xy_a, dtype=np.float64).reshape(-1, 2)
+    b = np.asarray(xy_b, dtype=np.float64).reshape(-1, 2)
+    R = np.float64(radius)
+    if tau.shape[0] == 0:
+        return dict(min_d2=np.inf, min_t=np.nan, first_t=np.nan, last_t=np.nan, counts=np.zeros(2, dtype=np.int32))
+    with np.errstate(over="ignore", invalid="ignore"):
+        ex, ey = a[:, 0] - b[:, 0], a[:, 1] - b[:, 1]
+        d2 = ex * ex + ey * ey
+        below = np.nonzero(d2 < R * R)[0]
+    key = np.where(np.isnan(d2), np.inf, d2)
+    j = int(np.argmin(key))                                         # the first occurrence of the minimum
+    return dict(min_d2=key[j], min_t=tau[j], first_t=tau[below[0]] if below.size else np.nan, last_t=tau[below[-1]] if below.size else np.nan,
+                counts=np.array([tau.shape[0], below.size], dtype=np.int32))
+
+
+def extent_rows(xy):
+    """Host mirror of one uph_extent_batch query on the vehicle's positions xy (K, 2) at the window's samples: box (4,) = xmin, xmax, ymin, ymax over
+    the rows without a NaN ((+inf, -inf, +inf, -inf): none) and counts (2,): samples, NaN samples."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    ok = ~np.isnan(xy).any(axis=1)
+    v = xy[ok]
+    box = np.array([v[:, 0].min(), v[:, 0].max(), v[:, 1].min(), v[:, 1].max()]) if v.shape[0] else np.array([np.inf, -np.inf, np.inf, -np.inf])
+    return dict(box=box, counts=np.array([xy.shape[0], xy.shape[0] - v.shape[0]], dtype=np.int32))
+
+
+def conflict_candidates(box, radius):
+    """Host mirror of uph_conflict_candidates: the pairs (i < j) of boxes box (n, 4) = xmin, xmax, ymin, ymax with radii radius (n,) that the rule does
+    not drop -- dropped iff xmin_i - xmax_j > R, xmin_j - xmax_i > R or either of the same in y, R = r_i + r_j -- as an (m, 2) int32 array in (i, j) order"""
+    box = np.asarray(box, dtype=np.float64).reshape(-1, 4)
+    r = np.asarray(radius, dtype=np.float64).reshape(-1)
+    n = box.shape[0]
+    R = r[:, None] + r[None, :]
+    with np.errstate(invalid="ignore"):
+        gx = box[:, None, 0] - box[None, :, 1]                      # [i, j] = xmin_i - xmax_j
+        gy = box[:, None, 2] - box[None, :, 3]
+        drop = (gx > R) | (gx.T > R) | (gy > R) | (gy.T > R)
+    keep = ~drop & (np.arange(n)[:, None] < np.arange(n)[None, :])
+    return np.argwhere(keep).astype(np.int32).reshape(-1, 2)
+
+
 class ALMTrajOpt:
     def __init__(self, uneven_map=None, params=None):
         self.L = _lib.load()
@@ -859,6 +929,66 @@ class ALMTrajOpt:
         """milliseconds of the kernel(s) of the last locate() or within(), whichever came last (events on the context's stream)"""
         ms = C.c_double(0)
         _lib.check(self.L.uph_locate_kernel_ms(self.h, C.byref(ms)), "uph_locate_kernel_ms")
+        return ms.value
+
+    # ---- resident trajectories against each other on a common clock (uph_extent_batch, uph_separation_batch, uph_conflicts_batch) ---------------------
+    def _clock(self, traj, t_from, t_to, who, **per_query):
+        """the query arrays of the common-clock calls: trajectories, the broadcast window bounds and the broadcast per-query values"""
+        tr = np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)
+        n = tr.shape[0]
+        if n == 0:
+            raise _lib.UnevenHipError(who + ": no query")
+        bc = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+        return tr, n, bc(t_from), bc(t_to), {k: bc(v) for k, v in per_query.items()}
+
+    def extent(self, traj, t_from, t_to, t0=0.0, dt=0.01):
+        """The bounding box, on the device, of vehicle q -- resident trajectory traj[q] started at t0[q] on a common clock -- over the samples
+        tau_k = t_from[q] + k dt <= t_to[q] of that clock (scalars are broadcast): box (n, 4) = xmin, xmax, ymin, ymax in map coordinates and counts
+        (n, 2: samples, NaN samples); see separation_times / extent_rows for the rule."""
+        tr, n, tf, tt, v = self._clock(traj, t_from, t_to, "extent", t0=t0)
+        out = dict(box=np.tile([np.inf, -np.inf, np.inf, -np.inf], (n, 1)), counts=np.zeros((n, 2), dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_extent_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), _dp(out["box"]), ip(out["counts"])), "uph_extent_batch")
+        return out
+
+    def separation(self, traj_a, traj_b, t_from, t_to, radius, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
+        """How close, on the device, vehicle a -- trajectory traj_a[q] of self started at t0_a[q] on a common clock -- and vehicle b -- trajectory
+        traj_b[q] of `other` (an ALMTrajOpt on the same device; None: self) started at t0_b[q] -- come over the samples tau_k = t_from[q] + k dt <=
+        t_to[q]: min_d2 and min_t (the smallest squared distance and its tau), first_t / last_t (tau of the first / last sample with d2 < radius[q]^2,
+        NaN: none) and counts (n, 2: samples, below).  A vehicle stands at its start before its t0 and at its goal after its end.  See separation_rows."""
+        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "separation", t0_a=t0_a, t0_b=t0_b, radius=radius)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        out = dict(min_d2=np.full(n, np.inf), min_t=np.full(n, np.nan), first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), counts=np.zeros((n, 2), dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_separation_batch(self.h, None if other is None else other.h, n, ip(tr), ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
+                                               _dp(v["radius"]), _dp(out["min_d2"]), _dp(out["min_t"]), _dp(out["first_t"]), _dp(out["last_t"]), ip(out["counts"])),
+                   "uph_separation_batch")
+        return out
+
+    def conflicts(self, traj, radius, t_from, t_to, t0=0.0, dt=0.05, cap=None):
+        """The pairs of a fleet that come too close: vehicle i is resident trajectory traj[i] started at t0[i] on a common clock with a disc of
+        radius[i] (scalars are broadcast), one window [t_from, t_to] for all.  Extents on the device, the broad phase on the host, the separation of
+        its candidates on the device.  Returns pairs (m, 2) -- indices into traj, i < j, in (i, j) order, every pair with a sample of d2 <
+        (radius[i] + radius[j])^2 or the first cap of them --, rows (m, 4) = min_d2, min_t, first_t, last_t, below (m,), n_conflicts (all of them) and
+        n_candidates (pairs the broad phase kept).  See conflict_candidates / separation_rows."""
+        tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "conflicts", t0=t0, radius=radius)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        room = max(1024, 4 * n) if cap is None else int(cap)
+        while True:
+            pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
+            nc, nk = C.c_int64(0), C.c_int64(0)
+            _lib.check(self.L.uph_conflicts_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(v["radius"]), float(t_from), float(t_to), float(dt), room, ip(pairs), _dp(rows),
+                                                  ip(below), C.byref(nc), C.byref(nk)), "uph_conflicts_batch")
+            if cap is not None or nc.value <= room:
+                break
+            room = int(nc.value)                                    # cap = None: every conflict (the call is repeated with room for all of them)
+        m = min(room, int(nc.value))
+        return dict(pairs=pairs[:m], rows=rows[:m], below=below[:m], n_conflicts=int(nc.value), n_candidates=int(nk.value))
+
+    def separation_kernel_ms(self):
+        """milliseconds of the kernels of the last extent(), separation() or conflicts() (events on the context's stream)"""
+        ms = C.c_double(0)
+        _lib.check(self.L.uph_separation_kernel_ms(self.h, C.byref(ms)), "uph_separation_kernel_ms")
         return ms.value
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------

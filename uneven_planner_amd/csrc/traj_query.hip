@@ -1,11 +1,13 @@
-// libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within and the switch / trajectory states
-// (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states).  Kernels for gfx950 and their host side; the
-// context, its buffers and the solver live in unevenhip.hip (uph_ctx.hpp is what the two share).
+// libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
+// separation / extent / conflicts on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states,
+// uph_separation_*, uph_extent_batch, uph_conflict*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record (WinQuery: trajectory,
 // window of the rollout's time table, end point), lanes striding over the window, a selection or an integer sum reduced by wave_dev.hpp's rowReduce /
 // rowLeaders / acrossWaves, thread 0 writes the row.  Host: formWindowQueries (refusals, windows, launch order, uploads), runQueryLaunch (events, launch,
-// rows back, the wait).
+// rows back, the wait).  The common-clock queries (ClockQuery: samples t_from + k dt instead of a window of the time table) keep the device half and
+// runQueryLaunch; clockRun is their launch former.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -411,6 +413,139 @@ __global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
     ((WithinOut*)a.out)[lq.out] = o;
 }
 
+// ---- separation / extent (uph_separation_batch, uph_extent_batch, uph_conflicts_batch): reductions over the positions of resident trajectories on a clock
+// that several vehicles share.  Sample k of a query sits at tau_k = t_from + k dt (the product rounded, then the sum: no time table, the clock may stand at
+// 1000 s); a vehicle is a trajectory and its start time t0 on that clock, and stands at uph_switch_state_kernel's state of u = tau - t0: at its start before
+// it leaves, at its goal after it arrives.  As locate / within: no terrain, no scratch, one wave for K <= LOC_SHORT samples and 256 lanes beyond.
+struct ClockTraj {              // one vehicle of a query
+    int32_t b, pad;             // resident trajectory (of its side's context)
+    double t0;                  // its start on the common clock
+    double shift[2];            // as RolloutTraj
+};
+struct ClockQuery {             // one query of a launch (formed on the host, in launch order: clockRun)
+    int32_t out, K;             // row of the launch's output; samples
+    double t_from, dt;
+};
+struct SepQuery : ClockQuery {
+    double R2;                  // a sample is below when d2 < R2
+    ClockTraj a, b;
+};
+struct ExtQuery : ClockQuery {
+    ClockTraj a;
+};
+struct SepOut {                 // one row per query
+    double min_d2, min_t;       // +inf, NaN: no sample
+    double first_t, last_t;     // first / last sample below (NaN: none)
+    int32_t counts[2];          // samples, below
+};
+struct ExtOut {
+    double box[4];              // xmin, xmax, ymin, ymax over the samples whose position is not NaN
+    int32_t counts[2];          // samples, NaN samples
+};
+struct SepArgs {
+    ResidentDev ra, rb;         // the two sides' resident batches (one context: the same)
+    const SepQuery* qs;
+    SepOut* out;
+    int framed_a, framed_b, q0; // as LocArgs, per side
+};
+struct ExtArgs {
+    ResidentDev r;
+    const ExtQuery* qs;
+    ExtOut* out;
+    int framed, q0;
+};
+
+// tau_k with the product rounded before the add
+__device__ __forceinline__ double clockTau(const ClockQuery& q, int k) {
+    double p = (double)k * q.dt;
+    asm volatile("" : "+v"(p));
+    return q.t_from + p;
+}
+struct ClockView {              // one vehicle as a kernel samples it (query-uniform)
+    TrajView tr;
+    double t0, total;
+};
+__device__ __forceinline__ ClockView clockView(const ResidentDev& r, const ClockTraj& c, bool framed) {
+    ClockView v;
+    v.tr = trajView(r, c.b, framed, c.shift);
+    v.t0 = c.t0;
+    v.total = trajTotal(v.tr.Nxy, v.tr.Tx, v.tr.Nyaw, v.tr.Ty);
+    return v;
+}
+// the vehicle's position at tau: uph_switch_state_kernel's clamp of its own time, then the STATE row's x, y there
+__device__ __forceinline__ void clockSample(const ClockView& v, double tau, double& X, double& Y) {
+    const double u = tau - v.t0;
+    const double t = u <= 0.0 ? 0.0 : (u >= v.total ? v.total : u);
+    TrajSample s;
+    locSample(v.tr, t, s, X, Y);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_separation_kernel(SepArgs a) {
+    __shared__ double s_red[NT / 64 * 24 / 8];
+    const SepQuery sq = a.qs[a.q0 + blockIdx.x];
+    const ClockView va = clockView(a.ra, sq.a, a.framed_a != 0), vb = clockView(a.rb, sq.b, a.framed_b != 0);
+    const int n = sq.K;
+    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
+    double v = inf;
+    int i = WIN_NONE, first = WIN_NONE, last = -1, cnt = 0;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        const double tau = clockTau(sq, j);
+        double Xa, Ya, Xb, Yb;
+        clockSample(va, tau, Xa, Ya);
+        clockSample(vb, tau, Xb, Yb);
+        const double d2 = locD2(Xa - Xb, Ya - Yb);
+        winTake<false>(v, i, d2 < inf ? d2 : inf, j);       // NaN: +inf
+        if (d2 < sq.R2) {                                   // (a NaN d2 is not below)
+            first = first == WIN_NONE ? j : first; last = j; cnt++;
+        }
+    }
+    const auto fold = [](double& v, int& i, int& lo, int& hi, int& c, double ov, int oi, int ol, int oh, int oc) {
+        winTake<false>(v, i, ov, oi);
+        lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; c += oc;
+    };
+    rowReduce(fold, v, i, first, last, cnt);
+    rowLeaders(fold, v, i, first, last, cnt);
+    if (!acrossWaves<NT / 64>(fold, s_red, v, i, first, last, cnt)) return;
+    SepOut o;
+    o.min_d2 = v;
+    o.min_t = i == WIN_NONE ? nan : clockTau(sq, i);
+    o.first_t = cnt == 0 ? nan : clockTau(sq, first);
+    o.last_t = cnt == 0 ? nan : clockTau(sq, last);
+    o.counts[0] = n; o.counts[1] = cnt;
+    a.out[sq.out] = o;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_extent_kernel(ExtArgs a) {
+    __shared__ double s_red[(NT / 64 * 36 + 7) / 8];
+    const ExtQuery eq = a.qs[a.q0 + blockIdx.x];
+    const ClockView va = clockView(a.r, eq.a, a.framed != 0);
+    const int n = eq.K;
+    const double inf = __builtin_huge_val();
+    double x0 = inf, x1 = -inf, y0 = inf, y1 = -inf;
+    int bad = 0;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        double X, Y;
+        clockSample(va, clockTau(eq, j), X, Y);
+        if (X == X && Y == Y) {
+            x0 = X < x0 ? X : x0; x1 = X > x1 ? X : x1; y0 = Y < y0 ? Y : y0; y1 = Y > y1 ? Y : y1;
+        } else {
+            bad++;
+        }
+    }
+    const auto hull = [](double& x0, double& x1, double& y0, double& y1, int& c, double ox0, double ox1, double oy0, double oy1, int oc) {
+        x0 = ox0 < x0 ? ox0 : x0; x1 = ox1 > x1 ? ox1 : x1; y0 = oy0 < y0 ? oy0 : y0; y1 = oy1 > y1 ? oy1 : y1; c += oc;
+    };
+    rowReduce(hull, x0, x1, y0, y1, bad);
+    rowLeaders(hull, x0, x1, y0, y1, bad);
+    if (!acrossWaves<NT / 64>(hull, s_red, x0, x1, y0, y1, bad)) return;
+    ExtOut o;
+    o.box[0] = x0; o.box[1] = x1; o.box[2] = y0; o.box[3] = y1;
+    o.counts[0] = n; o.counts[1] = bad;
+    a.out[eq.out] = o;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static ResidentDev residentDev(uph_ctx* c) {
     ResidentDev r;
@@ -663,6 +798,131 @@ static int locRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_fr
     }, out, c->last_locate_ms);
 }
 
+// ---- separation / extent / conflicts (include/uneven_hip.h uph_separation_*, uph_extent_batch, uph_conflict*) -----------------------------------------
+constexpr int64_t CLOCK_MAX_SAMPLES = (int64_t)1 << 22;     // samples of one query
+constexpr size_t CLOCK_CHUNK = (size_t)1 << 16;             // queries of one launch pair: bounds the records and rows on the device (a dense fleet's candidates)
+
+static double clockTauHost(double t_from, int64_t k, double dt) {
+#pragma clang fp contract(off)
+    const double p = (double)k * dt;
+    return t_from + p;
+}
+// K = the number of k >= 0 with tau_k <= t_to (tau_k does not decrease with k: rounding is monotone); the bounds and dt are finite, dt > 0
+static int clockCount(double t_from, double t_to, double dt, int64_t& K, const std::string& who) {
+    K = 0;
+    if (!(t_from <= t_to)) return UPH_OK;
+    if (clockTauHost(t_from, CLOCK_MAX_SAMPLES, dt) <= t_to) { setError(who + ": the window holds more than 2^22 samples at this dt"); return UPH_ERR_LIMIT; }
+    int64_t lo = 0, hi = CLOCK_MAX_SAMPLES;                 // tau_lo <= t_to < tau_hi
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (clockTauHost(t_from, mid, dt) <= t_to) lo = mid;
+        else hi = mid;
+    }
+    K = lo + 1;
+    return UPH_OK;
+}
+static int clockWindow(double t_from, double t_to, double dt, int64_t& K, const std::string& who) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(who + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (!std::isfinite(t_from) || !std::isfinite(t_to)) { setError(who + ": a window bound is not finite"); return UPH_ERR_INVALID; }
+    return clockCount(t_from, t_to, dt, K, who);
+}
+// c can answer queries on the common clock: solved trajectories, no solve in flight, every query names one of them with a finite start time
+static int clockSide(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const char* who) {
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
+    return checkTrajQueries(c, n, traj, t0, who);
+}
+static ClockTraj clockTraj(const uph_ctx* c, int32_t b, double t0) {
+    ClockTraj r;
+    r.b = b; r.pad = 0; r.t0 = t0;
+    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    return r;
+}
+
+// n <= CLOCK_CHUNK queries in the caller's order -> their rows in that order: the records in launch order (the most samples first, stable) on the device, 256
+// lanes for the queries of more than LOC_SHORT samples at the head and one wave for the rest (as locRun), the kernels' time added to ms
+template <class Q, class Out, class Args, class K256, class K64>
+static int clockRun(uph_ctx* c, Q* qs, size_t n, Args a, K256 k256, K64 k64, Out* rows, double& ms) {
+    for (size_t q = 0; q < n; q++) qs[q].out = (int32_t)q;
+    std::stable_sort(qs, qs + n, [](const Q& x, const Q& y) { return x.K > y.K; });
+    size_t n_long = 0;
+    while (n_long < n && qs[n_long].K > LOC_SHORT) n_long++;
+    if (c->d_win_q.ensure(sizeof(Q) * n) || c->d_win_out.ensure(sizeof(Out) * n)) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_win_q.p, qs, sizeof(Q) * n, hipMemcpyHostToDevice, c->stream));
+    a.qs = c->d_win_q.as<Q>(); a.out = c->d_win_out.as<Out>(); a.q0 = 0;
+    std::vector<Out> out(n);
+    double one = 0.0;
+    const int r = runQueryLaunch(c, [&]() {
+        hipError_t le = hipSuccess;
+        if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
+        if (n > n_long && le == hipSuccess) { a.q0 = (int)n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
+        return le;
+    }, out, one);
+    if (r != UPH_OK) return r;
+    ms += one;
+    std::copy(out.begin(), out.end(), rows);
+    return UPH_OK;
+}
+
+static SepArgs sepArgs(uph_ctx* ca, uph_ctx* cb) {
+    SepArgs a;
+    a.ra = residentDev(ca); a.rb = residentDev(cb);
+    a.framed_a = ca->frames.empty() ? 0 : 1; a.framed_b = cb->frames.empty() ? 0 : 1;
+    a.qs = nullptr; a.out = nullptr; a.q0 = 0;
+    return a;
+}
+
+// the extents of n vehicles of c (already checked: clockSide, the windows' K) in launches of at most CLOCK_CHUNK
+static int extentRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const int64_t* K, double dt, std::vector<ExtOut>& out, double& ms) {
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    ExtArgs a;
+    a.r = residentDev(c); a.framed = c->frames.empty() ? 0 : 1; a.qs = nullptr; a.out = nullptr; a.q0 = 0;
+    out.resize((size_t)n);
+    std::vector<ExtQuery> qs;
+    for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
+        const size_t m = std::min(CLOCK_CHUNK, (size_t)n - s);
+        qs.assign(m, ExtQuery());
+        for (size_t k = 0; k < m; k++) {
+            ExtQuery& q = qs[k];
+            q.K = (int32_t)K[s + k]; q.t_from = t_from[s + k]; q.dt = dt;
+            q.a = clockTraj(c, traj[s + k], t0[s + k]);
+        }
+        const int r = clockRun(c, qs.data(), m, a, uph_extent_kernel<256>, uph_extent_kernel<64>, out.data() + s, ms);
+        if (r != UPH_OK) return r;
+    }
+    return UPH_OK;
+}
+
+// the pairs (i < j) of n boxes the rule does not drop, sorted by (i, j): a sort by xmin and a sweep.  With the boxes in that order, the pairs of box p end at the
+// first q with xmin_q - xmax_p > r_p + r_max: rounding is monotone, so every later q has xmin_q - xmax_p > r_p + r_q too and is dropped by the rule itself.
+typedef std::pair<int32_t, int32_t> IdxPair;
+static int candidatePairs(int32_t n, const double* box, const double* radius, const char* who, std::vector<IdxPair>& pairs) {
+    double rmax = 0.0;
+    for (int32_t i = 0; i < n; i++) {
+        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError(std::string(who) + ": radius " + std::to_string(i) + " is negative or not finite"); return UPH_ERR_INVALID; }
+        for (int k = 0; k < 4; k++) if (std::isnan(box[4 * (size_t)i + k])) { setError(std::string(who) + ": box " + std::to_string(i) + " has a NaN bound"); return UPH_ERR_INVALID; }
+        rmax = std::max(rmax, radius[i]);
+    }
+    std::vector<int32_t> ord((size_t)n);
+    for (int32_t i = 0; i < n; i++) ord[(size_t)i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return box[4 * (size_t)x] < box[4 * (size_t)y] || (box[4 * (size_t)x] == box[4 * (size_t)y] && x < y); });
+    pairs.clear();
+    for (int32_t p = 0; p < n; p++) {
+        const int32_t i = ord[(size_t)p];
+        const double* bi = box + 4 * (size_t)i;
+        const double far = radius[i] + rmax;
+        for (int32_t q = p + 1; q < n; q++) {
+            const int32_t j = ord[(size_t)q];
+            const double* bj = box + 4 * (size_t)j;
+            if (bj[0] - bi[1] > far) break;
+            const double R = radius[i] + radius[j];
+            if (bi[0] - bj[1] > R || bj[0] - bi[1] > R || bi[2] - bj[3] > R || bj[2] - bi[3] > R) continue;
+            pairs.push_back(i < j ? IdxPair(i, j) : IdxPair(j, i));
+        }
+    }
+    std::sort(pairs.begin(), pairs.end());
+    return UPH_OK;
+}
+
 extern "C" {
 
 int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
@@ -834,6 +1094,143 @@ int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* r
 int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) {
     if (!c || !kernel_ms) { setError("uph_locate_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
     *kernel_ms = c->last_locate_ms;
+    return UPH_OK;
+}
+
+
+// ---- separation / extent / conflicts on a common clock (include/uneven_hip.h) -----------------------------------------------------------------------
+int uph_separation_times(double t_from, double t_to, double dt, int64_t* K) {
+    if (!K) { setError("uph_separation_times: bad arguments"); return UPH_ERR_INVALID; }
+    int64_t k = 0;
+    const int r = clockWindow(t_from, t_to, dt, k, "uph_separation_times");
+    if (r != UPH_OK) return r;
+    *K = k;
+    return UPH_OK;
+}
+
+int uph_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt, double* box, int32_t* counts) {
+    if (!c || n <= 0 || !traj || !t0 || !t_from || !t_to) { setError("uph_extent_batch: bad arguments"); return UPH_ERR_INVALID; }
+    int r = clockSide(c, n, traj, t0, "uph_extent_batch");
+    if (r != UPH_OK) return r;
+    std::vector<int64_t> K((size_t)n);
+    for (int32_t q = 0; q < n; q++) if ((r = clockWindow(t_from[q], t_to[q], dt, K[(size_t)q], "uph_extent_batch: query " + std::to_string(q))) != UPH_OK) return r;
+    std::vector<ExtOut> out;
+    double ms = 0.0;
+    r = extentRun(c, n, traj, t0, t_from, K.data(), dt, out, ms);
+    if (r != UPH_OK) return r;
+    c->last_sep_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const ExtOut& o = out[(size_t)q];
+        if (box) for (int k = 0; k < 4; k++) box[4 * (size_t)q + k] = o.box[k];
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_separation_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b, const double* t_from,
+                         const double* t_to, double dt, const double* radius, double* min_d2, double* min_t, double* first_t, double* last_t, int32_t* counts) {
+    const char* who = "uph_separation_batch";
+    if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError("uph_separation_batch: bad arguments"); return UPH_ERR_INVALID; }
+    if (!cb) cb = ca;
+    if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError("uph_separation_batch: the two contexts are on different devices"); return UPH_ERR_INVALID; }
+    int r = clockSide(ca, n, traj_a, t0_a, who);
+    if (r == UPH_OK) r = clockSide(cb, n, traj_b, t0_b, who);
+    if (r != UPH_OK) return r;
+    std::vector<SepQuery> qs((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError("uph_separation_batch: query " + std::to_string(q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+        int64_t K = 0;
+        if ((r = clockWindow(t_from[q], t_to[q], dt, K, "uph_separation_batch: query " + std::to_string(q))) != UPH_OK) return r;
+        SepQuery& k = qs[(size_t)q];
+        k.K = (int32_t)K; k.t_from = t_from[q]; k.dt = dt; k.R2 = radius[q] * radius[q];
+        k.a = clockTraj(ca, traj_a[q], t0_a[q]); k.b = clockTraj(cb, traj_b[q], t0_b[q]);
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
+    if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // what cb's stream still writes of its trajectories is there before the launch on ca's
+    std::vector<SepOut> out((size_t)n);
+    double ms = 0.0;
+    for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
+        r = clockRun(ca, qs.data() + s, std::min(CLOCK_CHUNK, (size_t)n - s), sepArgs(ca, cb), uph_separation_kernel<256>, uph_separation_kernel<64>, out.data() + s, ms);
+        if (r != UPH_OK) return r;
+    }
+    ca->last_sep_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const SepOut& o = out[(size_t)q];
+        if (min_d2) min_d2[q] = o.min_d2;
+        if (min_t) min_t[q] = o.min_t;
+        if (first_t) first_t[q] = o.first_t;
+        if (last_t) last_t[q] = o.last_t;
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_conflict_candidates(int32_t n, const double* box, const double* radius, int64_t cap, int32_t* pairs, int64_t* n_pairs) {
+    if (n < 0 || cap < 0 || (n > 0 && (!box || !radius)) || (cap > 0 && !pairs)) { setError("uph_conflict_candidates: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<IdxPair> found;
+    const int r = candidatePairs(n, box, radius, "uph_conflict_candidates", found);
+    if (r != UPH_OK) return r;
+    for (size_t k = 0; k < found.size() && (int64_t)k < cap; k++) { pairs[2 * k] = found[k].first; pairs[2 * k + 1] = found[k].second; }
+    if (n_pairs) *n_pairs = (int64_t)found.size();
+    return UPH_OK;
+}
+
+int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, double t_from, double t_to, double dt, int64_t cap,
+                        int32_t* pairs, double* rows, int32_t* below, int64_t* n_conflicts, int64_t* n_candidates) {
+    const char* who = "uph_conflicts_batch";
+    if (!c || n <= 0 || !traj || !t0 || !radius || cap < 0) { setError("uph_conflicts_batch: bad arguments"); return UPH_ERR_INVALID; }
+    int r = clockSide(c, n, traj, t0, who);
+    if (r != UPH_OK) return r;
+    for (int32_t i = 0; i < n; i++)
+        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError("uph_conflicts_batch: vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+    int64_t K = 0;
+    if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK) return r;
+    // extents on the device, candidates on the host
+    const std::vector<double> tf((size_t)n, t_from);
+    const std::vector<int64_t> Ks((size_t)n, K);
+    std::vector<ExtOut> ext;
+    double ms = 0.0;
+    r = extentRun(c, n, traj, t0, tf.data(), Ks.data(), dt, ext, ms);
+    if (r != UPH_OK) return r;
+    std::vector<double> box(4 * (size_t)n);
+    for (int32_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) box[4 * (size_t)i + k] = ext[(size_t)i].box[k];
+    std::vector<IdxPair> cand;
+    if ((r = candidatePairs(n, box.data(), radius, who, cand)) != UPH_OK) return r;
+    // separation of the candidates, a launch pair per CLOCK_CHUNK of them; the conflicts come out in the candidates' (i, j) order
+    std::vector<IdxPair> hit;
+    std::vector<SepOut> hit_rows;
+    std::vector<SepQuery> qs;
+    std::vector<SepOut> out;
+    for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
+        const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
+        qs.assign(m, SepQuery());
+        out.resize(m);
+        for (size_t k = 0; k < m; k++) {
+            const int32_t i = cand[s + k].first, j = cand[s + k].second;
+            const double R = radius[i] + radius[j];
+            SepQuery& q = qs[k];
+            q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.R2 = R * R;
+            q.a = clockTraj(c, traj[i], t0[i]); q.b = clockTraj(c, traj[j], t0[j]);
+        }
+        r = clockRun(c, qs.data(), m, sepArgs(c, c), uph_separation_kernel<256>, uph_separation_kernel<64>, out.data(), ms);
+        if (r != UPH_OK) return r;
+        for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
+    }
+    c->last_sep_ms = ms;
+    for (size_t k = 0; k < hit.size() && (int64_t)k < cap; k++) {
+        const SepOut& o = hit_rows[k];
+        if (pairs) { pairs[2 * k] = hit[k].first; pairs[2 * k + 1] = hit[k].second; }
+        if (rows) { rows[4 * k] = o.min_d2; rows[4 * k + 1] = o.min_t; rows[4 * k + 2] = o.first_t; rows[4 * k + 3] = o.last_t; }
+        if (below) below[k] = o.counts[1];
+    }
+    if (n_conflicts) *n_conflicts = (int64_t)hit.size();
+    if (n_candidates) *n_candidates = (int64_t)cand.size();
+    return UPH_OK;
+}
+
+int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_separation_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_sep_ms;
     return UPH_OK;
 }
 

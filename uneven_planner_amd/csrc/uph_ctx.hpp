@@ -109,9 +109,10 @@ struct uph_ctx {
     std::vector<double> end_bnd;           // [B][9] each problem's whole end boundary as uploaded: end_xy {P, V, A} (map coordinates), end_yaw (uph_refine_upload)
     DevBuf d_sw_q, d_sw_out;               // uph_replan_upload / uph_traj_states / uph_refine_upload: state queries and states (allocated at the first call)
     DevBuf d_refine_rec;                   // uph_refine_upload: staging records
-    DevBuf d_win_q, d_win_out;             // uph_check_batch / uph_locate_batch / uph_within_batch: query records and result rows (allocated at the first call)
+    DevBuf d_win_q, d_win_out;             // uph_check_batch / uph_locate_batch / uph_within_batch and the common-clock queries: query records and result rows (allocated at the first call)
     double last_check_ms = 0.0;            // uph_check_kernel of the last uph_check_batch (events on the context's stream)
     double last_locate_ms = 0.0;           // the kernel(s) of the last uph_locate_batch or uph_within_batch (events on the context's stream)
+    double last_sep_ms = 0.0;              // the kernels of the last uph_extent_batch, uph_separation_batch or uph_conflicts_batch (events on the context's stream)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;
