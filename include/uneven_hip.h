@@ -474,6 +474,11 @@ int uph_ctx_set_wps(uph_ctx* c, int32_t wps);
 int uph_ctx_set_sample_precision(uph_ctx* c, int32_t bits);
 int uph_ctx_set_rho(uph_ctx* c, double rho);
 int uph_ctx_get_rho(uph_ctx* c, double* rho);
+/* on = 1 (default): a line-search trial stops as soon as its rejection by the Armijo test is certain and no exit of the search can follow it --
+ * before its first constraint sample when a lower bound of the cost already exceeds the threshold, or before the adjoint once the cost is known.
+ * Results are the same bit for bit with on = 0 (every trial evaluated in full), except on a map with cells that make a sample non-finite: there a
+ * trial abandoned before that sample is bisected where the reference returns LBFGSERR_INVALID_FUNCVAL. */
+int uph_ctx_set_trial_abandon(uph_ctx* c, int32_t on);
 
 /* diagnostic: keep the first `cap` entries of each trajectory's cost trace of the next solves (cost after every accepted
  * L-BFGS iteration, -1 at the start of an ALM pass); cap = 0 switches it off.  uph_ctx_get_trace: out[B][cap]. */
@@ -511,6 +516,10 @@ int uph_batch_download(uph_ctx* c, uph_result* results);
 /* timing / work counters of the last uph_batch_solve: kernel ms (HIP events on the context's stream), total objective
  * evaluations, total constraint-sample evaluations, total L-BFGS iterations, bytes streamed from the L-BFGS history */
 int uph_batch_stats(uph_ctx* c, double* kernel_ms, int64_t* evals, int64_t* sample_evals, int64_t* lbfgs_iters, int64_t* hist_bytes);
+/* line-search trial counters of the last solve, summed over the batch: out5 = trials rejected by the Armijo test; of those, trials that an exit of the
+ * search could follow (always evaluated in full); trials abandoned before their first sample; sample chunks those did not run; adjoints not run.
+ * sample_evals of uph_batch_stats counts the samples actually evaluated. */
+int uph_batch_abandon_stats(uph_ctx* c, int64_t* out5);
 
 /* uph_batch_solve = two launches: reset+initScaling, then the ALM/L-BFGS solve kernel (uph_batch_stats reports the latter);
  * this returns the kernel milliseconds of the former */

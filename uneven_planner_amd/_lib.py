@@ -127,6 +127,7 @@ SYMBOLS = {
     "uph_ctx_set_sample_precision": (C.c_int, [_VP, _I32]),
     "uph_ctx_set_rho": (C.c_int, [_VP, C.c_double]),
     "uph_ctx_get_rho": (C.c_int, [_VP, DP]),
+    "uph_ctx_set_trial_abandon": (C.c_int, [_VP, _I32]),
     "uph_ctx_set_trace": (C.c_int, [_VP, _I32]),
     "uph_ctx_get_trace": (C.c_int, [_VP, DP]),
     "uph_optimize_batch": (C.c_int, [_VP, _I32, C.POINTER(Problem), C.POINTER(Result)]),
@@ -137,6 +138,7 @@ SYMBOLS = {
     "uph_batch_download": (C.c_int, [_VP, C.POINTER(Result)]),
     "uph_batch_stats": (C.c_int, [_VP, DP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "uph_batch_prepare_ms": (C.c_int, [_VP, DP]),
+    "uph_batch_abandon_stats": (C.c_int, [_VP, C.POINTER(_I64)]),
     "uph_batch_cycles": (C.c_int, [_VP, C.POINTER(C.c_longlong)]),
     "uph_build_id": (C.c_char_p, []),
     "uph_eval_batch": (C.c_int, [_VP, DP, DP, DP, _I32]),

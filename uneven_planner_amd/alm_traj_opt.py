@@ -467,6 +467,10 @@ class ALMTrajOpt:
     def set_rho(self, rho):
         _lib.check(self.L.uph_ctx_set_rho(self.h, float(rho)), "uph_ctx_set_rho")
 
+    def set_trial_abandon(self, on):
+        """line-search trials stop once their Armijo rejection is certain (default on; uph_ctx_set_trial_abandon): off evaluates every trial in full"""
+        _lib.check(self.L.uph_ctx_set_trial_abandon(self.h, 1 if on else 0), "uph_ctx_set_trial_abandon")
+
     def get_rho(self):
         r = C.c_double(0)
         _lib.check(self.L.uph_ctx_get_rho(self.h, C.byref(r)), "uph_ctx_get_rho")
@@ -501,7 +505,10 @@ class ALMTrajOpt:
         _lib.check(self.L.uph_batch_stats(self.h, C.byref(ms), *[C.byref(x) for x in v]), "uph_batch_stats")
         pm = C.c_double(0)
         _lib.check(self.L.uph_batch_prepare_ms(self.h, C.byref(pm)), "uph_batch_prepare_ms")
-        return dict(kernel_ms=ms.value, prepare_ms=pm.value, evals=v[0].value, sample_evals=v[1].value, lbfgs_iters=v[2].value, hist_bytes=v[3].value)
+        ab = (C.c_int64 * 5)()
+        _lib.check(self.L.uph_batch_abandon_stats(self.h, ab), "uph_batch_abandon_stats")
+        return dict(kernel_ms=ms.value, prepare_ms=pm.value, evals=v[0].value, sample_evals=v[1].value, lbfgs_iters=v[2].value, hist_bytes=v[3].value,
+                    ls_rejected=ab[0], ls_guarded=ab[1], ls_abandoned=ab[2], chunks_skipped=ab[3], adjoints_skipped=ab[4])
 
     def cycles(self):
         """(B,16) shader-clock cycles per phase of the last solve (generate, samples, scatter, adjoint, two-loop, scaling, total, ...)"""

@@ -44,6 +44,10 @@ namespace uph {
 #ifndef UPH_PHASE_MASK
 #define UPH_PHASE_MASK 15
 #endif
+// test scaffolding only (tests/emu): a host build may define this to look at the TrajState a solve leaves; empty in the library
+#ifndef UPH_STATE_PROBE
+#define UPH_STATE_PROBE(st) do { } while (0)
+#endif
 // columns of the knot operator fetched per batch in initScaling's row gathers (scalingGroup)
 #ifndef UPH_SCALING_WB
 #define UPH_SCALING_WB 8
@@ -75,6 +79,23 @@ struct Solver {
     // workgroup-shared arrays (LDS)
     int* rtag;
     double *x, *xp, *g, *gp, *d, *cxy, *cyaw, *Gxy, *Gyaw, *gamxy, *gamyaw, *bt, *rec, *wtab, *ttab, *pf, *hd;
+    // trial abandonment of the line search, kept in LDS so that it holds no register across the solve:
+    //   ab[0] = lb_dual = sum_s (lambda_s^2 + sum_q mu_qs^2) / (2 rho), the amount by which the samples' penalty costs can lie below zero; fixed within an
+    //           ALM pass (formDualBound / updateDualVars)
+    //   abn[0..3] (the ints of ab[1..2]) = counters (tally; read back by lane 0): Armijo rejections; of those, trials that an exit of the search could follow;
+    //           trials abandoned before the samples; adjoints skipped with the cost known
+    double* ab;
+    int* abn;
+    static constexpr int AB_DOUBLES = 4;
+    // counter k += 1 when `yes` (wave-uniform).  On the device every lane of wave 0 reads the word, adds one and writes the same value back: a scalar branch
+    // on two uniform values -- no atomic, and no branch on the lane index, whose exec-mask bookkeeping cost the solve kernel registers it does not have
+    UPH_HD void tally(int k, bool yes) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (yes && wg.wave == 0) abn[k] = abn[k] + 1;
+#else
+        if (yes) abn[k]++;
+#endif
+    }
     // HBM
     double *dual, *res, *scl, *hist;
     int hrow, hnp;       // history row length and padded vector length in doubles (uph_common.hpp histRowDoubles)
@@ -101,7 +122,7 @@ struct Solver {
         recd = recd < adj ? adj : recd;
         recd = recd < (size_t)mem ? (size_t)mem : recd;                  // ... and the two-loop's alphas
         const size_t td_ = (size_t)Nxy + K + 2;                          // sample-time tables; gamma lives in the same words after adjoint()
-        return (size_t)5 * n + (nvec < td_ ? td_ : nvec) + 2 * (12 * Nxy + 6 * Nyaw) + recd + (size_t)6 * (K + 1) + THOMAS_DOUBLES + MAX_PAST + 8 + 18;
+        return (size_t)5 * n + (nvec < td_ ? td_ : nvec) + 2 * (12 * Nxy + 6 * Nyaw) + recd + (size_t)6 * (K + 1) + THOMAS_DOUBLES + MAX_PAST + 8 + 18 + AB_DOUBLES;
     }
 
     UPH_HD Solver(WG& w, const GridDev& gr, const OptParams& p, const BatchDev& b, int bi, double* lds)
@@ -145,6 +166,8 @@ struct Solver {
         ttab = q; q += THOMAS_DOUBLES;                       // block-LU factors of the knot system
         pf = q; q += MAX_PAST + 8;
         hd = q; q += 18;                                     // head / tail states {P,V,A}: init_xy[6], end_xy[6], init_yaw[3], end_yaw[3]
+        ab = q; q += AB_DOUBLES;
+        abn = (int*)(ab + 1);
         dual = bd.dual + 7 * td.off_s; res = bd.res + 7 * td.off_s; scl = bd.scl + 7 * td.off_s;
         hist = bd.hist + td.off_hist; hrow = histRowDoubles(n); hnp = 64 * histNQ(n);
         Wr_xy = bd.ops[td.op_xy].Wr; Wr_yaw = bd.ops[td.op_yaw].Wr;
@@ -153,6 +176,7 @@ struct Solver {
         t_last_eval_end = 0;
         // read by every generate() / adjoint(): one copy per launch of the end states (descriptor) and the factor table (HBM) into LDS
         wg.pfor(18 + THOMAS_DOUBLES, [&](int t) {
+            if (t == 0) { ab[0] = 0.0; abn[0] = abn[1] = abn[2] = abn[3] = 0; }
             if (t < 18) hd[t] = t < 6 ? td.init_xy[t] : (t < 12 ? td.end_xy[t - 6] : (t < 15 ? td.init_yaw[t - 12] : td.end_yaw[t - 15]));
             else ttab[t - 18] = bd.thomas[t - 18];
         });
@@ -868,8 +892,23 @@ struct Solver {
 
     // ------------------------------------------------------------------ innerCallback (alm_traj_opt.cpp:280-347)
     // STEP: evaluates at x = xp + st d and leaves that point in xin (see generate).  last_gd = grad f . d afterwards.
+    // thr (line search only; infinity = evaluate in full): lineSearch has established that a trial whose cost exceeds thr is rejected by the Armijo test and
+    // that no exit of the search can follow that rejection.  Then nothing but the rejection itself is read from this evaluation -- the next trial
+    // overwrites x, g, f and last_gd -- and the evaluation stops at the first point where that is certain:
+    //   after expand():  L0 = jerk_cost + tau_cost - lb_dual is a lower bound of f.  The non-holonomic term h (lambda + rho h / 2) is >= -lambda^2 / (2 rho), every
+    //                    inequality term is >= -mu^2 / (2 rho) in both PHR branches (g (mu + rho g / 2) when active, -mu^2 / (2 rho) otherwise), and the terrain
+    //                    term omega sigma^2 is >= 0.  L0 > thr: no sample chunk, no scatter, no adjoint; L0 is returned in place of f (it fails the same tests).
+    //   after accEnd():  f itself is known.  f > thr: no adjoint.
+    // What an abandoned trial leaves behind is what generate() and expand() write: x = xp + st d, the coefficients, Txy / Tyaw, last_jerk (Q1).
+    // The rounding margins.  thr carries the one for its own terms (lineSearch).  Here: L0 and lb_dual are sums of a few terms (lb_dual of 7 S <= 2^14
+    // squares, blocked), the samples' cost sum of 8 S terms, each >= its bound up to a few ulps of the products it is made of: all of it is below
+    // 2^16 eps = 1.5e-11 of the magnitudes involved, and ABANDON_REL = 1e-9 of (|jerk_cost| + tau_cost + lb_dual) leaves two orders of magnitude.  A trial
+    // inside the margin is evaluated in full, which costs time and nothing else.  With f known, the sum below may be contracted differently from the
+    // returned one: two roundings, so ABANDON_REL_F = 1e-14 of the magnitudes of its terms.  Every comparison is false for NaN, and an infinite L0 or f
+    // never abandons: the search has to see it (LBFGSERR_INVALID_FUNCVAL).
+    static constexpr double ABANDON_REL = 1e-9, ABANDON_REL_F = 1e-14;
     template <bool STEP>
-    UPH_HD double eval(double* xin, double* gout, double st = 0.0) {
+    UPH_HD double eval(double* xin, double* gout, double st = 0.0, double thr = __builtin_huge_val()) {
         evals++;
         long long t0 = wg.clock();
         if (t_last_eval_end) cyc[5] += t0 - t_last_eval_end;      // from the end of the previous evaluation (or of the two-loop) to here
@@ -884,6 +923,20 @@ struct Solver {
         last_jerk = js[0];
         const double jerk_cost = wg.bcast(P.use_scaling ? js[0] * scale_fx * scale_trick_jerk : js[0] * scale_fx);
         evalConsts();
+        if (STEP && thr < __builtin_huge_val()) {
+            // (tau through a register of its own: this tau_cost must not merge with the one of the returned sum below, whose contraction stays what it was)
+            double tq = tau;
+            pinv(tq);
+            const double tau_lb = P.rho_T * expC2(tq) * scale_fx;
+            const double lbd = wg.bcast(ab[0]);
+            const double L0 = wg.bcast(jerk_cost + tau_lb - lbd);
+            const double mag = wg.bcast(fabs(jerk_cost) + fabs(tau_lb) + lbd);
+            if (L0 > thr + ABANDON_REL * mag && L0 < __builtin_huge_val() && ec_omega >= 0.0) {
+                tally(2, true);
+                t_last_eval_end = wg.clock();
+                return L0;
+            }
+        }
         // (cost, dT_xy, dT_yaw) of the samples: every lane keeps its partials across the chunks, ONE block reduction after the last chunk (wg.accEnd)
         double sm[3] = {0.0, 0.0, 0.0};
         wg.template accBegin<3>();
@@ -897,6 +950,18 @@ struct Solver {
         }
         wg.template accEnd<3>(sm);
         t1 = wg.clock();
+        if (STEP && thr < __builtin_huge_val()) {
+            double tq = tau;
+            pinv(tq);
+            const double tau_q = P.rho_T * expC2(tq) * scale_fx;
+            const double fq = wg.bcast(jerk_cost + sm[0] + tau_q);                               // f up to the contraction of this sum
+            const double mag = wg.bcast(fabs(jerk_cost) + fabs(sm[0]) + fabs(tau_q));
+            if (fq > thr + ABANDON_REL_F * mag && fq < __builtin_huge_val()) {
+                tally(3, true);
+                t_last_eval_end = wg.clock();
+                return fq;
+            }
+        }
         double chx = 0.0, chy = 0.0, gdw = 0.0;
         if (UPH_PHASE_MASK & 8) adjoint(chx, chy, gout, &gdw);
         t0 = wg.clock(); cyc[3] += t0 - t1;
@@ -1159,6 +1224,26 @@ struct Solver {
 
     // ------------------------------------------------------------------ line search (lbfgs.hpp:276-389)
     // dginit = gp . d is handed in: the caller gets it for free (from the two-loop's registers, or as -g.g when d = -g)
+    // the switch of the trial abandonment (uph_ctx_set_trial_abandon; 0 = on, so that a zeroed parameter block has it on), read from the parameter block in
+    // memory when a search starts instead of living in a scalar register across the solve.  The fp32 sample mode keeps every trial whole: its penalty
+    // terms meet their bounds only up to fp32 rounding.
+    UPH_HD bool abandonAllowed() const {
+        if (sizeof(SR) != sizeof(double)) return false;
+#if defined(__HIP_DEVICE_COMPILE__) && UPH_GRID_FROM_MEM
+        typedef const __attribute__((address_space(4))) int* pi_t;
+        pi_t pt = (pi_t)(const void*)&bd.params_mem->no_trial_abandon;
+        asm volatile("" : "+s"(pt));
+        return *pt == 0;
+#else
+        return P.no_trial_abandon == 0;
+#endif
+    }
+    // true: a trial at step stp, the (count + 1)-th of the search, that fails the Armijo test is followed by another trial -- none of the exits of
+    // lbfgs.hpp:349-378 fires (after the rejection nu = stp, brackt = true, the next step is 0.5 (mu + stp) <= stp).  Every comparison is written so that
+    // a NaN operand gives false.
+    static UPH_HD bool noExitAfterRejection(int count, double stp, double mu, double stpmin, double stpmax, int max_linesearch, double machine_prec) {
+        return count + 1 < max_linesearch && (stp - mu) >= machine_prec * stp && 0.5 * (mu + stp) >= stpmin && stp <= stpmax;
+    }
     UPH_HD int lineSearch(double& f, double& stp, double stpmin, double stpmax, double dginit) {
         int count = 0;
         bool brackt = false, touched = false;
@@ -1168,12 +1253,24 @@ struct Solver {
         const double finit = wg.bcast(f);                               // wave-uniform scalars of the search live in scalar registers
         const double dgtest = wg.bcast(P.f_dec_coeff * dginit);
         const double dstest = wg.bcast(P.s_curv_coeff * dginit);
+        const bool on = abandonAllowed();                               // (once per search: a scalar load and a division that no trial has to wait for)
+        const double pst = wg.bcast(P.past > 0 ? P.delta / P.past * (fabs(finit) + 1.0) : 0.0);
         while (true) {
-            f = eval<true>(x, g, stp);                                  // x = xp + stp d, f(x), g(x), last_gd = g . d
+            // may: should this trial fail the Armijo test, no exit of the search follows it (then its f, x, g would leave the solver: inner_cost, st.f, the
+            // iterate of the next ALM pass) -- not the trial cap (:349-353), not the interval width (:355-358; after the rejection nu = stp), not the minimum
+            // step (:365-368; the next step is 0.5 (mu + stp), below stp <= stpmax).  thr: the Armijo threshold, raised so that the `past` test above it
+            // (:327-330) is false as well for every cost beyond it.  The evaluation may stop as soon as its cost is certain to exceed it (eval).
+            // The threshold is formed a second time below and may be contracted differently there; ABANDON_REL of the magnitudes of its terms covers that
+            // (two roundings) many times over.
+            const double arm = stp * dgtest;
+            const bool may = on && noExitAfterRejection(count, stp, mu, stpmin, stpmax, P.max_linesearch, P.machine_prec);
+            const double thr = wg.bcast(may ? dmax(finit + arm, finit + pst) + ABANDON_REL * (fabs(finit) + fabs(arm) + pst) : __builtin_huge_val());
+            f = eval<true>(x, g, stp, thr);                             // x = xp + stp d, f(x), g(x), last_gd = g . d
             ++count;
             if (isinf(f) || isnan(f)) return LBFGSERR_INVALID_FUNCVAL;
             if (P.past > 0 && fabs(finit - f) / (fabs(finit) + 1.0) < P.delta / P.past) return count;   // :327-330
             if (f > finit + stp * dgtest) {
+                tally(0, on); tally(1, on && !may);   // (the counters describe the abandonment: all zero with the switch off)
                 nu = stp;
                 brackt = true;
             } else {
@@ -1305,14 +1402,34 @@ struct Solver {
     }
 
     // ------------------------------------------------------------------ ALM helpers (alm_traj_opt.h:132-151)
+    // lb_dual of the resident duals at the current rho (entry of optimize / resumeHook; updateDualVars keeps it up to date afterwards).
+    // A rho that is not positive has no bound: infinity, which no trial's L0 = ... - lb_dual can exceed.
+    UPH_HD void setDualBound(double sq) {
+        const double v = rho > 0.0 ? sq * (0.5 / rho) : __builtin_huge_val();
+        wg.one([&]() { ab[0] = v; });           // (read in eval, behind the barriers of generate / expand)
+    }
+    UPH_HD void formDualBound() {
+        double sq[1];
+        wg.template sum<1>(S, sq, [&](int s, double* acc) {
+            double a = 0.0;
+            for (int q = 0; q < 7; q++) { const double v = dual[q * S + s]; a += v * v; }
+            acc[0] += a;
+        });
+        setDualBound(sq[0]);
+    }
     UPH_HD void updateDualVars() {
         UPH_MARK("updateDualVars");
         const double r = rho;
-        wg.pfor(S, [&](int s) {
+        double sq[1];
+        wg.template sum<1>(S, sq, [&](int s, double* acc) {
             dual[s] += r * res[s];
             for (int q = 1; q < 7; q++) dual[q * S + s] = dmax(dual[q * S + s] + r * res[q * S + s], 0.0);
+            double a = 0.0;
+            for (int q = 0; q < 7; q++) { const double v = dual[q * S + s]; a += v * v; }
+            acc[0] += a;
         });
         rho = wg.bcast(dmin((1 + P.gamma) * rho, P.beta));
+        setDualBound(sq[0]);
     }
     UPH_HD bool judgeConvergence() {
         const double r = rho;
@@ -1328,11 +1445,14 @@ struct Solver {
         wg.pfor(1, [&](int) {
             st.T_xy = Txy; st.T_yaw = Tyaw; st.jerk_cost = last_jerk; st.scale_fx = scale_fx; st.rho = rho;
             st.evals = evals; st.hist_reads = hist_reads;
+            st.ls_rejected = abn[0]; st.ls_guarded = abn[1]; st.ls_abandoned = abn[2]; st.adjoints_skipped = abn[3] + abn[2];
+            st.chunks_skipped = abn[2] * ((S + CHS - 1) / CHS);
 #ifdef UPH_TL_PROF
             for (int q = 0; q < 6; q++) cyc[8 + q] = wg.tl[q];                  // two-loop profile of the device workgroup object
 #endif
             for (int q = 0; q < 16; q++) st.cyc[q] = cyc[q];
         });
+        UPH_STATE_PROBE(st);
 #ifdef UPH_BAR_PROF
         wg.sync();
         wg.dumpBar(&st.cyc[8]);
@@ -1364,6 +1484,7 @@ struct Solver {
         rho = wg.bcast(st.rho);
         scale_fx = wg.bcast(st.scale_fx);
         wg.pfor(n, [&](int t) { x[t] = gx0[t]; });
+        formDualBound();
         const long long tstart = wg.clock();
         cyc[14] = wg.realtime();                                         // residency timeline of the launch (tools/phase_breakdown.py): 100 MHz stamps
         int ret_code = 0, iter = 0, total_k = 0, last_ret = 0;
@@ -1401,6 +1522,7 @@ struct Solver {
         double* gd = bd.rs_d + td.off_x;
         double* rs = bd.rs + (size_t)bidx * 24;
         rho = wg.bcast(st.rho); scale_fx = wg.bcast(st.scale_fx);
+        formDualBound();
         wg.pfor(n + MAX_PAST, [&](int t) { if (t < n) { x[t] = gx[t]; g[t] = gg[t]; d[t] = gd[t]; } else pf[t - n] = rs[8 + t - n]; });
         ResumeIO io;
         io.step = wg.bcast(rs[0]); io.fx = wg.bcast(rs[1]);

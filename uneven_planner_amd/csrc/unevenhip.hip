@@ -987,6 +987,7 @@ int uph_ctx_create(uph_map* m, const uph_opt_params* p, uph_ctx** out) {
     P.inner_max_iter = (int)p->inner_max_iter; P.mem_size = p->mem_size; P.past = p->past; P.int_K = p->int_K;
     // lbfgs.hpp:76-128 defaults, not overridden at alm_traj_opt.cpp:219-225
     P.max_linesearch = 64; P.max_step = 1.0e20; P.f_dec_coeff = 1.0e-4; P.s_curv_coeff = 0.9; P.cautious_factor = 1.0e-6; P.machine_prec = 1.0e-16;
+    P.no_trial_abandon = 0; P.pad_ = 0;
     finishParams(P);
     c->rho = p->rho;
     {
@@ -1045,6 +1046,8 @@ int uph_ctx_set_sample_precision(uph_ctx* c, int32_t bits) {
     return UPH_OK;
 }
 int uph_ctx_set_rho(uph_ctx* c, double rho) { if (!c) return UPH_ERR_INVALID; c->rho = rho; return UPH_OK; }
+// line-search trials whose Armijo rejection is certain stop early (Solver::eval; default on); takes effect at the next launch (the parameter block is uploaded per launch)
+int uph_ctx_set_trial_abandon(uph_ctx* c, int32_t on) { if (!c || (on != 0 && on != 1)) return UPH_ERR_INVALID; c->P.no_trial_abandon = on ? 0 : 1; return UPH_OK; }
 int uph_ctx_get_rho(uph_ctx* c, double* rho) { if (!c || !rho) return UPH_ERR_INVALID; *rho = c->rho; return UPH_OK; }
 
 // diagnostic: keep the first `cap` entries of every trajectory's cost trace (0 = off); read back with uph_ctx_get_trace
@@ -1644,11 +1647,14 @@ int uph_batch_wait(uph_ctx* c) {
     int r = refreshStates(c);
     if (r != UPH_OK) return r;
     c->last_evals = c->last_sample_evals = c->last_iters = c->last_hist_bytes = 0;
+    for (int q = 0; q < 5; q++) c->last_abandon[q] = 0;
     for (int b = 0; b < c->B; b++) {
         if (c->rejected[b]) continue;
         const TrajState& s = c->state_host[b];
         c->last_evals += s.evals;
-        c->last_sample_evals += (int64_t)s.evals * c->desc[b].S;
+        c->last_sample_evals += (int64_t)(s.evals - s.ls_abandoned) * c->desc[b].S;      // samples actually evaluated: an abandoned trial runs none
+        c->last_abandon[0] += s.ls_rejected; c->last_abandon[1] += s.ls_guarded; c->last_abandon[2] += s.ls_abandoned;
+        c->last_abandon[3] += s.chunks_skipped; c->last_abandon[4] += s.adjoints_skipped;
         c->last_iters += s.lbfgs_iters;
         c->last_hist_bytes += s.hist_reads * 8;
     }
@@ -1676,6 +1682,12 @@ int uph_batch_stats(uph_ctx* c, double* kernel_ms, int64_t* evals, int64_t* samp
     if (sample_evals) *sample_evals = c->last_sample_evals;
     if (lbfgs_iters) *lbfgs_iters = c->last_iters;
     if (hist_bytes) *hist_bytes = c->last_hist_bytes;
+    return UPH_OK;
+}
+
+int uph_batch_abandon_stats(uph_ctx* c, int64_t* out5) {
+    if (!c || !out5) return UPH_ERR_INVALID;
+    for (int q = 0; q < 5; q++) out5[q] = c->last_abandon[q];
     return UPH_OK;
 }
 
@@ -1956,11 +1968,14 @@ int uph_report_batch(uph_ctx* c, double* out7) {
 // ---- test hooks of the teacher-forced late-state tests -------------------------------------------------------------------------
 static void collectSolveStats(uph_ctx* c) {
     c->last_evals = c->last_sample_evals = c->last_iters = c->last_hist_bytes = 0;
+    for (int q = 0; q < 5; q++) c->last_abandon[q] = 0;
     for (int b = 0; b < c->B; b++) {
         if (c->rejected[b]) continue;
         const TrajState& s = c->state_host[b];
         c->last_evals += s.evals;
-        c->last_sample_evals += (int64_t)s.evals * c->desc[b].S;
+        c->last_sample_evals += (int64_t)(s.evals - s.ls_abandoned) * c->desc[b].S;      // samples actually evaluated: an abandoned trial runs none
+        c->last_abandon[0] += s.ls_rejected; c->last_abandon[1] += s.ls_guarded; c->last_abandon[2] += s.ls_abandoned;
+        c->last_abandon[3] += s.chunks_skipped; c->last_abandon[4] += s.adjoints_skipped;
         c->last_iters += s.lbfgs_iters;
         c->last_hist_bytes += s.hist_reads * 8;
     }

@@ -95,6 +95,7 @@ struct OptParams {
     int max_linesearch;
     double max_step, f_dec_coeff, s_curv_coeff, cautious_factor, machine_prec;
     double max_vel2, max_acc_lon2, max_acc_lat2, max_kap2;      // squares of the limits (host-computed: scalar operands on the device)
+    int no_trial_abandon = 0, pad_ = 0;   // != 0: every line-search trial is evaluated in full (uph_ctx_set_trial_abandon(c, 0); Solver::abandonAllowed)
 };
 
 // derived fields, same expressions the device code used to evaluate per sample
@@ -156,6 +157,9 @@ struct TrajState {
     int ret_code, alm_iters, lbfgs_iters, evals, last_lbfgs_ret, pad;
     long long hist_reads;       // doubles read from the L-BFGS history (two-loop), for the roofline accounting
     long long cyc[16];          // shader-clock cycles per phase: 0 generate, 1 samples, 2 scatter, 3 adjoint, 4 two-loop, 5 scaling, 6 total; 8.. sub-steps (microbench)
+    // line-search trials of the solve (Solver::eval / lineSearch): rejected by the Armijo test; of those, trials that an exit of the search could follow
+    // (never abandoned); trials abandoned before their first sample; the sample chunks those did not run; adjoints not run (known cost, rejected)
+    int ls_rejected, ls_guarded, ls_abandoned, chunks_skipped, adjoints_skipped, pad2;
 };
 
 struct BatchDev {

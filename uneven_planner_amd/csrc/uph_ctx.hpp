@@ -120,6 +120,7 @@ struct uph_ctx {
     // stats of the last solve
     double last_ms = 0.0, last_prepare_ms = 0.0;
     int64_t last_evals = 0, last_sample_evals = 0, last_iters = 0, last_hist_bytes = 0;
+    int64_t last_abandon[5] = {0, 0, 0, 0, 0};   // line-search trial counters of the last solve (uph_batch_abandon_stats): rejected, guarded, abandoned, chunks skipped, adjoints skipped
 };
 
 #define HIPCHK(call)                                                                               \
