@@ -245,6 +245,17 @@ double orc_alm_constrain(void* h, const double* x, int n, double* gdCxy, double*
     std::memcpy(gdCyaw, a3.data(), 8 * a3.size()); std::memcpy(gdTyaw, a4.data(), 8 * a4.size());
     return cost;
 }
+// calConstrainCostGrad on the trajectory the object HOLDS (orc_alm_set_coeffs, or the last evaluation): nothing is generated, so the
+// coefficients and the piece durations are exactly the handed-in ones -- the counterpart of a penalty call on resident coefficients
+double orc_alm_constrain_resident(void* h, double* gdCxy, double* gdTxy, double* gdCyaw, double* gdTyaw) {
+    AlmTrajOpt& a = ((OrcAlm*)h)->opt;
+    double cost;
+    Vec a1, a2, a3, a4;
+    a.calConstrainCostGrad(cost, a1, a2, a3, a4);
+    std::memcpy(gdCxy, a1.data(), 8 * a1.size()); std::memcpy(gdTxy, a2.data(), 8 * a2.size());
+    std::memcpy(gdCyaw, a3.data(), 8 * a3.size()); std::memcpy(gdTyaw, a4.data(), 8 * a4.size());
+    return cost;
+}
 void orc_alm_get_coeffs(void* h, double* c_xy, double* c_yaw, double* T_xy, double* T_yaw, double* jerk_cost) {
     AlmTrajOpt& a = ((OrcAlm*)h)->opt;
     if (c_xy) std::memcpy(c_xy, a.minco.pos.c.data(), 8 * a.minco.pos.c.size());

@@ -77,6 +77,8 @@ def lib():
         L.orc_alm_constrain.restype = d
         L.orc_alm_constrain.argtypes = [vp, dp, i, dp, dp, dp, dp]
         L.orc_alm_get_coeffs.argtypes = [vp, dp, dp, dp, dp, dp]
+        L.orc_alm_constrain_resident.restype = d
+        L.orc_alm_constrain_resident.argtypes = [vp, dp, dp, dp, dp]
         L.orc_alm_optimize.restype = i
         L.orc_alm_optimize.argtypes = [vp, dp, dp, dp, i, dp, dp, dp, i, d, dp, dp]
         L.orc_alm_report.argtypes = [vp, dp]
@@ -351,6 +353,13 @@ class OracleALM:
         a1, a2 = np.zeros((6 * self.piece_xy, 2)), np.zeros(self.piece_xy)
         a3, a4 = np.zeros(6 * self.piece_yaw), np.zeros(self.piece_yaw)
         c = self.L.orc_alm_constrain(self.h, _dp(x), x.size, _dp(a1), _dp(a2), _dp(a3), _dp(a4))
+        return c, a1, a2, a3, a4
+
+    def constrain_resident(self):
+        """calConstrainCostGrad on the trajectory the object holds (after set_coeffs: exactly those coefficients and durations; nothing is generated)"""
+        a1, a2 = np.zeros((6 * self.piece_xy, 2)), np.zeros(self.piece_xy)
+        a3, a4 = np.zeros(6 * self.piece_yaw), np.zeros(self.piece_yaw)
+        c = self.L.orc_alm_constrain_resident(self.h, _dp(a1), _dp(a2), _dp(a3), _dp(a4))
         return c, a1, a2, a3, a4
 
     def coeffs(self):
