@@ -66,6 +66,22 @@ namespace uph {
 #define UPH_SC_WHI 3
 #endif
 
+// Placement of the wave-uniform scalar chains of an evaluation.  1: the sample-time tables and the quotients that depend on tau
+// alone (1 / Txy, 1 / Tyaw, Txy / K, expC2(tau), getTtoTauGrad(tau)) are formed ASIDE the knot solve of generate() -- on the wave that does not carry it --
+// and published through LDS words (Solver::up).  0: every lane forms them where they are used, as before.  The same operations on the same operands
+// either way, so the results are bit for bit the same.  A compile-time switch only (tools/build_variants.sh): section 7m shows what per-trial code costs.
+#ifndef UPH_ASIDE_PREP
+#define UPH_ASIDE_PREP 1
+#endif
+// f(t) for t = 0 .. n - 1 (n <= 64) aside the knot solve that follows (wg.thomas on lenW yaw / lenX position knots): no barrier of its own, what f writes to
+// LDS is read after the barrier that ends the solve.  Any workgroup object can run it as a plain parallel loop before the solve; the device's overload
+// (unevenhip.hip) gives it to the wave that does not carry the solve, where there is one.
+template <class WG, class F>
+UPH_HD void asideKnotSolve(WG& wg, int lenW, int lenX, int n, F f) {
+    (void)lenW; (void)lenX;
+    wg.pfor(n, f);
+}
+
 // SR = real type of the sample-phase arithmetic: double (the reference's, default) or f32r (fp32 sample mode, uph_common.hpp)
 template <class WG, class SR = double>
 struct Solver {
@@ -87,6 +103,10 @@ struct Solver {
     double* ab;
     int* abn;
     static constexpr int AB_DOUBLES = 4;
+    // wave-uniform values of one evaluation published through LDS (UPH_ASIDE_PREP): written aside the knot solve of generate(), read with wg.bcast
+    // behind the barrier that ends it:   up[0] = 1 / Txy   up[1] = 1 / Tyaw   up[2] = Txy / K   up[3] = expC2(tau)   up[4] = getTtoTauGrad(tau)
+    double* up;
+    static constexpr int UP_DOUBLES = 6;
     // counter k += 1 when `yes` (wave-uniform).  On the device every lane of wave 0 reads the word, adds one and writes the same value back: a scalar branch
     // on two uniform values -- no atomic, and no branch on the lane index, whose exec-mask bookkeeping cost the solve kernel registers it does not have
     UPH_HD void tally(int k, bool yes) {
@@ -122,7 +142,7 @@ struct Solver {
         recd = recd < adj ? adj : recd;
         recd = recd < (size_t)mem ? (size_t)mem : recd;                  // ... and the two-loop's alphas
         const size_t td_ = (size_t)Nxy + K + 2;                          // sample-time tables; gamma lives in the same words after adjoint()
-        return (size_t)5 * n + (nvec < td_ ? td_ : nvec) + 2 * (12 * Nxy + 6 * Nyaw) + recd + (size_t)6 * (K + 1) + THOMAS_DOUBLES + MAX_PAST + 8 + 18 + AB_DOUBLES;
+        return (size_t)5 * n + (nvec < td_ ? td_ : nvec) + 2 * (12 * Nxy + 6 * Nyaw) + recd + (size_t)6 * (K + 1) + THOMAS_DOUBLES + MAX_PAST + 8 + 18 + AB_DOUBLES + UP_DOUBLES;
     }
 
     UPH_HD Solver(WG& w, const GridDev& gr, const OptParams& p, const BatchDev& b, int bi, double* lds)
@@ -149,7 +169,7 @@ struct Solver {
         x = q; q += n; g = q; q += n; d = q; q += n;
         xp = q; q += n; gp = q; q += n;                      // iterate / gradient the line search starts from
         const int nvec = 2 * (Nxy + 5) + (Nyaw + 5);
-        bt = q;                                              // sample-time tables (fillTimes), alive from expand() to adjoint()
+        bt = q;                                              // sample-time tables (fillTimes), alive from generate() / expand() to adjoint()
         gamxy = q; gamyaw = q + 2 * (Nxy + 5);               // gamma (adjoint output) takes the same words afterwards
         q += nvec < Nxy + K + 2 ? Nxy + K + 2 : nvec;
         cxy = q; q += 12 * Nxy; cyaw = q; q += 6 * Nyaw;
@@ -168,6 +188,7 @@ struct Solver {
         hd = q; q += 18;                                     // head / tail states {P,V,A}: init_xy[6], end_xy[6], init_yaw[3], end_yaw[3]
         ab = q; q += AB_DOUBLES;
         abn = (int*)(ab + 1);
+        up = q; q += UP_DOUBLES;
         dual = bd.dual + 7 * td.off_s; res = bd.res + 7 * td.off_s; scl = bd.scl + 7 * td.off_s;
         hist = bd.hist + td.off_hist; hrow = histRowDoubles(n); hnp = 64 * histNQ(n);
         Wr_xy = bd.ops[td.op_xy].Wr; Wr_yaw = bd.ops[td.op_yaw].Wr;
@@ -232,7 +253,9 @@ struct Solver {
         const double Ttot = expC2(tau_);
         Txy = wg.bcast(Ttot / (double)Nxy);       // calTfromTau, alm_traj_opt.h:257-261 (wave-uniform: kept in scalar registers)
         Tyaw = wg.bcast(Ttot / (double)Nyaw);
+#if !(UPH_ASIDE_PREP)
         ec_iTyaw = wg.bcast(1.0 / Tyaw);
+#endif
         const double Tx = Txy, Ty = Tyaw;
         double* zxy = rec;                                   // knot j at knotOffJ(j, ks): padded per lane block of the solve (uph_common.hpp)
         double* zyaw = rec + knotBufDoubles(Nxy + 1, 4);
@@ -263,23 +286,50 @@ struct Solver {
             }
         });
         const long long tsub1 = wg.clock();
+#if UPH_ASIDE_PREP
+        // Aside the solve: everything of this evaluation that depends on tau alone.  Two lanes run the SAME instruction stream (no divergence): the five
+        // quotients as independent sequences side by side, then the two sample-time tables of fillTimes() in one loop -- lane 0 the piece bases
+        // (base += Txy), lane 1 the in-piece times (s1 += step): the reference's accumulations, Q2.  The tables alias gamma, which is dead here: eval()
+        // copies the gradient out of adjoint()'s pass itself, initScaling reads gamma before its explicit refill.
+        asideKnotSolve(wg, Nyaw - 1, Nxy - 1, 2, [&](int t) {
+            const double itx = 1.0 / Tx, ity = 1.0 / Ty, step = Tx / K, dtau = getTtoTauGrad(tau_);
+            if (t == 0) { up[0] = itx; up[1] = ity; up[2] = step; up[3] = Ttot; up[4] = dtau; }
+            const double add = t == 0 ? Tx : step;
+            double* tab = t == 0 ? bt : bt + Nxy + 1;
+            const int lim = t == 0 ? Nxy : K, top = Nxy > K ? Nxy : K;
+            double a = 0.0;
+            for (int i = 0; i <= top; i++) {
+                if (i <= lim) tab[i] = a;
+                a += add;
+            }
+        });
+#endif
         wg.thomas(ttab, false, zyaw + knotOffJ(1, 2), Nyaw - 1, zxy + knotOffJ(1, 4), Nxy - 1);
+#if UPH_ASIDE_PREP
+        ec_iTyaw = wg.bcast(up[1]);
+#endif
         if (sub_t) { sub_t[0] += tsub1 - tsub_start; sub_t[1] += wg.clock() - tsub1; }
     }
 
     // ------------------------------------------------------------------ MINCO generate, part 2, fused with the jerk terms
     // One lane per (piece, dimension): quintic Hermite expansion from the piece's end states (normalised time), c_k = c~_k T^-k,
     // the piece's share of the jerk energy and of its direct T-derivative (se2traj.hpp:697-710, 736-745), and G <- jerk_w dJ/dc
-    // (:722-734) -- the coefficients are still in registers.  Two more lanes fill the sample-time tables.
+    // (:722-734) -- the coefficients are still in registers.  (With UPH_ASIDE_PREP = 0 two more tasks of the pass fill the sample-time tables; otherwise
+    // generate() has filled them aside its knot solve.)
     // out[0] = energy_xy + energy_yaw, out[1] = sum_i gdT_xy(i), out[2] = sum_i gdT_yaw(i)   (unscaled)
     UPH_HD void expand(const double* xin, double jerk_w, double out[3]) {
         UPH_MARK("expand");
         const long long t0 = wg.clock();
+#if UPH_ASIDE_PREP
+        const double Tx = Txy, Ty = Tyaw, itx = wg.bcast(up[0]), ity = ec_iTyaw;     // (and the tables are filled: generate())
+        const int np = 2 * Nxy + Nyaw, ntask = np;
+#else
         const double Tx = Txy, Ty = Tyaw, itx = wg.bcast(1.0 / Tx), ity = wg.bcast(1.0 / Ty);
+        const int np = 2 * Nxy + Nyaw, ntask = np + 2;
+#endif
         const double* zxy = rec;
         const double* zyaw = rec + knotBufDoubles(Nxy + 1, 4);
-        const int np = 2 * Nxy + Nyaw;
-        wg.template sum<3>(np + 2, out, [&](int t, double* acc) {
+        wg.template sum<3>(ntask, out, [&](int t, double* acc) {
             if (t >= np) { fillTimes(t - np); return; }
             double p0, p1, v0, a0, v1, a1, it_, T1;
             double *oc, *og;
@@ -664,7 +714,7 @@ struct Solver {
     // sample-time tables of calConstrainCostGrad, built by the reference's own accumulations so that the roundings agree:
     //   bt[i] = base_time of piece i       (base += T1(i), alm_traj_opt.cpp:709,989)       i = 0..Nxy
     //   bt[Nxy+1+j] = in-piece time s1     (s1 += step, :713-714,987; Q2)                  j = 0..K
-    // Alive from expand() until adjoint() writes gamma into the same words.
+    // Alive from generate()'s aside (UPH_ASIDE_PREP = 0: from expand()) until adjoint() writes gamma into the same words.
     UPH_HD void fillTimes(int u) {
         if (u == 0) {
             double base = 0.0;
@@ -788,7 +838,11 @@ struct Solver {
     // receives sum_{t >= 1} gout[t] d[t] (the caller adds the tau entry): g . d for the line search without a pass of its own.
     UPH_HD void adjoint(double& chain_xy, double& chain_yaw, double* gout = nullptr, double* gd_out = nullptr) {
         UPH_MARK("adjoint");
+#if UPH_ASIDE_PREP
+        const double Tx = Txy, Ty = Tyaw, itx = wg.bcast(up[0]), ity = ec_iTyaw;
+#else
         const double Tx = Txy, Ty = Tyaw, itx = wg.bcast(1.0 / Txy), ity = wg.bcast(1.0 / Tyaw);
+#endif
         const long long ta0 = wg.clock();
         const int nbx = Nxy + 5, nby = Nyaw + 5;
         const int nvec = 2 * nbx + nby;
@@ -874,9 +928,17 @@ struct Solver {
         chain_yaw = ch[1] + hh[1];
     }
 
-    UPH_HD void evalConsts() {
+    // step = Txy / K (alm_traj_opt.cpp:713): published by generate(), or formed by the caller where no generate() ran (penaltyOnly)
+    UPH_HD double evalStep() {
+#if UPH_ASIDE_PREP
+        return wg.bcast(up[2]);
+#else
+        return Txy / K;
+#endif
+    }
+    UPH_HD void evalConsts(double step) {
         ec_irho = wg.bcast(1.0 / rho);
-        ec_step = wg.bcast(Txy / K);                                    // alm_traj_opt.cpp:713
+        ec_step = wg.bcast(step);
         ec_invK = wg.bcast(1.0 / K);
         ec_omega = wg.bcast(P.rho_ter * ec_step * scale_fx);
         ec_omega_h = wg.bcast(0.5 * P.rho_ter * ec_step * scale_fx);
@@ -922,12 +984,18 @@ struct Solver {
         long long t1 = wg.clock(); cyc[0] += t1 - t0;
         last_jerk = js[0];
         const double jerk_cost = wg.bcast(P.use_scaling ? js[0] * scale_fx * scale_trick_jerk : js[0] * scale_fx);
-        evalConsts();
+        evalConsts(evalStep());
         if (STEP && thr < __builtin_huge_val()) {
             // (tau through a register of its own: this tau_cost must not merge with the one of the returned sum below, whose contraction stays what it was)
+#if UPH_ASIDE_PREP
+            double eq = wg.bcast(up[3]);            // expC2(tau), formed in generate()
+            pinv(eq);
+            const double tau_lb = P.rho_T * eq * scale_fx;
+#else
             double tq = tau;
             pinv(tq);
             const double tau_lb = P.rho_T * expC2(tq) * scale_fx;
+#endif
             const double lbd = wg.bcast(ab[0]);
             const double L0 = wg.bcast(jerk_cost + tau_lb - lbd);
             const double mag = wg.bcast(fabs(jerk_cost) + fabs(tau_lb) + lbd);
@@ -951,9 +1019,15 @@ struct Solver {
         wg.template accEnd<3>(sm);
         t1 = wg.clock();
         if (STEP && thr < __builtin_huge_val()) {
+#if UPH_ASIDE_PREP
+            double eq = wg.bcast(up[3]);
+            pinv(eq);
+            const double tau_q = P.rho_T * eq * scale_fx;
+#else
             double tq = tau;
             pinv(tq);
             const double tau_q = P.rho_T * expC2(tq) * scale_fx;
+#endif
             const double fq = wg.bcast(jerk_cost + sm[0] + tau_q);                               // f up to the contraction of this sum
             const double mag = wg.bcast(fabs(jerk_cost) + fabs(sm[0]) + fabs(tau_q));
             if (fq > thr + ABANDON_REL_F * mag && fq < __builtin_huge_val()) {
@@ -968,10 +1042,16 @@ struct Solver {
         const double gTx = js[1] * jw + sm[1] + chx;       // sum_i gdTxy(i) after calGradCTtoQT
         const double gTy = js[2] * jw + sm[2] + chy;
         const double grad_Tsum = P.rho_T * scale_fx + gTx / Nxy + gTy / Nyaw;             // :341-344
+#if UPH_ASIDE_PREP
+        const double g0 = wg.bcast(grad_Tsum * wg.bcast(up[4]));                          // getTtoTauGrad(tau) and expC2(tau): formed in generate()
+        const double etau = wg.bcast(up[3]);
+#else
         const double g0 = wg.bcast(grad_Tsum * getTtoTauGrad(tau));
+        const double etau = expC2(tau);
+#endif
         wg.pfor(1, [&](int) { gout[0] = g0; });
         last_gd = wg.bcast(gdw + g0 * d[0]);
-        const double tau_cost = P.rho_T * expC2(tau) * scale_fx;                          // :340
+        const double tau_cost = P.rho_T * etau * scale_fx;                                // :340
         t_last_eval_end = wg.clock();
         return wg.bcast(jerk_cost + sm[0] + tau_cost);                                    // :346
     }
@@ -1561,7 +1641,7 @@ struct Solver {
         a[1] = wg.clock();
         for (int r = 0; r < reps; r++) { expand(x, 1.0, js); acc += js[0]; }
         a[2] = wg.clock();
-        for (int r = 0; r < reps; r++) evalConsts();
+        for (int r = 0; r < reps; r++) evalConsts(evalStep());
         a[3] = wg.clock();
         for (int r = 0; r < reps; r++) { wg.template sum<3>(cnt, part, [&](int t, double* ac) { sampleEval<false>(t, t, ac); }); acc += part[0]; }
         a[4] = wg.clock();
@@ -1629,7 +1709,7 @@ struct Solver {
         double sm[3] = {0.0, 0.0, 0.0};
         for (int r = 0; r < repeat; r++) {
             wg.pfor(nc + 2, [&](int t) { if (t < 12 * Nxy) Gxy[t] = 0.0; else if (t < nc) Gyaw[t - 12 * Nxy] = 0.0; else fillTimes(t - nc); });
-            evalConsts();
+            evalConsts(Txy / K);                        // (no generate() ran: the step is formed here)
             wg.template accBegin<3>();
             for (int s0 = 0; s0 < S; s0 += CHS) {
                 const int cnt = S - s0 < CHS ? S - s0 : CHS;

@@ -531,6 +531,19 @@ struct DevWG {
         __builtin_amdgcn_s_setprio(0);
         bar(2);
     }
+    // f(lane) for lane < n (n <= 64) on ONE wave, aside the knot solve that the caller starts next with the same chain lengths: no barrier here, the
+    // LDS words f writes are read after the barrier that ends the solve (bar(2) of thomasT).  The wave is the one the solve leaves idle -- wave 1 when all
+    // three chains ride on wave 0 (up to 64 position / 128 yaw pieces: thomasT's `packed`), wave 2 of the 256- and 512-lane forms otherwise.  Where every
+    // wave carries a chain (one wave per trajectory; longer trajectories at 128 lanes) wave 0 runs f before its solve: slower, never wrong.
+    template <class F>
+    __device__ __forceinline__ void aside(int lenW, int lenX, int n, F f) {
+        const bool packed = uni(lenW) <= 32 * UPH_THOMAS_KPL - 1 && uni(lenX) <= 16 * UPH_THOMAS_KPL - 1;
+        const int aw = NW >= 2 && packed ? 1 : (NW >= 3 ? 2 : 0);
+        if (wave == aw) {
+            const int l = flane();
+            if (l < n) f(l);
+        }
+    }
     __device__ __forceinline__ void thomas(const double* tab, bool adj, double* bw, int lenW, double* bx, int lenX) {
         if (adj) thomasT<true>(tab, bw, lenW, bx, lenX);
         else thomasT<false>(tab, bw, lenW, bx, lenX);
@@ -567,6 +580,10 @@ struct DevWG {
         return uni(t);
     }
 };
+
+// Solver's asideKnotSolve (solver_program.hpp) on the device: the idle wave's lanes instead of a parallel loop with a barrier
+template <int NT, class F>
+__device__ __forceinline__ void asideKnotSolve(DevWG<NT>& wg, int lenW, int lenX, int n, F f) { wg.aside(lenW, lenX, n, f); }
 
 // MODE 0: one (or `repeat`) objective evaluation(s)   1: reset + initScaling   2: ALM / L-BFGS solve (repeat > 0: at most that many ALM passes)
 // 3: post-solve report   4: initScaling only (test hook, keeps the resident duals)   5: phase microbenchmark
