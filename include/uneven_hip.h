@@ -55,6 +55,7 @@
  *   uph_within_batch        <- which resident trajectories enter a rect of the map (a changed region) and when
  *   uph_separation_batch    <- how close two resident trajectories come at the same moment of a clock they share (each starts at its own t0 on it)
  *   uph_conflicts_batch     <- the pairs of a fleet on one map that come closer than their radii allow: extents, a host broad phase, separation
+ *   uph_delays_batch        <- the smallest start delay that clears each vehicle of a fleet against all vehicles ahead of it in priority order
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -693,6 +694,56 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
                         int64_t* n_conflicts, int64_t* n_candidates);
 /* milliseconds of the kernels of the last uph_extent_batch, uph_separation_batch or uph_conflicts_batch of c (events on the context's stream) */
 int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
+/* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
+ * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /
+ * uph_extent_batch returns for the shifted start, bit for bit.
+ *   delay table    delay0 (finite), delay_step (finite, > 0) and a count D >= 1 give delta_j = delay0 + j * delay_step, 0 <= j < D -- the product rounded, then
+ *                  the sum, as tau_k above.  The table is formed once on the host (uph_delay_times) and the device reads delta_j from it: a delayed vehicle
+ *                  starts at t0 + delta_j, one rounded add, and there is no multiply on the device that could be fused into it.
+ *   sweep row      row (q, j) holds min_d2, min_t and below (the number of samples below) of uph_separation_batch for vehicle a (traj_a[q], t0_a[q]) against
+ *                  vehicle b (traj_b[q], t0_b[q] + delta_j) over the same window, dt and radius, its NaN and tie rules included; K = 0 gives +inf, NaN, 0.
+ *                  first_clear[q] is the smallest j with below == 0 (-1: none), taken on the host from the rows.
+ *   swept extent   per vehicle and window the hull over j of uph_extent_batch(traj, t0 + delta_j)'s boxes -- min and max are exact, the order of the fold cannot
+ *                  matter --, with K and the number of (j, k) samples whose position is NaN.  Every position the vehicle takes at any sample under any
+ *                  delay of the table lies in this box, so uph_conflict_candidates on swept boxes drops no pair that is below at any sample for any
+ *                  combination of delays: the proof of `candidates` above, unchanged, with no epsilon.
+ *   schedule       vehicles (traj[i], t0[i], radius[i]) in priority order, the smaller index first.  n_delays[i] in [1, D] (NULL: D for all) is the number of
+ *                  delays vehicle i may use; a vehicle already under way has 1.  The swept boxes are taken over the whole table.  Vehicle i is compared with
+ *                  every h < i the broad phase keeps, R = r_h + r_i, h at its EFFECTIVE start t0_h + delta_max(choice[h], 0) and i swept.  choice[i] is the
+ *                  smallest j < n_delays[i] with below == 0 against every such h (0 without a partner); -1 when there is none, and the vehicle then stays at
+ *                  j = 0 for all behind it, with blocker[i] the smallest h that is below at j = 0 (-1 otherwise).  start[i] is the effective start.  The
+ *                  result is the sequential greedy's; the vehicles whose kept partners of smaller index are all placed -- the levels of the candidate
+ *                  graph (uph_delay_levels) -- are swept in one round, since a choice depends on the choices of those partners alone.
+ * The sweep kernel takes the samples in tiles of UPH_DELAY_TILE; no result depends on the tile, on the launch width or on how a tile is split over lanes.
+ * The device calls are blocking, on the (first) context's stream; any output may be NULL; the two-context rules are uph_separation_batch's.  Every refusal of
+ * uph_separation_batch / uph_extent_batch / uph_conflicts_batch applies unchanged, outputs untouched, and so do: UPH_ERR_INVALID for a delay_step that is not
+ * positive and finite, a non-finite delay0, D < 1, a start t0 + delta_j that is not finite, an n_delays[i] outside [1, D], a pair of uph_delay_levels without
+ * 0 <= i < j < n; UPH_ERR_LIMIT for D > 4096 and for a query with K * D > 2^26 (one workgroup's serial work is then at most that of 16 separation queries
+ * of the largest length).  At most 2^20 sweep rows are on the device at a time: longer launches are split. */
+#define UPH_DELAY_TILE 128
+/* host only, no device needed: the table delta[D] by the rule above */
+int uph_delay_times(double delay0, double delay_step, int32_t D, double* delta);
+/* host only, no device needed: level[j] of n vehicles among pairs (i, j), i < j: 0 for a vehicle without a smaller partner, else 1 + the largest level of
+ * its smaller partners */
+int uph_delay_levels(int32_t n, int64_t n_pairs, const int32_t* pairs /* [n_pairs][2] */, int32_t* level /* [n] */);
+/* query q: vehicle (traj_a[q], t0_a[q]) of ca against vehicle (traj_b[q], t0_b[q] + delta_j) of cb for every delay of the table; counts[q] = K.  The kernel
+ * time is kept on ca. */
+int uph_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb /* NULL: ca */, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
+                          const double* t_from, const double* t_to, double dt, const double* radius, double delay0, double delay_step, int32_t D,
+                          double* min_d2 /* [n][D] */, double* min_t /* [n][D] */, int32_t* below /* [n][D] */, int32_t* first_clear /* [n] */,
+                          int32_t* counts /* [n]: K */);
+/* query q: the swept extent of vehicle (traj[q], t0[q]) over the window [t_from[q], t_to[q]] */
+int uph_delay_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt, double delay0,
+                           double delay_step, int32_t D, double* box /* [n][4] */, int32_t* counts /* [n][2]: K, NaN samples over all delays */);
+/* the fleet, one window for all as uph_conflicts_batch: swept extents on the device, candidates and their levels on the host, a sweep launch (or a few of
+ * bounded size) per level.  *n_candidates is the number of pairs the broad phase kept, *n_rounds the number of levels that were swept, *n_unresolved the
+ * number of vehicles with choice == -1. */
+int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays /* may be NULL */, double t_from,
+                     double t_to, double dt, double delay0, double delay_step, int32_t D, int32_t* choice /* [n] */, double* start /* [n] */,
+                     int32_t* blocker /* [n] */, int64_t* n_candidates, int32_t* n_rounds, int32_t* n_unresolved);
+/* milliseconds of the kernels of the last uph_delay_sweep_batch, uph_delay_extent_batch or uph_delays_batch of c (events on the context's stream) */
+int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 #ifdef __cplusplus
 }

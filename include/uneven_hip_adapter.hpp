@@ -695,6 +695,75 @@ public:
         }
         return out;
     }
+    // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are
+    // delta_j = delay0 + j * delay_step, 0 <= j < D.  separationSE2TrajBatch of a against b started at t0_b[q] + delta_j, for every j, in one call
+    // (uph_delay_sweep_batch).
+    struct TrajDelaySweep {
+        int32_t D = 0;
+        std::vector<double> min_d2, min_t;      // [n][D]
+        std::vector<int32_t> below;             // [n][D] samples below
+        std::vector<int32_t> first_clear;       // [n] the smallest j with below == 0 (-1: none)
+        std::vector<int32_t> counts;            // [n] samples of the window
+    };
+    TrajDelaySweep delaySweepSE2TrajBatch(const std::vector<int>& traj_a, const std::vector<int>& traj_b, const std::vector<double>& t0_a, const std::vector<double>& t0_b,
+                                          const std::vector<double>& t_from, const std::vector<double>& t_to, const std::vector<double>& radius, double delay0,
+                                          double delay_step, int D, double dt = 0.01, const ALMTrajOpt* other = nullptr) {
+        const size_t m = traj_a.size();
+        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || radius.size() != m)
+            throw std::runtime_error("delaySweepSE2TrajBatch: the query arrays differ in number");
+        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("delaySweepSE2TrajBatch: the last batch was split over several devices");
+        TrajDelaySweep out;
+        out.D = (int32_t)D;
+        if (m == 0) return out;
+        const size_t rows = m * (size_t)std::max(D, 1);
+        std::vector<int32_t> ta(traj_a.begin(), traj_a.end()), tb(traj_b.begin(), traj_b.end());
+        out.min_d2.assign(rows, 0.0); out.min_t.assign(rows, 0.0); out.below.assign(rows, 0); out.first_clear.assign(m, -1); out.counts.assign(m, 0);
+        if (uph_delay_sweep_batch(ctx_, other ? other->ctx_ : nullptr, (int32_t)m, ta.data(), tb.data(), t0_a.data(), t0_b.data(), t_from.data(), t_to.data(), dt,
+                                  radius.data(), delay0, delay_step, (int32_t)D, out.min_d2.data(), out.min_t.data(), out.below.data(), out.first_clear.data(),
+                                  out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_delay_sweep_batch: ") + uph_last_error());
+        return out;
+    }
+    // the box that holds a vehicle under every delay of the table (uph_delay_extent_batch): the broad phase on these boxes holds whatever delays are chosen
+    TrajExtent delayExtentSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                       double delay0, double delay_step, int D, double dt = 0.01) {
+        if (t0.size() != traj.size() || t_from.size() != traj.size() || t_to.size() != traj.size())
+            throw std::runtime_error("delayExtentSE2TrajBatch: traj, t0, t_from and t_to differ in number");
+        if (last_multi_) throw std::runtime_error("delayExtentSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajExtent out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        out.box.assign((size_t)4 * n, 0.0); out.counts.assign((size_t)2 * n, 0);
+        if (uph_delay_extent_batch(ctx_, n, tr.data(), t0.data(), t_from.data(), t_to.data(), dt, delay0, delay_step, (int32_t)D, out.box.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_delay_extent_batch: ") + uph_last_error());
+        return out;
+    }
+    // the fleet in priority order (the smaller index goes first): every vehicle gets the smallest delay -- among its first n_delays[i], empty: all D -- that
+    // clears it against all vehicles ahead of it at their chosen starts (uph_delays_batch).  After conflictsSE2TrajBatch has reported pairs; the vehicles left
+    // with choice == -1 go to replanSE2TrajBatch / refineSE2TrajBatch.
+    struct TrajDelays {
+        std::vector<int32_t> choice;            // [n] index into the table; -1: no delay clears the vehicle (it stays at delay 0)
+        std::vector<double> start;              // [n] the effective start on the common clock
+        std::vector<int32_t> blocker;           // [n] the first vehicle in the way of an unresolved one, else -1
+        int64_t n_candidates = 0;
+        int32_t n_rounds = 0, n_unresolved = 0;
+    };
+    TrajDelays delaysSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<double>& radius, double t_from, double t_to,
+                                  double delay0, double delay_step, int D, const std::vector<int>& n_delays = std::vector<int>(), double dt = 0.05) {
+        if (t0.size() != traj.size() || radius.size() != traj.size() || (!n_delays.empty() && n_delays.size() != traj.size()))
+            throw std::runtime_error("delaysSE2TrajBatch: traj, t0, radius and n_delays differ in number");
+        if (last_multi_) throw std::runtime_error("delaysSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajDelays out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end()), nd(n_delays.begin(), n_delays.end());
+        out.choice.assign((size_t)n, 0); out.start.assign((size_t)n, 0.0); out.blocker.assign((size_t)n, -1);
+        if (uph_delays_batch(ctx_, n, tr.data(), t0.data(), radius.data(), nd.empty() ? nullptr : nd.data(), t_from, t_to, dt, delay0, delay_step, (int32_t)D,
+                             out.choice.data(), out.start.data(), out.blocker.data(), &out.n_candidates, &out.n_rounds, &out.n_unresolved) != UPH_OK)
+            throw std::runtime_error(std::string("uph_delays_batch: ") + uph_last_error());
+        return out;
+    }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)
 
     // getMaxVxAxAyCurAttSig (alm_traj_opt.h:170-229): max vx, ax, ay, curvature, attitude (-cos xi), sigma sampled every 0.01 s -- evaluated

@@ -1,0 +1,658 @@
+"""GPU tier of the start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch; uph_delay_sweep_kernel, uph_delay_extent_kernel).  The
+yardstick is the existing device path: every number must be the one separation() / extent() returns for the shifted start, bit for bit.
+
+D1 (exact): every array of delay_sweep() EQUALS (np.array_equal, NaN = NaN) separation() called once per delay j with t0_b + delay_times(...)[j].
+D2: known answers -- a trajectory against itself, a delay longer than the window (b parked at its start), K = 0 rows.
+D3: two contexts -- refined trajectories (a second object, also in local frames and on fp32 cells) swept against their sources.
+D4: delay_extent() EQUALS the hull over j of extent(t0 + delta_j); no pair the broad phase drops on swept boxes is ever below, under any pair of delays.
+D5: delays() EQUALS delay_schedule, the sequential greedy, driven by separation() over the swept-box candidates; with the starts it returns applied,
+    conflicts() finds no pair whose later vehicle was given a delay.
+D6: refusals on live contexts, launches split at 2^20 rows, the C++ adapter against ctypes.
+Source: the 64 solved hill goals of test_gpu_separation.py."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_gpu_replan import _hill_map, _queries, _source
+from test_gpu_separation import _bc, _same, _totals, _valid
+from uneven_planner_amd import _lib
+from uneven_planner_amd.alm_traj_opt import conflict_candidates, delay_levels, delay_schedule, delay_times, separation_rows, separation_times
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INF = float("inf")
+NAN = float("nan")
+WKEYS = ("min_d2", "min_t", "below", "first_clear", "counts")
+TILE = _lib.DELAY_TILE
+
+
+@pytest.fixture(scope="module")
+def hill():
+    import uneven_planner_amd as U
+    m = _hill_map()
+    ka = U.KinoAstar(m)
+    S, G = _queries(m, 64, 14000)
+    src, res = _source(m, ka, S, G)
+    ok = np.array(_valid(res), dtype=np.int32)
+    assert len(ok) >= 40, len(ok)
+    total = _totals(src)
+    assert (total[ok] > 3.0).all()
+    return dict(m=m, ka=ka, S=S, G=G, src=src, res=res, ok=ok, total=total)
+
+
+def _first_clear(below):
+    clear = below == 0
+    return np.where(clear.any(axis=1), clear.argmax(axis=1), -1).astype(np.int32)
+
+
+def _looped(A, ta, tb, tf, tt, radius, delay0, step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
+    """the recipe the sweep replaces and the yardstick of D1: a separation() call per delay, b started at t0_b + delta_j"""
+    n = len(ta)
+    delta = delay_times(delay0, step, D)
+    t0_b = _bc(t0_b, n)
+    out = dict(min_d2=np.zeros((n, D)), min_t=np.zeros((n, D)), below=np.zeros((n, D), dtype=np.int32))
+    for j in range(D):
+        r = A.separation(ta, tb, tf, tt, radius, t0_a=t0_a, t0_b=t0_b + delta[j], other=other, dt=dt)
+        out["min_d2"][:, j], out["min_t"][:, j], out["below"][:, j], out["counts"] = r["min_d2"], r["min_t"], r["counts"][:, 1], r["counts"][:, 0].copy()
+    out["first_clear"] = _first_clear(out["below"])
+    return out
+
+
+def _held(A, ta, tb, tf, tt, radius, delay0, step, D, tag="", **kw):
+    """delay_sweep() held to D1"""
+    got = A.delay_sweep(ta, tb, tf, tt, radius, delay0, step, D, **kw)
+    want = _looped(A, ta, tb, tf, tt, radius, delay0, step, D, **kw)
+    _same(got, want, WKEYS, tag)
+    assert np.array_equal(got["first_clear"], _first_clear(got["below"])), tag
+    return got
+
+
+def _tails(hill, Ks, seed):
+    """queries with exactly K samples for every K of Ks, on a clock around 1000 s, the window anywhere around the later start; the radius is the median
+    smallest distance at delay 0 times 0.7, 1.25 or 2.5, so that below falls anywhere between 0 and K"""
+    src, ok = hill["src"], hill["ok"]
+    rng = np.random.default_rng(seed)
+    dt = 0.01
+    ta, tb, tf, tt, t0a, t0b = [], [], [], [], [], []
+    for k, K in enumerate(Ks):
+        s0, s1 = 1000.0 + rng.uniform(0.0, 2.0), 1000.0 + rng.uniform(0.0, 2.0)
+        f = max(s0, s1) + rng.uniform(-1.0, 1.5)
+        ta.append(int(ok[(3 * k) % ok.size])), tb.append(int(ok[(3 * k + 11) % ok.size])), t0a.append(s0), t0b.append(s1), tf.append(f)
+        tt.append(f + (K - 1) * dt if K else f - 0.5)               # exactly on the last sample
+    ta, tb = np.array(ta, dtype=np.int32), np.array(tb, dtype=np.int32)
+    tf, tt, t0a, t0b = np.array(tf), np.array(tt), np.array(t0a), np.array(t0b)
+    least = np.sqrt(src.separation(ta, tb, tf, tt, 0.0, t0_a=t0a, t0_b=t0b, dt=dt)["min_d2"])
+    radius = np.where(np.isfinite(least), least * np.array([0.7, 1.25, 2.5])[np.arange(len(Ks)) % 3], 1.0)
+    return ta, tb, tf, tt, t0a, t0b, radius, dt
+
+
+K_EDGES = (0, 1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 192, 193, 257, 2 * TILE + 1)
+
+
+@pytest.mark.parametrize("D", [1, 2, 63, 64, 65, 130, 257])
+def test_sweep_equals_separation_per_delay_at_every_edge(hill, D):
+    """D1: K on both sides of a wave, of a tile and of the lengths at which the launch width changes (K * D around 192), D on both sides of one wave and of
+    256 lanes (lanes that share a delay, a lane per delay, several passes), in one launch that mixes both kernels, holds duplicates and comes shuffled;
+    a negative delay0 and steps that span the windows"""
+    assert TILE == 128
+    src = hill["src"]
+    Ks = np.array(K_EDGES * 2)
+    ta, tb, tf, tt, t0a, t0b, radius, dt = _tails(hill, Ks, 53 + D)
+    rng = np.random.default_rng(D)
+    dup = np.array([5, 5, 9, 20, 9, 0, 1], dtype=np.int64)
+    idx = np.concatenate([np.arange(Ks.size), dup])
+    idx = idx[rng.permutation(idx.size)]
+    delay0, step = -0.7, max(0.013, 3.0 / D)
+    got = _held(src, ta[idx], tb[idx], tf[idx], tt[idx], radius[idx], delay0, step, D, tag="edges D=%d" % D, t0_a=t0a[idx], t0_b=t0b[idx], dt=dt)
+    assert np.array_equal(got["counts"], Ks[idx]) and got["below"].shape == (idx.size, D)
+    work = Ks[idx] * D
+    assert (work > 192).any() and (work <= 192).any()              # both launch widths
+    empty = Ks[idx] == 0
+    assert (got["min_d2"][empty] == INF).all() and np.isnan(got["min_t"][empty]).all() and (got["below"][empty] == 0).all() and (got["first_clear"][empty] == 0).all()
+    some = Ks[idx] > 1
+    print("D = %d: rows with no sample below %d, some %d, all %d" % (D, (got["below"][some] == 0).sum(), ((got["below"][some] > 0) & (got["below"][some] < Ks[idx][some, None])).sum(),
+                                                                      (got["below"][some] == Ks[idx][some, None]).sum()))
+    assert (got["below"][some] > 0).any() and (got["below"][some] < Ks[idx][some, None]).any()
+    # the same query answers the same wherever it stands in the launch, and alone
+    for q in np.unique(dup):
+        rows = np.nonzero(idx == q)[0]
+        assert rows.size >= 2
+        for k in WKEYS:
+            for r in rows[1:]:
+                assert np.array_equal(got[k][r], got[k][rows[0]], equal_nan=True), (q, k)
+    for r in (int(np.argmax(Ks[idx])), int(np.nonzero(Ks[idx] == TILE)[0][0]), int(np.nonzero(Ks[idx] == 1)[0][0])):
+        q = idx[r]
+        one = src.delay_sweep([ta[q]], [tb[q]], tf[q], tt[q], radius[q], delay0, step, D, t0_a=t0a[q], t0_b=t0b[q], dt=dt)
+        for k in WKEYS:
+            assert np.array_equal(one[k][0], got[k][r], equal_nan=True), (q, k)
+    assert src.delay_kernel_ms() > 0.0
+
+
+@pytest.mark.parametrize("dt", [0.01, 0.05])
+def test_sweep_over_whole_trajectories(hill, dt):
+    """D1: windows from before both starts to after both ends on a clock around 1000 s (many tiles), starts that differ, D = 16 at 0.5 s from -1 s; a
+    radius no delay clears, a radius 0, and trajectories against themselves from 2 s after the start, which only a later start clears"""
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    rng = np.random.default_rng(61)
+    D, delay0, step = 16, -1.0, 0.5
+    ta, tb = ok, np.roll(ok, 7)
+    t0_a, t0_b = 1000.0 + rng.uniform(0.0, 5.0, ok.size), 1000.0 + rng.uniform(0.0, 5.0, ok.size)
+    tf = np.minimum(t0_a, t0_b) - rng.uniform(0.2, 1.5, ok.size)
+    tt = np.maximum(t0_a + total[ta], t0_b + total[tb] + delay0 + step * D) + rng.uniform(0.2, 1.0, ok.size)
+    radius = rng.uniform(0.2, 4.0, ok.size)
+    radius[:3], radius[3:6] = 1e3, 0.0
+    got = _held(src, ta, tb, tf, tt, radius, delay0, step, D, tag="full %g" % dt, t0_a=t0_a, t0_b=t0_b, dt=dt)
+    K = np.array([separation_times(tf[q], tt[q], dt).shape[0] for q in range(ok.size)])
+    assert np.array_equal(got["counts"], K) and (K > 3 * TILE * (0.01 / dt)).all()
+    assert (got["first_clear"][:3] == -1).all() and (got["first_clear"][3:6] == 0).all() and np.isfinite(got["min_d2"]).all()
+    assert (got["min_t"] >= tf[:, None]).all() and (got["min_t"] <= tt[:, None]).all()
+    assert (got["below"].max(axis=1) > got["below"].min(axis=1)).sum() >= ok.size // 4      # the delay matters
+    t0 = 1000.0 + 0.25 * np.arange(ok.size)
+    own = _held(src, ok, ok, t0 + 2.0, t0 + total[ok] - 1.0, 0.02, 0.0, 0.5, D, tag="own %g" % dt, t0_a=t0, t0_b=t0, dt=dt)
+    assert (own["below"][:, 0] == own["counts"]).all() and (own["min_d2"][:, 0] == 0.0).all()
+    print("own trajectory, R = 0.02 m: first_clear", np.bincount(own["first_clear"] + 1).tolist(), "(from -1)")
+    assert (own["first_clear"] > 0).any()
+
+
+def test_known_answers(hill):
+    """D2"""
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    n, D = ok.size, 5
+    # a trajectory against itself with the same start and no delay: d2 = 0 at every sample
+    tf, tt = 999.5, 1000.0 + total[ok] + 0.5
+    for radius in (0.25, 1e-150):
+        r = src.delay_sweep(ok, ok, tf, tt, radius, 0.0, 0.75, D, t0_a=1000.0, t0_b=1000.0, dt=0.05)
+        assert (r["counts"] > 60).all() and (r["below"][:, 0] == r["counts"]).all() and (r["min_d2"][:, 0] == 0.0).all() and (r["min_t"][:, 0] == tf).all()
+        assert (r["min_d2"] == 0.0).all() and (r["min_t"] == tf).all()         # both stand at the start at the first sample, whatever the delay
+        assert (r["first_clear"] == -1).all()
+    r = src.delay_sweep(ok, ok, tf, tt, 0.0, 0.0, 0.75, D, t0_a=1000.0, t0_b=1000.0, dt=0.05)
+    assert (r["below"] == 0).all() and (r["first_clear"] == 0).all()
+    # a delay longer than the window: b stays parked at its start, every row is a's separation from that point
+    tb = np.roll(ok, 5)
+    t0_a, t0_b = 50.0 + 0.1 * np.arange(n), 52.0 - 0.05 * np.arange(n)
+    f, t = 49.0, 50.0 + float(total.max()) + 6.0
+    park = src.traj_states(tb, np.zeros(n))[:, :2]
+    tau = separation_times(f, t, 0.05)
+    r = src.delay_sweep(ok, tb, f, t, 2.0, t - 40.0, 3.0, D, t0_a=t0_a, t0_b=t0_b, dt=0.05)
+    assert (t0_b + (t - 40.0) > t).all() and (r["counts"] == tau.shape[0]).all()
+    for q in range(n):
+        pa = src.traj_states(np.full(tau.shape[0], ok[q], dtype=np.int32), tau - t0_a[q])[:, :2]
+        want = separation_rows(tau, pa, np.tile(park[q], (tau.shape[0], 1)), 2.0)
+        for j in range(D):
+            assert r["min_d2"][q, j] == want["min_d2"] and r["min_t"][q, j] == want["min_t"] and r["below"][q, j] == want["counts"][1], (q, j)
+    # K = 0: +inf, NaN, 0 and a first_clear of 0
+    r = src.delay_sweep(ok, tb, 60.0, 59.0, 2.0, 0.0, 0.5, D, t0_a=t0_a, t0_b=t0_b)
+    assert (r["min_d2"] == INF).all() and np.isnan(r["min_t"]).all() and (r["below"] == 0).all() and (r["first_clear"] == 0).all() and (r["counts"] == 0).all()
+    e = src.delay_extent(ok, 60.0, 59.0, 0.0, 0.5, D, t0=t0_a)
+    assert (e["box"] == [INF, -INF, INF, -INF]).all() and (e["counts"] == 0).all()
+
+
+def _refined_swept(src, m, tr, total, tag, t0_b):
+    """S3's setup: trajectories tr of src refined from 0.3 of their duration into a second object; each refined trajectory swept against its source"""
+    import uneven_planner_amd as U
+    tr = np.asarray(tr, dtype=np.int32)
+    t_sw = 0.3 * total[tr]
+    dst = U.ALMTrajOpt(m)
+    dst.set_rho(1.0)
+    out = dst.refine(src, tr, t_sw)
+    use = [q for q, r in enumerate(out) if r["status"] == 0 and r.get("ret", 4) != 4 and np.isfinite(r["c_xy"]).all()]
+    assert len(use) >= max(3, len(tr) // 2), (tag, len(use))
+    ta = np.array([out[q]["traj_of"] for q in use], dtype=np.int32)
+    tb, t_sw = tr[use], t_sw[use]
+    t0_b = _bc(t0_b, len(tr))[use]
+    t0_a = t0_b + t_sw
+    tt = np.maximum(t0_a + _totals(dst)[ta], t0_b + total[tb]) + 2.5
+    D, delay0, step = 7, -0.6, 0.3
+    for dt in (0.01, 0.05):
+        got = _held(dst, ta, tb, t0_b - 0.5, tt, 0.05, delay0, step, D, tag=tag, t0_a=t0_a, t0_b=t0_b, other=src, dt=dt)
+        assert (got["counts"] > 3.0 / dt).all()
+    # delta_2 = 0: the refined trajectory starts where its source is, the two coincide to 1e-9 m there
+    assert delay_times(delay0, step, D)[2] == 0.0
+    at = dst.delay_sweep(ta, tb, t0_a, t0_a, 1.0, delay0, step, D, t0_a=t0_a, t0_b=t0_b, other=src)
+    assert (at["counts"] == 1).all() and (np.sqrt(at["min_d2"][:, 2]) <= 1e-9).all() and (at["below"][:, 2] == 1).all()
+    # the order of the contexts: the source swept against the refined trajectories, and the extents of each side's own frame
+    _held(src, tb, ta, t0_b - 0.5, tt, 0.05, delay0, step, D, tag=tag + " back", t0_a=t0_b, t0_b=t0_a, other=dst, dt=0.05)
+    _extent_held(dst, ta, t0_b - 0.5, tt, delay0, step, D, t0_a, 0.05, tag)
+    return dst
+
+
+def test_two_contexts_refined_against_their_sources(hill):
+    """D3"""
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    _refined_swept(src, hill["m"], ok[:16], total, "hill", 1000.0 + 0.25 * np.arange(16))
+
+
+def test_two_contexts_in_local_frames_and_on_fp32_cells():
+    """D3: a grid beyond FRAME_EXTENT (every trajectory in its own local frame, each side with its own context's shift) and an fp32-cell map, built as
+    test_gpu_separation.test_two_contexts_in_local_frames_and_on_fp32_cells builds them"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    big = U.UnevenMap(dict(map_size_x=160.0, map_size_y=160.0, xy_resolution=0.25)).fill_fbm()
+    nx, ny = int(big.voxel_num[0]), int(big.voxel_num[1])
+    far, seed = [], 7300
+    while len(far) < 6:
+        p = scenes.local_problems(1, seed0=seed, half=75.0, dmin=4.0, dmax=9.0, occ_r2=big.occ_r2_buffer, grid=(nx, ny, big.xy_resolution, big.map_origin[0], big.map_origin[1]))[0]
+        seed += 1
+        if max(abs(p["init_xy"][0, 0]), abs(p["init_xy"][1, 0])) > 45.0:
+            far.append(p)
+    m32 = U.UnevenMap(dict(map_size_x=32.0, map_size_y=32.0, xy_resolution=0.25), storage="f32").fill_fbm(dict(patch_lambda=5.0, rough_threshold=0.5))
+    nx, ny = int(m32.voxel_num[0]), int(m32.voxel_num[1])
+    p32 = scenes.local_problems(6, seed0=5000, half=14.0, dmin=4.0, dmax=12.0, occ_r2=m32.occ_r2_buffer,
+                                grid=(nx, ny, m32.xy_resolution, m32.map_origin[0], m32.map_origin[1]))
+    for tag, m, probs in (("frames", big, far), ("f32", m32, p32)):
+        opt = U.ALMTrajOpt(m)
+        opt.set_rho(1.0)
+        opt.optimize_batch(probs)
+        tr = np.arange(len(probs), dtype=np.int32)
+        total = _totals(opt)
+        if tag == "frames":
+            assert np.abs(opt.traj_states(tr, np.zeros(tr.size))[:, :2]).max() > 45.0
+        _refined_swept(opt, m, tr, total, tag, 12.5)
+        _held(opt, tr, np.roll(tr, 1), 0.0, total.max() + 4.0, 3.0, 0.0, 0.4, 9, tag=tag + " own", t0_a=0.5 * np.arange(tr.size), t0_b=1.0, dt=0.05)
+
+
+def _extent_held(A, tr, tf, tt, delay0, step, D, t0, dt, tag=""):
+    """delay_extent() held to D4: the hull over j of extent(t0 + delta_j), the window's K and the NaN samples of all delays"""
+    n = len(tr)
+    delta = delay_times(delay0, step, D)
+    per = [A.extent(tr, tf, tt, t0=_bc(t0, n) + delta[j], dt=dt) for j in range(D)]
+    box = np.stack([p["box"] for p in per])
+    want = dict(box=np.stack([box[:, :, 0].min(axis=0), box[:, :, 1].max(axis=0), box[:, :, 2].min(axis=0), box[:, :, 3].max(axis=0)], axis=1),
+                counts=np.stack([per[0]["counts"][:, 0], sum(p["counts"][:, 1] for p in per)], axis=1).astype(np.int32))
+    got = A.delay_extent(tr, tf, tt, delay0, step, D, t0=t0, dt=dt)
+    _same(got, want, ("box", "counts"), tag + " swept extent")
+    return got, per
+
+
+def _fleet(hill, n=24):
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    tr = ok[:n]
+    t0 = 1000.0 + 0.4 * np.arange(n)
+    return src, tr, t0, 999.0, float((t0 + total[tr]).max()) + 1.0
+
+
+def test_swept_extent_equals_the_hull_and_its_broad_phase_loses_nothing(hill):
+    """D4"""
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    rng = np.random.default_rng(71)
+    # every K edge of D1 with D on both sides of a wave and of 256 lanes, then whole trajectories
+    Ks = np.array(K_EDGES)
+    ta, _, tf, tt, t0a, _, _, dt = _tails(hill, Ks, 73)
+    for D in (1, 2, 65, 257):
+        got, _ = _extent_held(src, ta, tf, tt, -0.7, max(0.013, 3.0 / D), D, t0a, dt, "edges D=%d" % D)
+        assert np.array_equal(got["counts"][:, 0], Ks) and (got["counts"][:, 1] == 0).all()
+    t0 = 1000.0 + rng.uniform(0.0, 5.0, ok.size)
+    got, per = _extent_held(src, ok, t0 - 1.0, t0 + total[ok] + 9.0, -1.0, 0.5, 16, t0, 0.05, "full")
+    assert (got["box"][:, 1] > got["box"][:, 0]).all() and src.delay_kernel_ms() > 0.0
+    # the fleet: a pair dropped on swept boxes is below at no sample, whichever delays the two take
+    src, tr, t0, tf, tt = _fleet(hill)
+    n, D, step, dt = tr.size, 16, 0.5, 0.05
+    delta = delay_times(0.0, step, D)
+    swept = src.delay_extent(tr, tf, tt, 0.0, step, D, t0=t0, dt=dt)
+    plain = src.extent(tr, tf, tt, t0=t0, dt=dt)
+    assert (swept["box"][:, [0, 2]] <= plain["box"][:, [0, 2]]).all() and (swept["box"][:, [1, 3]] >= plain["box"][:, [1, 3]]).all()
+    iu, ju = np.triu_indices(n, 1)
+    least = np.sqrt(src.separation(tr[iu], tr[ju], tf, tt, 0.0, t0_a=t0[iu], t0_b=t0[ju], dt=dt)["min_d2"])
+    radius = np.full(n, 0.5 * np.median(least))
+    kept = set(map(tuple, conflict_candidates(swept["box"], radius).tolist()))
+    dropped = np.array([(i, j) for i, j in zip(iu, ju) if (i, j) not in kept])
+    print("fleet: %d of 276 pairs dropped on swept boxes (%d on plain ones)" % (len(dropped), 276 - len(conflict_candidates(plain["box"], radius))))
+    assert 1 <= len(dropped) < 276 and len(kept) >= 1
+    di, dj = dropped[:, 0], dropped[:, 1]
+    for ja in range(D):
+        full = src.delay_sweep(tr[di], tr[dj], tf, tt, 2.0 * radius[0], 0.0, step, D, t0_a=t0[di] + delta[ja], t0_b=t0[dj], dt=dt)
+        assert (full["below"] == 0).all(), ja
+    # ... and the rule is not vacuous: kept pairs are below under some delays
+    ki, kj = np.array(sorted(kept)).T
+    assert (src.delay_sweep(tr[ki], tr[kj], tf, tt, 2.0 * radius[0], 0.0, step, D, t0_a=t0[ki], t0_b=t0[kj], dt=dt)["below"] > 0).any()
+
+
+def _greedy(src, tr, t0, radius, tf, tt, delay0, step, D, dt, n_delays=None):
+    """delay_schedule driven by separation() over the candidates of the swept boxes"""
+    delta = delay_times(delay0, step, D)
+    box = src.delay_extent(tr, tf, tt, delay0, step, D, t0=t0, dt=dt)["box"]
+    pairs = conflict_candidates(box, radius)
+
+    def sweep(h, at, i):
+        return src.separation(np.full(D, tr[h]), np.full(D, tr[i]), tf, tt, radius[h] + radius[i], t0_a=t0[h] + delta[at], t0_b=t0[i] + delta, dt=dt)["counts"][:, 1]
+
+    want = delay_schedule(sweep, pairs, tr.size, n_delays=n_delays)
+    want["start"] = t0 + delta[np.maximum(want["choice"], 0)]
+    want["n_candidates"], want["n_unresolved"] = pairs.shape[0], int((want["choice"] < 0).sum())
+    want["n_rounds"] = int(delay_levels(pairs, tr.size).max())
+    return want
+
+
+def test_the_schedule_is_the_sequential_greedy(hill):
+    """D5: 24 vehicles that start 0.4 s apart, D = 16 delays of 0.5 s.  The radius is a quantile of the pairs' smallest distances at delay 0 (S4 takes the
+    median: about half of the pairs conflict); the first quantile of a fixed list at which the fleet shows waiting vehicles, an unresolved vehicle under
+    n_delays = 1 and more than one round is the one the test runs at -- the assertions on these are made on that run and are not relaxed"""
+    src, tr, t0, tf, tt = _fleet(hill)
+    n, D, step, dt = tr.size, 16, 0.5, 0.05
+    iu, ju = np.triu_indices(n, 1)
+    least = np.sqrt(src.separation(tr[iu], tr[ju], tf, tt, 0.0, t0_a=t0[iu], t0_b=t0[ju], dt=dt)["min_d2"])
+    for quantile in (0.5, 0.35, 0.65, 0.25, 0.8, 0.15):
+        radius = np.full(n, 0.5 * np.quantile(least, quantile))
+        got = src.delays(tr, radius, tf, tt, 0.0, step, D, t0=t0, dt=dt)
+        one = src.delays(tr, radius, tf, tt, 0.0, step, D, t0=t0, n_delays=1, dt=dt)
+        print("quantile %.2f radius %.4g: choice %s rounds %d candidates %d unresolved %d (%d with one delay)" % (
+            quantile, radius[0], got["choice"].tolist(), got["n_rounds"], got["n_candidates"], got["n_unresolved"], one["n_unresolved"]))
+        if (got["choice"] > 0).sum() >= 3 and one["n_unresolved"] >= 1 and got["n_rounds"] >= 2:
+            break
+    assert (got["choice"] > 0).sum() >= 3 and one["n_unresolved"] >= 1 and got["n_rounds"] >= 2
+    assert src.delay_kernel_ms() > 0.0
+    keys = ("choice", "start", "blocker")
+    want = _greedy(src, tr, t0, radius, tf, tt, 0.0, step, D, dt)
+    _same(got, want, keys, "delays")
+    assert (got["n_candidates"], got["n_rounds"], got["n_unresolved"]) == (want["n_candidates"], want["n_rounds"], want["n_unresolved"])
+    assert got["choice"][0] == 0 and ((got["blocker"] >= 0) == (got["choice"] < 0)).all()
+    # with the effective starts applied no conflict is left whose later vehicle was placed
+    left = src.conflicts(tr, radius, tf, tt, t0=got["start"], dt=dt)
+    before = src.conflicts(tr, radius, tf, tt, t0=t0, dt=dt)
+    print("conflicts: %d before, %d after (unresolved %s)" % (before["n_conflicts"], left["n_conflicts"], np.nonzero(got["choice"] < 0)[0].tolist()))
+    assert before["n_conflicts"] >= 3 and (got["choice"][left["pairs"][:, 1]] < 0).all()
+    # one delay for all: stay or fail, and every blocker is in the way at delay 0
+    want1 = _greedy(src, tr, t0, radius, tf, tt, 0.0, step, D, dt, n_delays=np.ones(n, dtype=np.int32))
+    _same(one, want1, keys, "delays, one each")
+    assert (one["n_candidates"], one["n_rounds"], one["n_unresolved"]) == (want1["n_candidates"], want1["n_rounds"], want1["n_unresolved"])
+    assert set(one["choice"].tolist()) == {0, -1} and np.array_equal(one["start"], t0)
+    for i in np.nonzero(one["choice"] < 0)[0]:
+        h = int(one["blocker"][i])
+        assert 0 <= h < i
+        assert src.separation([tr[h]], [tr[i]], tf, tt, radius[h] + radius[i], t0_a=t0[h], t0_b=t0[i], dt=dt)["counts"][0, 1] > 0
+        for g in range(h):
+            assert src.separation([tr[g]], [tr[i]], tf, tt, radius[g] + radius[i], t0_a=t0[g], t0_b=t0[i], dt=dt)["counts"][0, 1] == 0
+    # per-vehicle limits and radii, a table that does not start at 0
+    nd = 1 + (np.arange(n) * 5) % D
+    rad2 = radius * (0.6 + 0.8 * (np.arange(n) % 3) / 2.0)
+    got2 = src.delays(tr, rad2, tf, tt, 0.25, 0.3, D, t0=t0, n_delays=nd, dt=dt)
+    want2 = _greedy(src, tr, t0, rad2, tf, tt, 0.25, 0.3, D, dt, n_delays=nd)
+    _same(got2, want2, keys, "delays, limits")
+    assert (got2["n_candidates"], got2["n_rounds"], got2["n_unresolved"]) == (want2["n_candidates"], want2["n_rounds"], want2["n_unresolved"])
+    assert (got2["choice"] < nd).all() and got2["start"][0] == t0[0] + 0.25
+
+
+def _raw(src, call, null=(), n=None, **kw):
+    """one of the three device calls through ctypes on pre-filled outputs: (rc, outputs)"""
+    a = dict(tr=[0, 1, 2, 3], tb=[1, 2, 3, 0], t0=np.zeros(4), t0b=np.zeros(4), tf=np.zeros(4), tt=np.full(4, 5.0), rad=np.full(4, 0.5), dt=None, delay0=0.0, step=0.5,
+             D=4, other=None, nd=None, f=0.0, t=5.0)
+    a.update(kw)
+    if a["dt"] is None:
+        a["dt"] = 0.05 if call == "delays" else 0.01
+    tr, tb = np.ascontiguousarray(a["tr"], dtype=np.int32), np.ascontiguousarray(a["tb"], dtype=np.int32)
+    t0, t0b, tf, tt, rad = (np.ascontiguousarray(a[k], dtype=np.float64) for k in ("t0", "t0b", "tf", "tt", "rad"))
+    nd = None if a["nd"] is None else np.ascontiguousarray(a["nd"], dtype=np.int32)
+    n = tr.size if n is None else n
+    ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))
+    dp = lambda v: v.ctypes.data_as(_lib.DP)
+    arg = lambda name, v: None if name in null else v
+    rows = 4 * max(1, min(a["D"], 4096))
+    if call == "sweep":
+        o = dict(min_d2=np.full(rows, -9.0), min_t=np.full(rows, -9.0), below=np.full(rows, -9, dtype=np.int32), first=np.full(4, -9, dtype=np.int32),
+                 K=np.full(4, -9, dtype=np.int32))
+        rc = src.L.uph_delay_sweep_batch(arg("ctx", src.h), None if a["other"] is None else a["other"].h, n, arg("traj_a", ip(tr)), arg("traj_b", ip(tb)), arg("t0_a", dp(t0)),
+                                         arg("t0_b", dp(t0b)), arg("t_from", dp(tf)), arg("t_to", dp(tt)), a["dt"], arg("radius", dp(rad)), a["delay0"], a["step"], a["D"],
+                                         dp(o["min_d2"]), dp(o["min_t"]), ip(o["below"]), ip(o["first"]), ip(o["K"]))
+    elif call == "extent":
+        o = dict(box=np.full((4, 4), -9.0), counts=np.full((4, 2), -9, dtype=np.int32))
+        rc = src.L.uph_delay_extent_batch(arg("ctx", src.h), n, arg("traj", ip(tr)), arg("t0", dp(t0)), arg("t_from", dp(tf)), arg("t_to", dp(tt)), a["dt"], a["delay0"], a["step"],
+                                          a["D"], dp(o["box"]), ip(o["counts"]))
+    else:
+        o = dict(choice=np.full(4, -9, dtype=np.int32), start=np.full(4, -9.0), blocker=np.full(4, -9, dtype=np.int32), nk=np.full(1, -9, dtype=np.int64),
+                 nr=np.full(1, -9, dtype=np.int32), nu=np.full(1, -9, dtype=np.int32))
+        rc = src.L.uph_delays_batch(arg("ctx", src.h), n, arg("traj", ip(tr)), arg("t0", dp(t0)), arg("radius", dp(rad)), None if nd is None else ip(nd), a["f"], a["t"],
+                                    a["dt"], a["delay0"], a["step"], a["D"], ip(o["choice"]), dp(o["start"]), ip(o["blocker"]),
+                                    o["nk"].ctypes.data_as(C.POINTER(C.c_int64)), ip(o["nr"]), ip(o["nu"]))
+    return rc, o
+
+
+def test_refusals(hill):
+    """D6: each refusal of include/uneven_hip.h on live contexts: UPH_ERR_INVALID (UPH_ERR_LIMIT where it says so) with every output as it was pre-filled"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    m, ka, src, ok = hill["m"], hill["ka"], hill["src"], hill["ok"]
+    F = src.L.uph_batch_count(src.h)
+    tr = ok[:4]
+    fresh = U.ALMTrajOpt(m)
+    fresh.plan_goals_upload(ka, hill["S"][:8], hill["G"][:8])                 # uploaded, not solved: no resident trajectory
+    probs = scenes.random_problems(3, seed0=2100)                              # an UPH_RET_UNSUPPORTED slot next to ordinary ones
+    big = dict(probs[0])
+    big["inner_xy"] = np.linspace([0.0, 0.0], [3.0, 0.5], 140).T.copy()
+    big["inner_yaw"] = np.zeros(140)
+    uns = U.ALMTrajOpt(m)
+    uns.set_rho(1.0)
+    assert uns.optimize_batch(probs + [big])[3]["ret"] == 4
+    src2, _ = _source(m, ka, hill["S"][:32], hill["G"][:32])
+
+    def refused(res, what, code=-1):
+        rc, o = res
+        assert rc == code and all((o[k] == -9).all() for k in o), (what, rc, src.L.uph_last_error())
+
+    calls = ("sweep", "extent", "delays")
+    run = lambda call, a=src, **kw: _raw(a, call, **dict(dict(tr=tr, tb=tr), **kw))
+    for call, nulls in (("sweep", ("ctx", "traj_a", "traj_b", "t0_a", "t0_b", "t_from", "t_to", "radius")), ("extent", ("ctx", "traj", "t0", "t_from", "t_to")),
+                        ("delays", ("ctx", "traj", "t0", "radius"))):
+        for null in nulls:
+            refused(run(call, null=(null,)), (call, null))
+            assert {"sweep": b"uph_delay_sweep_batch", "extent": b"uph_delay_extent_batch", "delays": b"uph_delays_batch"}[call] in src.L.uph_last_error()
+    for call in calls:
+        # what uph_separation_batch / uph_extent_batch / uph_conflicts_batch refuse
+        for n in (0, -3):
+            refused(run(call, n=n), (call, "n", n))
+        for dt in (0.0, -0.01, INF, NAN):
+            refused(run(call, dt=dt), (call, "dt", dt))
+        refused(run(call, dt=1e-7), (call, "too many samples"), code=_lib.UPH_ERR_LIMIT)
+        refused(run(call, fresh, tr=[0, 1, 2, 3], tb=[0, 1, 2, 3]), (call, "not resident"))
+        assert b"resident" in src.L.uph_last_error()
+        refused(run(call, U.ALMTrajOpt(m)), (call, "no batch"))
+        refused(run(call, uns, tr=[0, 3, 1, 2], tb=[0, 1, 2, 0]), (call, "unsupported slot"))
+        assert b"UNSUPPORTED" in src.L.uph_last_error()
+        for bad in ([int(ok[0]), F, int(ok[1]), int(ok[2])], [-1, 0, 0, 0]):
+            refused(run(call, tr=bad), (call, "index", bad))
+        src2.solve_async()                                                      # an asynchronous solve pending
+        res = run(call, src2, tr=[0, 1, 2, 3], tb=[0, 1, 2, 3])
+        src2.wait()
+        refused(res, (call, "pending"))
+        assert b"in flight" in src.L.uph_last_error()
+        for v in (NAN, INF, -INF):
+            bad = np.array([0.0, v, 0.0, 0.0])
+            refused(run(call, t0=bad), (call, "t0", v))
+            if call == "delays":
+                refused(run(call, f=v), (call, "t_from", v)), refused(run(call, t=v), (call, "t_to", v))
+            else:
+                refused(run(call, tf=bad), (call, "t_from", v)), refused(run(call, tt=bad + 5.0), (call, "t_to", v))
+            if call != "extent":
+                refused(run(call, rad=bad + 0.5), (call, "radius", v))
+            # the delays
+            refused(run(call, delay0=v), (call, "delay0", v)), refused(run(call, step=v), (call, "step", v))
+        if call != "extent":
+            refused(run(call, rad=np.array([0.5, 0.5, -1e-9, 0.5])), (call, "negative radius"))
+        for step in (0.0, -0.5):
+            refused(run(call, step=step), (call, "step", step))
+        for D in (0, -2):
+            refused(run(call, D=D), (call, "D", D))
+        refused(run(call, D=4097), (call, "D"), code=_lib.UPH_ERR_LIMIT)
+        assert b"4096" in src.L.uph_last_error()
+        # K * D > 2^26: 20001 samples at 4096 delays
+        refused(run(call, D=4096, tt=np.full(4, 200.0), t=200.0, dt=0.01), (call, "K * D"), code=_lib.UPH_ERR_LIMIT)
+        assert b"2^26" in src.L.uph_last_error()
+        # a delayed start that is not finite (t0 is finite, the table is a table)
+        key = "t0b" if call == "sweep" else "t0"
+        refused(run(call, **{key: np.array([0.0, 0.0, 1.7e308, 0.0]), "delay0": 1.7e308}), (call, "start"))
+        refused(run(call, step=1e308, D=4), (call, "start, by the last delay"))
+        assert b"not finite" in src.L.uph_last_error()
+    for nd in ([1, 2, 0, 4], [1, 2, 5, 4], [-1, 1, 1, 1]):
+        refused(run("delays", nd=nd), ("n_delays", nd))
+        assert b"n_delays" in src.L.uph_last_error()
+    # side b is checked against ITS context
+    refused(run("sweep", other=uns, tb=[0, 3, 1, 2]), "unsupported slot of b")
+    refused(run("sweep", other=fresh), "b not resident")
+    src2.solve_async()
+    res = run("sweep", other=src2, tb=[0, 1, 2, 3])
+    src2.wait()
+    refused(res, "b pending")
+    assert run("sweep", uns, tr=[0, 1, 2, 0], other=src)[0] == 0
+    # what is allowed: any output NULL, a reversed window, radius 0, n_delays at both ends of its range
+    ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))
+    dp = lambda v: v.ctypes.data_as(_lib.DP)
+    z4, w4, r4 = np.zeros(4), np.full(4, 5.0), np.full(4, 0.5)
+    cnt = np.full(4, -9, dtype=np.int32)
+    assert src.L.uph_delay_sweep_batch(src.h, None, 4, ip(tr), ip(tr), dp(z4), dp(z4), dp(z4), dp(w4), 0.01, dp(z4), 0.0, 0.5, 4, None, None, None, None, ip(cnt)) == 0
+    assert cnt.tolist() == [separation_times(0.0, 5.0, 0.01).shape[0]] * 4
+    assert src.L.uph_delay_sweep_batch(src.h, None, 4, ip(tr), ip(tr), dp(z4), dp(z4), dp(w4), dp(z4), 0.01, dp(r4), 0.0, 0.5, 4, None, None, None, None, None) == 0
+    assert src.L.uph_delay_extent_batch(src.h, 4, ip(tr), dp(z4), dp(z4), dp(w4), 0.01, 0.0, 0.5, 4, None, None) == 0
+    assert src.L.uph_delays_batch(src.h, 4, ip(tr), dp(z4), dp(r4), None, 0.0, 5.0, 0.05, 0.0, 0.5, 4, None, None, None, None, None, None) == 0
+    rc, o = run("delays", nd=[1, 4, 4, 1], rad=np.full(4, 50.0))             # everybody in everybody's way, whatever the delay
+    assert rc == 0 and o["choice"].tolist() == [0, -1, -1, -1] and o["blocker"].tolist() == [-1, 0, 0, 0] and (o["nk"][0], o["nr"][0], o["nu"][0]) == (6, 3, 3)
+    assert o["start"].tolist() == [0.0] * 4
+
+
+def test_launches_are_split_at_2_20_rows(hill):
+    """D6: 300 queries at D = 4096 are 1.2 M rows, more than the device holds at a time: the same rows as the queries sent one by one"""
+    src, ok = hill["src"], hill["ok"]
+    n, D = 300, 4096
+    assert n * D > _lib.DELAY_ROWS
+    rng = np.random.default_rng(83)
+    ta, tb = ok[np.arange(n) % ok.size], ok[(np.arange(n) * 7 + 3) % ok.size]
+    t0a, t0b = 1000.0 + rng.uniform(0.0, 3.0, n), 1000.0 + rng.uniform(0.0, 3.0, n)
+    tf = 1003.0 + rng.uniform(0.0, 4.0, n)
+    tt = tf + 0.05 * rng.integers(0, 3, n)                          # K = 1, 2 or 3
+    radius = rng.uniform(0.5, 6.0, n)
+    got = src.delay_sweep(ta, tb, tf, tt, radius, -2.0, 0.002, D, t0_a=t0a, t0_b=t0b, dt=0.05)
+    assert got["below"].shape == (n, D) and set(got["counts"].tolist()) == {1, 2, 3}
+    for q in range(n):
+        one = src.delay_sweep(ta[q:q + 1], tb[q:q + 1], tf[q], tt[q], radius[q], -2.0, 0.002, D, t0_a=t0a[q], t0_b=t0b[q], dt=0.05)
+        for k in WKEYS:
+            assert np.array_equal(one[k][0], got[k][q], equal_nan=True), (q, k)
+    # ... and a few of them against the yardstick itself
+    few = np.array([0, 255, 256, 299])
+    _held(src, ta[few], tb[few], tf[few], tt[few], radius[few], -2.0, 0.002 * 64, D // 64, tag="chunks", t0_a=t0a[few], t0_b=t0b[few], dt=0.05)
+    assert (got["below"] > 0).any() and (got["below"] == 0).any()
+
+
+CPP = r"""
+#include "uneven_hip_adapter.hpp"
+#include <array>
+#include <cstdio>
+using namespace uneven_hip;
+int main(int argc, char** argv) {
+    // in: {ncell, B}, cells, B x {start, goal, start time on the common clock, radius}
+    FILE* f = std::fopen(argv[1], "rb");
+    long long hdr[2];
+    if (argc < 3 || !f || fread(hdr, 8, 2, f) != 2) return 2;
+    std::vector<double> cells((size_t)hdr[0] * 4), sg((size_t)hdr[1] * 8);
+    if (fread(cells.data(), 8, cells.size(), f) != cells.size() || fread(sg.data(), 8, sg.size(), f) != sg.size()) return 2;
+    std::fclose(f);
+    uph_map_params mp = {2, 10.0, 10.0, 0.2, 0.1, 0.1, 0.05, 0.1, 0.8, 0.05, 9.81};
+    UnevenMapHandle map(mp, 0);
+    map.setCells(cells.data());
+    KinoAstar kino;
+    kino.setEnvironment(&map);
+    ALMTrajOpt opt, second;
+    opt.setEnvironment(&map);
+    second.setEnvironment(&map);
+    std::vector<std::array<double, 3>> starts((size_t)hdr[1]), goals((size_t)hdr[1]);
+    for (long long b = 0; b < hdr[1]; b++) for (int k = 0; k < 3; k++) { starts[b][k] = sg[8 * b + k]; goals[b][k] = sg[8 * b + 3 + k]; }
+    uph_manager_params mgr{0.3, 0.5, 1.2, 2.0, 0.05, 0, 0.5};
+    ALMTrajOpt::GoalPlan p = opt.planSE2TrajBatch(kino, starts, goals, mgr);
+    second.planSE2TrajBatch(kino, starts, goals, mgr);
+    std::vector<int> traj, other, nd;
+    std::vector<double> t0, rad, tf, tt, t0b;
+    for (long long b = 0; b < hdr[1]; b++)
+        if (p.traj_of[b] >= 0 && p.ret[b] != UPH_RET_UNSUPPORTED) {
+            traj.push_back(p.traj_of[b]); t0.push_back(sg[8 * b + 6]); rad.push_back(sg[8 * b + 7]);
+            tf.push_back(sg[8 * b + 6] - 0.5); tt.push_back(sg[8 * b + 6] + 12.0);
+        }
+    const size_t n = traj.size();
+    for (size_t k = 0; k < n; k++) { other.push_back(traj[(k + 1) % n]); t0b.push_back(t0[(k + 1) % n]); nd.push_back(1 + (int)(k % 12)); }
+    const int D = 12;
+    const ALMTrajOpt::TrajDelaySweep s = opt.delaySweepSE2TrajBatch(traj, other, t0, t0b, tf, tt, rad, -1.0, 0.5, D);
+    const ALMTrajOpt::TrajDelaySweep x = opt.delaySweepSE2TrajBatch(traj, other, t0, t0b, tf, tt, rad, -1.0, 0.5, D, 0.05, &second);
+    const ALMTrajOpt::TrajExtent e = opt.delayExtentSE2TrajBatch(traj, t0, tf, tt, -1.0, 0.5, D);
+    const ALMTrajOpt::TrajDelays d = opt.delaysSE2TrajBatch(traj, t0, rad, 99.0, 130.0, 0.0, 0.5, D);
+    const ALMTrajOpt::TrajDelays l = opt.delaysSE2TrajBatch(traj, t0, rad, 99.0, 130.0, 0.0, 0.5, D, nd, 0.1);
+    // out: n, per query traj; the two sweeps (3 D + 2 per query), the swept extents (6 per query), the two schedules (3 counts, then 3 per vehicle)
+    FILE* o = std::fopen(argv[2], "wb");
+    double nn = (double)n;
+    fwrite(&nn, 8, 1, o);
+    for (size_t k = 0; k < n; k++) { double q = (double)traj[k]; fwrite(&q, 8, 1, o); }
+    for (const ALMTrajOpt::TrajDelaySweep* r : {&s, &x})
+        for (size_t q = 0; q < n; q++) {
+            for (int j = 0; j < D; j++) { double h[3] = {r->min_d2[q * D + j], r->min_t[q * D + j], (double)r->below[q * D + j]}; fwrite(h, 8, 3, o); }
+            double h[2] = {(double)r->first_clear[q], (double)r->counts[q]};
+            fwrite(h, 8, 2, o);
+        }
+    for (size_t q = 0; q < n; q++) { double h[6] = {e.box[4 * q], e.box[4 * q + 1], e.box[4 * q + 2], e.box[4 * q + 3], (double)e.counts[2 * q], (double)e.counts[2 * q + 1]}; fwrite(h, 8, 6, o); }
+    for (const ALMTrajOpt::TrajDelays* r : {&d, &l}) {
+        double h[3] = {(double)r->n_candidates, (double)r->n_rounds, (double)r->n_unresolved};
+        fwrite(h, 8, 3, o);
+        for (size_t k = 0; k < n; k++) { double w[3] = {(double)r->choice[k], r->start[k], (double)r->blocker[k]}; fwrite(w, 8, 3, o); }
+    }
+    std::fclose(o);
+    return 0;
+}
+"""
+
+
+def test_cpp_adapter_matches_ctypes_bit_for_bit(tmp_path, analytic_cells):
+    """D6: ALMTrajOpt::delaySweepSE2TrajBatch (one object and two) / delayExtentSE2TrajBatch / delaysSE2TrajBatch from a compiled C++ consumer (after
+    planSE2TrajBatch) against plan_goals + delay_sweep / delay_extent / delays through ctypes"""
+    import uneven_planner_amd as U
+    from uneven_planner_amd import scenes
+    m = U.UnevenMap()
+    m.set_cells(analytic_cells)
+    ka = U.KinoAstar(m)
+    S, G = scenes.random_queries(24, seed0=9900)
+    t0 = 100.0 + 0.5 * np.arange(S.shape[0])
+    rad = 0.2 + 0.05 * (np.arange(S.shape[0]) % 5)
+    mk = dict(piece_len=0.3, mean_vel=0.5, init_time_times=1.2, yaw_piece_times=2.0, init_sig_vel=0.05, test_mode=0, test_max_vel=0.5)
+    opt = U.ALMTrajOpt(m)
+    opt.set_rho(1.0)
+    plan = opt.plan_goals(ka, S, G, **mk)
+    second = U.ALMTrajOpt(m)
+    second.set_rho(1.0)
+    second.plan_goals(ka, S, G, **mk)
+    src_ = tmp_path / "delay.cpp"
+    src_.write_text(CPP)
+    exe = str(tmp_path / "delay")
+    libdir = os.path.join(ROOT, "uneven_planner_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(src_), "-o", exe, "-L", libdir, "-lunevenhip",
+                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    cells = np.ascontiguousarray(analytic_cells, dtype=np.float64)
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<2q", cells.shape[0], S.shape[0]))
+        f.write(cells.tobytes())
+        f.write(np.ascontiguousarray(np.concatenate([S, G, t0[:, None], rad[:, None]], axis=1), dtype=np.float64).tobytes())
+    subprocess.check_call([exe, fin, fout])
+    raw = np.fromfile(fout, dtype=np.float64)
+    n, D = int(raw[0]), 12
+    live = [b for b in range(S.shape[0]) if plan[b]["status"] == 0 and plan[b]["ret"] != 4]
+    tr = np.array([plan[b]["traj_of"] for b in live], dtype=np.int32)
+    assert n == len(tr) >= 10 and raw[1:1 + n].astype(int).tolist() == tr.tolist()
+    t0, rad = t0[live], rad[live]
+    tf, tt = t0 - 0.5, t0 + 12.0
+    tb, t0b = np.roll(tr, -1), np.roll(t0, -1)
+    at = 1 + n
+    per = 3 * D + 2
+    for want in (opt.delay_sweep(tr, tb, tf, tt, rad, -1.0, 0.5, D, t0_a=t0, t0_b=t0b), opt.delay_sweep(tr, tb, tf, tt, rad, -1.0, 0.5, D, t0_a=t0, t0_b=t0b, other=second, dt=0.05)):
+        blk = raw[at:at + per * n].reshape(n, per)
+        rows = blk[:, :3 * D].reshape(n, D, 3)
+        _same(dict(min_d2=rows[:, :, 0], min_t=rows[:, :, 1], below=rows[:, :, 2].astype(np.int32), first_clear=blk[:, -2].astype(np.int32), counts=blk[:, -1].astype(np.int32)),
+              want, WKEYS, "adapter sweep")
+        assert (blk[:, -1] > 100).all() and np.isfinite(rows[:, :, 0]).all()
+        at += per * n
+    ext = raw[at:at + 6 * n].reshape(n, 6)
+    _same(dict(box=ext[:, :4], counts=ext[:, 4:].astype(np.int32)), opt.delay_extent(tr, tf, tt, -1.0, 0.5, D, t0=t0), ("box", "counts"), "adapter swept extent")
+    at += 6 * n
+    nd = 1 + np.arange(n) % 12
+    for want in (opt.delays(tr, rad, 99.0, 130.0, 0.0, 0.5, D, t0=t0), opt.delays(tr, rad, 99.0, 130.0, 0.0, 0.5, D, t0=t0, n_delays=nd, dt=0.1)):
+        assert tuple(int(v) for v in raw[at:at + 3]) == (want["n_candidates"], want["n_rounds"], want["n_unresolved"])
+        rows = raw[at + 3:at + 3 + 3 * n].reshape(n, 3)
+        at += 3 + 3 * n
+        _same(dict(choice=rows[:, 0].astype(np.int32), start=rows[:, 1], blocker=rows[:, 2].astype(np.int32)), want, ("choice", "start", "blocker"), "adapter delays")
+    assert at == raw.size

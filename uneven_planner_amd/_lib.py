@@ -184,6 +184,14 @@ SYMBOLS = {
     "uph_conflicts_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, C.c_double, C.c_double, _I64, C.POINTER(_I32), DP, C.POINTER(_I32),
                                       C.POINTER(_I64), C.POINTER(_I64)]),
     "uph_separation_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_delay_times": (C.c_int, [C.c_double, C.c_double, _I32, DP]),
+    "uph_delay_levels": (C.c_int, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_delay_sweep_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, C.c_double, C.c_double, _I32, DP, DP,
+                                        C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_delay_extent_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, C.c_double, C.c_double, _I32, DP, C.POINTER(_I32)]),
+    "uph_delays_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.POINTER(_I32), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I32,
+                                   C.POINTER(_I32), DP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_delay_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None
@@ -199,6 +207,10 @@ UPH_KINO_OK = 0
 UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
 UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
 SEPARATION_MAX_SAMPLES = 1 << 22     # include/uneven_hip.h: samples of one query on the common clock
+DELAY_MAX = 4096           # include/uneven_hip.h: delays of one table
+DELAY_MAX_WORK = 1 << 26   # include/uneven_hip.h: samples times delays of one query
+DELAY_ROWS = 1 << 20       # include/uneven_hip.h: sweep rows on the device at a time
+DELAY_TILE = 128           # include/uneven_hip.h UPH_DELAY_TILE: samples of a tile of the sweep kernel
 TRAJ_STATE_COLS = 10       # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
 
 

@@ -412,6 +412,60 @@ def conflict_candidates(box, radius):
     return np.argwhere(keep).astype(np.int32).reshape(-1, 2)
 
 
+# uph_delay_times / uph_delay_levels / uph_delays_batch (include/uneven_hip.h): numpy mirrors written from the rule
+def delay_times(delay0, delay_step, D):
+    """Host mirror of the table of start delays: delta_j = delay0 + j * delay_step (the product rounded, then the sum) for 0 <= j < D.  Raises for
+    what the library refuses."""
+    delay0, delay_step, D = float(delay0), float(delay_step), int(D)
+    if not (np.isfinite(delay0) and np.isfinite(delay_step) and delay_step > 0.0 and D >= 1):
+        raise _lib.UnevenHipError("delay_times: delay0 must be finite, delay_step positive and finite and D at least 1")
+    if D > _lib.DELAY_MAX:
+        raise _lib.UnevenHipError("delay_times: more than 4096 delays")
+    with np.errstate(over="ignore"):
+        p = np.arange(D, dtype=np.float64) * delay_step
+        return delay0 + p
+
+
+def delay_levels(pairs, n):
+    """Host mirror of uph_delay_levels: the level of each of n vehicles among pairs (m, 2), i < j: 0 for a vehicle without a smaller partner, else
+    1 + the largest level of its smaller partners.  The vehicles of one level do not depend on each other's choice."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.shape[0] and not ((0 <= pairs[:, 0]) & (pairs[:, 0] < pairs[:, 1]) & (pairs[:, 1] < n)).all():
+        raise _lib.UnevenHipError("delay_levels: a pair does not have 0 <= i < j < n")
+    level = np.zeros(n, dtype=np.int32)
+    for j, i in sorted(map(tuple, pairs[:, ::-1].tolist())):        # by the larger index j: the levels of its smaller partners i are final
+        level[j] = max(level[j], level[i] + 1)
+    return level
+
+
+def delay_schedule(sweep, pairs, n, n_delays=None, order=None):
+    """Host mirror of uph_delays_batch's schedule, the sequential greedy: vehicles 0 .. n - 1 in priority order, pairs (m, 2) the kept pairs h < i.
+    sweep(h, at_h, i) returns below (D,) of vehicle i swept against vehicle h standing at delay at_h = max(choice[h], 0) of the table; n_delays (n,)
+    limits the delays a vehicle may use (None: all).  choice[i] is the smallest j < n_delays[i] with below == 0 against every partner h < i (0 without
+    one); -1 when there is none -- the vehicle then counts at delay 0 for those behind it -- with blocker[i] the smallest h below at delay 0 (-1
+    otherwise).  order: the sequence in which the vehicles are placed (None: 0 .. n - 1); every partner ahead must have been placed before."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ahead = [[] for _ in range(n)]
+    for h, i in sorted(map(tuple, pairs.tolist())):
+        ahead[i].append(h)
+    choice, blocker = np.zeros(n, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    placed = np.zeros(n, dtype=bool)
+    for i in (range(n) if order is None else order):
+        assert all(placed[h] for h in ahead[i]), "delay_schedule: a vehicle ahead of %d is not placed yet" % i
+        placed[i] = True
+        if not ahead[i]:
+            continue
+        below = np.stack([np.asarray(sweep(h, max(int(choice[h]), 0), i)) for h in ahead[i]])
+        nd = below.shape[1] if n_delays is None else int(n_delays[i])
+        clear = np.nonzero((below[:, :nd] == 0).all(axis=0))[0]
+        if clear.size:
+            choice[i] = clear[0]
+        else:
+            choice[i] = -1
+            blocker[i] = ahead[i][int(np.nonzero(below[:, 0] > 0)[0][0])]
+    return dict(choice=choice, blocker=blocker)
+
+
 class ALMTrajOpt:
     def __init__(self, uneven_map=None, params=None):
         self.L = _lib.load()
@@ -996,6 +1050,56 @@ class ALMTrajOpt:
         """milliseconds of the kernels of the last extent(), separation() or conflicts() (events on the context's stream)"""
         ms = C.c_double(0)
         _lib.check(self.L.uph_separation_kernel_ms(self.h, C.byref(ms)), "uph_separation_kernel_ms")
+        return ms.value
+
+    # ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch) ----------------------------------------------------------------
+    def delay_sweep(self, traj_a, traj_b, t_from, t_to, radius, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
+        """separation() of vehicle a against vehicle b for every start t0_b[q] + delay_times(delay0, delay_step, D)[j] of b, on the device in one call:
+        min_d2, min_t and below (n, D) -- each what separation() returns for that start --, first_clear (n,) = the smallest j with below == 0 (-1:
+        none) and counts (n,) = the samples K of the window.  Broadcasting and `other` as separation()."""
+        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "delay_sweep", t0_a=t0_a, t0_b=t0_b, radius=radius)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        D = int(D)
+        m = max(D, 1)
+        out = dict(min_d2=np.full((n, m), np.inf), min_t=np.full((n, m), np.nan), below=np.zeros((n, m), dtype=np.int32), first_clear=np.full(n, -1, dtype=np.int32),
+                   counts=np.zeros(n, dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_delay_sweep_batch(self.h, None if other is None else other.h, n, ip(tr), ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
+                                                _dp(v["radius"]), float(delay0), float(delay_step), D, _dp(out["min_d2"]), _dp(out["min_t"]), ip(out["below"]),
+                                                ip(out["first_clear"]), ip(out["counts"])), "uph_delay_sweep_batch")
+        return out
+
+    def delay_extent(self, traj, t_from, t_to, delay0, delay_step, D, t0=0.0, dt=0.01):
+        """The hull over the delays of the table of extent(traj, t_from, t_to, t0 + delta_j), on the device in one call: box (n, 4) and counts (n, 2:
+        samples K of the window, samples with a NaN position over all delays).  The input of a broad phase that holds under every delay."""
+        tr, n, tf, tt, v = self._clock(traj, t_from, t_to, "delay_extent", t0=t0)
+        out = dict(box=np.tile([np.inf, -np.inf, np.inf, -np.inf], (n, 1)), counts=np.zeros((n, 2), dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(self.L.uph_delay_extent_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), float(delay0), float(delay_step), int(D), _dp(out["box"]),
+                                                 ip(out["counts"])), "uph_delay_extent_batch")
+        return out
+
+    def delays(self, traj, radius, t_from, t_to, delay0, delay_step, D, t0=0.0, n_delays=None, dt=0.05):
+        """Start delays that clear a fleet: vehicle i is resident trajectory traj[i] started at t0[i] with a disc of radius[i], in priority order (the
+        smaller index goes first), one window for all.  Each vehicle gets the smallest delay of delay_times(delay0, delay_step, D) -- among its first
+        n_delays[i] (None: all; a scalar is broadcast) -- at which it is never below r_h + r_i against any vehicle h ahead of it at ITS chosen start.
+        Returns choice (n,; -1: no such delay, the vehicle stays at delay 0 and needs a new plan), start (n,) the effective starts, blocker (n,; the
+        first vehicle in the way of an unresolved one, else -1), n_candidates, n_rounds and n_unresolved.  See delay_schedule."""
+        tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "delays", t0=t0, radius=radius)
+        nd = None if n_delays is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_delays, dtype=np.int32), (n,)))
+        out = dict(choice=np.zeros(n, dtype=np.int32), start=np.full(n, np.nan), blocker=np.full(n, -1, dtype=np.int32))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        nk, nr, nu = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(self.L.uph_delays_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(v["radius"]), None if nd is None else ip(nd), float(t_from), float(t_to), float(dt),
+                                           float(delay0), float(delay_step), int(D), ip(out["choice"]), _dp(out["start"]), ip(out["blocker"]), C.byref(nk), C.byref(nr),
+                                           C.byref(nu)), "uph_delays_batch")
+        out.update(n_candidates=int(nk.value), n_rounds=int(nr.value), n_unresolved=int(nu.value))
+        return out
+
+    def delay_kernel_ms(self):
+        """milliseconds of the kernels of the last delay_sweep(), delay_extent() or delays() (events on the context's stream)"""
+        ms = C.c_double(0)
+        _lib.check(self.L.uph_delay_kernel_ms(self.h, C.byref(ms)), "uph_delay_kernel_ms")
         return ms.value
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------

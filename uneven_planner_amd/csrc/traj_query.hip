@@ -1,6 +1,6 @@
 // libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
-// separation / extent / conflicts on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states,
-// uph_separation_*, uph_extent_batch, uph_conflict*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// separation / extent / conflicts and the start delays on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch,
+// uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record (WinQuery: trajectory,
@@ -546,6 +546,183 @@ __global__ __launch_bounds__(NT) void uph_extent_kernel(ExtArgs a) {
     a.out[eq.out] = o;
 }
 
+// ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch): the separation / the extent of a query for every start t0 + delta_j of a
+// table of D delays that all queries of a launch share (formed on the host: the device only adds).  One workgroup per query, lanes own DELAYS, not samples:
+// the samples are walked in tiles of DELAY_TILE, ascending inside a lane, so a lane's (d2, k) selection meets the tie rule without a cross-lane step.
+//   few delays (D * G <= NT, G the largest such power of two): the G lanes tid = dl * G + g of delay dl take the samples g, g + G, ... of each tile and are
+//       folded once, after the last tile, through LDS -- a selection under a total order and integer sums: the split cannot show in the result;
+//   many delays (D > NT): P = ceil(D / NT) passes per tile; a lane's rows carry its state from tile to tile (its own loads after its own stores).
+struct DelayQuery : ClockQuery {
+    int32_t D, pad;             // delays of the table; the query's rows are out * D .. out * D + D - 1
+};
+struct SweepQuery : DelayQuery {
+    double R2;
+    ClockTraj a, b;             // b is the one delayed
+};
+struct DextQuery : DelayQuery {
+    ClockTraj a;
+};
+struct SweepOut {               // one row per (query, delay)
+    double min_d2, min_t;       // as SepOut
+    int32_t below, k;           // samples below; the sample of the minimum (WIN_NONE: none)
+};
+struct SweepArgs {
+    ResidentDev ra, rb;
+    const SweepQuery* qs;
+    SweepOut* out;
+    const double* delta;        // [D]
+    int framed_a, framed_b, q0;
+};
+struct DextArgs {
+    ResidentDev r;
+    const DextQuery* qs;
+    ExtOut* out;
+    const double* delta;
+    int framed, q0;
+};
+constexpr int DELAY_TILE = 128;             // samples of a tile (UPH_DELAY_TILE)
+static_assert(DELAY_TILE == UPH_DELAY_TILE, "the tile length the header documents");
+
+struct DelaySplit {
+    int G, DL, P;               // lanes per delay, delays per pass, passes
+};
+template <int NT>
+__device__ __forceinline__ DelaySplit delaySplit(int D) {
+    DelaySplit s;
+    s.G = 1;
+    while (2 * s.G * D <= NT) s.G *= 2;
+    s.DL = NT / s.G;
+    s.P = (D + s.DL - 1) / s.DL;
+    return s;
+}
+// The double loop both kernels run.  A body provides
+//   park(k0, m)   the workgroup prepares samples k0 .. k0 + m - 1 of the tile (uniform; may hold barriers),
+//   open(j)       this lane begins delay j for the tile,
+//   sample(s, k)  sample k = k0 + s of the query under the delay that is open,
+//   close(j)      the delay's samples of the tile are done,
+//   release()     the tile is done (uniform).
+template <class Body>
+__device__ __forceinline__ void delayLoop(const DelayQuery& q, const DelaySplit& sp, Body& body) {
+    const int dl = (int)threadIdx.x / sp.G, g = (int)threadIdx.x % sp.G;
+    for (int k0 = 0; k0 < q.K; k0 += DELAY_TILE) {
+        const int m = q.K - k0 < DELAY_TILE ? q.K - k0 : DELAY_TILE;
+        body.park(k0, m);
+        for (int p = 0; p < sp.P; p++) {
+            const int j = p * sp.DL + dl;
+            if (j >= q.D) continue;
+            body.open(j);
+            for (int s = g; s < m; s += sp.G) body.sample(s, k0 + s);
+            body.close(j);
+        }
+        body.release();
+    }
+}
+
+template <int NT>
+struct SweepBody {
+    const SweepQuery& sq;
+    const SweepArgs& a;
+    ClockView va, vb;
+    double t0_b;
+    double* ax;                 // [DELAY_TILE] a's positions of the tile, in LDS
+    double* ay;
+    bool spill;                 // more than one pass: the state lives in the lane's row between tiles
+    double v;
+    int i, cnt;
+    __device__ __forceinline__ SweepOut* row(int j) const { return a.out + (size_t)sq.out * sq.D + j; }
+    __device__ __forceinline__ void put(int j) const {
+        SweepOut o;
+        o.min_d2 = v; o.min_t = i == WIN_NONE ? __builtin_nan("") : clockTau(sq, i);
+        o.below = cnt; o.k = i;
+        *row(j) = o;
+    }
+    __device__ __forceinline__ void park(int k0, int m) {
+        for (int s = (int)threadIdx.x; s < m; s += NT) {
+            double X, Y;
+            clockSample(va, clockTau(sq, k0 + s), X, Y);
+            ax[s] = X; ay[s] = Y;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void open(int j) {
+        vb.t0 = t0_b + a.delta[j];
+        if (spill) { const SweepOut o = *row(j); v = o.min_d2; i = o.k; cnt = o.below; }
+    }
+    __device__ __forceinline__ void sample(int s, int k) {
+        double Xb, Yb;
+        clockSample(vb, clockTau(sq, k), Xb, Yb);
+        const double d2 = locD2(ax[s] - Xb, ay[s] - Yb);
+        winTake<false>(v, i, d2 < __builtin_huge_val() ? d2 : __builtin_huge_val(), k);      // NaN: +inf
+        cnt += d2 < sq.R2 ? 1 : 0;                                                                // (a NaN d2 is not below)
+    }
+    __device__ __forceinline__ void close(int j) { if (spill) put(j); }
+    __device__ __forceinline__ void release() { __syncthreads(); }
+};
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(SweepArgs a) {
+    __shared__ double s_xy[2 * DELAY_TILE];
+    __shared__ double s_v[NT];
+    __shared__ int s_i[2 * NT];
+    const SweepQuery sq = a.qs[a.q0 + blockIdx.x];
+    const DelaySplit sp = delaySplit<NT>(sq.D);
+    SweepBody<NT> body{sq, a, clockView(a.ra, sq.a, a.framed_a != 0), clockView(a.rb, sq.b, a.framed_b != 0), sq.b.t0, s_xy, s_xy + DELAY_TILE, sp.P > 1,
+                       __builtin_huge_val(), WIN_NONE, 0};
+    const int dl = (int)threadIdx.x / sp.G, g = (int)threadIdx.x % sp.G;
+    if (body.spill) for (int j = (int)threadIdx.x; j < sq.D; j += NT) body.put(j);      // (G = 1: lane dl owns rows dl, dl + NT, ...)
+    delayLoop(sq, sp, body);
+    if (body.spill) return;
+    if (sp.G > 1) {             // the lanes of a delay, folded by its first lane
+        s_v[threadIdx.x] = body.v; s_i[2 * threadIdx.x] = body.i; s_i[2 * threadIdx.x + 1] = body.cnt;
+        __syncthreads();
+        if (g == 0)
+            for (int o = (int)threadIdx.x + 1; o < (int)threadIdx.x + sp.G; o++) { winTake<false>(body.v, body.i, s_v[o], s_i[2 * o]); body.cnt += s_i[2 * o + 1]; }
+    }
+    if (g == 0 && dl < sq.D) body.put(dl);
+}
+
+struct DextBody {
+    const DextQuery& eq;
+    const DextArgs& a;
+    ClockView va;
+    double t0;
+    double x0, x1, y0, y1;
+    int bad;
+    __device__ __forceinline__ void park(int, int) {}
+    __device__ __forceinline__ void open(int j) { va.t0 = t0 + a.delta[j]; }
+    __device__ __forceinline__ void sample(int, int k) {
+        double X, Y;
+        clockSample(va, clockTau(eq, k), X, Y);
+        if (X == X && Y == Y) {
+            x0 = X < x0 ? X : x0; x1 = X > x1 ? X : x1; y0 = Y < y0 ? Y : y0; y1 = Y > y1 ? Y : y1;
+        } else {
+            bad++;
+        }
+    }
+    __device__ __forceinline__ void close(int) {}
+    __device__ __forceinline__ void release() {}
+};
+
+// the hull over the delays of uph_extent_kernel's boxes: min and max are exact, so neither the split nor the fold can show
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_delay_extent_kernel(DextArgs a) {
+    __shared__ double s_red[(NT / 64 * 36 + 7) / 8];
+    const DextQuery eq = a.qs[a.q0 + blockIdx.x];
+    const double inf = __builtin_huge_val();
+    DextBody body{eq, a, clockView(a.r, eq.a, a.framed != 0), eq.a.t0, inf, -inf, inf, -inf, 0};
+    delayLoop(eq, delaySplit<NT>(eq.D), body);
+    const auto hull = [](double& x0, double& x1, double& y0, double& y1, int& c, double ox0, double ox1, double oy0, double oy1, int oc) {
+        x0 = ox0 < x0 ? ox0 : x0; x1 = ox1 > x1 ? ox1 : x1; y0 = oy0 < y0 ? oy0 : y0; y1 = oy1 > y1 ? oy1 : y1; c += oc;
+    };
+    rowReduce(hull, body.x0, body.x1, body.y0, body.y1, body.bad);
+    rowLeaders(hull, body.x0, body.x1, body.y0, body.y1, body.bad);
+    if (!acrossWaves<NT / 64>(hull, s_red, body.x0, body.x1, body.y0, body.y1, body.bad)) return;
+    ExtOut o;
+    o.box[0] = body.x0; o.box[1] = body.x1; o.box[2] = body.y0; o.box[3] = body.y1;
+    o.counts[0] = eq.K; o.counts[1] = body.bad;
+    a.out[eq.out] = o;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static ResidentDev residentDev(uph_ctx* c) {
     ResidentDev r;
@@ -838,18 +1015,22 @@ static ClockTraj clockTraj(const uph_ctx* c, int32_t b, double t0) {
     return r;
 }
 
-// n <= CLOCK_CHUNK queries in the caller's order -> their rows in that order: the records in launch order (the most samples first, stable) on the device, 256
-// lanes for the queries of more than LOC_SHORT samples at the head and one wave for the rest (as locRun), the kernels' time added to ms
+// the samples a query's workgroup evaluates: what the launch order and the launch width go by
+static int64_t clockWork(const ClockQuery& q) { return q.K; }
+static int64_t clockWork(const DelayQuery& q) { return (int64_t)q.K * q.D; }
+
+// n <= CLOCK_CHUNK queries in the caller's order -> their rows (`per` of them each) in that order: the records in launch order (the most samples first, stable) on
+// the device, 256 lanes for the queries of more than LOC_SHORT samples at the head and one wave for the rest (as locRun), the kernels' time added to ms
 template <class Q, class Out, class Args, class K256, class K64>
-static int clockRun(uph_ctx* c, Q* qs, size_t n, Args a, K256 k256, K64 k64, Out* rows, double& ms) {
+static int clockRun(uph_ctx* c, Q* qs, size_t n, Args a, K256 k256, K64 k64, Out* rows, double& ms, size_t per = 1) {
     for (size_t q = 0; q < n; q++) qs[q].out = (int32_t)q;
-    std::stable_sort(qs, qs + n, [](const Q& x, const Q& y) { return x.K > y.K; });
+    std::stable_sort(qs, qs + n, [](const Q& x, const Q& y) { return clockWork(x) > clockWork(y); });
     size_t n_long = 0;
-    while (n_long < n && qs[n_long].K > LOC_SHORT) n_long++;
-    if (c->d_win_q.ensure(sizeof(Q) * n) || c->d_win_out.ensure(sizeof(Out) * n)) return UPH_ERR_HIP;
+    while (n_long < n && clockWork(qs[n_long]) > LOC_SHORT) n_long++;
+    if (c->d_win_q.ensure(sizeof(Q) * n) || c->d_win_out.ensure(sizeof(Out) * n * per)) return UPH_ERR_HIP;
     HIPCHK(hipMemcpyAsync(c->d_win_q.p, qs, sizeof(Q) * n, hipMemcpyHostToDevice, c->stream));
     a.qs = c->d_win_q.as<Q>(); a.out = c->d_win_out.as<Out>(); a.q0 = 0;
-    std::vector<Out> out(n);
+    std::vector<Out> out(n * per);
     double one = 0.0;
     const int r = runQueryLaunch(c, [&]() {
         hipError_t le = hipSuccess;
@@ -921,6 +1102,86 @@ static int candidatePairs(int32_t n, const double* box, const double* radius, co
     }
     std::sort(pairs.begin(), pairs.end());
     return UPH_OK;
+}
+
+// ---- start delays (include/uneven_hip.h uph_delay_*) -------------------------------------------------------------------------------------------------
+constexpr int32_t DELAY_MAX = 4096;                         // delays of one table
+constexpr int64_t DELAY_MAX_WORK = (int64_t)1 << 26;        // K * D of one query: a workgroup's serial work is at most that of 16 separation queries of CLOCK_MAX_SAMPLES
+constexpr size_t DELAY_ROWS = (size_t)1 << 20;              // sweep rows of one launch pair (24 MB on the device)
+
+// delta_j = delay0 + j * delay_step by clockTau's rule
+static int delayTable(double delay0, double delay_step, int32_t D, std::vector<double>& delta, const std::string& who) {
+    if (!(delay_step > 0.0) || !std::isfinite(delay_step)) { setError(who + ": delay_step must be positive and finite"); return UPH_ERR_INVALID; }
+    if (!std::isfinite(delay0)) { setError(who + ": delay0 is not finite"); return UPH_ERR_INVALID; }
+    if (D < 1) { setError(who + ": D must be at least 1"); return UPH_ERR_INVALID; }
+    if (D > DELAY_MAX) { setError(who + ": more than 4096 delays"); return UPH_ERR_LIMIT; }
+    delta.resize((size_t)D);
+    for (int32_t j = 0; j < D; j++) delta[(size_t)j] = clockTauHost(delay0, j, delay_step);
+    return UPH_OK;
+}
+// every start t0[q] + delta_j is finite (delta_j does not decrease with j and rounding is monotone: the two ends decide)
+static int delayStarts(int32_t n, const double* t0, const std::vector<double>& delta, const std::string& who) {
+    for (int32_t q = 0; q < n; q++)
+        if (!std::isfinite(t0[q] + delta.front()) || !std::isfinite(t0[q] + delta.back())) {
+            setError(who + ": query " + std::to_string(q) + " has a delayed start that is not finite"); return UPH_ERR_INVALID;
+        }
+    return UPH_OK;
+}
+static int delayWork(int64_t K, int32_t D, const std::string& who) {
+    if (K * (int64_t)D > DELAY_MAX_WORK) { setError(who + ": more than 2^26 samples times delays"); return UPH_ERR_LIMIT; }
+    return UPH_OK;
+}
+static int delayUpload(uph_ctx* c, const std::vector<double>& delta) {
+    if (c->d_delay.ensure(8 * delta.size())) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_delay.p, delta.data(), 8 * delta.size(), hipMemcpyHostToDevice, c->stream));
+    return UPH_OK;
+}
+// the queries of one launch pair: the rows stay below DELAY_ROWS and the records below CLOCK_CHUNK
+static size_t delayChunk(int32_t D) { return std::max<size_t>(1, std::min(CLOCK_CHUNK, DELAY_ROWS / (size_t)D)); }
+
+// the sweeps of qs (K, t_from, dt, R2, a, b set; the table is on ca's device) -> rows [qs.size()][D] in the caller's order
+static int sweepRun(uph_ctx* ca, uph_ctx* cb, std::vector<SweepQuery>& qs, int32_t D, std::vector<SweepOut>& rows, double& ms) {
+    rows.resize(qs.size() * (size_t)D);
+    SweepArgs a;
+    a.ra = residentDev(ca); a.rb = residentDev(cb);
+    a.framed_a = ca->frames.empty() ? 0 : 1; a.framed_b = cb->frames.empty() ? 0 : 1;
+    a.qs = nullptr; a.out = nullptr; a.delta = ca->d_delay.as<double>(); a.q0 = 0;
+    const size_t chunk = delayChunk(D);
+    for (size_t s = 0; s < qs.size(); s += chunk) {
+        const size_t m = std::min(chunk, qs.size() - s);
+        for (size_t k = 0; k < m; k++) { qs[s + k].D = D; qs[s + k].pad = 0; }
+        const int r = clockRun(ca, qs.data() + s, m, a, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows.data() + s * (size_t)D, ms, (size_t)D);
+        if (r != UPH_OK) return r;
+    }
+    return UPH_OK;
+}
+// the swept extents of n vehicles of c (already checked), as extentRun
+static int delayExtentRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const int64_t* K, double dt, int32_t D,
+                          std::vector<ExtOut>& out, double& ms) {
+    DextArgs a;
+    a.r = residentDev(c); a.framed = c->frames.empty() ? 0 : 1; a.qs = nullptr; a.out = nullptr; a.delta = c->d_delay.as<double>(); a.q0 = 0;
+    out.resize((size_t)n);
+    std::vector<DextQuery> qs;
+    for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
+        const size_t m = std::min(CLOCK_CHUNK, (size_t)n - s);
+        qs.assign(m, DextQuery());
+        for (size_t k = 0; k < m; k++) {
+            DextQuery& q = qs[k];
+            q.K = (int32_t)K[s + k]; q.t_from = t_from[s + k]; q.dt = dt; q.D = D; q.pad = 0;
+            q.a = clockTraj(c, traj[s + k], t0[s + k]);
+        }
+        const int r = clockRun(c, qs.data(), m, a, uph_delay_extent_kernel<256>, uph_delay_extent_kernel<64>, out.data() + s, ms);
+        if (r != UPH_OK) return r;
+    }
+    return UPH_OK;
+}
+// level of vehicle j among pairs (i < j, already checked): 0 without a smaller partner, else 1 + the largest level of its smaller partners
+static void delayLevels(int32_t n, const std::vector<IdxPair>& pairs, std::vector<int32_t>& level) {
+    std::vector<IdxPair> by_j(pairs.size());
+    for (size_t k = 0; k < pairs.size(); k++) by_j[k] = IdxPair(pairs[k].second, pairs[k].first);
+    std::sort(by_j.begin(), by_j.end());
+    level.assign((size_t)n, 0);
+    for (const IdxPair& p : by_j) level[(size_t)p.first] = std::max(level[(size_t)p.first], level[(size_t)p.second] + 1);     // (the levels of i < j are final)
 }
 
 extern "C" {
@@ -1231,6 +1492,187 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
 int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms) {
     if (!c || !kernel_ms) { setError("uph_separation_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
     *kernel_ms = c->last_sep_ms;
+    return UPH_OK;
+}
+
+// ---- start delays (include/uneven_hip.h) -----------------------------------------------------------------------------------------------------------------
+int uph_delay_times(double delay0, double delay_step, int32_t D, double* delta) {
+    if (!delta) { setError("uph_delay_times: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<double> tab;
+    const int r = delayTable(delay0, delay_step, D, tab, "uph_delay_times");
+    if (r != UPH_OK) return r;
+    std::copy(tab.begin(), tab.end(), delta);
+    return UPH_OK;
+}
+
+int uph_delay_levels(int32_t n, int64_t n_pairs, const int32_t* pairs, int32_t* level) {
+    if (n < 0 || n_pairs < 0 || (n_pairs > 0 && !pairs) || (n > 0 && !level)) { setError("uph_delay_levels: bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<IdxPair> ps((size_t)n_pairs);
+    for (int64_t k = 0; k < n_pairs; k++) {
+        const int32_t i = pairs[2 * k], j = pairs[2 * k + 1];
+        if (!(0 <= i && i < j && j < n)) { setError("uph_delay_levels: pair " + std::to_string(k) + " does not have 0 <= i < j < n"); return UPH_ERR_INVALID; }
+        ps[(size_t)k] = IdxPair(i, j);
+    }
+    std::vector<int32_t> lv;
+    delayLevels(n, ps, lv);
+    std::copy(lv.begin(), lv.end(), level);
+    return UPH_OK;
+}
+
+int uph_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b, const double* t_from,
+                          const double* t_to, double dt, const double* radius, double delay0, double delay_step, int32_t D, double* min_d2, double* min_t, int32_t* below,
+                          int32_t* first_clear, int32_t* counts) {
+    const std::string who = "uph_delay_sweep_batch";
+    if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    if (!cb) cb = ca;
+    if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError(who + ": the two contexts are on different devices"); return UPH_ERR_INVALID; }
+    int r = clockSide(ca, n, traj_a, t0_a, who.c_str());
+    if (r == UPH_OK) r = clockSide(cb, n, traj_b, t0_b, who.c_str());
+    if (r != UPH_OK) return r;
+    std::vector<double> delta;
+    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0_b, delta, who)) != UPH_OK) return r;
+    std::vector<SweepQuery> qs((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError(who + ": query " + std::to_string(q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+        int64_t K = 0;
+        if ((r = clockWindow(t_from[q], t_to[q], dt, K, who + ": query " + std::to_string(q))) != UPH_OK) return r;
+        if ((r = delayWork(K, D, who + ": query " + std::to_string(q))) != UPH_OK) return r;
+        SweepQuery& k = qs[(size_t)q];
+        k.K = (int32_t)K; k.t_from = t_from[q]; k.dt = dt; k.R2 = radius[q] * radius[q];
+        k.a = clockTraj(ca, traj_a[q], t0_a[q]); k.b = clockTraj(cb, traj_b[q], t0_b[q]);
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
+    if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // as uph_separation_batch
+    if ((r = delayUpload(ca, delta)) != UPH_OK) return r;
+    std::vector<int32_t> Ks((size_t)n);
+    for (int32_t q = 0; q < n; q++) Ks[(size_t)q] = qs[(size_t)q].K;       // (sweepRun leaves qs in launch order)
+    std::vector<SweepOut> rows;
+    double ms = 0.0;
+    if ((r = sweepRun(ca, cb, qs, D, rows, ms)) != UPH_OK) return r;
+    ca->last_delay_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        int32_t clear = -1;
+        for (int32_t j = 0; j < D; j++) {
+            const size_t at = (size_t)q * D + j;
+            const SweepOut& o = rows[at];
+            if (min_d2) min_d2[at] = o.min_d2;
+            if (min_t) min_t[at] = o.min_t;
+            if (below) below[at] = o.below;
+            if (clear < 0 && o.below == 0) clear = j;
+        }
+        if (first_clear) first_clear[q] = clear;
+        if (counts) counts[q] = Ks[(size_t)q];
+    }
+    return UPH_OK;
+}
+
+int uph_delay_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt, double delay0, double delay_step,
+                           int32_t D, double* box, int32_t* counts) {
+    const std::string who = "uph_delay_extent_batch";
+    if (!c || n <= 0 || !traj || !t0 || !t_from || !t_to) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    int r = clockSide(c, n, traj, t0, who.c_str());
+    if (r != UPH_OK) return r;
+    std::vector<double> delta;
+    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0, delta, who)) != UPH_OK) return r;
+    std::vector<int64_t> K((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        if ((r = clockWindow(t_from[q], t_to[q], dt, K[(size_t)q], who + ": query " + std::to_string(q))) != UPH_OK) return r;
+        if ((r = delayWork(K[(size_t)q], D, who + ": query " + std::to_string(q))) != UPH_OK) return r;
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    if ((r = delayUpload(c, delta)) != UPH_OK) return r;
+    std::vector<ExtOut> out;
+    double ms = 0.0;
+    if ((r = delayExtentRun(c, n, traj, t0, t_from, K.data(), dt, D, out, ms)) != UPH_OK) return r;
+    c->last_delay_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const ExtOut& o = out[(size_t)q];
+        if (box) for (int k = 0; k < 4; k++) box[4 * (size_t)q + k] = o.box[k];
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays, double t_from, double t_to, double dt,
+                     double delay0, double delay_step, int32_t D, int32_t* choice, double* start, int32_t* blocker, int64_t* n_candidates, int32_t* n_rounds,
+                     int32_t* n_unresolved) {
+    const std::string who = "uph_delays_batch";
+    if (!c || n <= 0 || !traj || !t0 || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    int r = clockSide(c, n, traj, t0, who.c_str());
+    if (r != UPH_OK) return r;
+    for (int32_t i = 0; i < n; i++)
+        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError(who + ": vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+    std::vector<double> delta;
+    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0, delta, who)) != UPH_OK) return r;
+    if (n_delays) for (int32_t i = 0; i < n; i++)
+        if (n_delays[i] < 1 || n_delays[i] > D) { setError(who + ": vehicle " + std::to_string(i) + " has an n_delays outside [1, D]"); return UPH_ERR_INVALID; }
+    int64_t K = 0;
+    if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK || (r = delayWork(K, D, who)) != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    if ((r = delayUpload(c, delta)) != UPH_OK) return r;
+    // swept extents on the device, candidates and their levels on the host
+    const std::vector<double> tf((size_t)n, t_from);
+    const std::vector<int64_t> Ks((size_t)n, K);
+    std::vector<ExtOut> ext;
+    double ms = 0.0;
+    if ((r = delayExtentRun(c, n, traj, t0, tf.data(), Ks.data(), dt, D, ext, ms)) != UPH_OK) return r;
+    std::vector<double> box(4 * (size_t)n);
+    for (int32_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) box[4 * (size_t)i + k] = ext[(size_t)i].box[k];
+    std::vector<IdxPair> cand;
+    if ((r = candidatePairs(n, box.data(), radius, who.c_str(), cand)) != UPH_OK) return r;
+    std::vector<int32_t> level;
+    delayLevels(n, cand, level);
+    const int32_t rounds = *std::max_element(level.begin(), level.end());
+    // a round per level: the vehicles of the level swept against their partners ahead, which are all placed by then
+    std::vector<std::vector<size_t>> cand_of((size_t)rounds + 1);       // the candidates of each level (that of the later vehicle), in (h, i) order
+    std::vector<std::vector<int32_t>> veh_of((size_t)rounds + 1);
+    for (size_t p = 0; p < cand.size(); p++) cand_of[(size_t)level[(size_t)cand[p].second]].push_back(p);
+    for (int32_t i = 0; i < n; i++) veh_of[(size_t)level[(size_t)i]].push_back(i);
+    std::vector<int32_t> ch((size_t)n, 0), blk((size_t)n, -1);
+    std::vector<char> taken((size_t)n * D, 0);      // [i][j]: vehicle i is below a partner ahead at delay j
+    std::vector<SweepQuery> qs;
+    std::vector<SweepOut> rows;
+    for (int32_t lv = 1; lv <= rounds; lv++) {
+        const std::vector<size_t>& of = cand_of[(size_t)lv];
+        qs.assign(of.size(), SweepQuery());
+        for (size_t k = 0; k < of.size(); k++) {
+            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
+            const double R = radius[h] + radius[i];
+            SweepQuery& q = qs[k];
+            q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.R2 = R * R;
+            q.a = clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]); q.b = clockTraj(c, traj[i], t0[i]);
+        }
+        if ((r = sweepRun(c, c, qs, D, rows, ms)) != UPH_OK) return r;
+        for (size_t k = 0; k < of.size(); k++) {        // (h ascending for each vehicle: the first h below at delay 0 is the smallest)
+            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
+            for (int32_t j = 0; j < D; j++) if (rows[k * (size_t)D + j].below > 0) taken[(size_t)i * D + j] = 1;
+            if (blk[(size_t)i] < 0 && rows[k * (size_t)D].below > 0) blk[(size_t)i] = h;
+        }
+        for (const int32_t i : veh_of[(size_t)lv]) {
+            const int32_t nd = n_delays ? n_delays[i] : D;
+            int32_t j = 0;
+            while (j < nd && taken[(size_t)i * D + j]) j++;
+            ch[(size_t)i] = j < nd ? j : -1;
+            if (j < nd) blk[(size_t)i] = -1;
+        }
+    }
+    c->last_delay_ms = ms;
+    int32_t unresolved = 0;
+    for (int32_t i = 0; i < n; i++) {
+        if (choice) choice[i] = ch[(size_t)i];
+        if (start) start[i] = t0[i] + delta[(size_t)std::max(ch[(size_t)i], 0)];
+        if (blocker) blocker[i] = blk[(size_t)i];
+        unresolved += ch[(size_t)i] < 0 ? 1 : 0;
+    }
+    if (n_candidates) *n_candidates = (int64_t)cand.size();
+    if (n_rounds) *n_rounds = rounds;
+    if (n_unresolved) *n_unresolved = unresolved;
+    return UPH_OK;
+}
+
+int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_delay_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_delay_ms;
     return UPH_OK;
 }
 
