@@ -2,8 +2,10 @@
 python tools/locate_bitid.py OUT.npz [B = 1024] -- on B hill goals planned and solved by plan_goals: the check (full windows at dt 0.01 with the end
 point, and the middle third of every duration at dt 0.03), the STATE rollout at dt 0.01 with the end point and every channel at dt 0.05,
 uph_traj_states at a third and two thirds of every duration, locate (every output) for poses made from the recorded rollout rows plus seeded noise and
-within for rects around the same rows, both on the check's two kinds of windows, and the switch states replan_goals_upload returns at a third of every
-duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
+within for rects around the same rows, both on the check's two kinds of windows, the common-clock calls on the fleet of tools/separation_probe.py and
+tools/delay_probe.py (the valid trajectories, starts uniform in [0, 60] s from seed 91, discs of 0.1 m, D = 32 delays of 0.5 s; the probes' window of 101
+samples, one wave, and one of 401, 256 lanes): extent, separation of vehicle i against i + 1, conflicts, delay_sweep, delay_extent and delays, and the
+switch states replan_goals_upload returns at a third of every duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
 python tools/check_bitid.py compare A.npz B.npz (np.array_equal, NaN equal to NaN)."""
 import os
 import sys
@@ -45,6 +47,19 @@ for tag, kw in (("full", dict()), ("third", dict(t_from=total / 3.0, t_to=2.0 * 
     for name, res_ in (("locate", opt.locate(valid, poses, **kw)), ("within", opt.within(valid, rects, **kw))):
         for k, v in res_.items():
             arrs["%s_%s_%s" % (name, tag, k)] = v
+# the clock families on the probes' fleet
+t0 = np.random.default_rng(91).uniform(0.0, 60.0, valid.size)
+other, t0_other = np.roll(valid, -1), np.roll(t0, -1)
+for tag, (tf, tt) in (("101", (30.0, 35.0)), ("401", (20.0, 40.0))):
+    calls = (("extent", opt.extent(valid, tf, tt, t0=t0, dt=0.05)),
+             ("separation", opt.separation(valid, other, tf, tt, 0.2, t0_a=t0, t0_b=t0_other, dt=0.05)),
+             ("conflicts", opt.conflicts(valid, 0.1, tf, tt, t0=t0, dt=0.05)),
+             ("delay_sweep", opt.delay_sweep(valid, other, tf, tt, 0.2, 0.0, 0.5, 32, t0_a=t0, t0_b=t0_other, dt=0.05)),
+             ("delay_extent", opt.delay_extent(valid, tf, tt, 0.0, 0.5, 32, t0=t0, dt=0.05)),
+             ("delays", opt.delays(valid, 0.1, tf, tt, 0.0, 0.5, 32, t0=t0, dt=0.05)))
+    for name, res_ in calls:
+        for k, v in res_.items():
+            arrs["%s_%s_%s" % (name, tag, k)] = np.asarray(v)
 arrs["replan_switch_states"] = opt.replan_goals_upload(ka, opt, valid, total / 3.0)["switch_states"]
 np.savez(out, build=np.array(U._lib.build_id() or ""), **arrs)
 print("%s: build %s  goals %d  resident %d  rollout rows %d  checked %d" % (out, U._lib.build_id(), B, len(res), arrs["rollout_state_0.01_end"].shape[0], valid.size))

@@ -42,6 +42,10 @@ def _dp(a):
     return a.ctypes.data_as(_lib.DP)
 
 
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 def norm_so2(yaw):
     """UnevenMap::normSO2 (uneven_map.cpp:63-70) as the device forms it (csrc/uph_common.hpp): whole turns added / removed one at a time"""
     y = float(yaw)
@@ -180,8 +184,7 @@ def rollout_sizes(n_xy, T_xy, n_yaw, T_yaw, dt=0.01, with_end=False):
     T_xy, T_yaw = np.ascontiguousarray(T_xy, dtype=np.float64), np.ascontiguousarray(T_yaw, dtype=np.float64)
     B = n_xy.shape[0]
     offs = np.zeros(B + 1, dtype=np.int64)
-    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    _lib.check(_lib.load().uph_rollout_sizes(B, pi(n_xy), _dp(T_xy), pi(n_yaw), _dp(T_yaw), float(dt), int(bool(with_end)),
+    _lib.check(_lib.load().uph_rollout_sizes(B, _ip(n_xy), _dp(T_xy), _ip(n_yaw), _dp(T_yaw), float(dt), int(bool(with_end)),
                                              offs.ctypes.data_as(C.POINTER(C.c_int64))), "uph_rollout_sizes")
     return offs
 
@@ -573,7 +576,7 @@ class ALMTrajOpt:
     def origin(self):
         """caller's index of every problem this context holds (identity unless the batch came through optimize_batch_multi)"""
         idx = np.zeros(max(0, self.L.uph_batch_count(self.h)), dtype=np.int32)
-        _lib.check(self.L.uph_batch_origin(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32))), "uph_batch_origin")
+        _lib.check(self.L.uph_batch_origin(self.h, _ip(idx)), "uph_batch_origin")
         return idx
 
     def download(self, full=True):
@@ -669,9 +672,8 @@ class ALMTrajOpt:
         B = s.shape[0]
         st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
         nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         self._B, self._sizes, self._last = 0, [], []
-        rc = self.L.uph_plan_upload(kino.h, self.h, C.byref(mp), B, _dp(s), _dp(g), int(path_cap), ip(st), ip(to), ip(nx), ip(ny))
+        rc = self.L.uph_plan_upload(kino.h, self.h, C.byref(mp), B, _dp(s), _dp(g), int(path_cap), _ip(st), _ip(to), _ip(nx), _ip(ny))
         return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny), "uph_plan_upload")
 
     @staticmethod
@@ -739,9 +741,8 @@ class ALMTrajOpt:
         st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
         nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
         sw = np.full((B, 9), np.nan)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = self.L.uph_replan_upload(kino.h, src.h, self.h, C.byref(mp), B, ip(tr), _dp(ts), None if g is None else _dp(g), int(path_cap), _dp(sw),
-                                      ip(st), ip(to), ip(nx), ip(ny))
+        rc = self.L.uph_replan_upload(kino.h, src.h, self.h, C.byref(mp), B, _ip(tr), _dp(ts), None if g is None else _dp(g), int(path_cap), _dp(sw),
+                                      _ip(st), _ip(to), _ip(nx), _ip(ny))
         if rc not in (0, _lib.UPH_ERR_INVALID):        # a failure past the refusals (which leave self's batch as it was): no batch is resident
             self._B, self._sizes, self._last = 0, [], []
         return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny, switch_states=sw), "uph_replan_upload")
@@ -761,7 +762,7 @@ class ALMTrajOpt:
         if n == 0 or ts.shape[0] != n:
             raise _lib.UnevenHipError("traj_states: traj and t must be the same non-empty length")
         out = np.zeros((n, _lib.TRAJ_STATE_COLS))
-        _lib.check(self.L.uph_traj_states(self.h, n, tr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(ts), _dp(out)), "uph_traj_states")
+        _lib.check(self.L.uph_traj_states(self.h, n, _ip(tr), _dp(ts), _dp(out)), "uph_traj_states")
         return out
 
     def refine_upload(self, src, src_traj, t_switch):
@@ -777,8 +778,7 @@ class ALMTrajOpt:
         st, to = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
         nx, ny = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
         sw = np.full((B, _lib.TRAJ_STATE_COLS), np.nan)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = self.L.uph_refine_upload(src.h, self.h, B, ip(tr), _dp(ts), _dp(sw), ip(st), ip(to), ip(nx), ip(ny))
+        rc = self.L.uph_refine_upload(src.h, self.h, B, _ip(tr), _dp(ts), _dp(sw), _ip(st), _ip(to), _ip(nx), _ip(ny))
         if rc != 0 and (rc != _lib.UPH_ERR_INVALID or (st >= 0).any()):      # past the refusals (which leave self's batch as it was): no batch is resident
             self._B, self._sizes, self._last = 0, [], []
         return self._planned(rc, dict(status=st, traj_of=to, n_inner_xy=nx, n_inner_yaw=ny, switch_states=sw), "uph_refine_upload")
@@ -830,8 +830,7 @@ class ALMTrajOpt:
         ixy, exy, iyw, eyw = np.zeros((B, 6)), np.zeros((B, 6)), np.zeros((B, 3)), np.zeros((B, 3))
         oxy, oyw = np.zeros((B, 2 * max(cap_xy, 1))), np.zeros((B, max(cap_yaw, 1)))
         nxy, nyw, tt = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros(B)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = self.L.uph_plan_staged(self.h, int(cap_xy), int(cap_yaw), _dp(ixy), _dp(exy), _dp(iyw), _dp(eyw), _dp(oxy), _dp(oyw), ip(nxy), ip(nyw), _dp(tt))
+        rc = self.L.uph_plan_staged(self.h, int(cap_xy), int(cap_yaw), _dp(ixy), _dp(exy), _dp(iyw), _dp(eyw), _dp(oxy), _dp(oyw), _ip(nxy), _ip(nyw), _dp(tt))
         if rc != _lib.UPH_ERR_LIMIT:      # a problem had more way-points than fit (complete = False below), the rest is written
             _lib.check(rc, "uph_plan_staged")
         kx, ky = min(cap_xy, _lib.PLAN_STAGE_XY), min(cap_yaw, _lib.PLAN_STAGE_YAW)
@@ -936,17 +935,19 @@ class ALMTrajOpt:
         lim = None if limits is None else np.ascontiguousarray(limits, dtype=np.float64).reshape(7)
         out = dict(first_t=np.full(n, np.nan), first_mask=np.zeros(n, dtype=np.int32), counts=np.zeros((n, 3), dtype=np.int32),
                    worst=np.full((n, 7), -np.inf), worst_t=np.full((n, 7), np.nan))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_check_batch(self.h, n, ip(tr), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
-                                          None if lim is None else _dp(lim), _dp(out["first_t"]), ip(out["first_mask"]), ip(out["counts"]),
+        _lib.check(self.L.uph_check_batch(self.h, n, _ip(tr), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                          None if lim is None else _dp(lim), _dp(out["first_t"]), _ip(out["first_mask"]), _ip(out["counts"]),
                                           _dp(out["worst"]), _dp(out["worst_t"])), "uph_check_batch")
         return out
 
+    def _kernel_ms(self, fn_name):
+        ms = C.c_double(0)
+        _lib.check(getattr(self.L, fn_name)(self.h, C.byref(ms)), fn_name)
+        return ms.value
+
     def check_kernel_ms(self):
         """milliseconds of uph_check_kernel in the last check() (events on the context's stream)"""
-        ms = C.c_double(0)
-        _lib.check(self.L.uph_check_kernel_ms(self.h, C.byref(ms)), "uph_check_kernel_ms")
-        return ms.value
+        return self._kernel_ms("uph_check_kernel_ms")
 
     # ---- poses located on resident trajectories, rects crossed by them (uph_locate_batch, uph_within_batch) ---------------------------------------
     def _windows(self, traj, t_from, t_to, rows, width, who):
@@ -969,9 +970,8 @@ class ALMTrajOpt:
         tr, n, tf, tt, ps = self._windows(traj, t_from, t_to, poses, 3, "locate")
         out = dict(near_t=np.full(n, np.nan), near_d2=np.full(n, np.inf), count=np.zeros(n, dtype=np.int32), t=np.full(n, np.nan),
                    refined=np.zeros(n, dtype=np.int32), state=np.full((n, _lib.TRAJ_STATE_COLS), np.nan), d2=np.full(n, np.inf), err=np.full((n, 3), np.nan))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_locate_batch(self.h, n, ip(tr), _dp(ps), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
-                                           _dp(out["near_t"]), _dp(out["near_d2"]), ip(out["count"]), _dp(out["t"]), ip(out["refined"]), _dp(out["state"]),
+        _lib.check(self.L.uph_locate_batch(self.h, n, _ip(tr), _dp(ps), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                           _dp(out["near_t"]), _dp(out["near_d2"]), _ip(out["count"]), _dp(out["t"]), _ip(out["refined"]), _dp(out["state"]),
                                            _dp(out["d2"]), _dp(out["err"])), "uph_locate_batch")
         return out
 
@@ -981,16 +981,13 @@ class ALMTrajOpt:
         and counts (n, 2: samples, inside); see within_rows."""
         tr, n, tf, tt, rc = self._windows(traj, t_from, t_to, rects, 4, "within")
         out = dict(enter_t=np.full(n, np.nan), leave_t=np.full(n, np.nan), counts=np.zeros((n, 2), dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_within_batch(self.h, n, ip(tr), _dp(rc), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
-                                           _dp(out["enter_t"]), _dp(out["leave_t"]), ip(out["counts"])), "uph_within_batch")
+        _lib.check(self.L.uph_within_batch(self.h, n, _ip(tr), _dp(rc), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)),
+                                           _dp(out["enter_t"]), _dp(out["leave_t"]), _ip(out["counts"])), "uph_within_batch")
         return out
 
     def locate_kernel_ms(self):
         """milliseconds of the kernel(s) of the last locate() or within(), whichever came last (events on the context's stream)"""
-        ms = C.c_double(0)
-        _lib.check(self.L.uph_locate_kernel_ms(self.h, C.byref(ms)), "uph_locate_kernel_ms")
-        return ms.value
+        return self._kernel_ms("uph_locate_kernel_ms")
 
     # ---- resident trajectories against each other on a common clock (uph_extent_batch, uph_separation_batch, uph_conflicts_batch) ---------------------
     def _clock(self, traj, t_from, t_to, who, **per_query):
@@ -1008,8 +1005,7 @@ class ALMTrajOpt:
         (n, 2: samples, NaN samples); see separation_times / extent_rows for the rule."""
         tr, n, tf, tt, v = self._clock(traj, t_from, t_to, "extent", t0=t0)
         out = dict(box=np.tile([np.inf, -np.inf, np.inf, -np.inf], (n, 1)), counts=np.zeros((n, 2), dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_extent_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), _dp(out["box"]), ip(out["counts"])), "uph_extent_batch")
+        _lib.check(self.L.uph_extent_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), _dp(out["box"]), _ip(out["counts"])), "uph_extent_batch")
         return out
 
     def separation(self, traj_a, traj_b, t_from, t_to, radius, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
@@ -1020,9 +1016,8 @@ class ALMTrajOpt:
         tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "separation", t0_a=t0_a, t0_b=t0_b, radius=radius)
         tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
         out = dict(min_d2=np.full(n, np.inf), min_t=np.full(n, np.nan), first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), counts=np.zeros((n, 2), dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_separation_batch(self.h, None if other is None else other.h, n, ip(tr), ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
-                                               _dp(v["radius"]), _dp(out["min_d2"]), _dp(out["min_t"]), _dp(out["first_t"]), _dp(out["last_t"]), ip(out["counts"])),
+        _lib.check(self.L.uph_separation_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
+                                               _dp(v["radius"]), _dp(out["min_d2"]), _dp(out["min_t"]), _dp(out["first_t"]), _dp(out["last_t"]), _ip(out["counts"])),
                    "uph_separation_batch")
         return out
 
@@ -1033,13 +1028,12 @@ class ALMTrajOpt:
         (radius[i] + radius[j])^2 or the first cap of them --, rows (m, 4) = min_d2, min_t, first_t, last_t, below (m,), n_conflicts (all of them) and
         n_candidates (pairs the broad phase kept).  See conflict_candidates / separation_rows."""
         tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "conflicts", t0=t0, radius=radius)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         room = max(1024, 4 * n) if cap is None else int(cap)
         while True:
             pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
             nc, nk = C.c_int64(0), C.c_int64(0)
-            _lib.check(self.L.uph_conflicts_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(v["radius"]), float(t_from), float(t_to), float(dt), room, ip(pairs), _dp(rows),
-                                                  ip(below), C.byref(nc), C.byref(nk)), "uph_conflicts_batch")
+            _lib.check(self.L.uph_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(v["radius"]), float(t_from), float(t_to), float(dt), room, _ip(pairs), _dp(rows),
+                                                  _ip(below), C.byref(nc), C.byref(nk)), "uph_conflicts_batch")
             if cap is not None or nc.value <= room:
                 break
             room = int(nc.value)                                    # cap = None: every conflict (the call is repeated with room for all of them)
@@ -1048,9 +1042,7 @@ class ALMTrajOpt:
 
     def separation_kernel_ms(self):
         """milliseconds of the kernels of the last extent(), separation() or conflicts() (events on the context's stream)"""
-        ms = C.c_double(0)
-        _lib.check(self.L.uph_separation_kernel_ms(self.h, C.byref(ms)), "uph_separation_kernel_ms")
-        return ms.value
+        return self._kernel_ms("uph_separation_kernel_ms")
 
     # ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch) ----------------------------------------------------------------
     def delay_sweep(self, traj_a, traj_b, t_from, t_to, radius, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
@@ -1063,10 +1055,9 @@ class ALMTrajOpt:
         m = max(D, 1)
         out = dict(min_d2=np.full((n, m), np.inf), min_t=np.full((n, m), np.nan), below=np.zeros((n, m), dtype=np.int32), first_clear=np.full(n, -1, dtype=np.int32),
                    counts=np.zeros(n, dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_delay_sweep_batch(self.h, None if other is None else other.h, n, ip(tr), ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
-                                                _dp(v["radius"]), float(delay0), float(delay_step), D, _dp(out["min_d2"]), _dp(out["min_t"]), ip(out["below"]),
-                                                ip(out["first_clear"]), ip(out["counts"])), "uph_delay_sweep_batch")
+        _lib.check(self.L.uph_delay_sweep_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
+                                                _dp(v["radius"]), float(delay0), float(delay_step), D, _dp(out["min_d2"]), _dp(out["min_t"]), _ip(out["below"]),
+                                                _ip(out["first_clear"]), _ip(out["counts"])), "uph_delay_sweep_batch")
         return out
 
     def delay_extent(self, traj, t_from, t_to, delay0, delay_step, D, t0=0.0, dt=0.01):
@@ -1074,9 +1065,8 @@ class ALMTrajOpt:
         samples K of the window, samples with a NaN position over all delays).  The input of a broad phase that holds under every delay."""
         tr, n, tf, tt, v = self._clock(traj, t_from, t_to, "delay_extent", t0=t0)
         out = dict(box=np.tile([np.inf, -np.inf, np.inf, -np.inf], (n, 1)), counts=np.zeros((n, 2), dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(self.L.uph_delay_extent_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), float(delay0), float(delay_step), int(D), _dp(out["box"]),
-                                                 ip(out["counts"])), "uph_delay_extent_batch")
+        _lib.check(self.L.uph_delay_extent_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(tf), _dp(tt), float(dt), float(delay0), float(delay_step), int(D), _dp(out["box"]),
+                                                 _ip(out["counts"])), "uph_delay_extent_batch")
         return out
 
     def delays(self, traj, radius, t_from, t_to, delay0, delay_step, D, t0=0.0, n_delays=None, dt=0.05):
@@ -1088,19 +1078,16 @@ class ALMTrajOpt:
         tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "delays", t0=t0, radius=radius)
         nd = None if n_delays is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_delays, dtype=np.int32), (n,)))
         out = dict(choice=np.zeros(n, dtype=np.int32), start=np.full(n, np.nan), blocker=np.full(n, -1, dtype=np.int32))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         nk, nr, nu = C.c_int64(0), C.c_int32(0), C.c_int32(0)
-        _lib.check(self.L.uph_delays_batch(self.h, n, ip(tr), _dp(v["t0"]), _dp(v["radius"]), None if nd is None else ip(nd), float(t_from), float(t_to), float(dt),
-                                           float(delay0), float(delay_step), int(D), ip(out["choice"]), _dp(out["start"]), ip(out["blocker"]), C.byref(nk), C.byref(nr),
+        _lib.check(self.L.uph_delays_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(v["radius"]), None if nd is None else _ip(nd), float(t_from), float(t_to), float(dt),
+                                           float(delay0), float(delay_step), int(D), _ip(out["choice"]), _dp(out["start"]), _ip(out["blocker"]), C.byref(nk), C.byref(nr),
                                            C.byref(nu)), "uph_delays_batch")
         out.update(n_candidates=int(nk.value), n_rounds=int(nr.value), n_unresolved=int(nu.value))
         return out
 
     def delay_kernel_ms(self):
         """milliseconds of the kernels of the last delay_sweep(), delay_extent() or delays() (events on the context's stream)"""
-        ms = C.c_double(0)
-        _lib.check(self.L.uph_delay_kernel_ms(self.h, C.byref(ms)), "uph_delay_kernel_ms")
-        return ms.value
+        return self._kernel_ms("uph_delay_kernel_ms")
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------
     def x0_packed(self, probs):

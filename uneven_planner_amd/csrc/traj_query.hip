@@ -3,11 +3,13 @@
 // uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
-// One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record (WinQuery: trajectory,
-// window of the rollout's time table, end point), lanes striding over the window, a selection or an integer sum reduced by wave_dev.hpp's rowReduce /
-// rowLeaders / acrossWaves, thread 0 writes the row.  Host: formWindowQueries (refusals, windows, launch order, uploads), runQueryLaunch (events, launch,
-// rows back, the wait).  The common-clock queries (ClockQuery: samples t_from + k dt instead of a window of the time table) keep the device half and
-// runQueryLaunch; clockRun is their launch former.
+// One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
+// window of the rollout's time table and the end point; ClockQuery: samples t_from + k dt of a clock several vehicles share, for each of the D delays of the
+// launch's table (D = 1 and a null table without one) --, lanes striding over the samples (over the delays, in the two delay kernels), their accumulators (Span,
+// Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  Host: trajFrame (the frame of a trajectory, for every
+// record and argument block), checkTrajQueries (the refusals every query passes), formWindowQueries / pairQueries / fleetCandidates / extentCall (a call shape's
+// refusals in order, its records, its uploads), clockRun (the clock records in launch order), twoWidths (256 lanes for the head of a sorted launch, one wave
+// for the rest), runQueryLaunch (events, launch, rows back, the wait).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -167,6 +169,32 @@ __device__ __forceinline__ void winTake(double& v, int& i, double ov, int oi) {
     v = o ? ov : v; i = o ? oi : i;
 }
 
+// The samples of a window that meet a condition: the first, the last, how many.  A lane takes its samples in ascending order; SpanFold folds another lane's.
+struct Span {
+    int first = WIN_NONE, last = -1, cnt = 0;
+    __device__ __forceinline__ void take(int j) { first = first == WIN_NONE ? j : first; last = j; cnt++; }
+};
+struct SpanFold {
+    __device__ __forceinline__ void operator()(int& lo, int& hi, int& c, int ol, int oh, int oc) const { lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; c += oc; }
+};
+// The box of the positions that are not NaN, and the number of those that are.  Min and max are exact: no order of taking or folding can show.
+struct Box {
+    double x0 = __builtin_huge_val(), x1 = -__builtin_huge_val(), y0 = __builtin_huge_val(), y1 = -__builtin_huge_val();
+    int bad = 0;
+    __device__ __forceinline__ void take(double X, double Y) {
+        if (X == X && Y == Y) {
+            x0 = X < x0 ? X : x0; x1 = X > x1 ? X : x1; y0 = Y < y0 ? Y : y0; y1 = Y > y1 ? Y : y1;
+        } else {
+            bad++;
+        }
+    }
+};
+struct BoxFold {
+    __device__ __forceinline__ void operator()(double& x0, double& x1, double& y0, double& y1, int& c, double ox0, double ox1, double oy0, double oy1, int oc) const {
+        x0 = ox0 < x0 ? ox0 : x0; x1 = ox1 > x1 ? ox1 : x1; y0 = oy0 < y0 ? oy0 : y0; y1 = oy1 > y1 ? oy1 : y1; c += oc;
+    }
+};
+
 // ---- check (uph_check_batch): the window reduced against limits on the map as it is now.  A 256-lane workgroup; a lane keeps in registers the first sample with a
 // violation and its mask, per term the worst value and its sample, two counters (200 VGPRs at two waves per SIMD, no scratch).
 struct CheckOut {               // one row per query
@@ -184,9 +212,12 @@ struct CheckArgs {
 };
 constexpr int CHECK_NT = 256, CHECK_NW = CHECK_NT / 64;
 constexpr unsigned long long CHECK_NONE = ~0ull;
+// its waves' slots in LDS, in doubles: per term a (double, int), then the first violation, then the two counters
+constexpr int CHECK_RED_TERM = wavesBytes<double, int>(CHECK_NW) / 8, CHECK_RED_FIRST = 7 * CHECK_RED_TERM;
+constexpr int CHECK_RED_SUMS = CHECK_RED_FIRST + wavesBytes<unsigned long long>(CHECK_NW) / 8, CHECK_RED_END = CHECK_RED_SUMS + wavesBytes<int, int>(CHECK_NW) / 8;
 
 __global__ __launch_bounds__(CHECK_NT, 2) void uph_check_kernel(GridDev grid, CheckArgs a) {
-    __shared__ double s_red[CHECK_NW * (7 * 12 + 8 + 2 * 4) / 8];       // per term a double and an int, the first violation, two counters
+    __shared__ double s_red[CHECK_RED_END];
     const WinQuery cq = a.qs[blockIdx.x];
     const int b = cq.b;
     const TrajView tr = trajView(a.r, b, a.grid_mem != nullptr, cq.shift);
@@ -242,14 +273,14 @@ __global__ __launch_bounds__(CHECK_NT, 2) void uph_check_kernel(GridDev grid, Ch
     rowLeaders(sum2, nviol, nocc);
     // the waves' slots are disjoint: one barrier for all of them
 #pragma unroll
-    for (int k = 0; k < 7; k++) wavesPut<CHECK_NW>(s_red + 6 * k, wv[k], wi[k]);
-    wavesPut<CHECK_NW>(s_red + 42, first);
-    wavesPut<CHECK_NW>(s_red + 46, nviol, nocc);
+    for (int k = 0; k < 7; k++) wavesPut<CHECK_NW>(s_red + CHECK_RED_TERM * k, wv[k], wi[k]);
+    wavesPut<CHECK_NW>(s_red + CHECK_RED_FIRST, first);
+    wavesPut<CHECK_NW>(s_red + CHECK_RED_SUMS, nviol, nocc);
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 7; k++) wavesFold<CHECK_NW>(worst, s_red + 6 * k, wv[k], wi[k]);
-    wavesFold<CHECK_NW>(least, s_red + 42, first);
-    if (!wavesFold<CHECK_NW>(sum2, s_red + 46, nviol, nocc)) return;
+    for (int k = 0; k < 7; k++) wavesFold<CHECK_NW>(worst, s_red + CHECK_RED_TERM * k, wv[k], wi[k]);
+    wavesFold<CHECK_NW>(least, s_red + CHECK_RED_FIRST, first);
+    if (!wavesFold<CHECK_NW>(sum2, s_red + CHECK_RED_SUMS, nviol, nocc)) return;
     const double nan = __builtin_nan("");
     CheckOut o;
     o.first_t = first == CHECK_NONE ? nan : winTime(cq, a.r.tt, (int)(first >> 8));
@@ -328,7 +359,6 @@ __device__ __forceinline__ double locD2(double ex, double ey) {
 
 template <int NT>
 __global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
-    __shared__ double s_red[NT / 64 * 12 / 8];
     const LocQuery lq = a.qs[a.q0 + blockIdx.x];
     const TrajView tr = trajView(a.r, lq.b, a.framed != 0, lq.shift);
     const int n = winCount(lq);
@@ -344,9 +374,7 @@ __global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
         winTake<false>(v, i, d2 < inf ? d2 : inf, j);       // NaN: +inf
     }
     const auto nearest = [](double& v, int& i, double ov, int oi) { winTake<false>(v, i, ov, oi); };
-    rowReduce(nearest, v, i);
-    rowLeaders(nearest, v, i);
-    if (!acrossWaves<NT / 64>(nearest, s_red, v, i)) return;
+    if (!workgroupReduce<NT>(nearest, v, i)) return;
     // sample k of the window (NaN outside it: an empty window answers NaN by this path, not by a special one)
     auto tau = [&](int k) { return k < 0 || k >= n ? nan : winTime(lq, a.r.tt, k); };
     LocateOut o;
@@ -387,29 +415,23 @@ __global__ __launch_bounds__(NT) void uph_locate_kernel(LocArgs a) {
 
 template <int NT>
 __global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
-    __shared__ double s_red[NT / 64 * 12 / 8];
     const LocQuery lq = a.qs[a.q0 + blockIdx.x];
     const TrajView tr = trajView(a.r, lq.b, a.framed != 0, lq.shift);
     const int n = winCount(lq);
     const double x0 = lq.p[0], x1 = lq.p[1], y0 = lq.p[2], y1 = lq.p[3];
-    int first = WIN_NONE, last = -1, cnt = 0;
+    Span in;
     for (int j = (int)threadIdx.x; j < n; j += NT) {
         TrajSample s;
         double X, Y;
         locSample(tr, winTime(lq, a.r.tt, j), s, X, Y);
-        if (x0 <= X && X <= x1 && y0 <= Y && Y <= y1) {     // (a NaN position is not inside)
-            first = first == WIN_NONE ? j : first; last = j; cnt++;
-        }
+        if (x0 <= X && X <= x1 && y0 <= Y && Y <= y1) in.take(j);       // (a NaN position is not inside)
     }
-    const auto span = [](int& lo, int& hi, int& c, int ol, int oh, int oc) { lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; c += oc; };
-    rowReduce(span, first, last, cnt);
-    rowLeaders(span, first, last, cnt);
-    if (!acrossWaves<NT / 64>(span, s_red, first, last, cnt)) return;
+    if (!workgroupReduce<NT>(SpanFold(), in.first, in.last, in.cnt)) return;
     const double nan = __builtin_nan("");
     WithinOut o;
-    o.enter_t = cnt == 0 ? nan : winTime(lq, a.r.tt, first);
-    o.leave_t = cnt == 0 ? nan : winTime(lq, a.r.tt, last);
-    o.counts[0] = n; o.counts[1] = cnt;
+    o.enter_t = in.cnt == 0 ? nan : winTime(lq, a.r.tt, in.first);
+    o.leave_t = in.cnt == 0 ? nan : winTime(lq, a.r.tt, in.last);
+    o.counts[0] = n; o.counts[1] = in.cnt;
     ((WithinOut*)a.out)[lq.out] = o;
 }
 
@@ -422,13 +444,15 @@ struct ClockTraj {              // one vehicle of a query
     double t0;                  // its start on the common clock
     double shift[2];            // as RolloutTraj
 };
-struct ClockQuery {             // one query of a launch (formed on the host, in launch order: clockRun)
-    int32_t out, K;             // row of the launch's output; samples
+struct ClockQuery {             // one query of a launch (formed on the host by clockQuery, in launch order: clockRun)
+    int32_t out, K;             // row of the launch's output (with a delay table: rows out * D .. out * D + D - 1); samples
+    int32_t D, pad;             // delays of the launch's table; 1 without one.  (Ahead of the times: behind them the compiler loads t_from, dt and SepQuery's
+                                // R2 a wait later than the rest of the record, and uph_separation_kernel<64> at 101 samples runs 1.7 % longer.)
     double t_from, dt;
 };
 struct SepQuery : ClockQuery {
     double R2;                  // a sample is below when d2 < R2
-    ClockTraj a, b;
+    ClockTraj a, b;             // with a delay table, b is the one delayed
 };
 struct ExtQuery : ClockQuery {
     ClockTraj a;
@@ -442,17 +466,24 @@ struct ExtOut {
     double box[4];              // xmin, xmax, ymin, ymax over the samples whose position is not NaN
     int32_t counts[2];          // samples, NaN samples
 };
+struct SweepOut {               // one row per (query, delay)
+    double min_d2, min_t;       // as SepOut
+    int32_t below, k;           // samples below; the sample of the minimum (WIN_NONE: none)
+};
+template <class Out>            // SepOut, or SweepOut with a delay table
 struct SepArgs {
     ResidentDev ra, rb;         // the two sides' resident batches (one context: the same)
     const SepQuery* qs;
-    SepOut* out;
+    Out* out;
     int framed_a, framed_b, q0; // as LocArgs, per side
+    const double* delta;        // [D] the launch's delay table; nullptr without one
 };
 struct ExtArgs {
     ResidentDev r;
     const ExtQuery* qs;
     ExtOut* out;
     int framed, q0;
+    const double* delta;        // as SepArgs
 };
 
 // tau_k with the product rounded before the add
@@ -480,15 +511,25 @@ __device__ __forceinline__ void clockSample(const ClockView& v, double tau, doub
     locSample(v.tr, t, s, X, Y);
 }
 
+// the workgroup's box from its lanes', and the query's row (both extent kernels end here)
 template <int NT>
-__global__ __launch_bounds__(NT) void uph_separation_kernel(SepArgs a) {
-    __shared__ double s_red[NT / 64 * 24 / 8];
+__device__ __forceinline__ void extentRow(const ExtArgs& a, const ExtQuery& eq, Box& box) {
+    if (!workgroupReduce<NT>(BoxFold(), box.x0, box.x1, box.y0, box.y1, box.bad)) return;
+    ExtOut o;
+    o.box[0] = box.x0; o.box[1] = box.x1; o.box[2] = box.y0; o.box[3] = box.y1;
+    o.counts[0] = eq.K; o.counts[1] = box.bad;
+    a.out[eq.out] = o;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_separation_kernel(SepArgs<SepOut> a) {
     const SepQuery sq = a.qs[a.q0 + blockIdx.x];
     const ClockView va = clockView(a.ra, sq.a, a.framed_a != 0), vb = clockView(a.rb, sq.b, a.framed_b != 0);
     const int n = sq.K;
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
     double v = inf;
-    int i = WIN_NONE, first = WIN_NONE, last = -1, cnt = 0;
+    int i = WIN_NONE;
+    Span below;
     for (int j = (int)threadIdx.x; j < n; j += NT) {
         const double tau = clockTau(sq, j);
         double Xa, Ya, Xb, Yb;
@@ -496,90 +537,41 @@ __global__ __launch_bounds__(NT) void uph_separation_kernel(SepArgs a) {
         clockSample(vb, tau, Xb, Yb);
         const double d2 = locD2(Xa - Xb, Ya - Yb);
         winTake<false>(v, i, d2 < inf ? d2 : inf, j);       // NaN: +inf
-        if (d2 < sq.R2) {                                   // (a NaN d2 is not below)
-            first = first == WIN_NONE ? j : first; last = j; cnt++;
-        }
+        if (d2 < sq.R2) below.take(j);                      // (a NaN d2 is not below)
     }
     const auto fold = [](double& v, int& i, int& lo, int& hi, int& c, double ov, int oi, int ol, int oh, int oc) {
         winTake<false>(v, i, ov, oi);
-        lo = ol < lo ? ol : lo; hi = oh > hi ? oh : hi; c += oc;
+        SpanFold()(lo, hi, c, ol, oh, oc);
     };
-    rowReduce(fold, v, i, first, last, cnt);
-    rowLeaders(fold, v, i, first, last, cnt);
-    if (!acrossWaves<NT / 64>(fold, s_red, v, i, first, last, cnt)) return;
+    if (!workgroupReduce<NT>(fold, v, i, below.first, below.last, below.cnt)) return;
     SepOut o;
     o.min_d2 = v;
     o.min_t = i == WIN_NONE ? nan : clockTau(sq, i);
-    o.first_t = cnt == 0 ? nan : clockTau(sq, first);
-    o.last_t = cnt == 0 ? nan : clockTau(sq, last);
-    o.counts[0] = n; o.counts[1] = cnt;
+    o.first_t = below.cnt == 0 ? nan : clockTau(sq, below.first);
+    o.last_t = below.cnt == 0 ? nan : clockTau(sq, below.last);
+    o.counts[0] = n; o.counts[1] = below.cnt;
     a.out[sq.out] = o;
 }
 
 template <int NT>
 __global__ __launch_bounds__(NT) void uph_extent_kernel(ExtArgs a) {
-    __shared__ double s_red[(NT / 64 * 36 + 7) / 8];
     const ExtQuery eq = a.qs[a.q0 + blockIdx.x];
     const ClockView va = clockView(a.r, eq.a, a.framed != 0);
-    const int n = eq.K;
-    const double inf = __builtin_huge_val();
-    double x0 = inf, x1 = -inf, y0 = inf, y1 = -inf;
-    int bad = 0;
-    for (int j = (int)threadIdx.x; j < n; j += NT) {
+    Box box;
+    for (int j = (int)threadIdx.x; j < eq.K; j += NT) {
         double X, Y;
         clockSample(va, clockTau(eq, j), X, Y);
-        if (X == X && Y == Y) {
-            x0 = X < x0 ? X : x0; x1 = X > x1 ? X : x1; y0 = Y < y0 ? Y : y0; y1 = Y > y1 ? Y : y1;
-        } else {
-            bad++;
-        }
+        box.take(X, Y);
     }
-    const auto hull = [](double& x0, double& x1, double& y0, double& y1, int& c, double ox0, double ox1, double oy0, double oy1, int oc) {
-        x0 = ox0 < x0 ? ox0 : x0; x1 = ox1 > x1 ? ox1 : x1; y0 = oy0 < y0 ? oy0 : y0; y1 = oy1 > y1 ? oy1 : y1; c += oc;
-    };
-    rowReduce(hull, x0, x1, y0, y1, bad);
-    rowLeaders(hull, x0, x1, y0, y1, bad);
-    if (!acrossWaves<NT / 64>(hull, s_red, x0, x1, y0, y1, bad)) return;
-    ExtOut o;
-    o.box[0] = x0; o.box[1] = x1; o.box[2] = y0; o.box[3] = y1;
-    o.counts[0] = n; o.counts[1] = bad;
-    a.out[eq.out] = o;
+    extentRow<NT>(a, eq, box);
 }
 
-// ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch): the separation / the extent of a query for every start t0 + delta_j of a
-// table of D delays that all queries of a launch share (formed on the host: the device only adds).  One workgroup per query, lanes own DELAYS, not samples:
+// ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch): the separation / the extent of a query (the same records) for every start
+// t0 + delta_j of a table of D delays that all queries of a launch share (formed on the host: the device only adds).  One workgroup per query, lanes own DELAYS, not samples:
 // the samples are walked in tiles of DELAY_TILE, ascending inside a lane, so a lane's (d2, k) selection meets the tie rule without a cross-lane step.
 //   few delays (D * G <= NT, G the largest such power of two): the G lanes tid = dl * G + g of delay dl take the samples g, g + G, ... of each tile and are
 //       folded once, after the last tile, through LDS -- a selection under a total order and integer sums: the split cannot show in the result;
 //   many delays (D > NT): P = ceil(D / NT) passes per tile; a lane's rows carry its state from tile to tile (its own loads after its own stores).
-struct DelayQuery : ClockQuery {
-    int32_t D, pad;             // delays of the table; the query's rows are out * D .. out * D + D - 1
-};
-struct SweepQuery : DelayQuery {
-    double R2;
-    ClockTraj a, b;             // b is the one delayed
-};
-struct DextQuery : DelayQuery {
-    ClockTraj a;
-};
-struct SweepOut {               // one row per (query, delay)
-    double min_d2, min_t;       // as SepOut
-    int32_t below, k;           // samples below; the sample of the minimum (WIN_NONE: none)
-};
-struct SweepArgs {
-    ResidentDev ra, rb;
-    const SweepQuery* qs;
-    SweepOut* out;
-    const double* delta;        // [D]
-    int framed_a, framed_b, q0;
-};
-struct DextArgs {
-    ResidentDev r;
-    const DextQuery* qs;
-    ExtOut* out;
-    const double* delta;
-    int framed, q0;
-};
 constexpr int DELAY_TILE = 128;             // samples of a tile (UPH_DELAY_TILE)
 static_assert(DELAY_TILE == UPH_DELAY_TILE, "the tile length the header documents");
 
@@ -602,7 +594,7 @@ __device__ __forceinline__ DelaySplit delaySplit(int D) {
 //   close(j)      the delay's samples of the tile are done,
 //   release()     the tile is done (uniform).
 template <class Body>
-__device__ __forceinline__ void delayLoop(const DelayQuery& q, const DelaySplit& sp, Body& body) {
+__device__ __forceinline__ void delayLoop(const ClockQuery& q, const DelaySplit& sp, Body& body) {
     const int dl = (int)threadIdx.x / sp.G, g = (int)threadIdx.x % sp.G;
     for (int k0 = 0; k0 < q.K; k0 += DELAY_TILE) {
         const int m = q.K - k0 < DELAY_TILE ? q.K - k0 : DELAY_TILE;
@@ -620,8 +612,8 @@ __device__ __forceinline__ void delayLoop(const DelayQuery& q, const DelaySplit&
 
 template <int NT>
 struct SweepBody {
-    const SweepQuery& sq;
-    const SweepArgs& a;
+    const SepQuery& sq;
+    const SepArgs<SweepOut>& a;
     ClockView va, vb;
     double t0_b;
     double* ax;                 // [DELAY_TILE] a's positions of the tile, in LDS
@@ -660,11 +652,11 @@ struct SweepBody {
 };
 
 template <int NT>
-__global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(SweepArgs a) {
+__global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(SepArgs<SweepOut> a) {
     __shared__ double s_xy[2 * DELAY_TILE];
     __shared__ double s_v[NT];
     __shared__ int s_i[2 * NT];
-    const SweepQuery sq = a.qs[a.q0 + blockIdx.x];
+    const SepQuery sq = a.qs[a.q0 + blockIdx.x];
     const DelaySplit sp = delaySplit<NT>(sq.D);
     SweepBody<NT> body{sq, a, clockView(a.ra, sq.a, a.framed_a != 0), clockView(a.rb, sq.b, a.framed_b != 0), sq.b.t0, s_xy, s_xy + DELAY_TILE, sp.P > 1,
                        __builtin_huge_val(), WIN_NONE, 0};
@@ -682,22 +674,17 @@ __global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(SweepArgs a) {
 }
 
 struct DextBody {
-    const DextQuery& eq;
-    const DextArgs& a;
+    const ExtQuery& eq;
+    const ExtArgs& a;
     ClockView va;
     double t0;
-    double x0, x1, y0, y1;
-    int bad;
+    Box box;
     __device__ __forceinline__ void park(int, int) {}
     __device__ __forceinline__ void open(int j) { va.t0 = t0 + a.delta[j]; }
     __device__ __forceinline__ void sample(int, int k) {
         double X, Y;
         clockSample(va, clockTau(eq, k), X, Y);
-        if (X == X && Y == Y) {
-            x0 = X < x0 ? X : x0; x1 = X > x1 ? X : x1; y0 = Y < y0 ? Y : y0; y1 = Y > y1 ? Y : y1;
-        } else {
-            bad++;
-        }
+        box.take(X, Y);
     }
     __device__ __forceinline__ void close(int) {}
     __device__ __forceinline__ void release() {}
@@ -705,22 +692,11 @@ struct DextBody {
 
 // the hull over the delays of uph_extent_kernel's boxes: min and max are exact, so neither the split nor the fold can show
 template <int NT>
-__global__ __launch_bounds__(NT) void uph_delay_extent_kernel(DextArgs a) {
-    __shared__ double s_red[(NT / 64 * 36 + 7) / 8];
-    const DextQuery eq = a.qs[a.q0 + blockIdx.x];
-    const double inf = __builtin_huge_val();
-    DextBody body{eq, a, clockView(a.r, eq.a, a.framed != 0), eq.a.t0, inf, -inf, inf, -inf, 0};
+__global__ __launch_bounds__(NT) void uph_delay_extent_kernel(ExtArgs a) {
+    const ExtQuery eq = a.qs[a.q0 + blockIdx.x];
+    DextBody body{eq, a, clockView(a.r, eq.a, a.framed != 0), eq.a.t0, Box()};
     delayLoop(eq, delaySplit<NT>(eq.D), body);
-    const auto hull = [](double& x0, double& x1, double& y0, double& y1, int& c, double ox0, double ox1, double oy0, double oy1, int oc) {
-        x0 = ox0 < x0 ? ox0 : x0; x1 = ox1 > x1 ? ox1 : x1; y0 = oy0 < y0 ? oy0 : y0; y1 = oy1 > y1 ? oy1 : y1; c += oc;
-    };
-    rowReduce(hull, body.x0, body.x1, body.y0, body.y1, body.bad);
-    rowLeaders(hull, body.x0, body.x1, body.y0, body.y1, body.bad);
-    if (!acrossWaves<NT / 64>(hull, s_red, body.x0, body.x1, body.y0, body.y1, body.bad)) return;
-    ExtOut o;
-    o.box[0] = body.x0; o.box[1] = body.x1; o.box[2] = body.y0; o.box[3] = body.y1;
-    o.counts[0] = eq.K; o.counts[1] = body.bad;
-    a.out[eq.out] = o;
+    extentRow<NT>(a, eq, body.box);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -731,9 +707,18 @@ static ResidentDev residentDev(uph_ctx* c) {
     r.tt = c->d_roll_tt.as<double>();
     return r;
 }
+// Trajectory b of c as every record and argument block names its frame: whether the batch solves in local frames (the result), and, where asked for, the map
+// coordinate of b's frame corner (0 in the map's own frame).  The one reader of c->frames in this file.
+static int trajFrame(const uph_ctx* c, int32_t b = 0, double* shift = nullptr) {
+    const bool framed = !c->frames.empty();
+    if (shift) for (int d = 0; d < 2; d++) shift[d] = framed ? c->frames[(size_t)b].shift[d] : 0.0;
+    return framed ? 1 : 0;
+}
 
-// uph_traj_states / uph_replan_upload / uph_refine_upload and the window queries: c holds resident trajectories and every query names one of them at a finite time
+// The check every query on resident trajectories passes (uph_traj_states / uph_replan_upload / uph_refine_upload, the window queries, the common-clock queries): no
+// asynchronous solve is in flight on c, c holds resident trajectories and every query names one of them at a finite time
 int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t, const char* who) {
+    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     if (c->B <= 0 || !c->traj_resident) {
         setError(std::string(who) + ": no trajectory is resident (uph_batch_solve / uph_eval_batch after the upload first)"); return UPH_ERR_INVALID;
     }
@@ -762,8 +747,8 @@ int launchTrajStates(uph_ctx* c, const std::vector<SwitchQuery>& sq, int cols) {
 
 SwitchQuery trajQuery(const uph_ctx* c, int32_t b, double t) {
     SwitchQuery r;
-    r.b = b; r.framed = c->frames.empty() ? 0 : 1; r.t = t;
-    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    r.b = b; r.t = t;
+    r.framed = trajFrame(c, b, r.shift);
     return r;
 }
 
@@ -855,15 +840,14 @@ static int rolloutLaunch(uph_ctx* c, const GridDev& grid, const RolloutSizes& rs
         t.cnt = rs.cnt[b];
         t.rows = (int)(rs.offs[b + 1] - rs.offs[b]);
         t.total = rs.total[b];
-        t.shift[0] = c->frames.empty() ? 0.0 : c->frames[b].shift[0];
-        t.shift[1] = c->frames.empty() ? 0.0 : c->frames[b].shift[1];
+        trajFrame(c, b, t.shift);
         ychunks = std::max(ychunks, (t.rows + ROLL_NT - 1) / ROLL_NT);
     }
     if (c->d_roll_traj.ensure(sizeof(RolloutTraj) * n)) return UPH_ERR_HIP;
     HIPCHK(hipMemcpyAsync(c->d_roll_traj.p, rec.data(), sizeof(RolloutTraj) * n, hipMemcpyHostToDevice, c->stream));
     RolloutArgs a;
     a.r = residentDev(c);
-    a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>();
+    a.grid_mem = trajFrame(c) ? c->d_gridmem.as<GridDev>() : nullptr;
     a.traj = c->d_roll_traj.as<RolloutTraj>(); a.out = out_dev;
     a.b0 = b0; a.channels = channels; a.ncol = rolloutColumns(channels);
     hipLaunchKernelGGL(uph_rollout_kernel, dim3(n, ychunks), dim3(ROLL_NT), 0, c->stream, grid, a);
@@ -905,7 +889,6 @@ template <class Q, class Own>
 static int formWindowQueries(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const char* who,
                              std::vector<Q>& qs, Own own) {
     if (!(dt > 0.0) || !std::isfinite(dt)) { setError(std::string(who) + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     int r = checkTrajQueries(c, n, traj, t_from, who);
     if (r != UPH_OK) return r;
     if (t_to) for (int32_t q = 0; q < n; q++) if (std::isnan(t_to[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a NaN t_to"); return UPH_ERR_INVALID; }
@@ -922,7 +905,7 @@ static int formWindowQueries(uph_ctx* c, int32_t n, const int32_t* traj, const d
         checkWindow(rs.tab, rs.cnt[(size_t)b], with_end, rs.total[(size_t)b], t_from[q], t_to ? t_to[q] : __builtin_huge_val(), k.q_lo, q_hi, k.end_row);
         k.n_tab = q_hi - k.q_lo;
         k.total = rs.total[(size_t)b];
-        for (int d = 0; d < 2; d++) k.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+        trajFrame(c, b, k.shift);
     }
     std::stable_sort(qs.begin(), qs.end(), [](const Q& x, const Q& y) { return x.n_tab + x.end_row > y.n_tab + y.end_row; });
     if (c->d_roll_tt.ensure(8 * rs.tab.size()) || c->d_win_q.ensure(sizeof(Q) * (size_t)n)) return UPH_ERR_HIP;
@@ -947,8 +930,22 @@ static int runQueryLaunch(uph_ctx* c, Launch launch, std::vector<Out>& out, doub
     return UPH_OK;
 }
 
-// locate / within: the records in launch order with the caller's `extra` doubles per query (pose / rect) in each, then 256 lanes for the queries at the head of
-// the launch whose window exceeds LOC_SHORT samples and one wave for the rest
+// The launch of records sorted by work (the most first; work(q) of record q) at two widths: 256 lanes for the head of more than LOC_SHORT samples, one wave for
+// the rest, the second launch told where it starts (a.q0).  The split is found here; the result is runQueryLaunch's launch().
+template <class Work, class Args, class K256, class K64>
+static auto twoWidths(uph_ctx* c, size_t n, Work work, Args a, K256 k256, K64 k64) {
+    size_t n_long = 0;
+    while (n_long < n && work(n_long) > LOC_SHORT) n_long++;
+    return [=]() mutable {
+        hipError_t le = hipSuccess;
+        a.q0 = 0;
+        if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
+        if (n > n_long && le == hipSuccess) { a.q0 = (int)n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
+        return le;
+    };
+}
+
+// locate / within: the records in launch order with the caller's `extra` doubles per query (pose / rect) in each, launched at two widths
 template <class Out, class K256, class K64>
 static int locRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* rows, int extra,
                   const char* who, K256 k256, K64 k64, std::vector<Out>& out) {
@@ -961,18 +958,12 @@ static int locRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_fr
         return (int)UPH_OK;
     });
     if (r != UPH_OK) return r;
-    int32_t n_long = 0;
-    while (n_long < n && qs[(size_t)n_long].n_tab + qs[(size_t)n_long].end_row > LOC_SHORT) n_long++;
     if (c->d_win_out.ensure(sizeof(Out) * (size_t)n)) return UPH_ERR_HIP;
     LocArgs a;
-    a.r = residentDev(c); a.qs = c->d_win_q.as<LocQuery>(); a.out = c->d_win_out.p; a.framed = c->frames.empty() ? 0 : 1; a.q0 = 0;
+    a.r = residentDev(c); a.qs = c->d_win_q.as<LocQuery>(); a.out = c->d_win_out.p; a.framed = trajFrame(c); a.q0 = 0;
     out.resize((size_t)n);
-    return runQueryLaunch(c, [&]() {
-        hipError_t le = hipSuccess;
-        if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
-        if (n > n_long && le == hipSuccess) { a.q0 = n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
-        return le;
-    }, out, c->last_locate_ms);
+    const auto work = [&](size_t q) { return qs[q].n_tab + qs[q].end_row; };
+    return runQueryLaunch(c, twoWidths(c, (size_t)n, work, a, k256, k64), out, c->last_locate_ms);
 }
 
 // ---- separation / extent / conflicts (include/uneven_hip.h uph_separation_*, uph_extent_batch, uph_conflict*) -----------------------------------------
@@ -984,11 +975,13 @@ static double clockTauHost(double t_from, int64_t k, double dt) {
     const double p = (double)k * dt;
     return t_from + p;
 }
+// how a refusal names query q of a call (q < 0: the call has one window): formed only when something is refused
+static std::string whoQuery(const std::string& who, int32_t q) { return q < 0 ? who : who + ": query " + std::to_string(q); }
 // K = the number of k >= 0 with tau_k <= t_to (tau_k does not decrease with k: rounding is monotone); the bounds and dt are finite, dt > 0
-static int clockCount(double t_from, double t_to, double dt, int64_t& K, const std::string& who) {
+static int clockCount(double t_from, double t_to, double dt, int64_t& K, const std::string& who, int32_t q) {
     K = 0;
     if (!(t_from <= t_to)) return UPH_OK;
-    if (clockTauHost(t_from, CLOCK_MAX_SAMPLES, dt) <= t_to) { setError(who + ": the window holds more than 2^22 samples at this dt"); return UPH_ERR_LIMIT; }
+    if (clockTauHost(t_from, CLOCK_MAX_SAMPLES, dt) <= t_to) { setError(whoQuery(who, q) + ": the window holds more than 2^22 samples at this dt"); return UPH_ERR_LIMIT; }
     int64_t lo = 0, hi = CLOCK_MAX_SAMPLES;                 // tau_lo <= t_to < tau_hi
     while (hi - lo > 1) {
         const int64_t mid = lo + (hi - lo) / 2;
@@ -998,78 +991,54 @@ static int clockCount(double t_from, double t_to, double dt, int64_t& K, const s
     K = lo + 1;
     return UPH_OK;
 }
-static int clockWindow(double t_from, double t_to, double dt, int64_t& K, const std::string& who) {
-    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(who + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
-    if (!std::isfinite(t_from) || !std::isfinite(t_to)) { setError(who + ": a window bound is not finite"); return UPH_ERR_INVALID; }
-    return clockCount(t_from, t_to, dt, K, who);
-}
-// c can answer queries on the common clock: solved trajectories, no solve in flight, every query names one of them with a finite start time
-static int clockSide(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const char* who) {
-    if (c->pending) { setError(std::string(who) + ": an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
-    return checkTrajQueries(c, n, traj, t0, who);
+static int clockWindow(double t_from, double t_to, double dt, int64_t& K, const std::string& who, int32_t q = -1) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) { setError(whoQuery(who, q) + ": dt must be positive and finite"); return UPH_ERR_INVALID; }
+    if (!std::isfinite(t_from) || !std::isfinite(t_to)) { setError(whoQuery(who, q) + ": a window bound is not finite"); return UPH_ERR_INVALID; }
+    return clockCount(t_from, t_to, dt, K, who, q);
 }
 static ClockTraj clockTraj(const uph_ctx* c, int32_t b, double t0) {
     ClockTraj r;
     r.b = b; r.pad = 0; r.t0 = t0;
-    for (int d = 0; d < 2; d++) r.shift[d] = c->frames.empty() ? 0.0 : c->frames[(size_t)b].shift[d];
+    trajFrame(c, b, r.shift);
     return r;
 }
-
+// The start delays of a call: delta_j = delay0 + j * step.  The calls without delays pass no table: their records say D = 1 and their kernels get a null pointer.
+struct DelayTable {
+    double delay0, step;
+    int32_t D;
+    std::vector<double> delta;
+};
+static int32_t delayCount(const DelayTable* dl) { return dl ? dl->D : 1; }
+// The one former of a clock record's head: everything else zero, D from the call's delay table -- clockWork, and with it the launch width, goes by it
+template <class Q>
+static Q clockQuery(int64_t K, double t_from, double dt, const DelayTable* dl) {
+    Q q{};
+    q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.D = delayCount(dl);
+    return q;
+}
+static SepQuery sepQuery(int64_t K, double t_from, double dt, const DelayTable* dl, double R, const ClockTraj& a, const ClockTraj& b) {
+    SepQuery q = clockQuery<SepQuery>(K, t_from, dt, dl);
+    q.R2 = R * R; q.a = a; q.b = b;
+    return q;
+}
 // the samples a query's workgroup evaluates: what the launch order and the launch width go by
-static int64_t clockWork(const ClockQuery& q) { return q.K; }
-static int64_t clockWork(const DelayQuery& q) { return (int64_t)q.K * q.D; }
+static int64_t clockWork(const ClockQuery& q) { return (int64_t)q.K * q.D; }
 
 // n <= CLOCK_CHUNK queries in the caller's order -> their rows (`per` of them each) in that order: the records in launch order (the most samples first, stable) on
-// the device, 256 lanes for the queries of more than LOC_SHORT samples at the head and one wave for the rest (as locRun), the kernels' time added to ms
-template <class Q, class Out, class Args, class K256, class K64>
-static int clockRun(uph_ctx* c, Q* qs, size_t n, Args a, K256 k256, K64 k64, Out* rows, double& ms, size_t per = 1) {
+// the device, launched at two widths, the kernels' time added to ms
+template <class Q, class Out, class Args>
+static int clockRun(uph_ctx* c, Q* qs, size_t n, Args a, void (*k256)(Args), void (*k64)(Args), Out* rows, double& ms, size_t per = 1) {
     for (size_t q = 0; q < n; q++) qs[q].out = (int32_t)q;
     std::stable_sort(qs, qs + n, [](const Q& x, const Q& y) { return clockWork(x) > clockWork(y); });
-    size_t n_long = 0;
-    while (n_long < n && clockWork(qs[n_long]) > LOC_SHORT) n_long++;
     if (c->d_win_q.ensure(sizeof(Q) * n) || c->d_win_out.ensure(sizeof(Out) * n * per)) return UPH_ERR_HIP;
     HIPCHK(hipMemcpyAsync(c->d_win_q.p, qs, sizeof(Q) * n, hipMemcpyHostToDevice, c->stream));
-    a.qs = c->d_win_q.as<Q>(); a.out = c->d_win_out.as<Out>(); a.q0 = 0;
+    a.qs = c->d_win_q.as<Q>(); a.out = c->d_win_out.as<Out>();
     std::vector<Out> out(n * per);
     double one = 0.0;
-    const int r = runQueryLaunch(c, [&]() {
-        hipError_t le = hipSuccess;
-        if (n_long > 0) { hipLaunchKernelGGL(k256, dim3((unsigned)n_long), dim3(256), 0, c->stream, a); le = hipGetLastError(); }
-        if (n > n_long && le == hipSuccess) { a.q0 = (int)n_long; hipLaunchKernelGGL(k64, dim3((unsigned)(n - n_long)), dim3(64), 0, c->stream, a); le = hipGetLastError(); }
-        return le;
-    }, out, one);
+    const int r = runQueryLaunch(c, twoWidths(c, n, [&](size_t q) { return clockWork(qs[q]); }, a, k256, k64), out, one);
     if (r != UPH_OK) return r;
     ms += one;
     std::copy(out.begin(), out.end(), rows);
-    return UPH_OK;
-}
-
-static SepArgs sepArgs(uph_ctx* ca, uph_ctx* cb) {
-    SepArgs a;
-    a.ra = residentDev(ca); a.rb = residentDev(cb);
-    a.framed_a = ca->frames.empty() ? 0 : 1; a.framed_b = cb->frames.empty() ? 0 : 1;
-    a.qs = nullptr; a.out = nullptr; a.q0 = 0;
-    return a;
-}
-
-// the extents of n vehicles of c (already checked: clockSide, the windows' K) in launches of at most CLOCK_CHUNK
-static int extentRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const int64_t* K, double dt, std::vector<ExtOut>& out, double& ms) {
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    ExtArgs a;
-    a.r = residentDev(c); a.framed = c->frames.empty() ? 0 : 1; a.qs = nullptr; a.out = nullptr; a.q0 = 0;
-    out.resize((size_t)n);
-    std::vector<ExtQuery> qs;
-    for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
-        const size_t m = std::min(CLOCK_CHUNK, (size_t)n - s);
-        qs.assign(m, ExtQuery());
-        for (size_t k = 0; k < m; k++) {
-            ExtQuery& q = qs[k];
-            q.K = (int32_t)K[s + k]; q.t_from = t_from[s + k]; q.dt = dt;
-            q.a = clockTraj(c, traj[s + k], t0[s + k]);
-        }
-        const int r = clockRun(c, qs.data(), m, a, uph_extent_kernel<256>, uph_extent_kernel<64>, out.data() + s, ms);
-        if (r != UPH_OK) return r;
-    }
     return UPH_OK;
 }
 
@@ -1109,7 +1078,8 @@ constexpr int32_t DELAY_MAX = 4096;                         // delays of one tab
 constexpr int64_t DELAY_MAX_WORK = (int64_t)1 << 26;        // K * D of one query: a workgroup's serial work is at most that of 16 separation queries of CLOCK_MAX_SAMPLES
 constexpr size_t DELAY_ROWS = (size_t)1 << 20;              // sweep rows of one launch pair (24 MB on the device)
 
-// delta_j = delay0 + j * delay_step by clockTau's rule
+static const double* delayDev(uph_ctx* c, const DelayTable* dl) { return dl ? c->d_delay.as<double>() : nullptr; }
+// delta by clockTau's rule
 static int delayTable(double delay0, double delay_step, int32_t D, std::vector<double>& delta, const std::string& who) {
     if (!(delay_step > 0.0) || !std::isfinite(delay_step)) { setError(who + ": delay_step must be positive and finite"); return UPH_ERR_INVALID; }
     if (!std::isfinite(delay0)) { setError(who + ": delay0 is not finite"); return UPH_ERR_INVALID; }
@@ -1119,62 +1089,140 @@ static int delayTable(double delay0, double delay_step, int32_t D, std::vector<d
     for (int32_t j = 0; j < D; j++) delta[(size_t)j] = clockTauHost(delay0, j, delay_step);
     return UPH_OK;
 }
-// every start t0[q] + delta_j is finite (delta_j does not decrease with j and rounding is monotone: the two ends decide)
-static int delayStarts(int32_t n, const double* t0, const std::vector<double>& delta, const std::string& who) {
+// the table formed, and every start t0[q] + delta_j finite (delta_j does not decrease with j and rounding is monotone: the two ends decide)
+static int delayAdmit(DelayTable* dl, int32_t n, const double* t0, const std::string& who) {
+    if (!dl) return UPH_OK;
+    const int r = delayTable(dl->delay0, dl->step, dl->D, dl->delta, who);
+    if (r != UPH_OK) return r;
     for (int32_t q = 0; q < n; q++)
-        if (!std::isfinite(t0[q] + delta.front()) || !std::isfinite(t0[q] + delta.back())) {
+        if (!std::isfinite(t0[q] + dl->delta.front()) || !std::isfinite(t0[q] + dl->delta.back())) {
             setError(who + ": query " + std::to_string(q) + " has a delayed start that is not finite"); return UPH_ERR_INVALID;
         }
     return UPH_OK;
 }
-static int delayWork(int64_t K, int32_t D, const std::string& who) {
-    if (K * (int64_t)D > DELAY_MAX_WORK) { setError(who + ": more than 2^26 samples times delays"); return UPH_ERR_LIMIT; }
+static int delayWork(int64_t K, const DelayTable* dl, const std::string& who, int32_t q = -1) {
+    if (K * (int64_t)delayCount(dl) > DELAY_MAX_WORK) { setError(whoQuery(who, q) + ": more than 2^26 samples times delays"); return UPH_ERR_LIMIT; }
     return UPH_OK;
 }
-static int delayUpload(uph_ctx* c, const std::vector<double>& delta) {
-    if (c->d_delay.ensure(8 * delta.size())) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_delay.p, delta.data(), 8 * delta.size(), hipMemcpyHostToDevice, c->stream));
+static int delayUpload(uph_ctx* c, const DelayTable* dl) {
+    if (!dl) return UPH_OK;
+    if (c->d_delay.ensure(8 * dl->delta.size())) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_delay.p, dl->delta.data(), 8 * dl->delta.size(), hipMemcpyHostToDevice, c->stream));
     return UPH_OK;
 }
 // the queries of one launch pair: the rows stay below DELAY_ROWS and the records below CLOCK_CHUNK
 static size_t delayChunk(int32_t D) { return std::max<size_t>(1, std::min(CLOCK_CHUNK, DELAY_ROWS / (size_t)D)); }
 
-// the sweeps of qs (K, t_from, dt, R2, a, b set; the table is on ca's device) -> rows [qs.size()][D] in the caller's order
-static int sweepRun(uph_ctx* ca, uph_ctx* cb, std::vector<SweepQuery>& qs, int32_t D, std::vector<SweepOut>& rows, double& ms) {
-    rows.resize(qs.size() * (size_t)D);
-    SweepArgs a;
+// the pair queries qs (formed by sepQuery; the table, if any, is on ca's device) -> a row per query, or per (query, delay), in the caller's order; qs is left in
+// launch order
+template <class Out>
+static int pairRun(uph_ctx* ca, uph_ctx* cb, std::vector<SepQuery>& qs, const DelayTable* dl, void (*k256)(SepArgs<Out>), void (*k64)(SepArgs<Out>),
+                   std::vector<Out>& rows, double& ms) {
+    const size_t D = (size_t)delayCount(dl), chunk = delayChunk((int32_t)D);
+    for (const SepQuery& q : qs)        // the rows a workgroup writes and the rows allocated here both go by the table
+        if (q.D != (int32_t)D) { setError("pairRun: a record was not formed from this call's delay table"); return UPH_ERR_INVALID; }
+    rows.resize(qs.size() * D);
+    SepArgs<Out> a{};
     a.ra = residentDev(ca); a.rb = residentDev(cb);
-    a.framed_a = ca->frames.empty() ? 0 : 1; a.framed_b = cb->frames.empty() ? 0 : 1;
-    a.qs = nullptr; a.out = nullptr; a.delta = ca->d_delay.as<double>(); a.q0 = 0;
-    const size_t chunk = delayChunk(D);
+    a.framed_a = trajFrame(ca); a.framed_b = trajFrame(cb);
+    a.delta = delayDev(ca, dl);
     for (size_t s = 0; s < qs.size(); s += chunk) {
-        const size_t m = std::min(chunk, qs.size() - s);
-        for (size_t k = 0; k < m; k++) { qs[s + k].D = D; qs[s + k].pad = 0; }
-        const int r = clockRun(ca, qs.data() + s, m, a, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows.data() + s * (size_t)D, ms, (size_t)D);
+        const int r = clockRun(ca, qs.data() + s, std::min(chunk, qs.size() - s), a, k256, k64, rows.data() + s * D, ms, D);
         if (r != UPH_OK) return r;
     }
     return UPH_OK;
 }
-// the swept extents of n vehicles of c (already checked), as extentRun
-static int delayExtentRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const int64_t* K, double dt, int32_t D,
-                          std::vector<ExtOut>& out, double& ms) {
-    DextArgs a;
-    a.r = residentDev(c); a.framed = c->frames.empty() ? 0 : 1; a.qs = nullptr; a.out = nullptr; a.delta = c->d_delay.as<double>(); a.q0 = 0;
+// the extents of n vehicles of c (already checked: checkTrajQueries, the windows' K; c's device is current), over every delay of the table if there is one (already
+// uploaded), in launches of at most CLOCK_CHUNK
+static int extentRun(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const int64_t* K, double dt, const DelayTable* dl,
+                     std::vector<ExtOut>& out, double& ms) {
+    ExtArgs a{};
+    a.r = residentDev(c); a.framed = trajFrame(c); a.delta = delayDev(c, dl);
+    const auto k256 = dl ? uph_delay_extent_kernel<256> : uph_extent_kernel<256>, k64 = dl ? uph_delay_extent_kernel<64> : uph_extent_kernel<64>;
     out.resize((size_t)n);
-    std::vector<DextQuery> qs;
+    std::vector<ExtQuery> qs;
     for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
         const size_t m = std::min(CLOCK_CHUNK, (size_t)n - s);
-        qs.assign(m, DextQuery());
+        qs.resize(m);
         for (size_t k = 0; k < m; k++) {
-            DextQuery& q = qs[k];
-            q.K = (int32_t)K[s + k]; q.t_from = t_from[s + k]; q.dt = dt; q.D = D; q.pad = 0;
-            q.a = clockTraj(c, traj[s + k], t0[s + k]);
+            qs[k] = clockQuery<ExtQuery>(K[s + k], t_from[s + k], dt, dl);
+            qs[k].a = clockTraj(c, traj[s + k], t0[s + k]);
         }
-        const int r = clockRun(c, qs.data(), m, a, uph_delay_extent_kernel<256>, uph_delay_extent_kernel<64>, out.data() + s, ms);
+        const int r = clockRun(c, qs.data(), m, a, k256, k64, out.data() + s, ms);
         if (r != UPH_OK) return r;
     }
     return UPH_OK;
 }
+
+// What uph_extent_batch and uph_delay_extent_batch are: the refusals, a window per query, the (swept) extents, the rows to the caller's arrays, the kernels' time
+// to the context's `last_ms`
+static int extentCall(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt,
+                      DelayTable* dl, double* box, int32_t* counts, double uph_ctx::*last_ms) {
+    if (!c || n <= 0 || !traj || !t0 || !t_from || !t_to) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(c, n, traj, t0, who.c_str());
+    if (r != UPH_OK || (r = delayAdmit(dl, n, t0, who)) != UPH_OK) return r;
+    std::vector<int64_t> K((size_t)n);
+    for (int32_t q = 0; q < n; q++)
+        if ((r = clockWindow(t_from[q], t_to[q], dt, K[(size_t)q], who, q)) != UPH_OK || (r = delayWork(K[(size_t)q], dl, who, q)) != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    if ((r = delayUpload(c, dl)) != UPH_OK) return r;
+    std::vector<ExtOut> out;
+    double ms = 0.0;
+    if ((r = extentRun(c, n, traj, t0, t_from, K.data(), dt, dl, out, ms)) != UPH_OK) return r;
+    c->*last_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const ExtOut& o = out[(size_t)q];
+        if (box) for (int k = 0; k < 4; k++) box[4 * (size_t)q + k] = o.box[k];
+        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+// What the pair calls (uph_separation_batch, uph_delay_sweep_batch) share: every refusal in their one order, cb defaulting to ca, the pair records, ca's device
+// current with cb's stream drained, the table on it
+static int pairQueries(const std::string& who, uph_ctx* ca, uph_ctx*& cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
+                       const double* t_from, const double* t_to, double dt, const double* radius, DelayTable* dl, std::vector<SepQuery>& qs) {
+    if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    if (!cb) cb = ca;
+    if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError(who + ": the two contexts are on different devices"); return UPH_ERR_INVALID; }
+    int r = checkTrajQueries(ca, n, traj_a, t0_a, who.c_str());
+    if (r == UPH_OK) r = checkTrajQueries(cb, n, traj_b, t0_b, who.c_str());
+    if (r != UPH_OK || (r = delayAdmit(dl, n, t0_b, who)) != UPH_OK) return r;
+    qs.resize((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError(whoQuery(who, q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+        int64_t K = 0;
+        if ((r = clockWindow(t_from[q], t_to[q], dt, K, who, q)) != UPH_OK || (r = delayWork(K, dl, who, q)) != UPH_OK) return r;
+        qs[(size_t)q] = sepQuery(K, t_from[q], dt, dl, radius[q], clockTraj(ca, traj_a[q], t0_a[q]), clockTraj(cb, traj_b[q], t0_b[q]));
+    }
+    HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
+    if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // what cb's stream still writes of its trajectories is there before the launch on ca's
+    return delayUpload(ca, dl);
+}
+
+// What the fleet calls (uph_conflicts_batch, uph_delays_batch) share up to their candidates: every refusal in their one order, the one window's K, the (swept)
+// extents on the device, the pairs of vehicles whose boxes the rule does not drop
+static int fleetCandidates(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays,
+                           double t_from, double t_to, double dt, DelayTable* dl, int64_t& K, std::vector<IdxPair>& cand, double& ms) {
+    int r = checkTrajQueries(c, n, traj, t0, who.c_str());
+    if (r != UPH_OK) return r;
+    for (int32_t i = 0; i < n; i++)
+        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError(who + ": vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
+    if ((r = delayAdmit(dl, n, t0, who)) != UPH_OK) return r;
+    if (dl && n_delays) for (int32_t i = 0; i < n; i++)
+        if (n_delays[i] < 1 || n_delays[i] > dl->D) { setError(who + ": vehicle " + std::to_string(i) + " has an n_delays outside [1, D]"); return UPH_ERR_INVALID; }
+    if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK || (r = delayWork(K, dl, who)) != UPH_OK) return r;
+    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
+    if ((r = delayUpload(c, dl)) != UPH_OK) return r;
+    const std::vector<double> tf((size_t)n, t_from);
+    const std::vector<int64_t> Ks((size_t)n, K);
+    std::vector<ExtOut> ext;
+    if ((r = extentRun(c, n, traj, t0, tf.data(), Ks.data(), dt, dl, ext, ms)) != UPH_OK) return r;
+    std::vector<double> box(4 * (size_t)n);
+    for (int32_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) box[4 * (size_t)i + k] = ext[(size_t)i].box[k];
+    return candidatePairs(n, box.data(), radius, who.c_str(), cand);
+}
+
 // level of vehicle j among pairs (i < j, already checked): 0 without a smaller partner, else 1 + the largest level of its smaller partners
 static void delayLevels(int32_t n, const std::vector<IdxPair>& pairs, std::vector<int32_t>& level) {
     std::vector<IdxPair> by_j(pairs.size());
@@ -1188,7 +1236,6 @@ extern "C" {
 
 int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
     if (!c || n <= 0 || !traj || !t || !out10) { setError("uph_traj_states: bad arguments"); return UPH_ERR_INVALID; }
-    if (c->pending) { setError("uph_traj_states: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     int r = checkTrajQueries(c, n, traj, t, "uph_traj_states");
     if (r != UPH_OK) return r;
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
@@ -1290,7 +1337,7 @@ int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_
     if (r != UPH_OK) return r;
     if (c->d_win_out.ensure(sizeof(CheckOut) * (size_t)n)) return UPH_ERR_HIP;
     CheckArgs a;
-    a.r = residentDev(c); a.grid_mem = c->frames.empty() ? nullptr : c->d_gridmem.as<GridDev>(); a.qs = c->d_win_q.as<WinQuery>(); a.out = c->d_win_out.as<CheckOut>();
+    a.r = residentDev(c); a.grid_mem = trajFrame(c) ? c->d_gridmem.as<GridDev>() : nullptr; a.qs = c->d_win_q.as<WinQuery>(); a.out = c->d_win_out.as<CheckOut>();
     const char* occ_r2 = nullptr;
     uphMapOcc(c->map, &a.occ, &occ_r2);
     if (lim7) std::memcpy(a.lim, lim7, sizeof(a.lim));
@@ -1370,50 +1417,17 @@ int uph_separation_times(double t_from, double t_to, double dt, int64_t* K) {
 }
 
 int uph_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt, double* box, int32_t* counts) {
-    if (!c || n <= 0 || !traj || !t0 || !t_from || !t_to) { setError("uph_extent_batch: bad arguments"); return UPH_ERR_INVALID; }
-    int r = clockSide(c, n, traj, t0, "uph_extent_batch");
-    if (r != UPH_OK) return r;
-    std::vector<int64_t> K((size_t)n);
-    for (int32_t q = 0; q < n; q++) if ((r = clockWindow(t_from[q], t_to[q], dt, K[(size_t)q], "uph_extent_batch: query " + std::to_string(q))) != UPH_OK) return r;
-    std::vector<ExtOut> out;
-    double ms = 0.0;
-    r = extentRun(c, n, traj, t0, t_from, K.data(), dt, out, ms);
-    if (r != UPH_OK) return r;
-    c->last_sep_ms = ms;
-    for (int32_t q = 0; q < n; q++) {
-        const ExtOut& o = out[(size_t)q];
-        if (box) for (int k = 0; k < 4; k++) box[4 * (size_t)q + k] = o.box[k];
-        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
-    }
-    return UPH_OK;
+    return extentCall("uph_extent_batch", c, n, traj, t0, t_from, t_to, dt, nullptr, box, counts, &uph_ctx::last_sep_ms);
 }
 
 int uph_separation_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b, const double* t_from,
                          const double* t_to, double dt, const double* radius, double* min_d2, double* min_t, double* first_t, double* last_t, int32_t* counts) {
-    const char* who = "uph_separation_batch";
-    if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError("uph_separation_batch: bad arguments"); return UPH_ERR_INVALID; }
-    if (!cb) cb = ca;
-    if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError("uph_separation_batch: the two contexts are on different devices"); return UPH_ERR_INVALID; }
-    int r = clockSide(ca, n, traj_a, t0_a, who);
-    if (r == UPH_OK) r = clockSide(cb, n, traj_b, t0_b, who);
+    std::vector<SepQuery> qs;
+    int r = pairQueries("uph_separation_batch", ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, radius, nullptr, qs);
     if (r != UPH_OK) return r;
-    std::vector<SepQuery> qs((size_t)n);
-    for (int32_t q = 0; q < n; q++) {
-        if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError("uph_separation_batch: query " + std::to_string(q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
-        int64_t K = 0;
-        if ((r = clockWindow(t_from[q], t_to[q], dt, K, "uph_separation_batch: query " + std::to_string(q))) != UPH_OK) return r;
-        SepQuery& k = qs[(size_t)q];
-        k.K = (int32_t)K; k.t_from = t_from[q]; k.dt = dt; k.R2 = radius[q] * radius[q];
-        k.a = clockTraj(ca, traj_a[q], t0_a[q]); k.b = clockTraj(cb, traj_b[q], t0_b[q]);
-    }
-    HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
-    if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // what cb's stream still writes of its trajectories is there before the launch on ca's
-    std::vector<SepOut> out((size_t)n);
+    std::vector<SepOut> out;
     double ms = 0.0;
-    for (size_t s = 0; s < (size_t)n; s += CLOCK_CHUNK) {
-        r = clockRun(ca, qs.data() + s, std::min(CLOCK_CHUNK, (size_t)n - s), sepArgs(ca, cb), uph_separation_kernel<256>, uph_separation_kernel<64>, out.data() + s, ms);
-        if (r != UPH_OK) return r;
-    }
+    if ((r = pairRun(ca, cb, qs, nullptr, uph_separation_kernel<256>, uph_separation_kernel<64>, out, ms)) != UPH_OK) return r;
     ca->last_sep_ms = ms;
     for (int32_t q = 0; q < n; q++) {
         const SepOut& o = out[(size_t)q];
@@ -1440,23 +1454,11 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
                         int32_t* pairs, double* rows, int32_t* below, int64_t* n_conflicts, int64_t* n_candidates) {
     const char* who = "uph_conflicts_batch";
     if (!c || n <= 0 || !traj || !t0 || !radius || cap < 0) { setError("uph_conflicts_batch: bad arguments"); return UPH_ERR_INVALID; }
-    int r = clockSide(c, n, traj, t0, who);
-    if (r != UPH_OK) return r;
-    for (int32_t i = 0; i < n; i++)
-        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError("uph_conflicts_batch: vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
     int64_t K = 0;
-    if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK) return r;
-    // extents on the device, candidates on the host
-    const std::vector<double> tf((size_t)n, t_from);
-    const std::vector<int64_t> Ks((size_t)n, K);
-    std::vector<ExtOut> ext;
-    double ms = 0.0;
-    r = extentRun(c, n, traj, t0, tf.data(), Ks.data(), dt, ext, ms);
-    if (r != UPH_OK) return r;
-    std::vector<double> box(4 * (size_t)n);
-    for (int32_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) box[4 * (size_t)i + k] = ext[(size_t)i].box[k];
     std::vector<IdxPair> cand;
-    if ((r = candidatePairs(n, box.data(), radius, who, cand)) != UPH_OK) return r;
+    double ms = 0.0;
+    int r = fleetCandidates(who, c, n, traj, t0, radius, nullptr, t_from, t_to, dt, nullptr, K, cand, ms);
+    if (r != UPH_OK) return r;
     // separation of the candidates, a launch pair per CLOCK_CHUNK of them; the conflicts come out in the candidates' (i, j) order
     std::vector<IdxPair> hit;
     std::vector<SepOut> hit_rows;
@@ -1464,17 +1466,12 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
     std::vector<SepOut> out;
     for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
         const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
-        qs.assign(m, SepQuery());
-        out.resize(m);
+        qs.resize(m);
         for (size_t k = 0; k < m; k++) {
             const int32_t i = cand[s + k].first, j = cand[s + k].second;
-            const double R = radius[i] + radius[j];
-            SepQuery& q = qs[k];
-            q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.R2 = R * R;
-            q.a = clockTraj(c, traj[i], t0[i]); q.b = clockTraj(c, traj[j], t0[j]);
+            qs[k] = sepQuery(K, t_from, dt, nullptr, radius[i] + radius[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j]));
         }
-        r = clockRun(c, qs.data(), m, sepArgs(c, c), uph_separation_kernel<256>, uph_separation_kernel<64>, out.data(), ms);
-        if (r != UPH_OK) return r;
+        if ((r = pairRun(c, c, qs, nullptr, uph_separation_kernel<256>, uph_separation_kernel<64>, out, ms)) != UPH_OK) return r;
         for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
     }
     c->last_sep_ms = ms;
@@ -1522,33 +1519,15 @@ int uph_delay_levels(int32_t n, int64_t n_pairs, const int32_t* pairs, int32_t* 
 int uph_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b, const double* t_from,
                           const double* t_to, double dt, const double* radius, double delay0, double delay_step, int32_t D, double* min_d2, double* min_t, int32_t* below,
                           int32_t* first_clear, int32_t* counts) {
-    const std::string who = "uph_delay_sweep_batch";
-    if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
-    if (!cb) cb = ca;
-    if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError(who + ": the two contexts are on different devices"); return UPH_ERR_INVALID; }
-    int r = clockSide(ca, n, traj_a, t0_a, who.c_str());
-    if (r == UPH_OK) r = clockSide(cb, n, traj_b, t0_b, who.c_str());
+    DelayTable dl{delay0, delay_step, D};
+    std::vector<SepQuery> qs;
+    int r = pairQueries("uph_delay_sweep_batch", ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, radius, &dl, qs);
     if (r != UPH_OK) return r;
-    std::vector<double> delta;
-    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0_b, delta, who)) != UPH_OK) return r;
-    std::vector<SweepQuery> qs((size_t)n);
-    for (int32_t q = 0; q < n; q++) {
-        if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError(who + ": query " + std::to_string(q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
-        int64_t K = 0;
-        if ((r = clockWindow(t_from[q], t_to[q], dt, K, who + ": query " + std::to_string(q))) != UPH_OK) return r;
-        if ((r = delayWork(K, D, who + ": query " + std::to_string(q))) != UPH_OK) return r;
-        SweepQuery& k = qs[(size_t)q];
-        k.K = (int32_t)K; k.t_from = t_from[q]; k.dt = dt; k.R2 = radius[q] * radius[q];
-        k.a = clockTraj(ca, traj_a[q], t0_a[q]); k.b = clockTraj(cb, traj_b[q], t0_b[q]);
-    }
-    HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
-    if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // as uph_separation_batch
-    if ((r = delayUpload(ca, delta)) != UPH_OK) return r;
     std::vector<int32_t> Ks((size_t)n);
-    for (int32_t q = 0; q < n; q++) Ks[(size_t)q] = qs[(size_t)q].K;       // (sweepRun leaves qs in launch order)
+    for (int32_t q = 0; q < n; q++) Ks[(size_t)q] = qs[(size_t)q].K;       // (pairRun leaves qs in launch order)
     std::vector<SweepOut> rows;
     double ms = 0.0;
-    if ((r = sweepRun(ca, cb, qs, D, rows, ms)) != UPH_OK) return r;
+    if ((r = pairRun(ca, cb, qs, &dl, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows, ms)) != UPH_OK) return r;
     ca->last_delay_ms = ms;
     for (int32_t q = 0; q < n; q++) {
         int32_t clear = -1;
@@ -1568,29 +1547,8 @@ int uph_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* tr
 
 int uph_delay_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* t_from, const double* t_to, double dt, double delay0, double delay_step,
                            int32_t D, double* box, int32_t* counts) {
-    const std::string who = "uph_delay_extent_batch";
-    if (!c || n <= 0 || !traj || !t0 || !t_from || !t_to) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
-    int r = clockSide(c, n, traj, t0, who.c_str());
-    if (r != UPH_OK) return r;
-    std::vector<double> delta;
-    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0, delta, who)) != UPH_OK) return r;
-    std::vector<int64_t> K((size_t)n);
-    for (int32_t q = 0; q < n; q++) {
-        if ((r = clockWindow(t_from[q], t_to[q], dt, K[(size_t)q], who + ": query " + std::to_string(q))) != UPH_OK) return r;
-        if ((r = delayWork(K[(size_t)q], D, who + ": query " + std::to_string(q))) != UPH_OK) return r;
-    }
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    if ((r = delayUpload(c, delta)) != UPH_OK) return r;
-    std::vector<ExtOut> out;
-    double ms = 0.0;
-    if ((r = delayExtentRun(c, n, traj, t0, t_from, K.data(), dt, D, out, ms)) != UPH_OK) return r;
-    c->last_delay_ms = ms;
-    for (int32_t q = 0; q < n; q++) {
-        const ExtOut& o = out[(size_t)q];
-        if (box) for (int k = 0; k < 4; k++) box[4 * (size_t)q + k] = o.box[k];
-        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
-    }
-    return UPH_OK;
+    DelayTable dl{delay0, delay_step, D};
+    return extentCall("uph_delay_extent_batch", c, n, traj, t0, t_from, t_to, dt, &dl, box, counts, &uph_ctx::last_delay_ms);
 }
 
 int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays, double t_from, double t_to, double dt,
@@ -1598,28 +1556,14 @@ int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t
                      int32_t* n_unresolved) {
     const std::string who = "uph_delays_batch";
     if (!c || n <= 0 || !traj || !t0 || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
-    int r = clockSide(c, n, traj, t0, who.c_str());
-    if (r != UPH_OK) return r;
-    for (int32_t i = 0; i < n; i++)
-        if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError(who + ": vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
-    std::vector<double> delta;
-    if ((r = delayTable(delay0, delay_step, D, delta, who)) != UPH_OK || (r = delayStarts(n, t0, delta, who)) != UPH_OK) return r;
-    if (n_delays) for (int32_t i = 0; i < n; i++)
-        if (n_delays[i] < 1 || n_delays[i] > D) { setError(who + ": vehicle " + std::to_string(i) + " has an n_delays outside [1, D]"); return UPH_ERR_INVALID; }
+    DelayTable dl{delay0, delay_step, D};
+    const std::vector<double>& delta = dl.delta;
     int64_t K = 0;
-    if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK || (r = delayWork(K, D, who)) != UPH_OK) return r;
-    HIPCHK(hipSetDevice(uphMapDevice(c->map)));
-    if ((r = delayUpload(c, delta)) != UPH_OK) return r;
-    // swept extents on the device, candidates and their levels on the host
-    const std::vector<double> tf((size_t)n, t_from);
-    const std::vector<int64_t> Ks((size_t)n, K);
-    std::vector<ExtOut> ext;
-    double ms = 0.0;
-    if ((r = delayExtentRun(c, n, traj, t0, tf.data(), Ks.data(), dt, D, ext, ms)) != UPH_OK) return r;
-    std::vector<double> box(4 * (size_t)n);
-    for (int32_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) box[4 * (size_t)i + k] = ext[(size_t)i].box[k];
     std::vector<IdxPair> cand;
-    if ((r = candidatePairs(n, box.data(), radius, who.c_str(), cand)) != UPH_OK) return r;
+    double ms = 0.0;
+    int r = fleetCandidates(who, c, n, traj, t0, radius, n_delays, t_from, t_to, dt, &dl, K, cand, ms);
+    if (r != UPH_OK) return r;
+    // the candidates' levels on the host
     std::vector<int32_t> level;
     delayLevels(n, cand, level);
     const int32_t rounds = *std::max_element(level.begin(), level.end());
@@ -1630,19 +1574,16 @@ int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t
     for (int32_t i = 0; i < n; i++) veh_of[(size_t)level[(size_t)i]].push_back(i);
     std::vector<int32_t> ch((size_t)n, 0), blk((size_t)n, -1);
     std::vector<char> taken((size_t)n * D, 0);      // [i][j]: vehicle i is below a partner ahead at delay j
-    std::vector<SweepQuery> qs;
+    std::vector<SepQuery> qs;
     std::vector<SweepOut> rows;
     for (int32_t lv = 1; lv <= rounds; lv++) {
         const std::vector<size_t>& of = cand_of[(size_t)lv];
-        qs.assign(of.size(), SweepQuery());
+        qs.resize(of.size());
         for (size_t k = 0; k < of.size(); k++) {
             const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
-            const double R = radius[h] + radius[i];
-            SweepQuery& q = qs[k];
-            q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.R2 = R * R;
-            q.a = clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]); q.b = clockTraj(c, traj[i], t0[i]);
+            qs[k] = sepQuery(K, t_from, dt, &dl, radius[h] + radius[i], clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]), clockTraj(c, traj[i], t0[i]));
         }
-        if ((r = sweepRun(c, c, qs, D, rows, ms)) != UPH_OK) return r;
+        if ((r = pairRun(c, c, qs, &dl, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows, ms)) != UPH_OK) return r;
         for (size_t k = 0; k < of.size(); k++) {        // (h ascending for each vehicle: the first h below at delay 0 is the smallest)
             const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
             for (int32_t j = 0; j < D; j++) if (rows[k * (size_t)D + j].below > 0) taken[(size_t)i * D + j] = 1;

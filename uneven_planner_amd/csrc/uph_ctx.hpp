@@ -146,7 +146,8 @@ struct SwitchQuery {            // one state query (uph_switch_state_kernel), fo
     double shift[2];
 };
 constexpr int SWITCH_COLS = 9, TRAJ_STATE_COLS = 10;
-// c holds resident trajectories and every query names one of them at a finite time
+// the check every query on resident trajectories passes: no asynchronous solve is in flight on c, c holds resident trajectories and every query names one of
+// them at a finite time (`who` opens the message)
 int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const double* t, const char* who);
 SwitchQuery trajQuery(const uph_ctx* c, int32_t b, double t);
 // the states of queries sq on c's resident trajectories into c->d_sw_out [n][cols] (enqueued on c's stream, not waited for); cols = SWITCH_COLS or TRAJ_STATE_COLS

@@ -114,3 +114,24 @@ __device__ __forceinline__ bool acrossWaves(Op op, void* lds, T&... v) {
     if (NW > 1) __syncthreads();
     return wavesFold<NW>(op, lds, v...);
 }
+// the bytes wavesPut<NW> writes for values of types T..., and whether they are listed widest first
+template <class... T>
+constexpr int wavesBytes(int nw) { return nw * (int)(sizeof(T) + ...); }
+template <class... T>
+constexpr bool wavesOrdered() {
+    size_t prev = 8;
+    bool ok = true;
+    ((ok = ok && sizeof(T) <= prev, prev = sizeof(T)), ...);
+    return ok;
+}
+// the whole reduction over a workgroup of NT lanes, with the LDS it needs: rows, row leaders, waves.  Returns whether this thread holds the result (thread 0).
+// The array belongs to the instantiation <NT, Op, T...>: a kernel that makes the same call twice needs a barrier between the two (the second call's waves
+// would write the slots thread 0 may still be folding); no kernel does so today.
+template <int NT, class Op, class... T>
+__device__ __forceinline__ bool workgroupReduce(Op op, T&... v) {
+    static_assert(NT % 64 == 0 && wavesOrdered<T...>(), "whole waves; the 8-byte values first");
+    __shared__ double lds[(wavesBytes<T...>(NT / 64) + 7) / 8];
+    rowReduce(op, v...);
+    rowLeaders(op, v...);
+    return acrossWaves<NT / 64>(op, lds, v...);
+}
