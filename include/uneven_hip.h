@@ -55,6 +55,8 @@
  *   uph_within_batch        <- which resident trajectories enter a rect of the map (a changed region) and when
  *   uph_separation_batch    <- how close two resident trajectories come at the same moment of a clock they share (each starts at its own t0 on it)
  *   uph_conflicts_batch     <- the pairs of a fleet on one map that come closer than their radii allow: extents, a host broad phase, separation
+ *   uph_footprint_separation_batch / uph_footprint_conflicts_batch  <- the same two with the vehicles as oriented rectangles (front, rear, half width)
+ *                              turned by the trajectory's yaw instead of discs
  *   uph_delays_batch        <- the smallest start delay that clears each vehicle of a fleet against all vehicles ahead of it in priority order
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
@@ -694,6 +696,56 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
                         int64_t* n_conflicts, int64_t* n_candidates);
 /* milliseconds of the kernels of the last uph_extent_batch, uph_separation_batch or uph_conflicts_batch of c (events on the context's stream) */
 int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
+/* ---- the same with oriented rectangles for the vehicles.  Sample times, the clamp of a vehicle's own time and its position X, Y are uph_separation_batch's
+ * above, unchanged; its heading psi is column 9 of uph_traj_states(traj, u), the raw yaw, at the same u.
+ *   shape          front, rear, half_width in metres, all finite and >= 0: in the body frame the rectangle spans [-rear, front] x [-half_width, half_width]
+ *                  around the trajectory's point.  Zeros are allowed and give a segment or a point.  hl = (front + rear) / 2, o = (front - rear) / 2 and
+ *                  w = half_width are formed on the host.
+ *   pose at tau    c = cos psi, s = sin psi by sincosFast (csrc/uph_common.hpp, < 0.8 ulp each); u = (c, s), v = (-s, c).  Coordinates are taken relative to
+ *                  vehicle a's point, so that no rounding grows with the place on the map: D = (X_b - X_a, Y_b - Y_a), the centres C_a = (o_a c_a, o_a s_a)
+ *                  and C_b = (D_x + o_b c_b, D_y + o_b s_b), d = C_b - C_a.  Every product and every sum of this block is rounded on its own, in the order
+ *                  written; a dot product p . q is p_x q_x + p_y q_y.
+ *   overlap        for each axis n of u_a, v_a, u_b, v_b:
+ *                      gap_n = |d . n| - ((hl_a |n . u_a| + w_a |n . v_a|) + (hl_b |n . u_b| + w_b |n . v_b|))
+ *                  and g is the largest gap_n.  The rectangles OVERLAP iff g <= 0: touching counts.  For two rectangles these four axes decide overlap
+ *                  exactly, the crossed configuration in which no corner lies inside the other rectangle included.
+ *   clearance      c2 = 0 when the rectangles overlap.  Otherwise c2 is the smallest of the eight values ex ex + ey ey, one for each corner
+ *                  (C_x +- hl u_x) +- w v_x, (C_y +- hl u_y) +- w v_y of one rectangle against the other rectangle: with e = corner - C_other,
+ *                  ex = max(|e . u_other| - hl_other, 0) and ey = max(|e . v_other| - w_other, 0).  Two disjoint rectangles are closest at a corner of one
+ *                  of them, so this is the exact squared Euclidean distance between them.  A pose with a value that is not finite gives c2 = NaN: the
+ *                  sample is neither overlapping nor below, and reads +inf for the minimum, as a NaN d2 does in `separation`.
+ *   below          a sample is BELOW when it overlaps or when c2 < M2, strictly, M2 = M * M rounded; M >= 0 is the pair's margin.  With M = 0, "below"
+ *                  means "overlapping".
+ *   minimum        the smallest c2, the smaller k among equals: a selection under the total order of the other queries, no floating-point atomics.
+ *   radii          every point of rectangle i lies within rho_i = hypot(max(front_i, rear_i), half_width_i) of (X_i, Y_i).  uph_footprint_radii gives
+ *                  r_i = (rho_i + m_i) * (1 + 2^-40) for margins m_i: if two boxes of uph_extent_batch are further apart than r_i + r_j along an axis, the
+ *                  two points are at every sample, the rectangles' clearance exceeds m_i + m_j by the share of 2^-40 that the roundings of hypot, of the
+ *                  sums and of the device's c2 (a few 1e-16 of the distance) do not use up, and no sample is below M = m_i + m_j.  uph_conflict_candidates
+ *                  with these radii therefore drops no pair that is below at any sample.
+ * Not bit for bit against numpy -- a sine is involved -- but deterministic as the other queries: no answer depends on the launch width, on how samples are
+ * split over lanes or on the query's place in the batch.  The device calls follow uph_separation_batch / uph_conflicts_batch unchanged: two contexts, cb == NULL,
+ * any output NULL, blocking, each side's frame shift, K = 0 rows (+inf, NaN, NaN, NaN, 0), every refusal with the outputs untouched, UPH_ERR_LIMIT for K > 2^22;
+ * and UPH_ERR_INVALID for a shape component that is negative or not finite and for a margin that is negative or not finite. */
+/* host only, no device needed: the broad-phase radii r[n] by the rule above */
+int uph_footprint_radii(int32_t n, const double* shape /* [n][3]: front, rear, half_width */, const double* margin /* [n] */, double* r /* [n] */);
+/* query q: vehicle (traj_a[q], t0_a[q]) of ca with shape_a[q] against vehicle (traj_b[q], t0_b[q]) of cb with shape_b[q] over [t_from[q], t_to[q]],
+ * margin[q] = M itself.  min_t, first_t and last_t are tau on the common clock: of the minimum, of the first and of the last sample below (NaN: no such
+ * sample); min_c2 is +inf for K = 0.  The kernel time is kept on ca. */
+int uph_footprint_separation_batch(uph_ctx* ca, uph_ctx* cb /* NULL: ca */, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a,
+                                   const double* t0_b, const double* t_from, const double* t_to, double dt, const double* shape_a /* [n][3] */,
+                                   const double* shape_b /* [n][3] */, const double* margin /* [n] */, double* min_c2 /* [n] */, double* min_t /* [n] */,
+                                   double* first_t /* [n], NaN: none */, double* last_t /* [n] */, int32_t* counts /* [n][3]: samples, below, overlapping */);
+/* the fleet, as uph_conflicts_batch: vehicles (traj[i], t0[i]) of c's resident batch with shape[i] and margin[i] each, one window for all.  Extents on the
+ * device, candidates on the host with uph_footprint_radii's radii, then the footprint separation of every candidate (a = i, b = j, M = margin[i] + margin[j],
+ * one rounded add) on the device in launches of bounded size.  The pairs with below > 0, in (i, j) order, the first cap of them, with rows = min_c2, min_t,
+ * first_t, last_t and below = their number of samples below; *n_conflicts is the full number of such pairs, *n_candidates the number the broad phase kept. */
+int uph_footprint_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* shape /* [n][3] */,
+                                  const double* margin /* [n]: per vehicle */, double t_from, double t_to, double dt, int64_t cap, int32_t* pairs /* [cap][2] */,
+                                  double* rows /* [cap][4]: min_c2, min_t, first_t, last_t */, int32_t* below /* [cap] */, int64_t* n_conflicts,
+                                  int64_t* n_candidates);
+/* milliseconds of the kernels of the last uph_footprint_separation_batch or uph_footprint_conflicts_batch of c (events on the context's stream) */
+int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 /* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
  * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /

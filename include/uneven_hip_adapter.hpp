@@ -695,6 +695,74 @@ public:
         }
         return out;
     }
+    // ---- the same two with the vehicles as oriented rectangles: shape = {front, rear, half_width} in metres around the trajectory's point, turned by its yaw.
+    // For car-like vehicles in corridors, where the disc that covers a car reports vehicles passing side by side or following nose to tail.  margin[q] is the
+    // clearance the pair must keep (0: only an overlap counts); a sample is below when the rectangles overlap or are closer than the margin
+    // (uph_footprint_separation_batch).
+    struct TrajFootprintSeparation {
+        std::vector<double> min_c2, min_t;      // [n] the smallest squared distance between the rectangles (0: they overlap) and its time (+inf, NaN: no sample)
+        std::vector<double> first_t, last_t;    // [n] the first / last sample below (NaN: none)
+        std::vector<int32_t> counts;            // [n][3] samples, below, overlapping
+        bool conflicts(size_t q) const { return counts[3 * q + 1] > 0; }
+        bool overlaps(size_t q) const { return counts[3 * q + 2] > 0; }
+    };
+    TrajFootprintSeparation footprintSeparationSE2TrajBatch(const std::vector<int>& traj_a, const std::vector<int>& traj_b, const std::vector<double>& t0_a,
+                                                            const std::vector<double>& t0_b, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                                            const std::vector<std::array<double, 3>>& shape_a, const std::vector<std::array<double, 3>>& shape_b,
+                                                            const std::vector<double>& margin, double dt = 0.01, const ALMTrajOpt* other = nullptr) {
+        const size_t m = traj_a.size();
+        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || shape_a.size() != m || shape_b.size() != m ||
+            margin.size() != m)
+            throw std::runtime_error("footprintSeparationSE2TrajBatch: the query arrays differ in number");
+        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("footprintSeparationSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)m;
+        TrajFootprintSeparation out;
+        if (n == 0) return out;
+        std::vector<int32_t> ta(traj_a.begin(), traj_a.end()), tb(traj_b.begin(), traj_b.end());
+        out.min_c2.assign(m, 0.0); out.min_t.assign(m, 0.0); out.first_t.assign(m, 0.0); out.last_t.assign(m, 0.0); out.counts.assign(3 * m, 0);
+        if (uph_footprint_separation_batch(ctx_, other ? other->ctx_ : nullptr, n, ta.data(), tb.data(), t0_a.data(), t0_b.data(), t_from.data(), t_to.data(), dt,
+                                           shape_a[0].data(), shape_b[0].data(), margin.data(), out.min_c2.data(), out.min_t.data(), out.first_t.data(),
+                                           out.last_t.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_footprint_separation_batch: ") + uph_last_error());
+        return out;
+    }
+    // the whole fleet with rectangles: vehicles (traj[i], t0[i]) with shape[i] and margin[i], one window.  Every pair (i < j) with a sample that overlaps or is
+    // closer than margin[i] + margin[j], in (i, j) order (uph_footprint_conflicts_batch: extents, a host broad phase on the circumscribed radii, the
+    // footprint separation of its candidates).  delaysSE2TrajBatch with the radii hypot(max(front, rear), half_width) + margin clears these pairs too.
+    struct TrajFootprintConflicts {
+        std::vector<std::array<int32_t, 2>> pairs;      // [m]
+        std::vector<double> min_c2, min_t, first_t, last_t;
+        std::vector<int32_t> below;                     // [m] samples below
+        int64_t n_conflicts = 0, n_candidates = 0;      // all conflicts (m of them are listed); pairs the broad phase kept
+    };
+    TrajFootprintConflicts footprintConflictsSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<std::array<double, 3>>& shape,
+                                                          const std::vector<double>& margin, double t_from, double t_to, double dt = 0.05, int64_t cap = -1) {
+        if (t0.size() != traj.size() || shape.size() != traj.size() || margin.size() != traj.size())
+            throw std::runtime_error("footprintConflictsSE2TrajBatch: traj, t0, shape and margin differ in number");
+        if (last_multi_) throw std::runtime_error("footprintConflictsSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajFootprintConflicts out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        int64_t room = cap >= 0 ? cap : std::max<int64_t>(1024, 4 * (int64_t)n);
+        std::vector<int32_t> pairs, below;
+        std::vector<double> rows;
+        for (;;) {                                                    // cap < 0: every conflict (repeated once with room for all of them)
+            pairs.assign((size_t)2 * room + 2, 0); rows.assign((size_t)4 * room + 4, 0.0); below.assign((size_t)room + 1, 0);
+            if (uph_footprint_conflicts_batch(ctx_, n, tr.data(), t0.data(), shape[0].data(), margin.data(), t_from, t_to, dt, room, pairs.data(), rows.data(),
+                                              below.data(), &out.n_conflicts, &out.n_candidates) != UPH_OK)
+                throw std::runtime_error(std::string("uph_footprint_conflicts_batch: ") + uph_last_error());
+            if (cap >= 0 || out.n_conflicts <= room) break;
+            room = out.n_conflicts;
+        }
+        const size_t m = (size_t)std::min<int64_t>(room, out.n_conflicts);
+        for (size_t k = 0; k < m; k++) {
+            out.pairs.push_back({pairs[2 * k], pairs[2 * k + 1]});
+            out.min_c2.push_back(rows[4 * k]); out.min_t.push_back(rows[4 * k + 1]); out.first_t.push_back(rows[4 * k + 2]); out.last_t.push_back(rows[4 * k + 3]);
+            out.below.push_back(below[k]);
+        }
+        return out;
+    }
     // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are
     // delta_j = delay0 + j * delay_step, 0 <= j < D.  separationSE2TrajBatch of a against b started at t0_b[q] + delta_j, for every j, in one call
     // (uph_delay_sweep_batch).

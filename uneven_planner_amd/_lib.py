@@ -184,6 +184,12 @@ SYMBOLS = {
     "uph_conflicts_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, C.c_double, C.c_double, _I64, C.POINTER(_I32), DP, C.POINTER(_I32),
                                       C.POINTER(_I64), C.POINTER(_I64)]),
     "uph_separation_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_footprint_radii": (C.c_int, [_I32, DP, DP, DP]),
+    "uph_footprint_separation_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, DP, DP, DP, DP, DP, DP,
+                                                 C.POINTER(_I32)]),
+    "uph_footprint_conflicts_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, C.c_double, C.c_double, _I64, C.POINTER(_I32), DP,
+                                                C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64)]),
+    "uph_footprint_kernel_ms": (C.c_int, [_VP, DP]),
     "uph_delay_times": (C.c_int, [C.c_double, C.c_double, _I32, DP]),
     "uph_delay_levels": (C.c_int, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_delay_sweep_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, C.c_double, C.c_double, _I32, DP, DP,

@@ -415,6 +415,83 @@ def conflict_candidates(box, radius):
     return np.argwhere(keep).astype(np.int32).reshape(-1, 2)
 
 
+# uph_footprint_radii / uph_footprint_separation_batch / uph_footprint_conflicts_batch (include/uneven_hip.h): numpy mirrors written from the rule.  Every product
+# and every sum below is rounded on its own, in the order the header gives; against the device only the sine and the cosine differ (numpy's, not sincosFast).
+def _shapes(shape, n, who):
+    s = np.asarray(shape, dtype=np.float64)
+    if s.shape[-1:] != (3,):
+        raise _lib.UnevenHipError(who + ": a shape is (front, rear, half_width)")
+    s = np.ascontiguousarray(np.broadcast_to(s, (n, 3)))
+    if not (np.isfinite(s).all() and (s >= 0.0).all()):
+        raise _lib.UnevenHipError(who + ": a shape component is negative or not finite")
+    return s
+
+
+def footprint_radii(shape, margin):
+    """Host mirror of uph_footprint_radii: shape (n, 3) = front, rear, half_width and margin (n,) (a scalar is broadcast) give the broad-phase radius
+    r_i = (hypot(max(front, rear), half_width) + margin_i) * (1 + 2^-40) for conflict_candidates on extent()'s boxes.  Raises for what the library refuses."""
+    s = np.asarray(shape, dtype=np.float64).reshape(-1, 3)
+    s = _shapes(s, s.shape[0], "footprint_radii")
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(margin, dtype=np.float64), (s.shape[0],)))
+    if not (np.isfinite(m).all() and (m >= 0.0).all()):
+        raise _lib.UnevenHipError("footprint_radii: a margin is negative or not finite")
+    return (np.hypot(np.maximum(s[:, 0], s[:, 1]), s[:, 2]) + m) * (1.0 + 2.0 ** -40)
+
+
+def footprint_clearance2(xy_a, yaw_a, shape_a, xy_b, yaw_b, shape_b, gap=False):
+    """Host mirror of the footprint rule at K samples: xy (K, 2) and yaw (K,) the two vehicles' poses (traj_states' columns 0, 1 and 9), shape = (front,
+    rear, half_width) each.  Returns c2 (K,) -- the squared distance between the two rectangles, 0 where they overlap or touch, NaN where a pose is not
+    finite -- and the overlap flags (K,); gap = True adds g (K,), the largest of the four separating-axis gaps (overlap is g <= 0)."""
+    a, b = np.asarray(xy_a, dtype=np.float64).reshape(-1, 2), np.asarray(xy_b, dtype=np.float64).reshape(-1, 2)
+    K = a.shape[0]
+    wa, wb = (np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), (K,))) for w in (yaw_a, yaw_b))
+    (fa, ra, ha), (fb, rb, hb) = (_shapes(s, 1, "footprint_clearance2")[0] for s in (shape_a, shape_b))
+    hla, oa, hlb, ob = 0.5 * (fa + ra), 0.5 * (fa - ra), 0.5 * (fb + rb), 0.5 * (fb - rb)
+    with np.errstate(over="ignore", invalid="ignore"):
+        bad = ~(np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & np.isfinite(wa) & np.isfinite(wb))
+        ca, sa, cb, sb = np.cos(wa), np.sin(wa), np.cos(wb), np.sin(wb)
+        ua, va, ub, vb = (ca, sa), (-sa, ca), (cb, sb), (-sb, cb)
+        dot = lambda p, q: p[0] * q[0] + p[1] * q[1]
+        # coordinates relative to vehicle a's point
+        Ca = (oa * ca, oa * sa)
+        Cb = ((b[:, 0] - a[:, 0]) + ob * cb, (b[:, 1] - a[:, 1]) + ob * sb)
+        d = (Cb[0] - Ca[0], Cb[1] - Ca[1])
+        g = np.full(K, -np.inf)
+        for n in (ua, va, ub, vb):
+            reach = (hla * np.abs(dot(n, ua)) + ha * np.abs(dot(n, va))) + (hlb * np.abs(dot(n, ub)) + hb * np.abs(dot(n, vb)))
+            g = np.maximum(g, np.abs(dot(d, n)) - reach)
+        c2 = np.full(K, np.inf)
+        for (C, u, v, hl, w), (Co, uo, vo, hlo, wo) in (((Ca, ua, va, hla, ha), (Cb, ub, vb, hlb, hb)), ((Cb, ub, vb, hlb, hb), (Ca, ua, va, hla, ha))):
+            for sx in (1.0, -1.0):
+                for sy in (1.0, -1.0):
+                    e = ((C[0] + sx * (hl * u[0])) + sy * (w * v[0]) - Co[0], (C[1] + sx * (hl * u[1])) + sy * (w * v[1]) - Co[1])
+                    ex, ey = np.maximum(np.abs(dot(e, uo)) - hlo, 0.0), np.maximum(np.abs(dot(e, vo)) - wo, 0.0)
+                    c2 = np.minimum(c2, ex * ex + ey * ey)
+        over = ~bad & (g <= 0.0)
+        c2 = np.where(bad, np.nan, np.where(over, 0.0, c2))
+        g = np.where(bad, np.nan, g)
+    return (c2, over, g) if gap else (c2, over)
+
+
+def footprint_rows(tau, xy_a, yaw_a, shape_a, xy_b, yaw_b, shape_b, margin):
+    """Host mirror of one uph_footprint_separation_batch query: tau (K,) the sample times, the poses at them, the two shapes and margin = M.  A sample is
+    below when the rectangles overlap or c2 < M * M, strictly (a NaN c2 never is); for the minimum a NaN c2 reads +inf and a tie stays with the earlier
+    sample.  Returns min_c2, min_t, first_t, last_t (NaN: no such sample) and counts (3,): samples, below, overlapping."""
+    tau = np.asarray(tau, dtype=np.float64).reshape(-1)
+    M = np.float64(margin)
+    if not (np.isfinite(M) and M >= 0.0):
+        raise _lib.UnevenHipError("footprint_rows: the margin is negative or not finite")
+    if tau.shape[0] == 0:
+        return dict(min_c2=np.inf, min_t=np.nan, first_t=np.nan, last_t=np.nan, counts=np.zeros(3, dtype=np.int32))
+    c2, over = footprint_clearance2(xy_a, yaw_a, shape_a, xy_b, yaw_b, shape_b)
+    with np.errstate(invalid="ignore"):
+        below = np.nonzero(over | (c2 < M * M))[0]
+    key = np.where(np.isnan(c2), np.inf, c2)
+    j = int(np.argmin(key))                                         # the first occurrence of the minimum
+    return dict(min_c2=key[j], min_t=tau[j], first_t=tau[below[0]] if below.size else np.nan, last_t=tau[below[-1]] if below.size else np.nan,
+                counts=np.array([tau.shape[0], below.size, np.count_nonzero(over)], dtype=np.int32))
+
+
 # uph_delay_times / uph_delay_levels / uph_delays_batch (include/uneven_hip.h): numpy mirrors written from the rule
 def delay_times(delay0, delay_step, D):
     """Host mirror of the table of start delays: delta_j = delay0 + j * delay_step (the product rounded, then the sum) for 0 <= j < D.  Raises for
@@ -1043,6 +1120,45 @@ class ALMTrajOpt:
     def separation_kernel_ms(self):
         """milliseconds of the kernels of the last extent(), separation() or conflicts() (events on the context's stream)"""
         return self._kernel_ms("uph_separation_kernel_ms")
+
+    # ---- the same with oriented rectangles for the vehicles (uph_footprint_separation_batch, uph_footprint_conflicts_batch) ---------------------------
+    def footprint_separation(self, traj_a, traj_b, t_from, t_to, shape_a, shape_b, margin, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
+        """separation() for vehicles that are rectangles: shape = (front, rear, half_width) in metres around the trajectory's point, turned by the raw yaw
+        (one shape of (3,) is broadcast).  Over the samples tau_k = t_from[q] + k dt <= t_to[q]: min_c2 and min_t (the smallest squared distance between
+        the two rectangles, 0 when they overlap, and its tau), first_t / last_t (tau of the first / last sample that overlaps or has c2 < margin[q]^2,
+        NaN: none) and counts (n, 3: samples, below, overlapping).  Broadcasting and `other` as separation().  See footprint_rows."""
+        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "footprint_separation", t0_a=t0_a, t0_b=t0_b, margin=margin)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        sa, sb = (np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (n, 3))) for s in (shape_a, shape_b))
+        out = dict(min_c2=np.full(n, np.inf), min_t=np.full(n, np.nan), first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), counts=np.zeros((n, 3), dtype=np.int32))
+        _lib.check(self.L.uph_footprint_separation_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt),
+                                                         float(dt), _dp(sa), _dp(sb), _dp(v["margin"]), _dp(out["min_c2"]), _dp(out["min_t"]), _dp(out["first_t"]),
+                                                         _dp(out["last_t"]), _ip(out["counts"])), "uph_footprint_separation_batch")
+        return out
+
+    def footprint_conflicts(self, traj, shape, margin, t_from, t_to, t0=0.0, dt=0.05, cap=None):
+        """conflicts() for vehicles that are rectangles: vehicle i is resident trajectory traj[i] started at t0[i] with shape[i] = (front, rear,
+        half_width) and margin[i] (a shape of (3,) and scalars are broadcast), one window for all.  Extents on the device, the broad phase on the host with
+        footprint_radii, the footprint separation of its candidates on the device with the margin margin[i] + margin[j].  Returns pairs (m, 2), rows
+        (m, 4) = min_c2, min_t, first_t, last_t, below (m,), n_conflicts and n_candidates as conflicts() does: every pair with a sample that overlaps
+        or is closer than its margin, or the first cap of them."""
+        tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "footprint_conflicts", t0=t0, margin=margin)
+        sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shape, dtype=np.float64), (n, 3)))
+        room = max(1024, 4 * n) if cap is None else int(cap)
+        while True:
+            pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
+            nc, nk = C.c_int64(0), C.c_int64(0)
+            _lib.check(self.L.uph_footprint_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(sh), _dp(v["margin"]), float(t_from), float(t_to), float(dt), room,
+                                                            _ip(pairs), _dp(rows), _ip(below), C.byref(nc), C.byref(nk)), "uph_footprint_conflicts_batch")
+            if cap is not None or nc.value <= room:
+                break
+            room = int(nc.value)                                    # cap = None: every conflict (the call is repeated with room for all of them)
+        m = min(room, int(nc.value))
+        return dict(pairs=pairs[:m], rows=rows[:m], below=below[:m], n_conflicts=int(nc.value), n_candidates=int(nk.value))
+
+    def footprint_kernel_ms(self):
+        """milliseconds of the kernels of the last footprint_separation() or footprint_conflicts() (events on the context's stream)"""
+        return self._kernel_ms("uph_footprint_kernel_ms")
 
     # ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch) ----------------------------------------------------------------
     def delay_sweep(self, traj_a, traj_b, t_from, t_to, radius, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):

@@ -1,6 +1,6 @@
 // libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
-// separation / extent / conflicts and the start delays on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch,
-// uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// separation / extent / conflicts, the same with oriented rectangles, and the start delays on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*,
+// uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_footprint_*, uph_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
@@ -564,6 +564,120 @@ __global__ __launch_bounds__(NT) void uph_extent_kernel(ExtArgs a) {
         box.take(X, Y);
     }
     extentRow<NT>(a, eq, box);
+}
+
+// ---- footprints (uph_footprint_separation_batch, uph_footprint_conflicts_batch): the separation query with the vehicles as oriented rectangles.  The record, the
+// sample loop, the widths and the reduction are uph_separation_kernel's; a sample also takes the raw yaw of the two states it evaluates anyway, and the pair
+// metric is the rule of include/uneven_hip.h: four separating axes, then the eight corner distances.  Every product and sum of the rule is rounded on its own
+// (fp contract off in footClearance), so the two widths and any split of the samples over lanes compute the same bits.  No terrain, no scratch.
+struct FootShape {              // query-uniform, formed on the host (footShape)
+    double hl, o, w;            // half length (front + rear) / 2, the centre's offset along the heading (front - rear) / 2, half width
+};
+struct FootQuery : ClockQuery {
+    double M2;                  // a sample is below when it overlaps or c2 < M2
+    FootShape sa, sb;
+    ClockTraj a, b;
+};
+struct FootOut {                // one row per query
+    double min_c2, min_t;       // +inf, NaN: no sample
+    double first_t, last_t;     // first / last sample below (NaN: none)
+    int32_t counts[3], pad;     // samples, below, overlapping
+};
+struct FootArgs {
+    ResidentDev ra, rb;         // as SepArgs
+    const FootQuery* qs;
+    FootOut* out;
+    int framed_a, framed_b, q0;
+};
+
+// the vehicle's pose at tau: clockSample's position -- it leaves locSample as it does there -- and the raw yaw of the same state (uph_traj_states' column 9)
+__device__ __forceinline__ void clockPose(const ClockView& v, double tau, double& X, double& Y, double& psi) {
+    const double u = tau - v.t0;
+    const double t = u <= 0.0 ? 0.0 : (u >= v.total ? v.total : u);
+    TrajSample s;
+    locSample(v.tr, t, s, X, Y);
+    psi = s.yaw;
+    asm volatile("" : "+v"(psi));
+}
+// one corner of a rectangle (centre Cx, Cy; hx, hy = hl u; wx, wy = w v) against the other rectangle (centre Ox, Oy; heading co, so; half sizes hlo, wo)
+__device__ __forceinline__ double footCorner(double px, double py, double Ox, double Oy, double co, double so, double hlo, double wo) {
+#pragma clang fp contract(off)
+    const double e0 = px - Ox, e1 = py - Oy;
+    const double lx = fabs(e0 * co + e1 * so) - hlo, ly = fabs(e0 * (-so) + e1 * co) - wo;
+    const double ex = lx > 0.0 ? lx : 0.0, ey = ly > 0.0 ? ly : 0.0;
+    return ex * ex + ey * ey;
+}
+__device__ __forceinline__ double footCorners(double Cx, double Cy, double c, double s, const FootShape& R, double Ox, double Oy, double co, double so, const FootShape& O) {
+#pragma clang fp contract(off)
+    const double hx = R.hl * c, hy = R.hl * s, wx = R.w * (-s), wy = R.w * c;
+    double m = __builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const double sx = (k & 2) ? -1.0 : 1.0, sy = (k & 1) ? -1.0 : 1.0;
+        const double d2 = footCorner((Cx + sx * hx) + sy * wx, (Cy + sx * hy) + sy * wy, Ox, Oy, co, so, O.hl, O.w);
+        m = d2 < m ? d2 : m;
+    }
+    return m;
+}
+// c2 and whether the rectangles overlap, by the rule; a pose that is not finite: NaN, not overlapping
+__device__ __forceinline__ void footClearance(const FootShape& A, const FootShape& B, double Xa, double Ya, double psia, double Xb, double Yb, double psib, double& c2,
+                                              bool& over) {
+#pragma clang fp contract(off)
+    const double inf = __builtin_huge_val();
+    const bool finite = fabs(Xa) < inf && fabs(Ya) < inf && fabs(psia) < inf && fabs(Xb) < inf && fabs(Yb) < inf && fabs(psib) < inf;
+    double sa, ca, sb, cb;
+    sincosFast(psia, sa, ca);
+    sincosFast(psib, sb, cb);
+    const double Cax = A.o * ca, Cay = A.o * sa;
+    const double Cbx = (Xb - Xa) + B.o * cb, Cby = (Yb - Ya) + B.o * sb;
+    const double dx = Cbx - Cax, dy = Cby - Cay;
+    // the axes' products: n . u and n . v of the axis' own rectangle are c c + s s and exactly 0; across the two, u_a . u_b = v_a . v_b and |u_a . v_b| = |v_a . u_b|
+    const double naa = ca * ca + sa * sa, nbb = cb * cb + sb * sb;
+    const double uu = fabs(ca * cb + sa * sb), uv = fabs(ca * (-sb) + sa * cb);
+    const double g0 = fabs(dx * ca + dy * sa) - (A.hl * naa + (B.hl * uu + B.w * uv));
+    const double g1 = fabs(dx * (-sa) + dy * ca) - (A.w * naa + (B.hl * uv + B.w * uu));
+    const double g2 = fabs(dx * cb + dy * sb) - ((A.hl * uu + A.w * uv) + B.hl * nbb);
+    const double g3 = fabs(dx * (-sb) + dy * cb) - ((A.hl * uv + A.w * uu) + B.w * nbb);
+    const double g01 = g0 > g1 ? g0 : g1, g23 = g2 > g3 ? g2 : g3;
+    const double g = g01 > g23 ? g01 : g23;
+    const double ma = footCorners(Cax, Cay, ca, sa, A, Cbx, Cby, cb, sb, B), mb = footCorners(Cbx, Cby, cb, sb, B, Cax, Cay, ca, sa, A);
+    over = finite && g <= 0.0;
+    c2 = !finite ? __builtin_nan("") : (over ? 0.0 : (ma < mb ? ma : mb));
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_footprint_kernel(FootArgs a) {
+    const FootQuery fq = a.qs[a.q0 + blockIdx.x];
+    const ClockView va = clockView(a.ra, fq.a, a.framed_a != 0), vb = clockView(a.rb, fq.b, a.framed_b != 0);
+    const int n = fq.K;
+    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
+    double v = inf;
+    int i = WIN_NONE, nover = 0;
+    Span below;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        const double tau = clockTau(fq, j);
+        double Xa, Ya, Pa, Xb, Yb, Pb, c2;
+        bool over;
+        clockPose(va, tau, Xa, Ya, Pa);
+        clockPose(vb, tau, Xb, Yb, Pb);
+        footClearance(fq.sa, fq.sb, Xa, Ya, Pa, Xb, Yb, Pb, c2, over);
+        winTake<false>(v, i, c2 < inf ? c2 : inf, j);       // NaN: +inf
+        if (over || c2 < fq.M2) below.take(j);              // (a NaN c2 is not below)
+        nover += over ? 1 : 0;
+    }
+    const auto fold = [](double& v, int& i, int& lo, int& hi, int& c, int& no, double ov, int oi, int ol, int oh, int oc, int ono) {
+        winTake<false>(v, i, ov, oi);
+        SpanFold()(lo, hi, c, ol, oh, oc);
+        no += ono;
+    };
+    if (!workgroupReduce<NT>(fold, v, i, below.first, below.last, below.cnt, nover)) return;
+    FootOut o;
+    o.min_c2 = v;
+    o.min_t = i == WIN_NONE ? nan : clockTau(fq, i);
+    o.first_t = below.cnt == 0 ? nan : clockTau(fq, below.first);
+    o.last_t = below.cnt == 0 ? nan : clockTau(fq, below.last);
+    o.counts[0] = n; o.counts[1] = below.cnt; o.counts[2] = nover; o.pad = 0;
+    a.out[fq.out] = o;
 }
 
 // ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch): the separation / the extent of a query (the same records) for every start
@@ -1232,6 +1346,58 @@ static void delayLevels(int32_t n, const std::vector<IdxPair>& pairs, std::vecto
     for (const IdxPair& p : by_j) level[(size_t)p.first] = std::max(level[(size_t)p.first], level[(size_t)p.second] + 1);     // (the levels of i < j are final)
 }
 
+// ---- footprints (include/uneven_hip.h uph_footprint_*) ------------------------------------------------------------------------------------------------
+// the refusals of n shapes [n][3] and (margin != nullptr) n margins, named `what` in the message ("shape", "shape_a", ...)
+static int footAdmit(const std::string& who, int32_t n, const double* shape, const char* what, const double* margin) {
+    for (int32_t q = 0; q < n; q++) {
+        for (int k = 0; k < 3; k++) {
+            const double s = shape[3 * (size_t)q + k];
+            if (!std::isfinite(s) || s < 0.0) { setError(whoQuery(who, q) + " has a negative or non-finite " + what + " component"); return UPH_ERR_INVALID; }
+        }
+        if (margin && (!std::isfinite(margin[q]) || margin[q] < 0.0)) { setError(whoQuery(who, q) + " has a negative or non-finite margin"); return UPH_ERR_INVALID; }
+    }
+    return UPH_OK;
+}
+static FootShape footShape(const double* s3) {
+    FootShape s;
+    s.hl = 0.5 * (s3[0] + s3[1]); s.o = 0.5 * (s3[0] - s3[1]); s.w = s3[2];
+    return s;
+}
+// r = (hypot(max(front, rear), half_width) + margin) (1 + 2^-40), each operation rounded (shapes and margins already admitted)
+static double footRadius(const double* s3, double margin) {
+#pragma clang fp contract(off)
+    const double reach = std::hypot(std::max(s3[0], s3[1]), s3[2]) + margin;
+    return reach * (1.0 + 0x1p-40);
+}
+static int footRadii(const std::string& who, int32_t n, const double* shape, const double* margin, std::vector<double>& r) {
+    r.resize((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        r[(size_t)i] = footRadius(shape + 3 * (size_t)i, margin[i]);
+        if (!std::isfinite(r[(size_t)i])) { setError(whoQuery(who, i) + " has a shape and margin whose radius is not finite"); return UPH_ERR_INVALID; }
+    }
+    return UPH_OK;
+}
+// a footprint record from the pair record of the same query (pairQueries / sepQuery with R = M: the window, the two vehicles, M2 = M * M rounded)
+static FootQuery footQuery(const SepQuery& s, const double* shape_a, const double* shape_b) {
+    FootQuery q = clockQuery<FootQuery>(s.K, s.t_from, s.dt, nullptr);
+    q.M2 = s.R2; q.sa = footShape(shape_a); q.sb = footShape(shape_b); q.a = s.a; q.b = s.b;
+    return q;
+}
+// the footprint queries qs -> a row per query in the caller's order, in launches of at most CLOCK_CHUNK; qs is left in launch order
+static int footRun(uph_ctx* ca, uph_ctx* cb, std::vector<FootQuery>& qs, std::vector<FootOut>& rows, double& ms) {
+    rows.resize(qs.size());
+    FootArgs a{};
+    a.ra = residentDev(ca); a.rb = residentDev(cb);
+    a.framed_a = trajFrame(ca); a.framed_b = trajFrame(cb);
+    void (*const k256)(FootArgs) = uph_footprint_kernel<256>;
+    void (*const k64)(FootArgs) = uph_footprint_kernel<64>;
+    for (size_t s = 0; s < qs.size(); s += CLOCK_CHUNK) {
+        const int r = clockRun(ca, qs.data() + s, std::min(CLOCK_CHUNK, qs.size() - s), a, k256, k64, rows.data() + s, ms);
+        if (r != UPH_OK) return r;
+    }
+    return UPH_OK;
+}
+
 extern "C" {
 
 int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
@@ -1489,6 +1655,88 @@ int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double
 int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms) {
     if (!c || !kernel_ms) { setError("uph_separation_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
     *kernel_ms = c->last_sep_ms;
+    return UPH_OK;
+}
+
+// ---- footprints (include/uneven_hip.h) -------------------------------------------------------------------------------------------------------------------
+int uph_footprint_radii(int32_t n, const double* shape, const double* margin, double* r) {
+    const std::string who = "uph_footprint_radii";
+    if (n < 0 || (n > 0 && (!shape || !margin || !r))) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<double> out;
+    int rc = footAdmit(who, n, shape, "shape", margin);
+    if (rc != UPH_OK || (rc = footRadii(who, n, shape, margin, out)) != UPH_OK) return rc;
+    std::copy(out.begin(), out.end(), r);
+    return UPH_OK;
+}
+
+int uph_footprint_separation_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
+                                   const double* t_from, const double* t_to, double dt, const double* shape_a, const double* shape_b, const double* margin, double* min_c2,
+                                   double* min_t, double* first_t, double* last_t, int32_t* counts) {
+    const std::string who = "uph_footprint_separation_batch";
+    if (!ca || n <= 0 || !shape_a || !shape_b || !margin) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    int r = footAdmit(who, n, shape_a, "shape_a", margin);
+    if (r != UPH_OK || (r = footAdmit(who, n, shape_b, "shape_b", nullptr)) != UPH_OK) return r;
+    std::vector<SepQuery> pq;       // the pair call's refusals, windows and vehicles, the margin in the radius' place
+    if ((r = pairQueries(who, ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, margin, nullptr, pq)) != UPH_OK) return r;
+    std::vector<FootQuery> qs((size_t)n);
+    for (int32_t q = 0; q < n; q++) qs[(size_t)q] = footQuery(pq[(size_t)q], shape_a + 3 * (size_t)q, shape_b + 3 * (size_t)q);
+    std::vector<FootOut> out;
+    double ms = 0.0;
+    if ((r = footRun(ca, cb, qs, out, ms)) != UPH_OK) return r;
+    ca->last_foot_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        const FootOut& o = out[(size_t)q];
+        if (min_c2) min_c2[q] = o.min_c2;
+        if (min_t) min_t[q] = o.min_t;
+        if (first_t) first_t[q] = o.first_t;
+        if (last_t) last_t[q] = o.last_t;
+        if (counts) for (int k = 0; k < 3; k++) counts[3 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_footprint_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* shape, const double* margin, double t_from, double t_to,
+                                  double dt, int64_t cap, int32_t* pairs, double* rows, int32_t* below, int64_t* n_conflicts, int64_t* n_candidates) {
+    const std::string who = "uph_footprint_conflicts_batch";
+    if (!c || n <= 0 || !traj || !t0 || !shape || !margin || cap < 0) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<double> radius;
+    int r = footAdmit(who, n, shape, "shape", margin);
+    if (r != UPH_OK || (r = footRadii(who, n, shape, margin, radius)) != UPH_OK) return r;
+    int64_t K = 0;
+    std::vector<IdxPair> cand;
+    double ms = 0.0;
+    if ((r = fleetCandidates(who, c, n, traj, t0, radius.data(), nullptr, t_from, t_to, dt, nullptr, K, cand, ms)) != UPH_OK) return r;
+    // the footprint separation of the candidates; the conflicts come out in the candidates' (i, j) order
+    std::vector<FootQuery> qs;
+    std::vector<FootOut> out;
+    std::vector<IdxPair> hit;
+    std::vector<FootOut> hit_rows;
+    for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
+        const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
+        qs.resize(m);
+        for (size_t k = 0; k < m; k++) {
+            const int32_t i = cand[s + k].first, j = cand[s + k].second;
+            qs[k] = footQuery(sepQuery(K, t_from, dt, nullptr, margin[i] + margin[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j])), shape + 3 * (size_t)i,
+                              shape + 3 * (size_t)j);
+        }
+        if ((r = footRun(c, c, qs, out, ms)) != UPH_OK) return r;
+        for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
+    }
+    c->last_foot_ms = ms;
+    for (size_t k = 0; k < hit.size() && (int64_t)k < cap; k++) {
+        const FootOut& o = hit_rows[k];
+        if (pairs) { pairs[2 * k] = hit[k].first; pairs[2 * k + 1] = hit[k].second; }
+        if (rows) { rows[4 * k] = o.min_c2; rows[4 * k + 1] = o.min_t; rows[4 * k + 2] = o.first_t; rows[4 * k + 3] = o.last_t; }
+        if (below) below[k] = o.counts[1];
+    }
+    if (n_conflicts) *n_conflicts = (int64_t)hit.size();
+    if (n_candidates) *n_candidates = (int64_t)cand.size();
+    return UPH_OK;
+}
+
+int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError("uph_footprint_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->last_foot_ms;
     return UPH_OK;
 }
 
