@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -647,9 +648,7 @@ public:
                                           const std::vector<double>& t_from, const std::vector<double>& t_to, const std::vector<double>& radius, double dt = 0.01,
                                           const ALMTrajOpt* other = nullptr) {
         const size_t m = traj_a.size();
-        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || radius.size() != m)
-            throw std::runtime_error("separationSE2TrajBatch: the query arrays differ in number");
-        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("separationSE2TrajBatch: the last batch was split over several devices");
+        pairCheck("separationSE2TrajBatch", m, {traj_b.size(), t0_a.size(), t0_b.size(), t_from.size(), t_to.size(), radius.size()}, other);
         const int32_t n = (int32_t)m;
         TrajSeparation out;
         if (n == 0) return out;
@@ -676,23 +675,9 @@ public:
         TrajConflicts out;
         if (n == 0) return out;
         std::vector<int32_t> tr(traj.begin(), traj.end());
-        int64_t room = cap >= 0 ? cap : std::max<int64_t>(1024, 4 * (int64_t)n);
-        std::vector<int32_t> pairs, below;
-        std::vector<double> rows;
-        for (;;) {                                                    // cap < 0: every conflict (repeated once with room for all of them)
-            pairs.assign((size_t)2 * room + 2, 0); rows.assign((size_t)4 * room + 4, 0.0); below.assign((size_t)room + 1, 0);
-            if (uph_conflicts_batch(ctx_, n, tr.data(), t0.data(), radius.data(), t_from, t_to, dt, room, pairs.data(), rows.data(), below.data(), &out.n_conflicts,
-                                    &out.n_candidates) != UPH_OK)
-                throw std::runtime_error(std::string("uph_conflicts_batch: ") + uph_last_error());
-            if (cap >= 0 || out.n_conflicts <= room) break;
-            room = out.n_conflicts;
-        }
-        const size_t m = (size_t)std::min<int64_t>(room, out.n_conflicts);
-        for (size_t k = 0; k < m; k++) {
-            out.pairs.push_back({pairs[2 * k], pairs[2 * k + 1]});
-            out.min_d2.push_back(rows[4 * k]); out.min_t.push_back(rows[4 * k + 1]); out.first_t.push_back(rows[4 * k + 2]); out.last_t.push_back(rows[4 * k + 3]);
-            out.below.push_back(below[k]);
-        }
+        conflictList(out, out.min_d2, n, cap, "uph_conflicts_batch", [&](int64_t room, int32_t* pairs, double* rows, int32_t* below) {
+            return uph_conflicts_batch(ctx_, n, tr.data(), t0.data(), radius.data(), t_from, t_to, dt, room, pairs, rows, below, &out.n_conflicts, &out.n_candidates);
+        });
         return out;
     }
     // ---- the same two with the vehicles as oriented rectangles: shape = {front, rear, half_width} in metres around the trajectory's point, turned by its yaw.
@@ -711,10 +696,8 @@ public:
                                                             const std::vector<std::array<double, 3>>& shape_a, const std::vector<std::array<double, 3>>& shape_b,
                                                             const std::vector<double>& margin, double dt = 0.01, const ALMTrajOpt* other = nullptr) {
         const size_t m = traj_a.size();
-        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || shape_a.size() != m || shape_b.size() != m ||
-            margin.size() != m)
-            throw std::runtime_error("footprintSeparationSE2TrajBatch: the query arrays differ in number");
-        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("footprintSeparationSE2TrajBatch: the last batch was split over several devices");
+        pairCheck("footprintSeparationSE2TrajBatch", m, {traj_b.size(), t0_a.size(), t0_b.size(), t_from.size(), t_to.size(), shape_a.size(), shape_b.size(), margin.size()},
+                  other);
         const int32_t n = (int32_t)m;
         TrajFootprintSeparation out;
         if (n == 0) return out;
@@ -744,23 +727,10 @@ public:
         TrajFootprintConflicts out;
         if (n == 0) return out;
         std::vector<int32_t> tr(traj.begin(), traj.end());
-        int64_t room = cap >= 0 ? cap : std::max<int64_t>(1024, 4 * (int64_t)n);
-        std::vector<int32_t> pairs, below;
-        std::vector<double> rows;
-        for (;;) {                                                    // cap < 0: every conflict (repeated once with room for all of them)
-            pairs.assign((size_t)2 * room + 2, 0); rows.assign((size_t)4 * room + 4, 0.0); below.assign((size_t)room + 1, 0);
-            if (uph_footprint_conflicts_batch(ctx_, n, tr.data(), t0.data(), shape[0].data(), margin.data(), t_from, t_to, dt, room, pairs.data(), rows.data(),
-                                              below.data(), &out.n_conflicts, &out.n_candidates) != UPH_OK)
-                throw std::runtime_error(std::string("uph_footprint_conflicts_batch: ") + uph_last_error());
-            if (cap >= 0 || out.n_conflicts <= room) break;
-            room = out.n_conflicts;
-        }
-        const size_t m = (size_t)std::min<int64_t>(room, out.n_conflicts);
-        for (size_t k = 0; k < m; k++) {
-            out.pairs.push_back({pairs[2 * k], pairs[2 * k + 1]});
-            out.min_c2.push_back(rows[4 * k]); out.min_t.push_back(rows[4 * k + 1]); out.first_t.push_back(rows[4 * k + 2]); out.last_t.push_back(rows[4 * k + 3]);
-            out.below.push_back(below[k]);
-        }
+        conflictList(out, out.min_c2, n, cap, "uph_footprint_conflicts_batch", [&](int64_t room, int32_t* pairs, double* rows, int32_t* below) {
+            return uph_footprint_conflicts_batch(ctx_, n, tr.data(), t0.data(), shape[0].data(), margin.data(), t_from, t_to, dt, room, pairs, rows, below, &out.n_conflicts,
+                                                 &out.n_candidates);
+        });
         return out;
     }
     // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are
@@ -777,9 +747,7 @@ public:
                                           const std::vector<double>& t_from, const std::vector<double>& t_to, const std::vector<double>& radius, double delay0,
                                           double delay_step, int D, double dt = 0.01, const ALMTrajOpt* other = nullptr) {
         const size_t m = traj_a.size();
-        if (traj_b.size() != m || t0_a.size() != m || t0_b.size() != m || t_from.size() != m || t_to.size() != m || radius.size() != m)
-            throw std::runtime_error("delaySweepSE2TrajBatch: the query arrays differ in number");
-        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error("delaySweepSE2TrajBatch: the last batch was split over several devices");
+        pairCheck("delaySweepSE2TrajBatch", m, {traj_b.size(), t0_a.size(), t0_b.size(), t_from.size(), t_to.size(), radius.size()}, other);
         TrajDelaySweep out;
         out.D = (int32_t)D;
         if (m == 0) return out;
@@ -886,6 +854,31 @@ public:
     }
 
 private:
+    // what the calls on pairs of vehicles check first: every query array has traj_a's length m, neither side's last batch was split
+    void pairCheck(const char* who, size_t m, std::initializer_list<size_t> sizes, const ALMTrajOpt* other) const {
+        for (const size_t s : sizes) if (s != m) throw std::runtime_error(std::string(who) + ": the query arrays differ in number");
+        if (last_multi_ || (other && other->last_multi_)) throw std::runtime_error(std::string(who) + ": the last batch was split over several devices");
+    }
+    // the conflict list of a fleet call -- call(room, pairs, rows, below): the C call `who` with room for `room` conflicts, which also sets out.n_conflicts; cap < 0:
+    // every conflict (repeated once with room for all of them) -- unpacked into out.pairs, min (out.min_d2 / out.min_c2), out.min_t, first_t, last_t and below
+    template <class Out, class Call>
+    static void conflictList(Out& out, std::vector<double>& min, int32_t n, int64_t cap, const char* who, Call call) {
+        int64_t room = cap >= 0 ? cap : std::max<int64_t>(1024, 4 * (int64_t)n);
+        std::vector<int32_t> pairs, below;
+        std::vector<double> rows;
+        for (;;) {
+            pairs.assign((size_t)2 * room + 2, 0); rows.assign((size_t)4 * room + 4, 0.0); below.assign((size_t)room + 1, 0);
+            if (call(room, pairs.data(), rows.data(), below.data()) != UPH_OK) throw std::runtime_error(std::string(who) + ": " + uph_last_error());
+            if (cap >= 0 || out.n_conflicts <= room) break;
+            room = out.n_conflicts;
+        }
+        const size_t m = (size_t)std::min<int64_t>(room, out.n_conflicts);
+        for (size_t k = 0; k < m; k++) {
+            out.pairs.push_back({pairs[2 * k], pairs[2 * k + 1]});
+            min.push_back(rows[4 * k]); out.min_t.push_back(rows[4 * k + 1]); out.first_t.push_back(rows[4 * k + 2]); out.last_t.push_back(rows[4 * k + 3]);
+            out.below.push_back(below[k]);
+        }
+    }
     GoalPlan finishGoalPlan(int rc, int32_t B, GoalPlan& out, const std::vector<int32_t>& nxy, const std::vector<int32_t>& nyw, const char* who, const char* caller);
     // coefficient blocks of the C-ABI (lowest order first, xy interleaved per row) -> pieces with the highest order first (se2traj.hpp:682-695)
     static SE2Trajectory makeTraj(const double* cxy, int Nxy, double Txy, const double* cyaw, int Nyaw, double Tyaw) {

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from test_gpu_replan import _hill_map, _queries, _source
+from test_gpu_separation import _totals, _valid
 from uneven_planner_amd import _lib
 from uneven_planner_amd.alm_traj_opt import conflict_candidates, footprint_clearance2, footprint_radii, separation_times
 
@@ -34,15 +35,6 @@ INF = float("inf")
 NAN = float("nan")
 TOL = 1e-9
 FKEYS = ("min_c2", "min_t", "first_t", "last_t", "counts")
-
-
-def _valid(res):
-    return [j for j, r in enumerate(res) if r["ret"] != 4 and np.isfinite(r["c_xy"]).all() and np.isfinite([r["T_xy"], r["T_yaw"]]).all()]
-
-
-def _totals(opt):
-    offs, rows = opt.rollout(1.0, 1, with_end=True)
-    return rows[offs[1:] - 1, 0]
 
 
 def _bc(v, n, width=None):

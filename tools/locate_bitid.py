@@ -4,8 +4,9 @@ point, and the middle third of every duration at dt 0.03), the STATE rollout at 
 uph_traj_states at a third and two thirds of every duration, locate (every output) for poses made from the recorded rollout rows plus seeded noise and
 within for rects around the same rows, both on the check's two kinds of windows, the common-clock calls on the fleet of tools/separation_probe.py and
 tools/delay_probe.py (the valid trajectories, starts uniform in [0, 60] s from seed 91, discs of 0.1 m, D = 32 delays of 0.5 s; the probes' window of 101
-samples, one wave, and one of 401, 256 lanes): extent, separation of vehicle i against i + 1, conflicts, delay_sweep, delay_extent and delays, and the
-switch states replan_goals_upload returns at a third of every duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
+samples, one wave, and one of 401, 256 lanes): extent, separation of vehicle i against i + 1, conflicts, delay_sweep, delay_extent and delays, the same
+separation and conflicts with the car and margin of tools/footprint_probe.py (footprint_separation, footprint_conflicts: shape 0.45, 0.15, 0.15 m, margin
+0.05 m per vehicle), every returned key, and the switch states replan_goals_upload returns at a third of every duration.  Run it once per library (UNEVENHIP_LIB selects another build), then
 python tools/check_bitid.py compare A.npz B.npz (np.array_equal, NaN equal to NaN)."""
 import os
 import sys
@@ -49,6 +50,7 @@ for tag, kw in (("full", dict()), ("third", dict(t_from=total / 3.0, t_to=2.0 * 
             arrs["%s_%s_%s" % (name, tag, k)] = v
 # the clock families on the probes' fleet
 t0 = np.random.default_rng(91).uniform(0.0, 60.0, valid.size)
+CAR, MARGIN = np.array([0.45, 0.15, 0.15]), 0.05
 other, t0_other = np.roll(valid, -1), np.roll(t0, -1)
 for tag, (tf, tt) in (("101", (30.0, 35.0)), ("401", (20.0, 40.0))):
     calls = (("extent", opt.extent(valid, tf, tt, t0=t0, dt=0.05)),
@@ -56,7 +58,9 @@ for tag, (tf, tt) in (("101", (30.0, 35.0)), ("401", (20.0, 40.0))):
              ("conflicts", opt.conflicts(valid, 0.1, tf, tt, t0=t0, dt=0.05)),
              ("delay_sweep", opt.delay_sweep(valid, other, tf, tt, 0.2, 0.0, 0.5, 32, t0_a=t0, t0_b=t0_other, dt=0.05)),
              ("delay_extent", opt.delay_extent(valid, tf, tt, 0.0, 0.5, 32, t0=t0, dt=0.05)),
-             ("delays", opt.delays(valid, 0.1, tf, tt, 0.0, 0.5, 32, t0=t0, dt=0.05)))
+             ("delays", opt.delays(valid, 0.1, tf, tt, 0.0, 0.5, 32, t0=t0, dt=0.05)),
+             ("footprint_separation", opt.footprint_separation(valid, other, tf, tt, CAR, CAR, 2.0 * MARGIN, t0_a=t0, t0_b=t0_other, dt=0.05)),
+             ("footprint_conflicts", opt.footprint_conflicts(valid, CAR, MARGIN, tf, tt, t0=t0, dt=0.05)))
     for name, res_ in calls:
         for k, v in res_.items():
             arrs["%s_%s_%s" % (name, tag, k)] = np.asarray(v)

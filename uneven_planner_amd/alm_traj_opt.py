@@ -1076,6 +1076,26 @@ class ALMTrajOpt:
         bc = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
         return tr, n, bc(t_from), bc(t_to), {k: bc(v) for k, v in per_query.items()}
 
+    def _pair(self, traj_a, traj_b, t_from, t_to, other, who, **per_query):
+        """_clock for the calls on pairs of vehicles, with traj_b broadcast against traj_a and the handle of b's context (None: self)"""
+        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, who, **per_query)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        return tr, tb, n, tf, tt, v, None if other is None else other.h
+
+    @staticmethod
+    def _conflict_list(call, n, cap, who):
+        """the conflict list of a fleet call, call(room, pairs, rows, below, n_conflicts, n_candidates); cap = None: repeated with room for every conflict"""
+        room = max(1024, 4 * n) if cap is None else int(cap)
+        while True:
+            pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
+            nc, nk = C.c_int64(0), C.c_int64(0)
+            _lib.check(call(room, _ip(pairs), _dp(rows), _ip(below), C.byref(nc), C.byref(nk)), who)
+            if cap is not None or nc.value <= room:
+                break
+            room = int(nc.value)
+        m = min(room, int(nc.value))
+        return dict(pairs=pairs[:m], rows=rows[:m], below=below[:m], n_conflicts=int(nc.value), n_candidates=int(nk.value))
+
     def extent(self, traj, t_from, t_to, t0=0.0, dt=0.01):
         """The bounding box, on the device, of vehicle q -- resident trajectory traj[q] started at t0[q] on a common clock -- over the samples
         tau_k = t_from[q] + k dt <= t_to[q] of that clock (scalars are broadcast): box (n, 4) = xmin, xmax, ymin, ymax in map coordinates and counts
@@ -1090,12 +1110,10 @@ class ALMTrajOpt:
         traj_b[q] of `other` (an ALMTrajOpt on the same device; None: self) started at t0_b[q] -- come over the samples tau_k = t_from[q] + k dt <=
         t_to[q]: min_d2 and min_t (the smallest squared distance and its tau), first_t / last_t (tau of the first / last sample with d2 < radius[q]^2,
         NaN: none) and counts (n, 2: samples, below).  A vehicle stands at its start before its t0 and at its goal after its end.  See separation_rows."""
-        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "separation", t0_a=t0_a, t0_b=t0_b, radius=radius)
-        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        tr, tb, n, tf, tt, v, hb = self._pair(traj_a, traj_b, t_from, t_to, other, "separation", t0_a=t0_a, t0_b=t0_b, radius=radius)
         out = dict(min_d2=np.full(n, np.inf), min_t=np.full(n, np.nan), first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), counts=np.zeros((n, 2), dtype=np.int32))
-        _lib.check(self.L.uph_separation_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
-                                               _dp(v["radius"]), _dp(out["min_d2"]), _dp(out["min_t"]), _dp(out["first_t"]), _dp(out["last_t"]), _ip(out["counts"])),
-                   "uph_separation_batch")
+        _lib.check(self.L.uph_separation_batch(self.h, hb, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt), _dp(v["radius"]),
+                                               _dp(out["min_d2"]), _dp(out["min_t"]), _dp(out["first_t"]), _dp(out["last_t"]), _ip(out["counts"])), "uph_separation_batch")
         return out
 
     def conflicts(self, traj, radius, t_from, t_to, t0=0.0, dt=0.05, cap=None):
@@ -1105,17 +1123,8 @@ class ALMTrajOpt:
         (radius[i] + radius[j])^2 or the first cap of them --, rows (m, 4) = min_d2, min_t, first_t, last_t, below (m,), n_conflicts (all of them) and
         n_candidates (pairs the broad phase kept).  See conflict_candidates / separation_rows."""
         tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "conflicts", t0=t0, radius=radius)
-        room = max(1024, 4 * n) if cap is None else int(cap)
-        while True:
-            pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
-            nc, nk = C.c_int64(0), C.c_int64(0)
-            _lib.check(self.L.uph_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(v["radius"]), float(t_from), float(t_to), float(dt), room, _ip(pairs), _dp(rows),
-                                                  _ip(below), C.byref(nc), C.byref(nk)), "uph_conflicts_batch")
-            if cap is not None or nc.value <= room:
-                break
-            room = int(nc.value)                                    # cap = None: every conflict (the call is repeated with room for all of them)
-        m = min(room, int(nc.value))
-        return dict(pairs=pairs[:m], rows=rows[:m], below=below[:m], n_conflicts=int(nc.value), n_candidates=int(nk.value))
+        return self._conflict_list(lambda room, *out: self.L.uph_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(v["radius"]), float(t_from), float(t_to), float(dt),
+                                                                                 room, *out), n, cap, "uph_conflicts_batch")
 
     def separation_kernel_ms(self):
         """milliseconds of the kernels of the last extent(), separation() or conflicts() (events on the context's stream)"""
@@ -1127,12 +1136,11 @@ class ALMTrajOpt:
         (one shape of (3,) is broadcast).  Over the samples tau_k = t_from[q] + k dt <= t_to[q]: min_c2 and min_t (the smallest squared distance between
         the two rectangles, 0 when they overlap, and its tau), first_t / last_t (tau of the first / last sample that overlaps or has c2 < margin[q]^2,
         NaN: none) and counts (n, 3: samples, below, overlapping).  Broadcasting and `other` as separation().  See footprint_rows."""
-        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "footprint_separation", t0_a=t0_a, t0_b=t0_b, margin=margin)
-        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        tr, tb, n, tf, tt, v, hb = self._pair(traj_a, traj_b, t_from, t_to, other, "footprint_separation", t0_a=t0_a, t0_b=t0_b, margin=margin)
         sa, sb = (np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (n, 3))) for s in (shape_a, shape_b))
         out = dict(min_c2=np.full(n, np.inf), min_t=np.full(n, np.nan), first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), counts=np.zeros((n, 3), dtype=np.int32))
-        _lib.check(self.L.uph_footprint_separation_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt),
-                                                         float(dt), _dp(sa), _dp(sb), _dp(v["margin"]), _dp(out["min_c2"]), _dp(out["min_t"]), _dp(out["first_t"]),
+        _lib.check(self.L.uph_footprint_separation_batch(self.h, hb, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt), _dp(sa),
+                                                         _dp(sb), _dp(v["margin"]), _dp(out["min_c2"]), _dp(out["min_t"]), _dp(out["first_t"]),
                                                          _dp(out["last_t"]), _ip(out["counts"])), "uph_footprint_separation_batch")
         return out
 
@@ -1144,17 +1152,8 @@ class ALMTrajOpt:
         or is closer than its margin, or the first cap of them."""
         tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "footprint_conflicts", t0=t0, margin=margin)
         sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shape, dtype=np.float64), (n, 3)))
-        room = max(1024, 4 * n) if cap is None else int(cap)
-        while True:
-            pairs, rows, below = np.zeros((max(room, 1), 2), dtype=np.int32), np.full((max(room, 1), 4), np.nan), np.zeros(max(room, 1), dtype=np.int32)
-            nc, nk = C.c_int64(0), C.c_int64(0)
-            _lib.check(self.L.uph_footprint_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(sh), _dp(v["margin"]), float(t_from), float(t_to), float(dt), room,
-                                                            _ip(pairs), _dp(rows), _ip(below), C.byref(nc), C.byref(nk)), "uph_footprint_conflicts_batch")
-            if cap is not None or nc.value <= room:
-                break
-            room = int(nc.value)                                    # cap = None: every conflict (the call is repeated with room for all of them)
-        m = min(room, int(nc.value))
-        return dict(pairs=pairs[:m], rows=rows[:m], below=below[:m], n_conflicts=int(nc.value), n_candidates=int(nk.value))
+        return self._conflict_list(lambda room, *out: self.L.uph_footprint_conflicts_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(sh), _dp(v["margin"]), float(t_from),
+                                                                                           float(t_to), float(dt), room, *out), n, cap, "uph_footprint_conflicts_batch")
 
     def footprint_kernel_ms(self):
         """milliseconds of the kernels of the last footprint_separation() or footprint_conflicts() (events on the context's stream)"""
@@ -1165,14 +1164,13 @@ class ALMTrajOpt:
         """separation() of vehicle a against vehicle b for every start t0_b[q] + delay_times(delay0, delay_step, D)[j] of b, on the device in one call:
         min_d2, min_t and below (n, D) -- each what separation() returns for that start --, first_clear (n,) = the smallest j with below == 0 (-1:
         none) and counts (n,) = the samples K of the window.  Broadcasting and `other` as separation()."""
-        tr, n, tf, tt, v = self._clock(traj_a, t_from, t_to, "delay_sweep", t0_a=t0_a, t0_b=t0_b, radius=radius)
-        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(traj_b, dtype=np.int32), (n,)))
+        tr, tb, n, tf, tt, v, hb = self._pair(traj_a, traj_b, t_from, t_to, other, "delay_sweep", t0_a=t0_a, t0_b=t0_b, radius=radius)
         D = int(D)
         m = max(D, 1)
         out = dict(min_d2=np.full((n, m), np.inf), min_t=np.full((n, m), np.nan), below=np.zeros((n, m), dtype=np.int32), first_clear=np.full(n, -1, dtype=np.int32),
                    counts=np.zeros(n, dtype=np.int32))
-        _lib.check(self.L.uph_delay_sweep_batch(self.h, None if other is None else other.h, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt),
-                                                _dp(v["radius"]), float(delay0), float(delay_step), D, _dp(out["min_d2"]), _dp(out["min_t"]), _ip(out["below"]),
+        _lib.check(self.L.uph_delay_sweep_batch(self.h, hb, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt), _dp(v["radius"]),
+                                                float(delay0), float(delay_step), D, _dp(out["min_d2"]), _dp(out["min_t"]), _ip(out["below"]),
                                                 _ip(out["first_clear"]), _ip(out["counts"])), "uph_delay_sweep_batch")
         return out
 

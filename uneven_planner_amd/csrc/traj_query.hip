@@ -6,10 +6,12 @@
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
 // window of the rollout's time table and the end point; ClockQuery: samples t_from + k dt of a clock several vehicles share, for each of the D delays of the
 // launch's table (D = 1 and a null table without one) --, lanes striding over the samples (over the delays, in the two delay kernels), their accumulators (Span,
-// Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  Host: trajFrame (the frame of a trajectory, for every
-// record and argument block), checkTrajQueries (the refusals every query passes), formWindowQueries / pairQueries / fleetCandidates / extentCall (a call shape's
-// refusals in order, its records, its uploads), clockRun (the clock records in launch order), twoWidths (256 lanes for the head of a sorted launch, one wave
-// for the rest), runQueryLaunch (events, launch, rows back, the wait).
+// Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  The queries on a pair of vehicles are one family: one
+// record (SepQuery; FootQuery adds the two shapes), one argument block (PairArgs), one body (pairBody) over a metric -- discs or oriented rectangles.  Host:
+// trajFrame (the frame of a trajectory, for every record and argument block), checkTrajQueries (the refusals every query passes), formWindowQueries / pairQueries /
+// fleetCandidates / extentCall (a call shape's refusals in order, its records, its uploads), clockRun (the clock records in launch order), pairRun (the pair
+// records of any metric, chunked by the delay table), fleetConflicts (a fleet's candidates through a pair kernel to the conflict list), twoWidths (256 lanes for the
+// head of a sorted launch, one wave for the rest), runQueryLaunch (events, launch, rows back, the wait).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -435,7 +437,8 @@ __global__ __launch_bounds__(NT) void uph_within_kernel(LocArgs a) {
     ((WithinOut*)a.out)[lq.out] = o;
 }
 
-// ---- separation / extent (uph_separation_batch, uph_extent_batch, uph_conflicts_batch): reductions over the positions of resident trajectories on a clock
+// ---- separation / extent (uph_separation_batch, uph_extent_batch, uph_conflicts_batch; the pair kernels themselves follow the footprint rule below): reductions
+// over the positions of resident trajectories on a clock
 // that several vehicles share.  Sample k of a query sits at tau_k = t_from + k dt (the product rounded, then the sum: no time table, the clock may stand at
 // 1000 s); a vehicle is a trajectory and its start time t0 on that clock, and stands at uph_switch_state_kernel's state of u = tau - t0: at its start before
 // it leaves, at its goal after it arrives.  As locate / within: no terrain, no scratch, one wave for K <= LOC_SHORT samples and 256 lanes beyond.
@@ -450,8 +453,8 @@ struct ClockQuery {             // one query of a launch (formed on the host by 
                                 // R2 a wait later than the rest of the record, and uph_separation_kernel<64> at 101 samples runs 1.7 % longer.)
     double t_from, dt;
 };
-struct SepQuery : ClockQuery {
-    double R2;                  // a sample is below when d2 < R2
+struct SepQuery : ClockQuery {  // the record of a pair of vehicles
+    double R2;                  // a sample is below when its squared distance (d2; footprints: c2) < R2
     ClockTraj a, b;             // with a delay table, b is the one delayed
 };
 struct ExtQuery : ClockQuery {
@@ -461,6 +464,7 @@ struct SepOut {                 // one row per query
     double min_d2, min_t;       // +inf, NaN: no sample
     double first_t, last_t;     // first / last sample below (NaN: none)
     int32_t counts[2];          // samples, below
+    static constexpr int NC = 2;        // counts of a row
 };
 struct ExtOut {
     double box[4];              // xmin, xmax, ymin, ymax over the samples whose position is not NaN
@@ -470,10 +474,10 @@ struct SweepOut {               // one row per (query, delay)
     double min_d2, min_t;       // as SepOut
     int32_t below, k;           // samples below; the sample of the minimum (WIN_NONE: none)
 };
-template <class Out>            // SepOut, or SweepOut with a delay table
-struct SepArgs {
+template <class Q, class Out>   // SepQuery -> SepOut, or SweepOut with a delay table; FootQuery -> FootOut
+struct PairArgs {
     ResidentDev ra, rb;         // the two sides' resident batches (one context: the same)
-    const SepQuery* qs;
+    const Q* qs;
     Out* out;
     int framed_a, framed_b, q0; // as LocArgs, per side
     const double* delta;        // [D] the launch's delay table; nullptr without one
@@ -483,7 +487,7 @@ struct ExtArgs {
     const ExtQuery* qs;
     ExtOut* out;
     int framed, q0;
-    const double* delta;        // as SepArgs
+    const double* delta;        // as PairArgs
 };
 
 // tau_k with the product rounded before the add
@@ -503,12 +507,18 @@ __device__ __forceinline__ ClockView clockView(const ResidentDev& r, const Clock
     v.total = trajTotal(v.tr.Nxy, v.tr.Tx, v.tr.Nyaw, v.tr.Ty);
     return v;
 }
-// the vehicle's position at tau: uph_switch_state_kernel's clamp of its own time, then the STATE row's x, y there
-__device__ __forceinline__ void clockSample(const ClockView& v, double tau, double& X, double& Y) {
+// the vehicle's position at tau: uph_switch_state_kernel's clamp of its own time, then the STATE row's x, y there; YAW: its pose, with the raw yaw of the same state
+// (uph_traj_states' column 9) in *psi
+template <bool YAW = false>
+__device__ __forceinline__ void clockSample(const ClockView& v, double tau, double& X, double& Y, double* psi = nullptr) {
     const double u = tau - v.t0;
     const double t = u <= 0.0 ? 0.0 : (u >= v.total ? v.total : u);
     TrajSample s;
     locSample(v.tr, t, s, X, Y);
+    if constexpr (YAW) {
+        *psi = s.yaw;
+        asm volatile("" : "+v"(*psi));
+    }
 }
 
 // the workgroup's box from its lanes', and the query's row (both extent kernels end here)
@@ -519,38 +529,6 @@ __device__ __forceinline__ void extentRow(const ExtArgs& a, const ExtQuery& eq, 
     o.box[0] = box.x0; o.box[1] = box.x1; o.box[2] = box.y0; o.box[3] = box.y1;
     o.counts[0] = eq.K; o.counts[1] = box.bad;
     a.out[eq.out] = o;
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT) void uph_separation_kernel(SepArgs<SepOut> a) {
-    const SepQuery sq = a.qs[a.q0 + blockIdx.x];
-    const ClockView va = clockView(a.ra, sq.a, a.framed_a != 0), vb = clockView(a.rb, sq.b, a.framed_b != 0);
-    const int n = sq.K;
-    const double inf = __builtin_huge_val(), nan = __builtin_nan("");
-    double v = inf;
-    int i = WIN_NONE;
-    Span below;
-    for (int j = (int)threadIdx.x; j < n; j += NT) {
-        const double tau = clockTau(sq, j);
-        double Xa, Ya, Xb, Yb;
-        clockSample(va, tau, Xa, Ya);
-        clockSample(vb, tau, Xb, Yb);
-        const double d2 = locD2(Xa - Xb, Ya - Yb);
-        winTake<false>(v, i, d2 < inf ? d2 : inf, j);       // NaN: +inf
-        if (d2 < sq.R2) below.take(j);                      // (a NaN d2 is not below)
-    }
-    const auto fold = [](double& v, int& i, int& lo, int& hi, int& c, double ov, int oi, int ol, int oh, int oc) {
-        winTake<false>(v, i, ov, oi);
-        SpanFold()(lo, hi, c, ol, oh, oc);
-    };
-    if (!workgroupReduce<NT>(fold, v, i, below.first, below.last, below.cnt)) return;
-    SepOut o;
-    o.min_d2 = v;
-    o.min_t = i == WIN_NONE ? nan : clockTau(sq, i);
-    o.first_t = below.cnt == 0 ? nan : clockTau(sq, below.first);
-    o.last_t = below.cnt == 0 ? nan : clockTau(sq, below.last);
-    o.counts[0] = n; o.counts[1] = below.cnt;
-    a.out[sq.out] = o;
 }
 
 template <int NT>
@@ -566,39 +544,22 @@ __global__ __launch_bounds__(NT) void uph_extent_kernel(ExtArgs a) {
     extentRow<NT>(a, eq, box);
 }
 
-// ---- footprints (uph_footprint_separation_batch, uph_footprint_conflicts_batch): the separation query with the vehicles as oriented rectangles.  The record, the
-// sample loop, the widths and the reduction are uph_separation_kernel's; a sample also takes the raw yaw of the two states it evaluates anyway, and the pair
-// metric is the rule of include/uneven_hip.h: four separating axes, then the eight corner distances.  Every product and sum of the rule is rounded on its own
-// (fp contract off in footClearance), so the two widths and any split of the samples over lanes compute the same bits.  No terrain, no scratch.
+// ---- footprints (uph_footprint_separation_batch, uph_footprint_conflicts_batch): the separation query with the vehicles as oriented rectangles.  A sample also
+// takes the raw yaw of the two states it evaluates anyway, and the pair metric is the rule of include/uneven_hip.h: four separating axes, then the eight corner
+// distances.  Every product and sum of the rule is rounded on its own (fp contract off in footClearance), so the two widths and any split of the samples over lanes
+// compute the same bits.  No terrain, no scratch.
 struct FootShape {              // query-uniform, formed on the host (footShape)
     double hl, o, w;            // half length (front + rear) / 2, the centre's offset along the heading (front - rear) / 2, half width
 };
-struct FootQuery : ClockQuery {
-    double M2;                  // a sample is below when it overlaps or c2 < M2
+struct FootQuery : SepQuery {   // R2 = M2: a sample is below when it overlaps or c2 < M2
     FootShape sa, sb;
-    ClockTraj a, b;
 };
-struct FootOut {                // one row per query
-    double min_c2, min_t;       // +inf, NaN: no sample
-    double first_t, last_t;     // first / last sample below (NaN: none)
-    int32_t counts[3], pad;     // samples, below, overlapping
+struct FootOut : SepOut {       // min_d2 is min_c2; counts: samples, below, and behind them
+    int32_t over, pad;          // overlapping
+    static constexpr int NC = 3;
 };
-struct FootArgs {
-    ResidentDev ra, rb;         // as SepArgs
-    const FootQuery* qs;
-    FootOut* out;
-    int framed_a, framed_b, q0;
-};
+static_assert(sizeof(SepOut) == 40 && sizeof(FootOut) == 48, "4 doubles, then counts[3] contiguous");
 
-// the vehicle's pose at tau: clockSample's position -- it leaves locSample as it does there -- and the raw yaw of the same state (uph_traj_states' column 9)
-__device__ __forceinline__ void clockPose(const ClockView& v, double tau, double& X, double& Y, double& psi) {
-    const double u = tau - v.t0;
-    const double t = u <= 0.0 ? 0.0 : (u >= v.total ? v.total : u);
-    TrajSample s;
-    locSample(v.tr, t, s, X, Y);
-    psi = s.yaw;
-    asm volatile("" : "+v"(psi));
-}
 // one corner of a rectangle (centre Cx, Cy; hx, hy = hl u; wx, wy = w v) against the other rectangle (centre Ox, Oy; heading co, so; half sizes hlo, wo)
 __device__ __forceinline__ double footCorner(double px, double py, double Ox, double Oy, double co, double so, double hlo, double wo) {
 #pragma clang fp contract(off)
@@ -645,40 +606,76 @@ __device__ __forceinline__ void footClearance(const FootShape& A, const FootShap
     c2 = !finite ? __builtin_nan("") : (over ? 0.0 : (ma < mb ? ma : mb));
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void uph_footprint_kernel(FootArgs a) {
-    const FootQuery fq = a.qs[a.q0 + blockIdx.x];
-    const ClockView va = clockView(a.ra, fq.a, a.framed_a != 0), vb = clockView(a.rb, fq.b, a.framed_b != 0);
-    const int n = fq.K;
+// ---- the pair queries (uph_separation_kernel, uph_footprint_kernel): one body over a metric.  A metric names its record and row, says whether it counts
+// overlaps, and evaluates one sample: the squared distance m2 of the two vehicles at tau and whether they overlap.  A sample is below when it overlaps or m2 < R2
+// (a NaN m2 is not below).
+struct DiscMetric {             // points: d2 of the two positions
+    typedef SepQuery Query;
+    typedef SepOut Out;
+    static constexpr bool OVERLAPS = false;
+    static __device__ __forceinline__ void sample(const Query&, const ClockView& va, const ClockView& vb, double tau, double& m2, bool& over) {
+        double Xa, Ya, Xb, Yb;
+        clockSample(va, tau, Xa, Ya);
+        clockSample(vb, tau, Xb, Yb);
+        m2 = locD2(Xa - Xb, Ya - Yb);
+        over = false;
+    }
+};
+struct RectMetric {             // oriented rectangles: footClearance of the two poses
+    typedef FootQuery Query;
+    typedef FootOut Out;
+    static constexpr bool OVERLAPS = true;
+    static __device__ __forceinline__ void sample(const Query& q, const ClockView& va, const ClockView& vb, double tau, double& m2, bool& over) {
+        double Xa, Ya, Pa, Xb, Yb, Pb;
+        clockSample<true>(va, tau, Xa, Ya, &Pa);
+        clockSample<true>(vb, tau, Xb, Yb, &Pb);
+        footClearance(q.sa, q.sb, Xa, Ya, Pa, Xb, Yb, Pb, m2, over);
+    }
+};
+struct PairFold {               // the (value, sample) selection and the span; with a sixth value, the sum of the overlaps
+    __device__ __forceinline__ void operator()(double& v, int& i, int& lo, int& hi, int& c, double ov, int oi, int ol, int oh, int oc) const {
+        winTake<false>(v, i, ov, oi);
+        SpanFold()(lo, hi, c, ol, oh, oc);
+    }
+    __device__ __forceinline__ void operator()(double& v, int& i, int& lo, int& hi, int& c, int& no, double ov, int oi, int ol, int oh, int oc, int ono) const {
+        (*this)(v, i, lo, hi, c, ov, oi, ol, oh, oc);
+        no += ono;
+    }
+};
+template <int NT, class M>
+__device__ __forceinline__ void pairBody(const PairArgs<typename M::Query, typename M::Out>& a) {
+    const typename M::Query pq = a.qs[a.q0 + blockIdx.x];
+    const ClockView va = clockView(a.ra, pq.a, a.framed_a != 0), vb = clockView(a.rb, pq.b, a.framed_b != 0);
+    const int n = pq.K;
     const double inf = __builtin_huge_val(), nan = __builtin_nan("");
     double v = inf;
     int i = WIN_NONE, nover = 0;
     Span below;
     for (int j = (int)threadIdx.x; j < n; j += NT) {
-        const double tau = clockTau(fq, j);
-        double Xa, Ya, Pa, Xb, Yb, Pb, c2;
+        double m2;
         bool over;
-        clockPose(va, tau, Xa, Ya, Pa);
-        clockPose(vb, tau, Xb, Yb, Pb);
-        footClearance(fq.sa, fq.sb, Xa, Ya, Pa, Xb, Yb, Pb, c2, over);
-        winTake<false>(v, i, c2 < inf ? c2 : inf, j);       // NaN: +inf
-        if (over || c2 < fq.M2) below.take(j);              // (a NaN c2 is not below)
+        M::sample(pq, va, vb, clockTau(pq, j), m2, over);
+        winTake<false>(v, i, m2 < inf ? m2 : inf, j);       // NaN: +inf
+        if (over || m2 < pq.R2) below.take(j);
         nover += over ? 1 : 0;
     }
-    const auto fold = [](double& v, int& i, int& lo, int& hi, int& c, int& no, double ov, int oi, int ol, int oh, int oc, int ono) {
-        winTake<false>(v, i, ov, oi);
-        SpanFold()(lo, hi, c, ol, oh, oc);
-        no += ono;
-    };
-    if (!workgroupReduce<NT>(fold, v, i, below.first, below.last, below.cnt, nover)) return;
-    FootOut o;
-    o.min_c2 = v;
-    o.min_t = i == WIN_NONE ? nan : clockTau(fq, i);
-    o.first_t = below.cnt == 0 ? nan : clockTau(fq, below.first);
-    o.last_t = below.cnt == 0 ? nan : clockTau(fq, below.last);
-    o.counts[0] = n; o.counts[1] = below.cnt; o.counts[2] = nover; o.pad = 0;
-    a.out[fq.out] = o;
+    bool mine;
+    if constexpr (M::OVERLAPS) mine = workgroupReduce<NT>(PairFold(), v, i, below.first, below.last, below.cnt, nover);
+    else mine = workgroupReduce<NT>(PairFold(), v, i, below.first, below.last, below.cnt);
+    if (!mine) return;
+    typename M::Out o;
+    o.min_d2 = v;
+    o.min_t = i == WIN_NONE ? nan : clockTau(pq, i);
+    o.first_t = below.cnt == 0 ? nan : clockTau(pq, below.first);
+    o.last_t = below.cnt == 0 ? nan : clockTau(pq, below.last);
+    o.counts[0] = n; o.counts[1] = below.cnt;
+    if constexpr (M::OVERLAPS) { o.over = nover; o.pad = 0; }
+    a.out[pq.out] = o;
 }
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_separation_kernel(PairArgs<SepQuery, SepOut> a) { pairBody<NT, DiscMetric>(a); }
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_footprint_kernel(PairArgs<FootQuery, FootOut> a) { pairBody<NT, RectMetric>(a); }
 
 // ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch): the separation / the extent of a query (the same records) for every start
 // t0 + delta_j of a table of D delays that all queries of a launch share (formed on the host: the device only adds).  One workgroup per query, lanes own DELAYS, not samples:
@@ -727,7 +724,7 @@ __device__ __forceinline__ void delayLoop(const ClockQuery& q, const DelaySplit&
 template <int NT>
 struct SweepBody {
     const SepQuery& sq;
-    const SepArgs<SweepOut>& a;
+    const PairArgs<SepQuery, SweepOut>& a;
     ClockView va, vb;
     double t0_b;
     double* ax;                 // [DELAY_TILE] a's positions of the tile, in LDS
@@ -766,7 +763,7 @@ struct SweepBody {
 };
 
 template <int NT>
-__global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(SepArgs<SweepOut> a) {
+__global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(PairArgs<SepQuery, SweepOut> a) {
     __shared__ double s_xy[2 * DELAY_TILE];
     __shared__ double s_v[NT];
     __shared__ int s_i[2 * NT];
@@ -1130,8 +1127,10 @@ static Q clockQuery(int64_t K, double t_from, double dt, const DelayTable* dl) {
     q.K = (int32_t)K; q.t_from = t_from; q.dt = dt; q.D = delayCount(dl);
     return q;
 }
-static SepQuery sepQuery(int64_t K, double t_from, double dt, const DelayTable* dl, double R, const ClockTraj& a, const ClockTraj& b) {
-    SepQuery q = clockQuery<SepQuery>(K, t_from, dt, dl);
+// the record of a pair of vehicles, SepQuery or one that extends it: the head and the pair fields (R: the radius, or the margin), the rest zero
+template <class Q = SepQuery>
+static Q pairQuery(int64_t K, double t_from, double dt, const DelayTable* dl, double R, const ClockTraj& a, const ClockTraj& b) {
+    Q q = clockQuery<Q>(K, t_from, dt, dl);
     q.R2 = R * R; q.a = a; q.b = b;
     return q;
 }
@@ -1227,16 +1226,16 @@ static int delayUpload(uph_ctx* c, const DelayTable* dl) {
 // the queries of one launch pair: the rows stay below DELAY_ROWS and the records below CLOCK_CHUNK
 static size_t delayChunk(int32_t D) { return std::max<size_t>(1, std::min(CLOCK_CHUNK, DELAY_ROWS / (size_t)D)); }
 
-// the pair queries qs (formed by sepQuery; the table, if any, is on ca's device) -> a row per query, or per (query, delay), in the caller's order; qs is left in
+// the pair queries qs (formed by pairQuery; the table, if any, is on ca's device) -> a row per query, or per (query, delay), in the caller's order; qs is left in
 // launch order
-template <class Out>
-static int pairRun(uph_ctx* ca, uph_ctx* cb, std::vector<SepQuery>& qs, const DelayTable* dl, void (*k256)(SepArgs<Out>), void (*k64)(SepArgs<Out>),
+template <class Q, class Out>
+static int pairRun(uph_ctx* ca, uph_ctx* cb, std::vector<Q>& qs, const DelayTable* dl, void (*k256)(PairArgs<Q, Out>), void (*k64)(PairArgs<Q, Out>),
                    std::vector<Out>& rows, double& ms) {
     const size_t D = (size_t)delayCount(dl), chunk = delayChunk((int32_t)D);
-    for (const SepQuery& q : qs)        // the rows a workgroup writes and the rows allocated here both go by the table
+    for (const Q& q : qs)               // the rows a workgroup writes and the rows allocated here both go by the table
         if (q.D != (int32_t)D) { setError("pairRun: a record was not formed from this call's delay table"); return UPH_ERR_INVALID; }
     rows.resize(qs.size() * D);
-    SepArgs<Out> a{};
+    PairArgs<Q, Out> a{};
     a.ra = residentDev(ca); a.rb = residentDev(cb);
     a.framed_a = trajFrame(ca); a.framed_b = trajFrame(cb);
     a.delta = delayDev(ca, dl);
@@ -1292,10 +1291,11 @@ static int extentCall(const std::string& who, uph_ctx* c, int32_t n, const int32
     return UPH_OK;
 }
 
-// What the pair calls (uph_separation_batch, uph_delay_sweep_batch) share: every refusal in their one order, cb defaulting to ca, the pair records, ca's device
-// current with cb's stream drained, the table on it
+// What the pair calls (uph_separation_batch, uph_footprint_separation_batch, uph_delay_sweep_batch) share: every refusal in their one order, cb defaulting to ca,
+// the pair fields of their records (radius: the margin, for footprints), ca's device current with cb's stream drained, the table on it
+template <class Q>
 static int pairQueries(const std::string& who, uph_ctx* ca, uph_ctx*& cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
-                       const double* t_from, const double* t_to, double dt, const double* radius, DelayTable* dl, std::vector<SepQuery>& qs) {
+                       const double* t_from, const double* t_to, double dt, const double* radius, DelayTable* dl, std::vector<Q>& qs) {
     if (!ca || n <= 0 || !traj_a || !traj_b || !t0_a || !t0_b || !t_from || !t_to || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
     if (!cb) cb = ca;
     if (uphMapDevice(ca->map) != uphMapDevice(cb->map)) { setError(who + ": the two contexts are on different devices"); return UPH_ERR_INVALID; }
@@ -1307,14 +1307,28 @@ static int pairQueries(const std::string& who, uph_ctx* ca, uph_ctx*& cb, int32_
         if (!std::isfinite(radius[q]) || radius[q] < 0.0) { setError(whoQuery(who, q) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
         int64_t K = 0;
         if ((r = clockWindow(t_from[q], t_to[q], dt, K, who, q)) != UPH_OK || (r = delayWork(K, dl, who, q)) != UPH_OK) return r;
-        qs[(size_t)q] = sepQuery(K, t_from[q], dt, dl, radius[q], clockTraj(ca, traj_a[q], t0_a[q]), clockTraj(cb, traj_b[q], t0_b[q]));
+        qs[(size_t)q] = pairQuery<Q>(K, t_from[q], dt, dl, radius[q], clockTraj(ca, traj_a[q], t0_a[q]), clockTraj(cb, traj_b[q], t0_b[q]));
     }
     HIPCHK(hipSetDevice(uphMapDevice(ca->map)));
     if (cb != ca) HIPCHK(hipStreamSynchronize(cb->stream));     // what cb's stream still writes of its trajectories is there before the launch on ca's
     return delayUpload(ca, dl);
 }
 
-// What the fleet calls (uph_conflicts_batch, uph_delays_batch) share up to their candidates: every refusal in their one order, the one window's K, the (swept)
+// the rows of a pair call to the caller's arrays, each of which may be null (min: min_d2 / min_c2)
+template <class Out>
+static void pairRowsOut(const std::vector<Out>& out, double* min, double* min_t, double* first_t, double* last_t, int32_t* counts) {
+    for (size_t q = 0; q < out.size(); q++) {
+        const Out& o = out[q];
+        if (min) min[q] = o.min_d2;
+        if (min_t) min_t[q] = o.min_t;
+        if (first_t) first_t[q] = o.first_t;
+        if (last_t) last_t[q] = o.last_t;
+        if (counts) for (int k = 0; k < 2; k++) counts[Out::NC * q + k] = o.counts[k];
+        if constexpr (Out::NC == 3) if (counts) counts[3 * q + 2] = o.over;
+    }
+}
+
+// What the fleet calls (uph_conflicts_batch, uph_footprint_conflicts_batch, uph_delays_batch) share up to their candidates: every refusal in their one order, the one window's K, the (swept)
 // extents on the device, the pairs of vehicles whose boxes the rule does not drop
 static int fleetCandidates(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays,
                            double t_from, double t_to, double dt, DelayTable* dl, int64_t& K, std::vector<IdxPair>& cand, double& ms) {
@@ -1337,6 +1351,46 @@ static int fleetCandidates(const std::string& who, uph_ctx* c, int32_t n, const 
     return candidatePairs(n, box.data(), radius, who.c_str(), cand);
 }
 
+// What the fleet conflict calls are behind their own refusals: fleetCandidates with the broad-phase radii, the pair query of every candidate -- form(K, i, j), its
+// record -- a launch pair per CLOCK_CHUNK of them, the conflicts in the candidates' (i, j) order, the first cap of them to the caller's arrays (each may be null), the
+// kernels' time to the context's `last_ms`
+template <class Q, class Out, class Form>
+static int fleetConflicts(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, double t_from, double t_to, double dt,
+                          Form form, void (*k256)(PairArgs<Q, Out>), void (*k64)(PairArgs<Q, Out>), double uph_ctx::*last_ms, int64_t cap, int32_t* pairs, double* rows,
+                          int32_t* below, int64_t* n_conflicts, int64_t* n_candidates) {
+    int64_t K = 0;
+    std::vector<IdxPair> cand;
+    double ms = 0.0;
+    int r = fleetCandidates(who, c, n, traj, t0, radius, nullptr, t_from, t_to, dt, nullptr, K, cand, ms);
+    if (r != UPH_OK) return r;
+    std::vector<IdxPair> hit;
+    std::vector<Out> hit_rows, out;
+    std::vector<Q> qs;
+    for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
+        const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
+        qs.resize(m);
+        for (size_t k = 0; k < m; k++) qs[k] = form(K, cand[s + k].first, cand[s + k].second);
+        if ((r = pairRun(c, c, qs, nullptr, k256, k64, out, ms)) != UPH_OK) return r;
+        for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
+    }
+    c->*last_ms = ms;
+    for (size_t k = 0; k < hit.size() && (int64_t)k < cap; k++) {
+        const Out& o = hit_rows[k];
+        if (pairs) { pairs[2 * k] = hit[k].first; pairs[2 * k + 1] = hit[k].second; }
+        if (rows) { rows[4 * k] = o.min_d2; rows[4 * k + 1] = o.min_t; rows[4 * k + 2] = o.first_t; rows[4 * k + 3] = o.last_t; }
+        if (below) below[k] = o.counts[1];
+    }
+    if (n_conflicts) *n_conflicts = (int64_t)hit.size();
+    if (n_candidates) *n_candidates = (int64_t)cand.size();
+    return UPH_OK;
+}
+// the getter of a call family's kernel time (`who`: the call's own name)
+static int kernelMs(const char* who, const uph_ctx* c, double uph_ctx::*last_ms, double* kernel_ms) {
+    if (!c || !kernel_ms) { setError(std::string(who) + ": bad arguments"); return UPH_ERR_INVALID; }
+    *kernel_ms = c->*last_ms;
+    return UPH_OK;
+}
+
 // level of vehicle j among pairs (i < j, already checked): 0 without a smaller partner, else 1 + the largest level of its smaller partners
 static void delayLevels(int32_t n, const std::vector<IdxPair>& pairs, std::vector<int32_t>& level) {
     std::vector<IdxPair> by_j(pairs.size());
@@ -1346,7 +1400,7 @@ static void delayLevels(int32_t n, const std::vector<IdxPair>& pairs, std::vecto
     for (const IdxPair& p : by_j) level[(size_t)p.first] = std::max(level[(size_t)p.first], level[(size_t)p.second] + 1);     // (the levels of i < j are final)
 }
 
-// ---- footprints (include/uneven_hip.h uph_footprint_*) ------------------------------------------------------------------------------------------------
+// ---- footprints (include/uneven_hip.h uph_footprint_*): what the calls add to the pair family -- the shapes' refusals, the record's shapes, the broad-phase radii
 // the refusals of n shapes [n][3] and (margin != nullptr) n margins, named `what` in the message ("shape", "shape_a", ...)
 static int footAdmit(const std::string& who, int32_t n, const double* shape, const char* what, const double* margin) {
     for (int32_t q = 0; q < n; q++) {
@@ -1377,27 +1431,6 @@ static int footRadii(const std::string& who, int32_t n, const double* shape, con
     }
     return UPH_OK;
 }
-// a footprint record from the pair record of the same query (pairQueries / sepQuery with R = M: the window, the two vehicles, M2 = M * M rounded)
-static FootQuery footQuery(const SepQuery& s, const double* shape_a, const double* shape_b) {
-    FootQuery q = clockQuery<FootQuery>(s.K, s.t_from, s.dt, nullptr);
-    q.M2 = s.R2; q.sa = footShape(shape_a); q.sb = footShape(shape_b); q.a = s.a; q.b = s.b;
-    return q;
-}
-// the footprint queries qs -> a row per query in the caller's order, in launches of at most CLOCK_CHUNK; qs is left in launch order
-static int footRun(uph_ctx* ca, uph_ctx* cb, std::vector<FootQuery>& qs, std::vector<FootOut>& rows, double& ms) {
-    rows.resize(qs.size());
-    FootArgs a{};
-    a.ra = residentDev(ca); a.rb = residentDev(cb);
-    a.framed_a = trajFrame(ca); a.framed_b = trajFrame(cb);
-    void (*const k256)(FootArgs) = uph_footprint_kernel<256>;
-    void (*const k64)(FootArgs) = uph_footprint_kernel<64>;
-    for (size_t s = 0; s < qs.size(); s += CLOCK_CHUNK) {
-        const int r = clockRun(ca, qs.data() + s, std::min(CLOCK_CHUNK, qs.size() - s), a, k256, k64, rows.data() + s, ms);
-        if (r != UPH_OK) return r;
-    }
-    return UPH_OK;
-}
-
 extern "C" {
 
 int uph_traj_states(uph_ctx* c, int32_t n, const int32_t* traj, const double* t, double* out10) {
@@ -1522,11 +1555,7 @@ int uph_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_
     return UPH_OK;
 }
 
-int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_check_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_check_ms;
-    return UPH_OK;
-}
+int uph_check_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_check_kernel_ms", c, &uph_ctx::last_check_ms, kernel_ms); }
 
 
 // ---- locate / within (include/uneven_hip.h uph_locate_*, uph_within_batch) ---------------------------------------------------------------------------
@@ -1565,11 +1594,7 @@ int uph_within_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* r
     return UPH_OK;
 }
 
-int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_locate_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_locate_ms;
-    return UPH_OK;
-}
+int uph_locate_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_locate_kernel_ms", c, &uph_ctx::last_locate_ms, kernel_ms); }
 
 
 // ---- separation / extent / conflicts on a common clock (include/uneven_hip.h) -----------------------------------------------------------------------
@@ -1595,14 +1620,7 @@ int uph_separation_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* tra
     double ms = 0.0;
     if ((r = pairRun(ca, cb, qs, nullptr, uph_separation_kernel<256>, uph_separation_kernel<64>, out, ms)) != UPH_OK) return r;
     ca->last_sep_ms = ms;
-    for (int32_t q = 0; q < n; q++) {
-        const SepOut& o = out[(size_t)q];
-        if (min_d2) min_d2[q] = o.min_d2;
-        if (min_t) min_t[q] = o.min_t;
-        if (first_t) first_t[q] = o.first_t;
-        if (last_t) last_t[q] = o.last_t;
-        if (counts) for (int k = 0; k < 2; k++) counts[2 * (size_t)q + k] = o.counts[k];
-    }
+    pairRowsOut(out, min_d2, min_t, first_t, last_t, counts);
     return UPH_OK;
 }
 
@@ -1618,45 +1636,15 @@ int uph_conflict_candidates(int32_t n, const double* box, const double* radius, 
 
 int uph_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, double t_from, double t_to, double dt, int64_t cap,
                         int32_t* pairs, double* rows, int32_t* below, int64_t* n_conflicts, int64_t* n_candidates) {
-    const char* who = "uph_conflicts_batch";
     if (!c || n <= 0 || !traj || !t0 || !radius || cap < 0) { setError("uph_conflicts_batch: bad arguments"); return UPH_ERR_INVALID; }
-    int64_t K = 0;
-    std::vector<IdxPair> cand;
-    double ms = 0.0;
-    int r = fleetCandidates(who, c, n, traj, t0, radius, nullptr, t_from, t_to, dt, nullptr, K, cand, ms);
-    if (r != UPH_OK) return r;
-    // separation of the candidates, a launch pair per CLOCK_CHUNK of them; the conflicts come out in the candidates' (i, j) order
-    std::vector<IdxPair> hit;
-    std::vector<SepOut> hit_rows;
-    std::vector<SepQuery> qs;
-    std::vector<SepOut> out;
-    for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
-        const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
-        qs.resize(m);
-        for (size_t k = 0; k < m; k++) {
-            const int32_t i = cand[s + k].first, j = cand[s + k].second;
-            qs[k] = sepQuery(K, t_from, dt, nullptr, radius[i] + radius[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j]));
-        }
-        if ((r = pairRun(c, c, qs, nullptr, uph_separation_kernel<256>, uph_separation_kernel<64>, out, ms)) != UPH_OK) return r;
-        for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
-    }
-    c->last_sep_ms = ms;
-    for (size_t k = 0; k < hit.size() && (int64_t)k < cap; k++) {
-        const SepOut& o = hit_rows[k];
-        if (pairs) { pairs[2 * k] = hit[k].first; pairs[2 * k + 1] = hit[k].second; }
-        if (rows) { rows[4 * k] = o.min_d2; rows[4 * k + 1] = o.min_t; rows[4 * k + 2] = o.first_t; rows[4 * k + 3] = o.last_t; }
-        if (below) below[k] = o.counts[1];
-    }
-    if (n_conflicts) *n_conflicts = (int64_t)hit.size();
-    if (n_candidates) *n_candidates = (int64_t)cand.size();
-    return UPH_OK;
+    const auto form = [&](int64_t K, int32_t i, int32_t j) {
+        return pairQuery(K, t_from, dt, nullptr, radius[i] + radius[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j]));
+    };
+    return fleetConflicts("uph_conflicts_batch", c, n, traj, t0, radius, t_from, t_to, dt, form, uph_separation_kernel<256>, uph_separation_kernel<64>,
+                          &uph_ctx::last_sep_ms, cap, pairs, rows, below, n_conflicts, n_candidates);
 }
 
-int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_separation_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_sep_ms;
-    return UPH_OK;
-}
+int uph_separation_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_separation_kernel_ms", c, &uph_ctx::last_sep_ms, kernel_ms); }
 
 // ---- footprints (include/uneven_hip.h) -------------------------------------------------------------------------------------------------------------------
 int uph_footprint_radii(int32_t n, const double* shape, const double* margin, double* r) {
@@ -1676,22 +1664,14 @@ int uph_footprint_separation_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const in
     if (!ca || n <= 0 || !shape_a || !shape_b || !margin) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
     int r = footAdmit(who, n, shape_a, "shape_a", margin);
     if (r != UPH_OK || (r = footAdmit(who, n, shape_b, "shape_b", nullptr)) != UPH_OK) return r;
-    std::vector<SepQuery> pq;       // the pair call's refusals, windows and vehicles, the margin in the radius' place
-    if ((r = pairQueries(who, ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, margin, nullptr, pq)) != UPH_OK) return r;
-    std::vector<FootQuery> qs((size_t)n);
-    for (int32_t q = 0; q < n; q++) qs[(size_t)q] = footQuery(pq[(size_t)q], shape_a + 3 * (size_t)q, shape_b + 3 * (size_t)q);
+    std::vector<FootQuery> qs;      // the pair call's refusals, windows and vehicles, the margin in the radius' place
+    if ((r = pairQueries(who, ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, margin, nullptr, qs)) != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) { qs[(size_t)q].sa = footShape(shape_a + 3 * (size_t)q); qs[(size_t)q].sb = footShape(shape_b + 3 * (size_t)q); }
     std::vector<FootOut> out;
     double ms = 0.0;
-    if ((r = footRun(ca, cb, qs, out, ms)) != UPH_OK) return r;
+    if ((r = pairRun(ca, cb, qs, nullptr, uph_footprint_kernel<256>, uph_footprint_kernel<64>, out, ms)) != UPH_OK) return r;
     ca->last_foot_ms = ms;
-    for (int32_t q = 0; q < n; q++) {
-        const FootOut& o = out[(size_t)q];
-        if (min_c2) min_c2[q] = o.min_c2;
-        if (min_t) min_t[q] = o.min_t;
-        if (first_t) first_t[q] = o.first_t;
-        if (last_t) last_t[q] = o.last_t;
-        if (counts) for (int k = 0; k < 3; k++) counts[3 * (size_t)q + k] = o.counts[k];
-    }
+    pairRowsOut(out, min_c2, min_t, first_t, last_t, counts);
     return UPH_OK;
 }
 
@@ -1702,43 +1682,16 @@ int uph_footprint_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, co
     std::vector<double> radius;
     int r = footAdmit(who, n, shape, "shape", margin);
     if (r != UPH_OK || (r = footRadii(who, n, shape, margin, radius)) != UPH_OK) return r;
-    int64_t K = 0;
-    std::vector<IdxPair> cand;
-    double ms = 0.0;
-    if ((r = fleetCandidates(who, c, n, traj, t0, radius.data(), nullptr, t_from, t_to, dt, nullptr, K, cand, ms)) != UPH_OK) return r;
-    // the footprint separation of the candidates; the conflicts come out in the candidates' (i, j) order
-    std::vector<FootQuery> qs;
-    std::vector<FootOut> out;
-    std::vector<IdxPair> hit;
-    std::vector<FootOut> hit_rows;
-    for (size_t s = 0; s < cand.size(); s += CLOCK_CHUNK) {
-        const size_t m = std::min(CLOCK_CHUNK, cand.size() - s);
-        qs.resize(m);
-        for (size_t k = 0; k < m; k++) {
-            const int32_t i = cand[s + k].first, j = cand[s + k].second;
-            qs[k] = footQuery(sepQuery(K, t_from, dt, nullptr, margin[i] + margin[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j])), shape + 3 * (size_t)i,
-                              shape + 3 * (size_t)j);
-        }
-        if ((r = footRun(c, c, qs, out, ms)) != UPH_OK) return r;
-        for (size_t k = 0; k < m; k++) if (out[k].counts[1] > 0) { hit.push_back(cand[s + k]); hit_rows.push_back(out[k]); }
-    }
-    c->last_foot_ms = ms;
-    for (size_t k = 0; k < hit.size() && (int64_t)k < cap; k++) {
-        const FootOut& o = hit_rows[k];
-        if (pairs) { pairs[2 * k] = hit[k].first; pairs[2 * k + 1] = hit[k].second; }
-        if (rows) { rows[4 * k] = o.min_c2; rows[4 * k + 1] = o.min_t; rows[4 * k + 2] = o.first_t; rows[4 * k + 3] = o.last_t; }
-        if (below) below[k] = o.counts[1];
-    }
-    if (n_conflicts) *n_conflicts = (int64_t)hit.size();
-    if (n_candidates) *n_candidates = (int64_t)cand.size();
-    return UPH_OK;
+    const auto form = [&](int64_t K, int32_t i, int32_t j) {
+        FootQuery q = pairQuery<FootQuery>(K, t_from, dt, nullptr, margin[i] + margin[j], clockTraj(c, traj[i], t0[i]), clockTraj(c, traj[j], t0[j]));
+        q.sa = footShape(shape + 3 * (size_t)i); q.sb = footShape(shape + 3 * (size_t)j);
+        return q;
+    };
+    return fleetConflicts(who, c, n, traj, t0, radius.data(), t_from, t_to, dt, form, uph_footprint_kernel<256>, uph_footprint_kernel<64>, &uph_ctx::last_foot_ms, cap,
+                          pairs, rows, below, n_conflicts, n_candidates);
 }
 
-int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_footprint_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_foot_ms;
-    return UPH_OK;
-}
+int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_footprint_kernel_ms", c, &uph_ctx::last_foot_ms, kernel_ms); }
 
 // ---- start delays (include/uneven_hip.h) -----------------------------------------------------------------------------------------------------------------
 int uph_delay_times(double delay0, double delay_step, int32_t D, double* delta) {
@@ -1829,7 +1782,7 @@ int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t
         qs.resize(of.size());
         for (size_t k = 0; k < of.size(); k++) {
             const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
-            qs[k] = sepQuery(K, t_from, dt, &dl, radius[h] + radius[i], clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]), clockTraj(c, traj[i], t0[i]));
+            qs[k] = pairQuery(K, t_from, dt, &dl, radius[h] + radius[i], clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]), clockTraj(c, traj[i], t0[i]));
         }
         if ((r = pairRun(c, c, qs, &dl, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows, ms)) != UPH_OK) return r;
         for (size_t k = 0; k < of.size(); k++) {        // (h ascending for each vehicle: the first h below at delay 0 is the smallest)
@@ -1859,10 +1812,6 @@ int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t
     return UPH_OK;
 }
 
-int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms) {
-    if (!c || !kernel_ms) { setError("uph_delay_kernel_ms: bad arguments"); return UPH_ERR_INVALID; }
-    *kernel_ms = c->last_delay_ms;
-    return UPH_OK;
-}
+int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_delay_kernel_ms", c, &uph_ctx::last_delay_ms, kernel_ms); }
 
 }  // extern "C"
