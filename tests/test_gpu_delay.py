@@ -327,6 +327,14 @@ def _greedy(src, tr, t0, radius, tf, tt, delay0, step, D, dt, n_delays=None):
     return want
 
 
+def _schedule_held(src, got, tr, t0, radius, tf, tt, delay0, step, D, dt, n_delays=None, tag="delays"):
+    """D5: the result `got` of delays() EQUALS the sequential greedy driven by separation() over the swept-box candidates"""
+    want = _greedy(src, tr, t0, radius, tf, tt, delay0, step, D, dt, n_delays=n_delays)
+    _same(got, want, ("choice", "start", "blocker"), tag)
+    assert (got["n_candidates"], got["n_rounds"], got["n_unresolved"]) == (want["n_candidates"], want["n_rounds"], want["n_unresolved"]), tag
+    return want
+
+
 def test_the_schedule_is_the_sequential_greedy(hill):
     """D5: 24 vehicles that start 0.4 s apart, D = 16 delays of 0.5 s.  The radius is a quantile of the pairs' smallest distances at delay 0 (S4 takes the
     median: about half of the pairs conflict); the first quantile of a fixed list at which the fleet shows waiting vehicles, an unresolved vehicle under
@@ -345,10 +353,7 @@ def test_the_schedule_is_the_sequential_greedy(hill):
             break
     assert (got["choice"] > 0).sum() >= 3 and one["n_unresolved"] >= 1 and got["n_rounds"] >= 2
     assert src.delay_kernel_ms() > 0.0
-    keys = ("choice", "start", "blocker")
-    want = _greedy(src, tr, t0, radius, tf, tt, 0.0, step, D, dt)
-    _same(got, want, keys, "delays")
-    assert (got["n_candidates"], got["n_rounds"], got["n_unresolved"]) == (want["n_candidates"], want["n_rounds"], want["n_unresolved"])
+    _schedule_held(src, got, tr, t0, radius, tf, tt, 0.0, step, D, dt)
     assert got["choice"][0] == 0 and ((got["blocker"] >= 0) == (got["choice"] < 0)).all()
     # with the effective starts applied no conflict is left whose later vehicle was placed
     left = src.conflicts(tr, radius, tf, tt, t0=got["start"], dt=dt)
@@ -356,9 +361,7 @@ def test_the_schedule_is_the_sequential_greedy(hill):
     print("conflicts: %d before, %d after (unresolved %s)" % (before["n_conflicts"], left["n_conflicts"], np.nonzero(got["choice"] < 0)[0].tolist()))
     assert before["n_conflicts"] >= 3 and (got["choice"][left["pairs"][:, 1]] < 0).all()
     # one delay for all: stay or fail, and every blocker is in the way at delay 0
-    want1 = _greedy(src, tr, t0, radius, tf, tt, 0.0, step, D, dt, n_delays=np.ones(n, dtype=np.int32))
-    _same(one, want1, keys, "delays, one each")
-    assert (one["n_candidates"], one["n_rounds"], one["n_unresolved"]) == (want1["n_candidates"], want1["n_rounds"], want1["n_unresolved"])
+    _schedule_held(src, one, tr, t0, radius, tf, tt, 0.0, step, D, dt, n_delays=np.ones(n, dtype=np.int32), tag="delays, one each")
     assert set(one["choice"].tolist()) == {0, -1} and np.array_equal(one["start"], t0)
     for i in np.nonzero(one["choice"] < 0)[0]:
         h = int(one["blocker"][i])
@@ -370,9 +373,7 @@ def test_the_schedule_is_the_sequential_greedy(hill):
     nd = 1 + (np.arange(n) * 5) % D
     rad2 = radius * (0.6 + 0.8 * (np.arange(n) % 3) / 2.0)
     got2 = src.delays(tr, rad2, tf, tt, 0.25, 0.3, D, t0=t0, n_delays=nd, dt=dt)
-    want2 = _greedy(src, tr, t0, rad2, tf, tt, 0.25, 0.3, D, dt, n_delays=nd)
-    _same(got2, want2, keys, "delays, limits")
-    assert (got2["n_candidates"], got2["n_rounds"], got2["n_unresolved"]) == (want2["n_candidates"], want2["n_rounds"], want2["n_unresolved"])
+    _schedule_held(src, got2, tr, t0, rad2, tf, tt, 0.25, 0.3, D, dt, n_delays=nd, tag="delays, limits")
     assert (got2["choice"] < nd).all() and got2["start"][0] == t0[0] + 0.25
 
 

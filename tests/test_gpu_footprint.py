@@ -316,16 +316,10 @@ def test_two_contexts_in_local_frames_and_on_fp32_cells():
         tally.close(tag)
 
 
-def test_the_fleet(hill):
-    """F4: 24 cars of 0.6 m x 0.3 m (their sizes vary a little) that start 0.4 s apart"""
-    src, ok, total = hill["src"], hill["ok"], hill["total"]
-    n, dt = 24, 0.05
-    tr = ok[:n]
-    rng = np.random.default_rng(53)
-    t0 = 1000.0 + 0.4 * np.arange(n)
-    tf, tt = 999.0, float((t0 + total[tr]).max()) + 1.0
-    shape = np.stack([rng.uniform(0.4, 0.5, n), rng.uniform(0.1, 0.2, n), rng.uniform(0.12, 0.18, n)], axis=1)
-    margin = rng.uniform(0.0, 0.1, n) * (np.arange(n) % 3 != 0)
+def _fleet_held(src, tr, t0, tf, tt, dt, shape, margin, tag="F4"):
+    """F4: footprint_conflicts() over a fleet against the brute force of the mirror over all pairs, by F1's classes, and its broad phase against the mirror's on
+    the extents the device computed.  Returns the call's result, its pairs as a dict pair -> row, and the pairs the mirror is sure / not sure of."""
+    n = len(tr)
     tau = separation_times(tf, tt, dt)
     pose = _poses(src, tr, t0, [tau] * n)
     got = src.footprint_conflicts(tr, shape, margin, tf, tt, t0=t0, dt=dt)
@@ -346,16 +340,30 @@ def test_the_fleet(hill):
             if (i, j) in listed:
                 k = listed[(i, j)]
                 _hold_row((got["rows"][k, 0], got["rows"][k, 1], got["rows"][k, 2], got["rows"][k, 3], int(got["below"][k]), None), tau, pose[i], pose[j], shape[i],
-                          shape[j], M, tally, ("F4", i, j))
+                          shape[j], M, tally, (tag, i, j))
             else:
                 tally.samples += tau.shape[0]
                 tally.undecided += int((~sure_below & ~sure_clear).sum())
-    tally.close("F4")
+    tally.close(tag)
     assert set(sure) <= set(listed) <= set(sure) | set(maybe), (sorted(set(sure) - set(listed)), sorted(set(listed) - set(sure) - set(maybe)))
     # the broad phase is the mirror's on the extents the device computed, with the radii of uph_footprint_radii
     ext = src.extent(tr, tf, tt, t0=t0, dt=dt)
     cand = conflict_candidates(ext["box"], footprint_radii(shape, margin))
     assert cand.shape[0] == got["n_candidates"] and set(listed) <= set(map(tuple, cand.tolist()))
+    return got, listed, sure, maybe, tau
+
+
+def test_the_fleet(hill):
+    """F4: 24 cars of 0.6 m x 0.3 m (their sizes vary a little) that start 0.4 s apart"""
+    src, ok, total = hill["src"], hill["ok"], hill["total"]
+    n, dt = 24, 0.05
+    tr = ok[:n]
+    rng = np.random.default_rng(53)
+    t0 = 1000.0 + 0.4 * np.arange(n)
+    tf, tt = 999.0, float((t0 + total[tr]).max()) + 1.0
+    shape = np.stack([rng.uniform(0.4, 0.5, n), rng.uniform(0.1, 0.2, n), rng.uniform(0.12, 0.18, n)], axis=1)
+    margin = rng.uniform(0.0, 0.1, n) * (np.arange(n) % 3 != 0)
+    got, listed, sure, maybe, tau = _fleet_held(src, tr, t0, tf, tt, dt, shape, margin)
     # the circumscribed discs report every pair the rectangles report, and pairs the rectangles do not: vehicles that pass side by side or nose to tail
     rho = np.hypot(np.maximum(shape[:, 0], shape[:, 1]), shape[:, 2])
     disc = src.conflicts(tr, rho + margin, tf, tt, t0=t0, dt=dt)

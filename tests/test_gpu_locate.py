@@ -77,8 +77,9 @@ def _bar(v, e, a):
     return 1e-9 * np.maximum(1.0, (v * v).sum(axis=1) + np.hypot(e[:, 0], e[:, 1]) * np.hypot(a[:, 0], a[:, 1]))
 
 
-def _properties(opt, got, want, traj, poses, tag=""):
-    """P2, P3 and P5 on the result `got` of a locate() whose coarse stage equals `want` (P1)"""
+def _properties(opt, got, want, traj, poses, tag="", assert_p3=True):
+    """P2, P3 and P5 on the result `got` of a locate() whose coarse stage equals `want` (P1).  assert_p3 = False (trajectories that are no solved ones: P3's bar
+    was established on solved trajectories) only measures P3.  Returns per query |g| / G where P3 applies, NaN elsewhere."""
     traj = np.asarray(traj, dtype=np.int32)
     n = len(traj)
     poses = np.broadcast_to(np.asarray(poses, dtype=np.float64), (n, 3))
@@ -86,8 +87,9 @@ def _properties(opt, got, want, traj, poses, tag=""):
     empty = ~some
     assert np.isnan(got["t"][empty]).all() and np.isnan(got["near_t"][empty]).all() and (got["d2"][empty] == INF).all() and (got["near_d2"][empty] == INF).all()
     assert (got["refined"][empty] == 0).all() and np.isnan(got["state"][empty]).all() and np.isnan(got["err"][empty]).all()
+    ratio = np.full(n, np.nan)
     if not some.any():
-        return
+        return ratio
     t, st, ps = got["t"][some], got["state"][some], poses[some]
     assert np.array_equal(st, opt.traj_states(traj[some], t), equal_nan=True), tag
     assert (want["lo"][some] <= t).all() and (t <= want["hi"][some]).all(), tag
@@ -107,7 +109,8 @@ def _properties(opt, got, want, traj, poses, tag=""):
     if inner.any():
         MEASURED["g"] = max(MEASURED["g"], float((g[inner] / G[inner]).max()))
         print("P3 %s: %d interior, largest |g| / G = %.3g" % (tag, int(inner.sum()), (g[inner] / G[inner]).max()))
-        assert (g[inner] <= G[inner]).all(), (tag, float((g[inner] / G[inner]).max()))
+        ratio[np.nonzero(some)[0][inner]] = g[inner] / G[inner]
+        assert not assert_p3 or (g[inner] <= G[inner]).all(), (tag, float((g[inner] / G[inner]).max()))
     psi = st[:, 9]
     rx, ry = -ex, -ey
     err = np.stack([rx * np.cos(psi) + ry * np.sin(psi), ry * np.cos(psi) - rx * np.sin(psi), np.array([norm_so2(v) for v in ps[:, 2] - psi])], axis=1)
@@ -116,6 +119,7 @@ def _properties(opt, got, want, traj, poses, tag=""):
         MEASURED["err"] = max(MEASURED["err"], diff)
         print("P5 %s: largest error difference = %.3g" % (tag, diff))
         assert diff <= 1e-9, (tag, diff)
+    return ratio
 
 
 def _poses_near(ref, traj, rng, spread=0.1):

@@ -318,7 +318,7 @@ def test_refine_staging_every_piece_count(dev):
     mid = np.array([out[b]["T_xy"] * ((7 * b) % _pieces(out[b])[0] + 0.5) for b in sel])
     close = lambda got, want: float((np.abs(np.asarray(got) - np.asarray(want)) / np.maximum(1.0, np.abs(want))).max()) if np.size(want) else 0.0
     for tag, ts in (("r_refine_staging_t0", np.zeros(tr.size)), ("r_refine_staging_mid", mid)):
-        dst = U.ALMTrajOpt(dev)
+        dst = U.ALMTrajOpt(src.uneven_map)              # the source's map object: the resident batch is shared with test_gpu_query_sweep.py, whichever ran first made it
         plan = dst.refine_upload(src, tr, ts)
         staged = dst.plan_staged()
         assert (plan["status"] == 0).all() and np.array_equal(plan["traj_of"], np.arange(tr.size)) and np.array_equal(dst.origin(), np.arange(tr.size)), tag

@@ -282,6 +282,29 @@ def test_two_contexts_in_local_frames_and_on_fp32_cells():
         assert dst.L.uph_batch_count(dst.h) > 0
 
 
+def _fleet_brute(src, tr, t0, tf, tt, dt, radius=None):
+    """S4's brute force: separation_rows over all pairs of the fleet on positions from traj_states.  radius None: every vehicle gets half the median of the
+    pairs' smallest distances in that brute force.  Returns the sample times, the positions, the radii and what conflicts() must list."""
+    n = len(tr)
+    tau = separation_times(tf, tt, dt)
+    pos = _positions(src, tr, t0, [tau] * n)
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    if radius is None:
+        least = np.array([np.sqrt(separation_rows(tau, pos[i], pos[j], 0.0)["min_d2"]) for i, j in pairs])
+        radius = np.full(n, 0.5 * np.median(least))
+    brute = [separation_rows(tau, pos[i], pos[j], radius[i] + radius[j]) for i, j in pairs]
+    hits = [k for k, b in enumerate(brute) if b["counts"][1] > 0]
+    return dict(tau=tau, pos=pos, radius=radius, n_pairs=len(pairs), hits=hits, pairs=np.array([pairs[k] for k in hits], dtype=np.int32).reshape(-1, 2),
+                rows=np.array([[brute[k][c] for c in ("min_d2", "min_t", "first_t", "last_t")] for k in hits]).reshape(-1, 4),
+                below=np.array([brute[k]["counts"][1] for k in hits], dtype=np.int32))
+
+
+def _fleet_listed(got, want):
+    """conflicts()' list EQUALS the brute force's"""
+    assert got["n_conflicts"] == len(want["hits"]) and np.array_equal(got["pairs"], want["pairs"]) and np.array_equal(got["rows"], want["rows"], equal_nan=True)
+    assert np.array_equal(got["below"], want["below"])
+
+
 def test_the_fleet(hill):
     """S4: 24 vehicles that start 0.4 s apart.  The brute force is separation_rows over all 276 pairs on positions from traj_states; the radius of every
     vehicle is half the median of the pairs' smallest distances in that brute force, so about half of the pairs conflict"""
@@ -290,21 +313,12 @@ def test_the_fleet(hill):
     tr = ok[:n]
     t0 = 1000.0 + 0.4 * np.arange(n)
     tf, tt = 999.0, float((t0 + total[tr]).max()) + 1.0
-    tau = separation_times(tf, tt, dt)
-    pos = _positions(src, tr, t0, [tau] * n)
-    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-    assert len(pairs) == 276
-    least = np.array([np.sqrt(separation_rows(tau, pos[i], pos[j], 0.0)["min_d2"]) for i, j in pairs])
-    radius = np.full(n, 0.5 * np.median(least))
-    brute = [separation_rows(tau, pos[i], pos[j], radius[i] + radius[j]) for i, j in pairs]
-    hits = [k for k, b in enumerate(brute) if b["counts"][1] > 0]
-    want_pairs = np.array([pairs[k] for k in hits], dtype=np.int32)
-    want_rows = np.array([[brute[k][c] for c in ("min_d2", "min_t", "first_t", "last_t")] for k in hits])
-    want_below = np.array([brute[k]["counts"][1] for k in hits], dtype=np.int32)
+    want = _fleet_brute(src, tr, t0, tf, tt, dt)
+    assert want["n_pairs"] == 276
+    tau, pos, radius, hits, want_pairs, want_rows, want_below = (want[k] for k in ("tau", "pos", "radius", "hits", "pairs", "rows", "below"))
     got = src.conflicts(tr, radius, tf, tt, t0=t0, dt=dt)
     print("fleet: K = %d, radius = %.4g, conflicts %d, candidates %d of 276" % (tau.shape[0], radius[0], got["n_conflicts"], got["n_candidates"]))
-    assert got["n_conflicts"] == len(hits) and np.array_equal(got["pairs"], want_pairs) and np.array_equal(got["rows"], want_rows, equal_nan=True)
-    assert np.array_equal(got["below"], want_below)
+    _fleet_listed(got, want)
     # what keeps this honest: conflicts exist, the broad phase dropped pairs, and it kept pairs that are no conflict
     assert len(hits) >= 1 and got["n_candidates"] < 276 and got["n_candidates"] > got["n_conflicts"]
     # the broad phase is the mirror's on the extents the device computed
