@@ -58,6 +58,7 @@
  *   uph_footprint_separation_batch / uph_footprint_conflicts_batch  <- the same two with the vehicles as oriented rectangles (front, rear, half width)
  *                              turned by the trajectory's yaw instead of discs
  *   uph_delays_batch        <- the smallest start delay that clears each vehicle of a fleet against all vehicles ahead of it in priority order
+ *   uph_footprint_delay_sweep_batch / uph_footprint_delays_batch  <- the delay sweep and the schedule with the vehicles as oriented rectangles
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
  */
 #ifndef UNEVEN_HIP_H
@@ -794,7 +795,42 @@ int uph_delay_extent_batch(uph_ctx* c, int32_t n, const int32_t* traj, const dou
 int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays /* may be NULL */, double t_from,
                      double t_to, double dt, double delay0, double delay_step, int32_t D, int32_t* choice /* [n] */, double* start /* [n] */,
                      int32_t* blocker /* [n] */, int64_t* n_candidates, int32_t* n_rounds, int32_t* n_unresolved);
-/* milliseconds of the kernels of the last uph_delay_sweep_batch, uph_delay_extent_batch or uph_delays_batch of c (events on the context's stream) */
+
+/* ---- start delays with oriented rectangles: the sweep and the schedule above with the footprint rule for the pair, so that a fleet whose conflicts were
+ * reported by uph_footprint_conflicts_batch is cleared by the same metric and no vehicle waits for a pass side by side or nose to tail that the rectangles allow.
+ *   footprint sweep row   row (q, j) holds min_c2, min_t, below and overlapping of uph_footprint_separation_batch for vehicle a (traj_a[q], t0_a[q], shape_a[q])
+ *                  against vehicle b (traj_b[q], t0_b[q] + delta_j, shape_b[q]) over the same window, dt and margin, bit for bit, its NaN and tie rules
+ *                  included; K = 0 gives +inf, NaN, 0, 0.  delta_j is uph_delay_times' table and the device performs only the add t0_b + delta_j.
+ *                  first_clear[q] is the smallest j with below == 0 (-1: none), taken on the host from the rows; counts[q] = K.  Vehicle a does not move
+ *                  with the delay: the kernel takes its pose and the sine and cosine of its heading once per sample and b's once per (delay, sample), by
+ *                  the same sincosFast and the same statements of the rule as uph_footprint_separation_batch, which is why the bits agree.
+ *   footprint schedule   the schedule above, unchanged in every rule -- priority order, n_delays, the effective start of the vehicles ahead, choice, start,
+ *                  blocker, the levels as rounds -- with the footprint sweep for the narrow phase: vehicle h at its effective start with shape[h] is a,
+ *                  vehicle i with shape[i] is b and is swept, M = margin[h] + margin[i], one rounded add as in uph_footprint_conflicts_batch.  The broad
+ *                  phase is uph_conflict_candidates on the swept boxes of uph_delay_extent_batch with uph_footprint_radii's radii r_i.
+ *   why the footprint broad phase loses nothing   every position a vehicle takes at any sample under any delay of the table lies in its swept box (swept
+ *                  extent, above).  If two swept boxes are further apart than r_h + r_i along an axis, then so are the two points at every sample under
+ *                  every combination of delays, and the argument of `radii` above applies to each such sample as it stands: the rectangles' clearance
+ *                  exceeds m_h + m_i by the share of 2^-40 that the roundings do not use up, and the sample is not below M = m_h + m_i.  No new epsilon.
+ * The two-context rules, NULL outputs and blocking are those of uph_delay_sweep_batch / uph_delays_batch.  The refusals are the union of the refusals of
+ * uph_footprint_separation_batch / uph_footprint_conflicts_batch and of uph_delay_sweep_batch / uph_delays_batch -- UPH_ERR_LIMIT for D > 4096 and for a query
+ * with K * D > 2^26 among them --, each before any output is written; the shape and margin checks come first, as in the footprint calls, then the delay
+ * table's and n_delays', all before a context is read.  A footprint sweep row is 32 bytes: 2^20 of them, the most on the device at a time, are 32 MB. */
+/* query q: vehicle (traj_a[q], t0_a[q]) of ca with shape_a[q] against vehicle (traj_b[q], t0_b[q] + delta_j) of cb with shape_b[q] for every delay of the
+ * table, margin[q] = M itself.  The kernel time is kept on ca. */
+int uph_footprint_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb /* NULL: ca */, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a,
+                                    const double* t0_b, const double* t_from, const double* t_to, double dt, const double* shape_a /* [n][3] */,
+                                    const double* shape_b /* [n][3] */, const double* margin /* [n] */, double delay0, double delay_step, int32_t D,
+                                    double* min_c2 /* [n][D] */, double* min_t /* [n][D] */, int32_t* below /* [n][D] */, int32_t* overlapping /* [n][D] */,
+                                    int32_t* first_clear /* [n] */, int32_t* counts /* [n]: K */);
+/* the fleet with rectangles, as uph_delays_batch: vehicles (traj[i], t0[i]) with shape[i] and margin[i] in priority order, one window for all.  Swept extents
+ * on the device, candidates (uph_footprint_radii's radii) and their levels on the host, a footprint sweep launch (or a few of bounded size) per level. */
+int uph_footprint_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* shape /* [n][3] */, const double* margin /* [n] */,
+                               const int32_t* n_delays /* may be NULL */, double t_from, double t_to, double dt, double delay0, double delay_step, int32_t D,
+                               int32_t* choice /* [n] */, double* start /* [n] */, int32_t* blocker /* [n] */, int64_t* n_candidates, int32_t* n_rounds,
+                               int32_t* n_unresolved);
+/* milliseconds of the kernels of the last uph_delay_sweep_batch, uph_delay_extent_batch or uph_delays_batch of c (events on the context's stream); also of the
+ * last uph_footprint_delay_sweep_batch or uph_footprint_delays_batch, which keep their kernel time in the same place */
 int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 #ifdef __cplusplus

@@ -711,7 +711,8 @@ public:
     }
     // the whole fleet with rectangles: vehicles (traj[i], t0[i]) with shape[i] and margin[i], one window.  Every pair (i < j) with a sample that overlaps or is
     // closer than margin[i] + margin[j], in (i, j) order (uph_footprint_conflicts_batch: extents, a host broad phase on the circumscribed radii, the
-    // footprint separation of its candidates).  delaysSE2TrajBatch with the radii hypot(max(front, rear), half_width) + margin clears these pairs too.
+    // footprint separation of its candidates).  footprintDelaysSE2TrajBatch clears these pairs with the same rectangles; delaysSE2TrajBatch with the radii
+    // hypot(max(front, rear), half_width) + margin clears them too, but also postpones passes that the rectangles allow.
     struct TrajFootprintConflicts {
         std::vector<std::array<int32_t, 2>> pairs;      // [m]
         std::vector<double> min_c2, min_t, first_t, last_t;
@@ -798,6 +799,57 @@ public:
         if (uph_delays_batch(ctx_, n, tr.data(), t0.data(), radius.data(), nd.empty() ? nullptr : nd.data(), t_from, t_to, dt, delay0, delay_step, (int32_t)D,
                              out.choice.data(), out.start.data(), out.blocker.data(), &out.n_candidates, &out.n_rounds, &out.n_unresolved) != UPH_OK)
             throw std::runtime_error(std::string("uph_delays_batch: ") + uph_last_error());
+        return out;
+    }
+    // ---- clearing the conflicts of footprintConflictsSE2TrajBatch by starting later, with the same rectangles: no vehicle waits for a pass side by side or
+    // nose to tail that the rectangles allow (delaysSE2TrajBatch on the circumscribed discs would make it wait).  footprintSeparationSE2TrajBatch of a against
+    // b started at t0_b[q] + delta_j, for every j, in one call and bit for bit (uph_footprint_delay_sweep_batch).
+    struct TrajFootprintDelaySweep {
+        int32_t D = 0;
+        std::vector<double> min_c2, min_t;      // [n][D]
+        std::vector<int32_t> below;             // [n][D] samples below
+        std::vector<int32_t> overlapping;       // [n][D] samples that overlap
+        std::vector<int32_t> first_clear;       // [n] the smallest j with below == 0 (-1: none)
+        std::vector<int32_t> counts;            // [n] samples of the window
+    };
+    TrajFootprintDelaySweep footprintDelaySweepSE2TrajBatch(const std::vector<int>& traj_a, const std::vector<int>& traj_b, const std::vector<double>& t0_a,
+                                                            const std::vector<double>& t0_b, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                                            const std::vector<std::array<double, 3>>& shape_a, const std::vector<std::array<double, 3>>& shape_b,
+                                                            const std::vector<double>& margin, double delay0, double delay_step, int D, double dt = 0.01,
+                                                            const ALMTrajOpt* other = nullptr) {
+        const size_t m = traj_a.size();
+        pairCheck("footprintDelaySweepSE2TrajBatch", m, {traj_b.size(), t0_a.size(), t0_b.size(), t_from.size(), t_to.size(), shape_a.size(), shape_b.size(), margin.size()},
+                  other);
+        TrajFootprintDelaySweep out;
+        out.D = (int32_t)D;
+        if (m == 0) return out;
+        const size_t rows = m * (size_t)std::max(D, 1);
+        std::vector<int32_t> ta(traj_a.begin(), traj_a.end()), tb(traj_b.begin(), traj_b.end());
+        out.min_c2.assign(rows, 0.0); out.min_t.assign(rows, 0.0); out.below.assign(rows, 0); out.overlapping.assign(rows, 0); out.first_clear.assign(m, -1);
+        out.counts.assign(m, 0);
+        if (uph_footprint_delay_sweep_batch(ctx_, other ? other->ctx_ : nullptr, (int32_t)m, ta.data(), tb.data(), t0_a.data(), t0_b.data(), t_from.data(), t_to.data(), dt,
+                                            shape_a[0].data(), shape_b[0].data(), margin.data(), delay0, delay_step, (int32_t)D, out.min_c2.data(), out.min_t.data(),
+                                            out.below.data(), out.overlapping.data(), out.first_clear.data(), out.counts.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_footprint_delay_sweep_batch: ") + uph_last_error());
+        return out;
+    }
+    // the fleet in priority order with rectangles: delaysSE2TrajBatch with shape[i] and margin[i] for radius[i] (uph_footprint_delays_batch).  After
+    // footprintConflictsSE2TrajBatch has reported pairs; with the returned starts it reports none whose later vehicle was placed.
+    TrajDelays footprintDelaysSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t0, const std::vector<std::array<double, 3>>& shape,
+                                           const std::vector<double>& margin, double t_from, double t_to, double delay0, double delay_step, int D,
+                                           const std::vector<int>& n_delays = std::vector<int>(), double dt = 0.05) {
+        if (t0.size() != traj.size() || shape.size() != traj.size() || margin.size() != traj.size() || (!n_delays.empty() && n_delays.size() != traj.size()))
+            throw std::runtime_error("footprintDelaysSE2TrajBatch: traj, t0, shape, margin and n_delays differ in number");
+        if (last_multi_) throw std::runtime_error("footprintDelaysSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajDelays out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end()), nd(n_delays.begin(), n_delays.end());
+        out.choice.assign((size_t)n, 0); out.start.assign((size_t)n, 0.0); out.blocker.assign((size_t)n, -1);
+        if (uph_footprint_delays_batch(ctx_, n, tr.data(), t0.data(), shape[0].data(), margin.data(), nd.empty() ? nullptr : nd.data(), t_from, t_to, dt, delay0,
+                                       delay_step, (int32_t)D, out.choice.data(), out.start.data(), out.blocker.data(), &out.n_candidates, &out.n_rounds,
+                                       &out.n_unresolved) != UPH_OK)
+            throw std::runtime_error(std::string("uph_footprint_delays_batch: ") + uph_last_error());
         return out;
     }
     double getTrajJerkCost() const { return last_.jerk_cost; }   // minco_se2.getTrajJerkCost() (alm_traj_opt.cpp:273)

@@ -197,6 +197,10 @@ SYMBOLS = {
     "uph_delay_extent_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, C.c_double, C.c_double, _I32, DP, C.POINTER(_I32)]),
     "uph_delays_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.POINTER(_I32), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I32,
                                    C.POINTER(_I32), DP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_footprint_delay_sweep_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, DP, DP, C.c_double, C.c_double,
+                                                  _I32, DP, DP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_footprint_delays_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.POINTER(_I32), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                             _I32, C.POINTER(_I32), DP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_delay_kernel_ms": (C.c_int, [_VP, DP]),
 }
 

@@ -1200,8 +1200,43 @@ class ALMTrajOpt:
         return out
 
     def delay_kernel_ms(self):
-        """milliseconds of the kernels of the last delay_sweep(), delay_extent() or delays() (events on the context's stream)"""
+        """milliseconds of the kernels of the last delay_sweep(), delay_extent() or delays() -- or footprint_delay_sweep() / footprint_delays() -- (events on
+        the context's stream)"""
         return self._kernel_ms("uph_delay_kernel_ms")
+
+    # ---- start delays with oriented rectangles (uph_footprint_delay_sweep_batch, uph_footprint_delays_batch) -------------------------------------------
+    def footprint_delay_sweep(self, traj_a, traj_b, t_from, t_to, shape_a, shape_b, margin, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
+        """footprint_separation() of vehicle a against vehicle b for every start t0_b[q] + delay_times(delay0, delay_step, D)[j] of b, on the device in one
+        call: min_c2, min_t, below and overlapping (n, D) -- each what footprint_separation() returns for that start, bit for bit --, first_clear (n,) =
+        the smallest j with below == 0 (-1: none) and counts (n,) = the samples K of the window.  Broadcasting and `other` as footprint_separation()."""
+        tr, tb, n, tf, tt, v, hb = self._pair(traj_a, traj_b, t_from, t_to, other, "footprint_delay_sweep", t0_a=t0_a, t0_b=t0_b, margin=margin)
+        sa, sb = (np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (n, 3))) for s in (shape_a, shape_b))
+        D = int(D)
+        m = max(D, 1)
+        out = dict(min_c2=np.full((n, m), np.inf), min_t=np.full((n, m), np.nan), below=np.zeros((n, m), dtype=np.int32), overlapping=np.zeros((n, m), dtype=np.int32),
+                   first_clear=np.full(n, -1, dtype=np.int32), counts=np.zeros(n, dtype=np.int32))
+        _lib.check(self.L.uph_footprint_delay_sweep_batch(self.h, hb, n, _ip(tr), _ip(tb), _dp(v["t0_a"]), _dp(v["t0_b"]), _dp(tf), _dp(tt), float(dt), _dp(sa), _dp(sb),
+                                                          _dp(v["margin"]), float(delay0), float(delay_step), D, _dp(out["min_c2"]), _dp(out["min_t"]),
+                                                          _ip(out["below"]), _ip(out["overlapping"]), _ip(out["first_clear"]), _ip(out["counts"])),
+                   "uph_footprint_delay_sweep_batch")
+        return out
+
+    def footprint_delays(self, traj, shape, margin, t_from, t_to, delay0, delay_step, D, t0=0.0, n_delays=None, dt=0.05):
+        """delays() for vehicles that are rectangles: vehicle i is resident trajectory traj[i] started at t0[i] with shape[i] = (front, rear, half_width) and
+        margin[i] (a shape of (3,) and scalars are broadcast), in priority order, one window for all.  Each vehicle gets the smallest delay of the table --
+        among its first n_delays[i] -- at which its rectangle never overlaps, nor comes closer than margin[h] + margin[i] to, that of any vehicle h ahead of
+        it at ITS chosen start.  The broad phase takes footprint_radii on delay_extent's boxes.  Returns what delays() returns.  The remedy that goes with
+        footprint_conflicts(): delays() on the circumscribed discs also postpones passes side by side that the rectangles allow."""
+        tr, n, _, _, v = self._clock(traj, 0.0, 0.0, "footprint_delays", t0=t0, margin=margin)
+        sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shape, dtype=np.float64), (n, 3)))
+        nd = None if n_delays is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_delays, dtype=np.int32), (n,)))
+        out = dict(choice=np.zeros(n, dtype=np.int32), start=np.full(n, np.nan), blocker=np.full(n, -1, dtype=np.int32))
+        nk, nr, nu = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(self.L.uph_footprint_delays_batch(self.h, n, _ip(tr), _dp(v["t0"]), _dp(sh), _dp(v["margin"]), None if nd is None else _ip(nd), float(t_from),
+                                                     float(t_to), float(dt), float(delay0), float(delay_step), int(D), _ip(out["choice"]), _dp(out["start"]),
+                                                     _ip(out["blocker"]), C.byref(nk), C.byref(nr), C.byref(nu)), "uph_footprint_delays_batch")
+        out.update(n_candidates=int(nk.value), n_rounds=int(nr.value), n_unresolved=int(nu.value))
+        return out
 
     # ---- test / bench hooks -----------------------------------------------------------------------------------------
     def x0_packed(self, probs):

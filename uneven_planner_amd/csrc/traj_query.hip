@@ -1,16 +1,16 @@
 // libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
 // separation / extent / conflicts, the same with oriented rectangles, and the start delays on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*,
-// uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_footprint_*, uph_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_footprint_*, uph_delay*, uph_footprint_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
 // window of the rollout's time table and the end point; ClockQuery: samples t_from + k dt of a clock several vehicles share, for each of the D delays of the
-// launch's table (D = 1 and a null table without one) --, lanes striding over the samples (over the delays, in the two delay kernels), their accumulators (Span,
+// launch's table (D = 1 and a null table without one) --, lanes striding over the samples (over the delays, in the delay kernels), their accumulators (Span,
 // Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  The queries on a pair of vehicles are one family: one
 // record (SepQuery; FootQuery adds the two shapes), one argument block (PairArgs), one body (pairBody) over a metric -- discs or oriented rectangles.  Host:
 // trajFrame (the frame of a trajectory, for every record and argument block), checkTrajQueries (the refusals every query passes), formWindowQueries / pairQueries /
 // fleetCandidates / extentCall (a call shape's refusals in order, its records, its uploads), clockRun (the clock records in launch order), pairRun (the pair
-// records of any metric, chunked by the delay table), fleetConflicts (a fleet's candidates through a pair kernel to the conflict list), twoWidths (256 lanes for the
+// records of any metric, chunked by the delay table), fleetConflicts (a fleet's candidates through a pair kernel to the conflict list), fleetDelays (the same through a sweep kernel, level by level, to the schedule), twoWidths (256 lanes for the
 // head of a sorted launch, one wave for the rest), runQueryLaunch (events, launch, rows back, the wait).
 #include <hip/hip_runtime.h>
 
@@ -474,7 +474,7 @@ struct SweepOut {               // one row per (query, delay)
     double min_d2, min_t;       // as SepOut
     int32_t below, k;           // samples below; the sample of the minimum (WIN_NONE: none)
 };
-template <class Q, class Out>   // SepQuery -> SepOut, or SweepOut with a delay table; FootQuery -> FootOut
+template <class Q, class Out>   // SepQuery -> SepOut, or SweepOut with a delay table; FootQuery -> FootOut, or FootSweepOut with a delay table
 struct PairArgs {
     ResidentDev ra, rb;         // the two sides' resident batches (one context: the same)
     const Q* qs;
@@ -580,15 +580,22 @@ __device__ __forceinline__ double footCorners(double Cx, double Cy, double c, do
     }
     return m;
 }
-// c2 and whether the rectangles overlap, by the rule; a pose that is not finite: NaN, not overlapping
-__device__ __forceinline__ void footClearance(const FootShape& A, const FootShape& B, double Xa, double Ya, double psia, double Xb, double Yb, double psib, double& c2,
-                                              bool& over) {
-#pragma clang fp contract(off)
+// The rule in two parts, so that a kernel that meets one vehicle's pose many times (uph_footprint_sweep_kernel) takes its sine and cosine once.  The front, per
+// vehicle: whether its pose is finite (footFinite) and c, s of its heading (sincosFast); footPose is the two for one vehicle.  The core: c2 and whether the
+// rectangles overlap, from the two points, the two headings' c, s and `finite` (both fronts'); a pose that is not finite: NaN, not overlapping.  footClearance
+// is the front of both vehicles and the core.
+__device__ __forceinline__ bool footFinite(double X, double Y, double psi, bool so_far = true) {     // (one chain of && over both vehicles, in footClearance)
     const double inf = __builtin_huge_val();
-    const bool finite = fabs(Xa) < inf && fabs(Ya) < inf && fabs(psia) < inf && fabs(Xb) < inf && fabs(Yb) < inf && fabs(psib) < inf;
-    double sa, ca, sb, cb;
-    sincosFast(psia, sa, ca);
-    sincosFast(psib, sb, cb);
+    return so_far && fabs(X) < inf && fabs(Y) < inf && fabs(psi) < inf;
+}
+__device__ __forceinline__ bool footPose(double X, double Y, double psi, double& c, double& s) {
+    const bool finite = footFinite(X, Y, psi);
+    sincosFast(psi, s, c);
+    return finite;
+}
+__device__ __forceinline__ void footCore(const FootShape& A, const FootShape& B, double Xa, double Ya, double ca, double sa, double Xb, double Yb, double cb, double sb,
+                                         bool finite, double& c2, bool& over) {
+#pragma clang fp contract(off)
     const double Cax = A.o * ca, Cay = A.o * sa;
     const double Cbx = (Xb - Xa) + B.o * cb, Cby = (Yb - Ya) + B.o * sb;
     const double dx = Cbx - Cax, dy = Cby - Cay;
@@ -604,6 +611,14 @@ __device__ __forceinline__ void footClearance(const FootShape& A, const FootShap
     const double ma = footCorners(Cax, Cay, ca, sa, A, Cbx, Cby, cb, sb, B), mb = footCorners(Cbx, Cby, cb, sb, B, Cax, Cay, ca, sa, A);
     over = finite && g <= 0.0;
     c2 = !finite ? __builtin_nan("") : (over ? 0.0 : (ma < mb ? ma : mb));
+}
+__device__ __forceinline__ void footClearance(const FootShape& A, const FootShape& B, double Xa, double Ya, double psia, double Xb, double Yb, double psib, double& c2,
+                                              bool& over) {
+    const bool finite = footFinite(Xb, Yb, psib, footFinite(Xa, Ya, psia));
+    double sa, ca, sb, cb;
+    sincosFast(psia, sa, ca);
+    sincosFast(psib, sb, cb);
+    footCore(A, B, Xa, Ya, ca, sa, Xb, Yb, cb, sb, finite, c2, over);
 }
 
 // ---- the pair queries (uph_separation_kernel, uph_footprint_kernel): one body over a metric.  A metric names its record and row, says whether it counts
@@ -782,6 +797,87 @@ __global__ __launch_bounds__(NT) void uph_delay_sweep_kernel(PairArgs<SepQuery, 
             for (int o = (int)threadIdx.x + 1; o < (int)threadIdx.x + sp.G; o++) { winTake<false>(body.v, body.i, s_v[o], s_i[2 * o]); body.cnt += s_i[2 * o + 1]; }
     }
     if (g == 0 && dl < sq.D) body.put(dl);
+}
+
+// ---- the delay sweep with oriented rectangles (uph_footprint_delay_sweep_batch, uph_footprint_delays_batch): SweepBody with the footprint rule.  Vehicle a does
+// not move with the delay, so its pose AND the sine and cosine of its heading are taken once per tile (footPose) and parked: a (delay, sample) pays one pose and
+// one sincosFast, b's, where uph_footprint_kernel pays two of each.  The row carries the overlap count next to SweepOut's fields.
+struct FootSweepOut {           // one row per (query, delay)
+    double min_c2, min_t;       // as FootOut
+    int32_t below, k;           // as SweepOut
+    int32_t over, pad;          // samples that overlap
+};
+static_assert(sizeof(SweepOut) == 24 && sizeof(FootSweepOut) == 32, "the rows DELAY_ROWS counts");
+
+template <int NT>
+struct FootSweepBody {
+    const FootQuery& fq;
+    const PairArgs<FootQuery, FootSweepOut>& a;
+    ClockView va, vb;
+    double t0_b;
+    double* pa;                 // [4][DELAY_TILE] a's X, Y, cos, sin of the tile, in LDS; X is NaN where a's pose is not finite
+    bool spill;                 // as SweepBody
+    double v;
+    int i, cnt, nover;
+    __device__ __forceinline__ FootSweepOut* row(int j) const { return a.out + (size_t)fq.out * fq.D + j; }
+    __device__ __forceinline__ void put(int j) const {
+        FootSweepOut o;
+        o.min_c2 = v; o.min_t = i == WIN_NONE ? __builtin_nan("") : clockTau(fq, i);
+        o.below = cnt; o.k = i; o.over = nover; o.pad = 0;
+        *row(j) = o;
+    }
+    __device__ __forceinline__ void park(int k0, int m) {
+        for (int s = (int)threadIdx.x; s < m; s += NT) {
+            double X, Y, P, c, sn;
+            clockSample<true>(va, clockTau(fq, k0 + s), X, Y, &P);
+            const bool finite = footPose(X, Y, P, c, sn);
+            pa[s] = finite ? X : __builtin_nan(""); pa[DELAY_TILE + s] = Y; pa[2 * DELAY_TILE + s] = c; pa[3 * DELAY_TILE + s] = sn;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void open(int j) {
+        vb.t0 = t0_b + a.delta[j];
+        if (spill) { const FootSweepOut o = *row(j); v = o.min_c2; i = o.k; cnt = o.below; nover = o.over; }
+    }
+    __device__ __forceinline__ void sample(int s, int k) {
+        const double inf = __builtin_huge_val();
+        double Xb, Yb, Pb, cb, sb, c2;
+        bool over;
+        clockSample<true>(vb, clockTau(fq, k), Xb, Yb, &Pb);
+        const bool fb = footPose(Xb, Yb, Pb, cb, sb);
+        const double Xa = pa[s];
+        footCore(fq.sa, fq.sb, Xa, pa[DELAY_TILE + s], pa[2 * DELAY_TILE + s], pa[3 * DELAY_TILE + s], Xb, Yb, cb, sb, fabs(Xa) < inf && fb, c2, over);
+        winTake<false>(v, i, c2 < inf ? c2 : inf, k);               // NaN: +inf
+        cnt += over || c2 < fq.R2 ? 1 : 0;                          // (a NaN c2 is not below)
+        nover += over ? 1 : 0;
+    }
+    __device__ __forceinline__ void close(int j) { if (spill) put(j); }
+    __device__ __forceinline__ void release() { __syncthreads(); }
+};
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_footprint_sweep_kernel(PairArgs<FootQuery, FootSweepOut> a) {
+    __shared__ double s_pa[4 * DELAY_TILE];
+    __shared__ double s_v[NT];
+    __shared__ int s_i[3 * NT];
+    const FootQuery fq = a.qs[a.q0 + blockIdx.x];
+    const DelaySplit sp = delaySplit<NT>(fq.D);
+    FootSweepBody<NT> body{fq, a, clockView(a.ra, fq.a, a.framed_a != 0), clockView(a.rb, fq.b, a.framed_b != 0), fq.b.t0, s_pa, sp.P > 1,
+                           __builtin_huge_val(), WIN_NONE, 0, 0};
+    const int dl = (int)threadIdx.x / sp.G, g = (int)threadIdx.x % sp.G;
+    if (body.spill) for (int j = (int)threadIdx.x; j < fq.D; j += NT) body.put(j);      // (G = 1: lane dl owns rows dl, dl + NT, ...)
+    delayLoop(fq, sp, body);
+    if (body.spill) return;
+    if (sp.G > 1) {             // the lanes of a delay, folded by its first lane
+        s_v[threadIdx.x] = body.v; s_i[3 * threadIdx.x] = body.i; s_i[3 * threadIdx.x + 1] = body.cnt; s_i[3 * threadIdx.x + 2] = body.nover;
+        __syncthreads();
+        if (g == 0)
+            for (int o = (int)threadIdx.x + 1; o < (int)threadIdx.x + sp.G; o++) {
+                winTake<false>(body.v, body.i, s_v[o], s_i[3 * o]);
+                body.cnt += s_i[3 * o + 1]; body.nover += s_i[3 * o + 2];
+            }
+    }
+    if (g == 0 && dl < fq.D) body.put(dl);
 }
 
 struct DextBody {
@@ -1189,7 +1285,7 @@ static int candidatePairs(int32_t n, const double* box, const double* radius, co
 // ---- start delays (include/uneven_hip.h uph_delay_*) -------------------------------------------------------------------------------------------------
 constexpr int32_t DELAY_MAX = 4096;                         // delays of one table
 constexpr int64_t DELAY_MAX_WORK = (int64_t)1 << 26;        // K * D of one query: a workgroup's serial work is at most that of 16 separation queries of CLOCK_MAX_SAMPLES
-constexpr size_t DELAY_ROWS = (size_t)1 << 20;              // sweep rows of one launch pair (24 MB on the device)
+constexpr size_t DELAY_ROWS = (size_t)1 << 20;              // sweep rows of one launch pair (24 MB on the device; 32 MB of footprint rows)
 
 static const double* delayDev(uph_ctx* c, const DelayTable* dl) { return dl ? c->d_delay.as<double>() : nullptr; }
 // delta by clockTau's rule
@@ -1211,6 +1307,12 @@ static int delayAdmit(DelayTable* dl, int32_t n, const double* t0, const std::st
         if (!std::isfinite(t0[q] + dl->delta.front()) || !std::isfinite(t0[q] + dl->delta.back())) {
             setError(who + ": query " + std::to_string(q) + " has a delayed start that is not finite"); return UPH_ERR_INVALID;
         }
+    return UPH_OK;
+}
+// the number of delays each vehicle may use (nullptr: D for all)
+static int delayLimits(const std::string& who, int32_t n, const int32_t* n_delays, int32_t D) {
+    if (n_delays) for (int32_t i = 0; i < n; i++)
+        if (n_delays[i] < 1 || n_delays[i] > D) { setError(who + ": vehicle " + std::to_string(i) + " has an n_delays outside [1, D]"); return UPH_ERR_INVALID; }
     return UPH_OK;
 }
 static int delayWork(int64_t K, const DelayTable* dl, const std::string& who, int32_t q = -1) {
@@ -1291,7 +1393,7 @@ static int extentCall(const std::string& who, uph_ctx* c, int32_t n, const int32
     return UPH_OK;
 }
 
-// What the pair calls (uph_separation_batch, uph_footprint_separation_batch, uph_delay_sweep_batch) share: every refusal in their one order, cb defaulting to ca,
+// What the pair calls (uph_separation_batch, uph_footprint_separation_batch, uph_delay_sweep_batch, uph_footprint_delay_sweep_batch) share: every refusal in their one order, cb defaulting to ca,
 // the pair fields of their records (radius: the margin, for footprints), ca's device current with cb's stream drained, the table on it
 template <class Q>
 static int pairQueries(const std::string& who, uph_ctx* ca, uph_ctx*& cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
@@ -1328,7 +1430,7 @@ static void pairRowsOut(const std::vector<Out>& out, double* min, double* min_t,
     }
 }
 
-// What the fleet calls (uph_conflicts_batch, uph_footprint_conflicts_batch, uph_delays_batch) share up to their candidates: every refusal in their one order, the one window's K, the (swept)
+// What the fleet calls (uph_conflicts_batch, uph_footprint_conflicts_batch, uph_delays_batch, uph_footprint_delays_batch) share up to their candidates: every refusal in their one order, the one window's K, the (swept)
 // extents on the device, the pairs of vehicles whose boxes the rule does not drop
 static int fleetCandidates(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays,
                            double t_from, double t_to, double dt, DelayTable* dl, int64_t& K, std::vector<IdxPair>& cand, double& ms) {
@@ -1337,8 +1439,7 @@ static int fleetCandidates(const std::string& who, uph_ctx* c, int32_t n, const 
     for (int32_t i = 0; i < n; i++)
         if (!std::isfinite(radius[i]) || radius[i] < 0.0) { setError(who + ": vehicle " + std::to_string(i) + " has a negative or non-finite radius"); return UPH_ERR_INVALID; }
     if ((r = delayAdmit(dl, n, t0, who)) != UPH_OK) return r;
-    if (dl && n_delays) for (int32_t i = 0; i < n; i++)
-        if (n_delays[i] < 1 || n_delays[i] > dl->D) { setError(who + ": vehicle " + std::to_string(i) + " has an n_delays outside [1, D]"); return UPH_ERR_INVALID; }
+    if (dl && (r = delayLimits(who, n, n_delays, dl->D)) != UPH_OK) return r;
     if ((r = clockWindow(t_from, t_to, dt, K, who)) != UPH_OK || (r = delayWork(K, dl, who)) != UPH_OK) return r;
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     if ((r = delayUpload(c, dl)) != UPH_OK) return r;
@@ -1429,6 +1530,67 @@ static int footRadii(const std::string& who, int32_t n, const double* shape, con
         r[(size_t)i] = footRadius(shape + 3 * (size_t)i, margin[i]);
         if (!std::isfinite(r[(size_t)i])) { setError(whoQuery(who, i) + " has a shape and margin whose radius is not finite"); return UPH_ERR_INVALID; }
     }
+    return UPH_OK;
+}
+// What the schedule calls (uph_delays_batch, uph_footprint_delays_batch) are behind their own refusals: fleetCandidates on swept boxes with the broad-phase radii,
+// the candidates' levels, a round per level -- the sweep record of every candidate of the level, form(K, dl, h, start_h, i) with h at its effective start, through
+// a sweep kernel whose rows carry `below` --, the sequential greedy's choice per vehicle, the kernels' time to the context's last_delay_ms
+template <class Q, class Row, class Form>
+static int fleetDelays(const std::string& who, uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* radius, const int32_t* n_delays, double t_from,
+                       double t_to, double dt, double delay0, double delay_step, int32_t D, Form form, void (*k256)(PairArgs<Q, Row>), void (*k64)(PairArgs<Q, Row>),
+                       int32_t* choice, double* start, int32_t* blocker, int64_t* n_candidates, int32_t* n_rounds, int32_t* n_unresolved) {
+    DelayTable dl{delay0, delay_step, D};
+    const std::vector<double>& delta = dl.delta;
+    int64_t K = 0;
+    std::vector<IdxPair> cand;
+    double ms = 0.0;
+    int r = fleetCandidates(who, c, n, traj, t0, radius, n_delays, t_from, t_to, dt, &dl, K, cand, ms);
+    if (r != UPH_OK) return r;
+    // the candidates' levels on the host
+    std::vector<int32_t> level;
+    delayLevels(n, cand, level);
+    const int32_t rounds = *std::max_element(level.begin(), level.end());
+    // a round per level: the vehicles of the level swept against their partners ahead, which are all placed by then
+    std::vector<std::vector<size_t>> cand_of((size_t)rounds + 1);       // the candidates of each level (that of the later vehicle), in (h, i) order
+    std::vector<std::vector<int32_t>> veh_of((size_t)rounds + 1);
+    for (size_t p = 0; p < cand.size(); p++) cand_of[(size_t)level[(size_t)cand[p].second]].push_back(p);
+    for (int32_t i = 0; i < n; i++) veh_of[(size_t)level[(size_t)i]].push_back(i);
+    std::vector<int32_t> ch((size_t)n, 0), blk((size_t)n, -1);
+    std::vector<char> taken((size_t)n * D, 0);      // [i][j]: vehicle i is below a partner ahead at delay j
+    std::vector<Q> qs;
+    std::vector<Row> rows;
+    for (int32_t lv = 1; lv <= rounds; lv++) {
+        const std::vector<size_t>& of = cand_of[(size_t)lv];
+        qs.resize(of.size());
+        for (size_t k = 0; k < of.size(); k++) {
+            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
+            qs[k] = form(K, &dl, h, t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)], i);
+        }
+        if ((r = pairRun(c, c, qs, &dl, k256, k64, rows, ms)) != UPH_OK) return r;
+        for (size_t k = 0; k < of.size(); k++) {        // (h ascending for each vehicle: the first h below at delay 0 is the smallest)
+            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
+            for (int32_t j = 0; j < D; j++) if (rows[k * (size_t)D + j].below > 0) taken[(size_t)i * D + j] = 1;
+            if (blk[(size_t)i] < 0 && rows[k * (size_t)D].below > 0) blk[(size_t)i] = h;
+        }
+        for (const int32_t i : veh_of[(size_t)lv]) {
+            const int32_t nd = n_delays ? n_delays[i] : D;
+            int32_t j = 0;
+            while (j < nd && taken[(size_t)i * D + j]) j++;
+            ch[(size_t)i] = j < nd ? j : -1;
+            if (j < nd) blk[(size_t)i] = -1;
+        }
+    }
+    c->last_delay_ms = ms;
+    int32_t unresolved = 0;
+    for (int32_t i = 0; i < n; i++) {
+        if (choice) choice[i] = ch[(size_t)i];
+        if (start) start[i] = t0[i] + delta[(size_t)std::max(ch[(size_t)i], 0)];
+        if (blocker) blocker[i] = blk[(size_t)i];
+        unresolved += ch[(size_t)i] < 0 ? 1 : 0;
+    }
+    if (n_candidates) *n_candidates = (int64_t)cand.size();
+    if (n_rounds) *n_rounds = rounds;
+    if (n_unresolved) *n_unresolved = unresolved;
     return UPH_OK;
 }
 extern "C" {
@@ -1757,59 +1919,70 @@ int uph_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t
                      int32_t* n_unresolved) {
     const std::string who = "uph_delays_batch";
     if (!c || n <= 0 || !traj || !t0 || !radius) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    const auto form = [&](int64_t K, const DelayTable* dl, int32_t h, double start_h, int32_t i) {
+        return pairQuery(K, t_from, dt, dl, radius[h] + radius[i], clockTraj(c, traj[h], start_h), clockTraj(c, traj[i], t0[i]));
+    };
+    return fleetDelays<SepQuery, SweepOut>(who, c, n, traj, t0, radius, n_delays, t_from, t_to, dt, delay0, delay_step, D, form, uph_delay_sweep_kernel<256>,
+                                           uph_delay_sweep_kernel<64>, choice, start, blocker, n_candidates, n_rounds, n_unresolved);
+}
+
+// ---- start delays with oriented rectangles (include/uneven_hip.h) -----------------------------------------------------------------------------------------
+int uph_footprint_delay_sweep_batch(uph_ctx* ca, uph_ctx* cb, int32_t n, const int32_t* traj_a, const int32_t* traj_b, const double* t0_a, const double* t0_b,
+                                    const double* t_from, const double* t_to, double dt, const double* shape_a, const double* shape_b, const double* margin, double delay0,
+                                    double delay_step, int32_t D, double* min_c2, double* min_t, int32_t* below, int32_t* overlapping, int32_t* first_clear,
+                                    int32_t* counts) {
+    const std::string who = "uph_footprint_delay_sweep_batch";
+    if (!ca || n <= 0 || !shape_a || !shape_b || !margin) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    int r = footAdmit(who, n, shape_a, "shape_a", margin);
+    if (r != UPH_OK || (r = footAdmit(who, n, shape_b, "shape_b", nullptr)) != UPH_OK) return r;
     DelayTable dl{delay0, delay_step, D};
-    const std::vector<double>& delta = dl.delta;
-    int64_t K = 0;
-    std::vector<IdxPair> cand;
+    if ((r = delayTable(delay0, delay_step, D, dl.delta, who)) != UPH_OK) return r;         // with the shapes: what needs no context is refused before one is read
+    std::vector<FootQuery> qs;      // the pair call's refusals, windows and vehicles, the margin in the radius' place
+    if ((r = pairQueries(who, ca, cb, n, traj_a, traj_b, t0_a, t0_b, t_from, t_to, dt, margin, &dl, qs)) != UPH_OK) return r;
+    std::vector<int32_t> Ks((size_t)n);
+    for (int32_t q = 0; q < n; q++) {                                       // (pairRun leaves qs in launch order)
+        qs[(size_t)q].sa = footShape(shape_a + 3 * (size_t)q); qs[(size_t)q].sb = footShape(shape_b + 3 * (size_t)q);
+        Ks[(size_t)q] = qs[(size_t)q].K;
+    }
+    std::vector<FootSweepOut> rows;
     double ms = 0.0;
-    int r = fleetCandidates(who, c, n, traj, t0, radius, n_delays, t_from, t_to, dt, &dl, K, cand, ms);
-    if (r != UPH_OK) return r;
-    // the candidates' levels on the host
-    std::vector<int32_t> level;
-    delayLevels(n, cand, level);
-    const int32_t rounds = *std::max_element(level.begin(), level.end());
-    // a round per level: the vehicles of the level swept against their partners ahead, which are all placed by then
-    std::vector<std::vector<size_t>> cand_of((size_t)rounds + 1);       // the candidates of each level (that of the later vehicle), in (h, i) order
-    std::vector<std::vector<int32_t>> veh_of((size_t)rounds + 1);
-    for (size_t p = 0; p < cand.size(); p++) cand_of[(size_t)level[(size_t)cand[p].second]].push_back(p);
-    for (int32_t i = 0; i < n; i++) veh_of[(size_t)level[(size_t)i]].push_back(i);
-    std::vector<int32_t> ch((size_t)n, 0), blk((size_t)n, -1);
-    std::vector<char> taken((size_t)n * D, 0);      // [i][j]: vehicle i is below a partner ahead at delay j
-    std::vector<SepQuery> qs;
-    std::vector<SweepOut> rows;
-    for (int32_t lv = 1; lv <= rounds; lv++) {
-        const std::vector<size_t>& of = cand_of[(size_t)lv];
-        qs.resize(of.size());
-        for (size_t k = 0; k < of.size(); k++) {
-            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
-            qs[k] = pairQuery(K, t_from, dt, &dl, radius[h] + radius[i], clockTraj(c, traj[h], t0[h] + delta[(size_t)std::max(ch[(size_t)h], 0)]), clockTraj(c, traj[i], t0[i]));
+    if ((r = pairRun(ca, cb, qs, &dl, uph_footprint_sweep_kernel<256>, uph_footprint_sweep_kernel<64>, rows, ms)) != UPH_OK) return r;
+    ca->last_delay_ms = ms;
+    for (int32_t q = 0; q < n; q++) {
+        int32_t clear = -1;
+        for (int32_t j = 0; j < D; j++) {
+            const size_t at = (size_t)q * D + j;
+            const FootSweepOut& o = rows[at];
+            if (min_c2) min_c2[at] = o.min_c2;
+            if (min_t) min_t[at] = o.min_t;
+            if (below) below[at] = o.below;
+            if (overlapping) overlapping[at] = o.over;
+            if (clear < 0 && o.below == 0) clear = j;
         }
-        if ((r = pairRun(c, c, qs, &dl, uph_delay_sweep_kernel<256>, uph_delay_sweep_kernel<64>, rows, ms)) != UPH_OK) return r;
-        for (size_t k = 0; k < of.size(); k++) {        // (h ascending for each vehicle: the first h below at delay 0 is the smallest)
-            const int32_t h = cand[of[k]].first, i = cand[of[k]].second;
-            for (int32_t j = 0; j < D; j++) if (rows[k * (size_t)D + j].below > 0) taken[(size_t)i * D + j] = 1;
-            if (blk[(size_t)i] < 0 && rows[k * (size_t)D].below > 0) blk[(size_t)i] = h;
-        }
-        for (const int32_t i : veh_of[(size_t)lv]) {
-            const int32_t nd = n_delays ? n_delays[i] : D;
-            int32_t j = 0;
-            while (j < nd && taken[(size_t)i * D + j]) j++;
-            ch[(size_t)i] = j < nd ? j : -1;
-            if (j < nd) blk[(size_t)i] = -1;
-        }
+        if (first_clear) first_clear[q] = clear;
+        if (counts) counts[q] = Ks[(size_t)q];
     }
-    c->last_delay_ms = ms;
-    int32_t unresolved = 0;
-    for (int32_t i = 0; i < n; i++) {
-        if (choice) choice[i] = ch[(size_t)i];
-        if (start) start[i] = t0[i] + delta[(size_t)std::max(ch[(size_t)i], 0)];
-        if (blocker) blocker[i] = blk[(size_t)i];
-        unresolved += ch[(size_t)i] < 0 ? 1 : 0;
-    }
-    if (n_candidates) *n_candidates = (int64_t)cand.size();
-    if (n_rounds) *n_rounds = rounds;
-    if (n_unresolved) *n_unresolved = unresolved;
     return UPH_OK;
+}
+
+int uph_footprint_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t0, const double* shape, const double* margin, const int32_t* n_delays,
+                               double t_from, double t_to, double dt, double delay0, double delay_step, int32_t D, int32_t* choice, double* start, int32_t* blocker,
+                               int64_t* n_candidates, int32_t* n_rounds, int32_t* n_unresolved) {
+    const std::string who = "uph_footprint_delays_batch";
+    if (!c || n <= 0 || !traj || !t0 || !shape || !margin) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    std::vector<double> radius;
+    int r = footAdmit(who, n, shape, "shape", margin);
+    if (r != UPH_OK || (r = footRadii(who, n, shape, margin, radius)) != UPH_OK) return r;
+    std::vector<double> table;      // with the shapes: what needs no context is refused before one is read
+    if ((r = delayTable(delay0, delay_step, D, table, who)) != UPH_OK || (r = delayLimits(who, n, n_delays, D)) != UPH_OK) return r;
+    const auto form = [&](int64_t K, const DelayTable* dl, int32_t h, double start_h, int32_t i) {
+        FootQuery q = pairQuery<FootQuery>(K, t_from, dt, dl, margin[h] + margin[i], clockTraj(c, traj[h], start_h), clockTraj(c, traj[i], t0[i]));
+        q.sa = footShape(shape + 3 * (size_t)h); q.sb = footShape(shape + 3 * (size_t)i);
+        return q;
+    };
+    return fleetDelays<FootQuery, FootSweepOut>(who, c, n, traj, t0, radius.data(), n_delays, t_from, t_to, dt, delay0, delay_step, D, form,
+                                                uph_footprint_sweep_kernel<256>, uph_footprint_sweep_kernel<64>, choice, start, blocker, n_candidates, n_rounds,
+                                                n_unresolved);
 }
 
 int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_delay_kernel_ms", c, &uph_ctx::last_delay_ms, kernel_ms); }
