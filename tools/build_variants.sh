@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds named variants of libunevenhip.so for A/B measurements on the GPU box: build/variants/libunevenhip_<name>.so
 # usage: tools/build_variants.sh name1="-DFLAG=1 ..." name2="..."      (run in the repo root; select with UNEVENHIP_LIB=<path>)
+# placement switches: aside0="-DUPH_ASIDE_PREP=0" (DESIGN.md 7n), overlap0="-DUPH_CHUNK_OVERLAP=0" (7r: the chunk loop with a barrier behind every scatter)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build/variants

@@ -82,6 +82,26 @@ UPH_HD void asideKnotSolve(WG& wg, int lenW, int lenX, int n, F f) {
     wg.pfor(n, f);
 }
 
+// Placement of the barriers of eval()'s chunk loop.  1: a chunk's scatter has no barrier of its own; the wave that finishes its half
+// first goes on into the next chunk's sample arithmetic and meets the other one in front of the record stores (sampleChunk below).  0: sample pass,
+// barrier, scatter, barrier, as before.  The same operations on the same operands either way; a compile-time switch only (tools/build_variants.sh).
+#ifndef UPH_CHUNK_OVERLAP
+#define UPH_CHUNK_OVERLAP 1
+#endif
+// One chunk of a sample pass in two parts: compute(t, acc, h) forms sample t's terms, adds its M sums to the lane's partials (wg.accBegin / accEnd) and
+// leaves in h what commit(t, h) then stores into the chunk's record slots; compute itself touches no record word.  n <= wg.size(): a chunk has one record
+// slot per lane.  Ends like wg.accChunk: with the barrier behind which the records are complete.  `first` = the pass's first chunk (no scatter of an
+// earlier chunk may still be reading the slots).  Any workgroup object can run the two parts back to back; the device's overload (unevenhip.hip) puts
+// the barrier that waits for the previous chunk's scatter BETWEEN them.
+template <int M, class H, class WG, class C, class P>
+UPH_HD void sampleChunk(WG& wg, int n, bool first, C compute, P commit) {
+    (void)first;
+    wg.template accChunk<M>(n, [&](int t, double* acc) { H h; compute(t, acc, h); commit(t, h); });
+}
+// f(t) for t = 0 .. n - 1 WITHOUT the barrier that ends wg.pfor (the caller names the barrier that orders what f wrote); sequential objects have none anyway
+template <class WG, class F>
+UPH_HD void pforOpen(WG& wg, int n, F f) { wg.pfor(n, f); }
+
 // SR = real type of the sample-phase arithmetic: double (the reference's, default) or f32r (fp32 sample mode, uph_common.hpp)
 template <class WG, class SR = double>
 struct Solver {
@@ -491,28 +511,47 @@ struct Solver {
     //                tabulated once per evaluation (wtab, written by the 17 samples of piece 0)
     //   rec[6+k]   = beta0_k(u) grad_yaw + beta1_k(u) grad_dyaw   -> gdCyaw block of its yaw piece (grad_d2yaw == 0, Q8)
     //   rtag       = that yaw piece (int32)
+    // In two steps, so that a sample pass can form the record where it always did and store it later (sampleChunk): formRec is the arithmetic, storeRec the
+    // stores -- and the power table of piece 0, products of s1 alone.  putRec is one after the other.
     template <class R>
-    UPH_HD void putRec(int slot, int i, int j, const R gp_[2], const R gv_[2], const R ga_[2], R gyaw, R gdyaw, const KinT<R>& k) {
-        rec[0 * CHP + slot] = gp_[0]; rec[1 * CHP + slot] = gp_[1];
-        rec[2 * CHP + slot] = gv_[0]; rec[3 * CHP + slot] = gv_[1];
-        rec[4 * CHP + slot] = ga_[0]; rec[5 * CHP + slot] = ga_[1];
+    struct SampleRec {
+        R f[12], s1;
+        int yaw_idx, i, j;
+    };
+    template <class R>
+    UPH_HD void formRec(SampleRec<R>& o, int i, int j, const R gp_[2], const R gv_[2], const R ga_[2], R gyaw, R gdyaw, const KinT<R>& k) {
+        o.f[0] = gp_[0]; o.f[1] = gp_[1];
+        o.f[2] = gv_[0]; o.f[3] = gv_[1];
+        o.f[4] = ga_[0]; o.f[5] = ga_[1];
         R u1 = k.u;
         if (UPH_DIET) pinv(u1);                          // (the powers are REBUILT here: not carried from kin() across the gather and the penalties)
         const R u2 = u1 * u1, u3 = u2 * u1, u4 = u2 * u2, u5 = u4 * u1;
-        rec[6 * CHP + slot] = gyaw;
-        rec[7 * CHP + slot] = (u1 * gyaw + gdyaw);
-        rec[8 * CHP + slot] = (u2 * gyaw + 2.0 * u1 * gdyaw);
-        rec[9 * CHP + slot] = (u3 * gyaw + 3.0 * u2 * gdyaw);
-        rec[10 * CHP + slot] = (u4 * gyaw + 4.0 * u3 * gdyaw);
-        rec[11 * CHP + slot] = (u5 * gyaw + 5.0 * u4 * gdyaw);
-        rtag[slot] = k.yaw_idx;
-        if (i == 0) {                                    // the powers behind beta0/1/2 of alm_traj_opt.cpp:738-740 at s1(j) (rebuilt from s1: not kept live across the sample)
-            double* w = wtab + 6 * j;
-            R s1 = k.s1;
+        o.f[6] = gyaw;
+        o.f[7] = (u1 * gyaw + gdyaw);
+        o.f[8] = (u2 * gyaw + 2.0 * u1 * gdyaw);
+        o.f[9] = (u3 * gyaw + 3.0 * u2 * gdyaw);
+        o.f[10] = (u4 * gyaw + 4.0 * u3 * gdyaw);
+        o.f[11] = (u5 * gyaw + 5.0 * u4 * gdyaw);
+        o.yaw_idx = k.yaw_idx; o.s1 = k.s1; o.i = i; o.j = j;
+    }
+    template <class R>
+    UPH_HD void storeRec(int slot, const SampleRec<R>& o) {
+#pragma unroll
+        for (int q = 0; q < 12; q++) rec[q * CHP + slot] = o.f[q];
+        rtag[slot] = o.yaw_idx;
+        if (o.i == 0) {                                  // the powers behind beta0/1/2 of alm_traj_opt.cpp:738-740 at s1(j) (rebuilt from s1: not kept live across the sample)
+            double* w = wtab + 6 * o.j;
+            R s1 = o.s1;
             if (UPH_DIET) pinv(s1);
             const R s2 = s1 * s1, s3 = s2 * s1, s4 = s2 * s2, s5 = s4 * s1;
             w[0] = 1.0; w[1] = s1; w[2] = s2; w[3] = s3; w[4] = s4; w[5] = s5;
         }
+    }
+    template <class R>
+    UPH_HD void putRec(int slot, int i, int j, const R gp_[2], const R gv_[2], const R ga_[2], R gyaw, R gdyaw, const KinT<R>& k) {
+        SampleRec<R> o;
+        formRec<R>(o, i, j, gp_, gv_, ga_, gyaw, gdyaw, k);
+        storeRec<R>(slot, o);
     }
 
     // one constraint sample of calConstrainCostGrad (alm_traj_opt.cpp:716-988).  acc[0] += cost, acc[1] += gdTxy part, acc[2] += gdTyaw part.
@@ -521,8 +560,19 @@ struct Solver {
     // same code up to the residuals, run once over the last evaluated trajectory when the pass ends (refreshResiduals).
     // RES: 0 = cost and gradient, no residual stores (the solve's evaluations); 1 = residuals only; 2 = both -- calConstrainCostGrad as the
     // reference runs it, hx / gx written by every call (penaltyOnly, the A5-alone measurement entry).
+    // The sample in two parts (sampleChunk): sampleCompute is everything but the stores of putRec -- the record is formed where it always was, in the
+    // same expressions; it touches neither rec / rtag nor wtab -- and leaves in a SampleRec what sampleCommit (storeRec) stores.  sampleEval runs
+    // them back to back.
+    template <class R>
+    UPH_HD void sampleCommit(int slot, const SampleRec<R>& o) { storeRec<R>(slot, o); }
     template <int RES, class R = double>
     UPH_HD void sampleEval(int s, int slot, double* acc) {
+        SampleRec<R> o;
+        sampleCompute<RES, R>(s, acc, o);
+        if (RES != 1) sampleCommit<R>(slot, o);
+    }
+    template <int RES, class R = double>
+    UPH_HD void sampleCompute(int s, double* acc, SampleRec<R>& o) {
         constexpr bool RES_ONLY = RES == 1;
         UPH_MARK("sampleEval");
         const int i = divSmall(s, K + 1, inv_k1), j = s - i * (K + 1);
@@ -678,7 +728,7 @@ struct Solver {
         grad_p[0] += grad_se2[0]; grad_p[1] += grad_se2[1];
         grad_yaw += grad_se2[2];
         // scatter terms (:966-985): the C-blocks are reduced per piece in scatter(); the T parts are summed here
-        putRec<R>(slot, i, j, grad_p, grad_v, grad_a, grad_yaw, grad_dyaw, k);
+        formRec<R>(o, i, j, grad_p, grad_v, grad_a, grad_yaw, grad_dyaw, k);
         tx += ((grad_p[0] * k.vel[0] + grad_p[1] * k.vel[1]) + (grad_v[0] * k.acc[0] + grad_v[1] * k.acc[1]) +
                (grad_a[0] * k.jer[0] + grad_a[1] * k.jer[1])) * alpha;
         const R yawdot = (grad_yaw * k.dyaw + grad_dyaw * k.d2yaw);
@@ -731,6 +781,8 @@ struct Solver {
     // each summing its two record fields over the candidate slots whose tag names its piece.  XYL is a multiple of the wave size.
     // Every LDS operand is read at base + constant without clamping: reads next to a piece's slots land in neighbouring words of the
     // same allocation (wtab sits right before rec) and are discarded by the selects.
+    // BAR = false: without the barrier that ends the pass -- for eval()'s chunk loop alone, where the next chunk's sampleChunk (or accEnd) has it.
+    template <bool BAR = true>
     UPH_HD void scatterChunk(int s0, int cnt) {
         UPH_MARK("scatterChunk");
         const int K1 = K + 1;
@@ -820,15 +872,18 @@ struct Solver {
                 UPH_MARK("scatter.mfma");
                 wg.scatterXY17(rec, wtab, Gxy, i0, i1 - i0 + 1, s0, cnt);
                 UPH_MARK("scatter.yaw");
-                wg.pforRev(3 * (m1 - m0 + 1), yawTask);
+                if (BAR) wg.pforRev(3 * (m1 - m0 + 1), yawTask);
+                else wg.pforRevOpen(3 * (m1 - m0 + 1), yawTask);
                 return;
             }
         }
         UPH_MARK("scatter.vector(cold for K=16)");
-        wg.pfor(XYL + 3 * (m1 - m0 + 1), [&](int t) {
+        auto task = [&](int t) {
             if (t < XYL) { if (t < nxyt) xyTask(t); }
             else yawTask(t - XYL);
-        });
+        };
+        if (BAR) wg.pfor(XYL + 3 * (m1 - m0 + 1), task);
+        else pforOpen(wg, XYL + 3 * (m1 - m0 + 1), task);
     }
 
     // ------------------------------------------------------------------ adjoint: (dK/dc, direct dK/dT sums) -> gradient w.r.t. (q, T)
@@ -1008,6 +1063,27 @@ struct Solver {
         // (cost, dT_xy, dT_yaw) of the samples: every lane keeps its partials across the chunks, ONE block reduction after the last chunk (wg.accEnd)
         double sm[3] = {0.0, 0.0, 0.0};
         wg.template accBegin<3>();
+#if UPH_CHUNK_OVERLAP
+        // Per chunk c:  compute(c) | barrier A (c > 0) | commit(c) | barrier B | scatter(c), no barrier behind it.  A wave that is through with its half of
+        // scatter(c) runs compute(c + 1) while the other one still sums.  Why that is enough (A and B sit in sampleChunk, reached by every lane):
+        //   - rec / rtag: scatter(c) reads them on every wave; the next writer is commit(c + 1), behind barrier A, which no wave passes before every wave has
+        //     left scatter(c).  compute() touches no record word, and scatter(c) reads complete records: it comes behind barrier B of its chunk.
+        //   - wtab is written by commit(0) alone (the samples of piece 0 lie in chunk 0) and read by every scatter: barrier B of chunk 0 lies between.
+        //   - G: a piece that straddles chunks c and c + 1 has its words added to in both scatters, possibly by different waves; barriers A and B of chunk
+        //     c + 1 lie between the two.  Within one scatter every word has one owner.  compute() does not read G.
+        //   - after the last chunk: accEnd's barrier comes before its first read, and every wave reaches it behind its last scatter -- adjoint (which reads G
+        //     and takes rec for its knot buffers) and the return of a trial abandoned with f known (the next generate() writes rec) both lie behind it.
+        for (int s0 = 0; s0 < S; s0 += CHS) {
+            const int cnt = S - s0 < CHS ? S - s0 : CHS;
+            t0 = wg.clock();
+            if (UPH_PHASE_MASK & 2)
+                sampleChunk<3, SampleRec<SR>>(wg, cnt, s0 == 0, [&](int t, double* acc, SampleRec<SR>& h) { sampleCompute<0, SR>(s0 + t, acc, h); },
+                                              [&](int t, const SampleRec<SR>& h) { sampleCommit<SR>(t, h); });
+            t1 = wg.clock(); cyc[1] += t1 - t0;           // (includes the wait for the previous chunk's scatter on the other wave)
+            if (UPH_PHASE_MASK & 4) scatterChunk<false>(s0, cnt);
+            cyc[2] += wg.clock() - t1;
+        }
+#else
         for (int s0 = 0; s0 < S; s0 += CHS) {
             const int cnt = S - s0 < CHS ? S - s0 : CHS;
             t0 = wg.clock();
@@ -1016,6 +1092,7 @@ struct Solver {
             if (UPH_PHASE_MASK & 4) scatterChunk(s0, cnt);
             cyc[2] += wg.clock() - t1;
         }
+#endif
         wg.template accEnd<3>(sm);
         t1 = wg.clock();
         if (STEP && thr < __builtin_huge_val()) {

@@ -86,6 +86,15 @@ struct DevWG {
         for (int i = (NW - 1 - wave) * 64 + flane(); i < n; i += NT) f(i);
         bar(3);
     }
+    // pfor / pforRev without the barrier: the chunk loop of Solver::eval, where the barrier that orders the scatter sits in the next sampleChunk (or accEnd)
+    template <class F>
+    __device__ __forceinline__ void pforOpen(int n, F f) {
+        for (int i = ftid(); i < n; i += NT) f(i);
+    }
+    template <class F>
+    __device__ __forceinline__ void pforRevOpen(int n, F f) {
+        for (int i = (NW - 1 - wave) * 64 + flane(); i < n; i += NT) f(i);
+    }
     // ---------------------------------------------------------------------------------------------------------------------------
     // xy half of Solver::scatterChunk on the matrix cores (alm_traj_opt.cpp:966-979 for all pieces of a sample chunk at once):
     //     G(6 x 2P) += B(6 x 51) R(51 x 2P),    v_mfma_f64_16x16x4_f64, 13 steps of four contraction indices per tile of 16 columns
@@ -192,6 +201,20 @@ struct DevWG {
     template <int M, class F>
     __device__ __forceinline__ void accChunk(int n, F f) {
         for (int i = ftid(); i < n; i += NT) f(i, pacc);
+        bar(0);
+    }
+    // Solver's sampleChunk (solver_program.hpp): accChunk with the region's body in two parts and a barrier between them.  compute() reads nothing that the
+    // scatter of the previous chunk writes and writes nothing it reads, so a wave enters it straight from its half of that scatter; the first barrier (class 3
+    // of the barrier profile: it waits for a scatter) holds the record stores of commit() back until every wave has left the scatter, the second one is
+    // accChunk's.  Both are reached by every lane in uniform control flow (n and first are wave-uniform, a lane without a sample skips the two parts only).
+    // n <= NT: one record slot per lane.
+    template <int M, class H, class C, class P>
+    __device__ __forceinline__ void accChunkSplit(int n, bool first, C compute, P commit) {
+        const int i = ftid();
+        H h;
+        if (i < n) compute(i, pacc, h);
+        if (!first) bar(3);
+        if (i < n) commit(i, h);
         bar(0);
     }
     template <int M>
@@ -584,6 +607,12 @@ struct DevWG {
 // Solver's asideKnotSolve (solver_program.hpp) on the device: the idle wave's lanes instead of a parallel loop with a barrier
 template <int NT, class F>
 __device__ __forceinline__ void asideKnotSolve(DevWG<NT>& wg, int lenW, int lenX, int n, F f) { wg.aside(lenW, lenX, n, f); }
+
+// Solver's sampleChunk and pforOpen on the device
+template <int M, class H, int NT, class C, class P>
+__device__ __forceinline__ void sampleChunk(DevWG<NT>& wg, int n, bool first, C compute, P commit) { wg.template accChunkSplit<M, H>(n, first, compute, commit); }
+template <int NT, class F>
+__device__ __forceinline__ void pforOpen(DevWG<NT>& wg, int n, F f) { wg.pforOpen(n, f); }
 
 // MODE 0: one (or `repeat`) objective evaluation(s)   1: reset + initScaling   2: ALM / L-BFGS solve (repeat > 0: at most that many ALM passes)
 // 3: post-solve report   4: initScaling only (test hook, keeps the resident duals)   5: phase microbenchmark
