@@ -833,6 +833,65 @@ int uph_footprint_delays_batch(uph_ctx* c, int32_t n, const int32_t* traj, const
  * last uph_footprint_delay_sweep_batch or uph_footprint_delays_batch, which keep their kernel time in the same place */
 int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
+/* ---- a fleet of resident trajectories: a long-lived uph_ctx whose resident batch is `slots` SLOTS, filled by adopting solved trajectories of other contexts
+ * on the device.  Every call that looks at a whole fleet (uph_conflicts_batch, uph_delays_batch, their footprint forms, check / locate / within over the live
+ * vehicles) takes ONE context, while the trajectories a fleet drives are solved in several and every upload replaces the batch of its context: a fleet is the
+ * one context that holds what every vehicle drives NOW.  Solve anywhere, adopt the result into the vehicle's slot, ask the fleet.
+ *   layout       slot s owns 12 cap_xy doubles of the fleet's c_xy array and 6 cap_yaw doubles of its c_yaw array (fixed stride), one TrajDesc row (208 B) and
+ *                one TrajState row (232 B): 96 cap_xy + 48 cap_yaw + UPH_FLEET_SLOT_ROW_BYTES bytes of device memory per slot, all allocated at creation and
+ *                zeroed.  At the largest caps (128 / 256) that is 24 KiB of coefficients + 440 B per slot: 4096 slots take 96 MiB + 1.7 MiB.  Replacing a slot's
+ *                trajectory by one of any piece counts within the caps moves no other slot and cannot fail for lack of space.  uph_fleet_bytes is that figure
+ *                (pure host arithmetic; the query calls allocate their own small record / row buffers at their first use, as on any context).
+ *   empty slot   is to every call what an UPH_RET_UNSUPPORTED slot of a batch is: a query that names it is refused ("... names an empty slot"), the rollout
+ *                gives it no rows (uph_rollout_plan: offsets[s + 1] == offsets[s]).
+ *   per slot     the fleet keeps what queries and re-plans read of a batch: the TrajDesc / TrajState rows (piece counts, T_xy, T_yaw, ret_code, f, jerk_cost, ...),
+ *                the local frame when the map is one that solves in local frames (the same rule as any batch on that map), the end boundary of the problem in map
+ *                coordinates (uph_replan_upload with goals == NULL and uph_refine_upload work from a fleet), and a start time t0 on the common clock (host side).
+ *   adoption     uph_fleet_adopt copies trajectory src_traj[q] of src's resident batch into slot[q], with start t0[q] (NULL: 0), in ONE kernel launch
+ *                (uph_fleet_adopt_kernel: a workgroup per trajectory, 16-byte loads and stores over its 12 Nxy + 6 Nyaw coefficient doubles, one lane writes the
+ *                two rows; no coefficient crosses the host) and returns when the copy has completed.  Bit for bit: the coefficients, the piece counts, the whole
+ *                TrajState row, the frame, the end boundary.  src is unchanged, and later uploads into src do not touch the fleet.  src may itself be a fleet.
+ *                All or nothing: everything is validated before the first device write; a refusal leaves the fleet as it was.  UPH_ERR_INVALID: fleet is not a
+ *                fleet, src == fleet, different maps, an asynchronous solve pending on either, src holding no resident trajectory, an src_traj[q] out of range or
+ *                naming an unsupported / empty slot, a slot[q] out of range or named twice in one call (the same src_traj twice is fine), a non-finite t0[q], a
+ *                map whose geometry changed since src's frames or the fleet's were formed, n <= 0, a NULL pointer.  UPH_ERR_LIMIT, naming the query: Nxy > cap_xy
+ *                or Nyaw > cap_yaw.
+ *   the three classes of entry points that take a uph_ctx
+ *     work on a fleet, their numbers unchanged: uph_batch_count, uph_traj_states, uph_rollout_plan, uph_rollout_batch, uph_rollout_batch_dev, uph_check_limits,
+ *                uph_check_batch, uph_locate_batch, uph_within_batch, uph_extent_batch, uph_separation_batch and uph_footprint_separation_batch (the fleet as
+ *                side a, side b or both), uph_conflicts_batch, uph_footprint_conflicts_batch, uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch,
+ *                uph_footprint_delay_sweep_batch, uph_footprint_delays_batch, every uph_*_kernel_ms getter, uph_ctx_get_rho, uph_ctx_destroy, and
+ *                uph_replan_upload / uph_refine_upload with the fleet as src.  The t0 arguments of these calls are the caller's: uph_fleet_info returns the stored
+ *                starts to pass.
+ *     refused with UPH_ERR_INVALID ("... the context is a fleet"), the fleet untouched: everything that uploads into, solves, evaluates, reports on or downloads
+ *                a batch or sets its state -- uph_batch_upload, uph_optimize_batch, uph_optimize_batch_multi, uph_plan_upload into it, a fleet as dst of
+ *                uph_replan_upload / uph_refine_upload, uph_batch_solve, uph_batch_solve_async, uph_batch_wait, uph_batch_download, uph_eval_batch,
+ *                uph_penalty_batch, uph_init_scaling_batch, uph_microbench_batch, uph_report_batch, uph_batch_set_state, uph_batch_set_x, uph_batch_alm_passes,
+ *                uph_batch_set_lbfgs_state, uph_batch_lbfgs_resume, uph_batch_get_lbfgs_state, uph_plan_staged, uph_batch_origin, uph_batch_stats, and the solve
+ *                knobs uph_ctx_set_lanes, uph_ctx_set_xcd_locality, uph_ctx_set_wps, uph_ctx_set_sample_precision, uph_ctx_set_rho, uph_ctx_set_trial_abandon,
+ *                uph_ctx_set_trace.
+ *     fleet only: the uph_fleet_* calls below, refused with UPH_ERR_INVALID ("... is not a fleet") on any other context. */
+#define UPH_FLEET_SLOT_ROW_BYTES 440   /* the TrajDesc + TrajState rows of one slot */
+/* device memory of a fleet of that shape: slots * (96 cap_xy + 48 cap_yaw + UPH_FLEET_SLOT_ROW_BYTES).  UPH_ERR_INVALID: slots < 1, a cap outside
+ * [1, UPH_MAX_PIECE_*], bytes NULL. */
+int uph_fleet_bytes(int32_t slots, int32_t cap_xy, int32_t cap_yaw, int64_t* bytes);
+/* a fleet of `slots` empty slots on the map's device; p is kept for uph_check_limits / uph_check_batch.  uph_ctx_destroy frees it, uph_batch_count returns slots.
+ * UPH_ERR_INVALID: a NULL argument, slots < 1, a cap outside [1, UPH_MAX_PIECE_*]; UPH_ERR_NO_DEVICE: no HIP device visible (there is no host fall-back);
+ * then uph_ctx_create's own refusals. */
+int uph_fleet_create(uph_map* m, const uph_opt_params* p, int32_t slots, int32_t cap_xy, int32_t cap_yaw, uph_ctx** out);
+int uph_fleet_adopt(uph_ctx* fleet, uph_ctx* src, int32_t n, const int32_t* src_traj, const int32_t* slot, const double* t0 /* [n], NULL: 0 */);
+/* empties the slots (an empty one stays empty: idempotent); their coefficients stay where they lie until the next adoption overwrites them */
+int uph_fleet_release(uph_ctx* fleet, int32_t n, const int32_t* slot);
+/* every output may be NULL: the shape, occupied[s] = 1 / 0, t0[s] = the stored start (0 for an empty slot) */
+int uph_fleet_info(const uph_ctx* fleet, int32_t* slots, int32_t* cap_xy, int32_t* cap_yaw, int32_t* occupied /* [slots], may be NULL */, double* t0 /* [slots], may be NULL */);
+/* the trajectories of the named slots (any order, repeats allowed; every output may be NULL): counts, piece durations, ret_code, and the slot's whole coefficient
+ * regions, of which the first 12 n_xy / 6 n_yaw doubles are the trajectory -- in map coordinates, exactly the doubles uph_batch_download gives for the source --
+ * and the rest whatever earlier adoptions left (zeros at first).  An empty slot: counts 0, durations 0, ret_code UPH_RET_UNSUPPORTED, its regions as they lie. */
+int uph_fleet_get(uph_ctx* fleet, int32_t n, const int32_t* slot, int32_t* n_xy, int32_t* n_yaw, double* T_xy, double* T_yaw, int32_t* ret_code,
+                  double* c_xy /* [n][12*cap_xy] */, double* c_yaw /* [n][6*cap_yaw] */);
+/* milliseconds of uph_fleet_adopt_kernel in the last uph_fleet_adopt (events on the fleet's stream) */
+int uph_fleet_kernel_ms(const uph_ctx* fleet, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -366,6 +366,7 @@ public:
         const uph_opt_params p = optParams();
         if (uph_ctx_create(env->get(), &p, &ctx_) != UPH_OK) throw std::runtime_error(std::string("uph_ctx_create: ") + uph_last_error());
     }
+    uph_ctx* get() const { return ctx_; }                // the device context (nullptr before setEnvironment), as UnevenMapHandle::get() is the map's
 
     // int ALMTrajOpt::optimizeSE2Traj(initStateXY 2x3, endStateXY 2x3, innerPtsXY 2x(Nxy-1), initYaw 3, endYaw 3, innerPtsYaw, totalTime)
     template <class MatXY, class MatIn, class VecYaw, class VecIn>
@@ -905,7 +906,7 @@ public:
         return out;
     }
 
-private:
+protected:      // (TrajFleet below is the same object over a context made by uph_fleet_create)
     // what the calls on pairs of vehicles check first: every query array has traj_a's length m, neither side's last batch was split
     void pairCheck(const char* who, size_t m, std::initializer_list<size_t> sizes, const ALMTrajOpt* other) const {
         for (const size_t s : sizes) if (s != m) throw std::runtime_error(std::string(who) + ": the query arrays differ in number");
@@ -979,6 +980,72 @@ private:
     bool last_multi_ = false;
     std::vector<uph_ctx*> last_ctxs_;       // the contexts of the last optimizeSE2TrajBatch (getSE3PathBatch after a call with peers)
     int32_t last_B_ = 0;
+};
+
+// A fleet of resident trajectories (include/uneven_hip.h uph_fleet_*): `slots` slots on one map that the trajectories ALMTrajOpt objects solved are adopted
+// into on the device, one slot per vehicle.  It IS an ALMTrajOpt as far as the queries on resident trajectories go -- checkSE2TrajBatch, locateSE2TrajBatch,
+// withinSE2TrajBatch, extentSE2TrajBatch, separationSE2TrajBatch, conflictsSE2TrajBatch, their footprint and delay forms, getSE3PathBatch -- with `traj` meaning
+// slots, and is accepted as `other`; what uploads, solves or reports (optimizeSE2Traj, optimizeSE2TrajBatch, getMaxVxAxAyCurAttSig, ...) throws: the C-ABI
+// refuses it on a fleet.  The parameter members are those uph_check_limits reads.
+class TrajFleet : public ALMTrajOpt {
+public:
+    // slots empty slots of at most cap_xy / cap_yaw pieces each on env's device (uph_fleet_bytes of device memory)
+    void setEnvironment(UnevenMapHandle* env, int slots, int cap_xy = UPH_MAX_PIECE_XY, int cap_yaw = UPH_MAX_PIECE_YAW) {
+        env_ = env;
+        if (ctx_) { uph_ctx_destroy(ctx_); ctx_ = nullptr; }
+        const uph_opt_params p = optParams();
+        if (uph_fleet_create(env->get(), &p, slots, cap_xy, cap_yaw, &ctx_) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_create: ") + uph_last_error());
+        cap_xy_ = cap_xy; cap_yaw_ = cap_yaw;
+    }
+    int slots() const { return uph_batch_count(ctx_); }
+    // trajectory traj[q] of src's last batch (or of another fleet's slots) into slot[q], started at t0[q] on the common clock (empty: 0).  All or nothing.
+    void adoptSE2TrajBatch(const ALMTrajOpt& src, const std::vector<int>& traj, const std::vector<int>& slot, const std::vector<double>& t0 = std::vector<double>()) {
+        if (slot.size() != traj.size() || (!t0.empty() && t0.size() != traj.size())) throw std::runtime_error("adoptSE2TrajBatch: traj, slot and t0 differ in number");
+        if (src.get() == nullptr) throw std::runtime_error("adoptSE2TrajBatch: the source has no device context");
+        std::vector<int32_t> tr(traj.begin(), traj.end()), sl(slot.begin(), slot.end());
+        if (uph_fleet_adopt(ctx_, src.get(),(int32_t)tr.size(), tr.data(), sl.data(), t0.empty() ? nullptr : t0.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_fleet_adopt: ") + uph_last_error());
+    }
+    void releaseSlots(const std::vector<int>& slot) {
+        std::vector<int32_t> sl(slot.begin(), slot.end());
+        if (uph_fleet_release(ctx_, (int32_t)sl.size(), sl.data()) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_release: ") + uph_last_error());
+    }
+    std::vector<int32_t> occupied() const {
+        std::vector<int32_t> o((size_t)std::max(0, slots()), 0);
+        if (uph_fleet_info(ctx_, nullptr, nullptr, nullptr, o.data(), nullptr) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_info: ") + uph_last_error());
+        return o;
+    }
+    std::vector<double> startTimes() const {      // the starts stored at adoption: the t0 to pass to the fleet-wide queries
+        std::vector<double> t((size_t)std::max(0, slots()), 0.0);
+        if (uph_fleet_info(ctx_, nullptr, nullptr, nullptr, nullptr, t.data()) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_info: ") + uph_last_error());
+        return t;
+    }
+    // the trajectory of a slot as the reference's SE2Trajectory (what getTraj() gave for it on the object that solved it, bit for bit)
+    SE2Trajectory getTraj(int slot) const {
+        const int32_t s = slot;
+        int32_t nx = 0, ny = 0, ret = 0;
+        double tx = 0.0, ty = 0.0;
+        std::vector<double> cx((size_t)12 * cap_xy_), cy((size_t)6 * cap_yaw_);
+        if (uph_fleet_get(ctx_, 1, &s, &nx, &ny, &tx, &ty, &ret, cx.data(), cy.data()) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_get: ") + uph_last_error());
+        if (nx == 0) throw std::runtime_error("getTraj: the slot is empty");
+        return makeTraj(cx.data(), nx, tx, cy.data(), ny, ty);
+    }
+    // uph_traj_states' rows [n][10] of slot[q] at t[q]
+    std::vector<double> trajStates(const std::vector<int>& slot, const std::vector<double>& t) {
+        if (t.size() != slot.size()) throw std::runtime_error("trajStates: slot and t differ in number");
+        std::vector<int32_t> sl(slot.begin(), slot.end());
+        std::vector<double> out((size_t)10 * sl.size(), 0.0);
+        if (!sl.empty() && uph_traj_states(ctx_, (int32_t)sl.size(), sl.data(), t.data(), out.data()) != UPH_OK) throw std::runtime_error(std::string("uph_traj_states: ") + uph_last_error());
+        return out;
+    }
+    double adoptKernelMs() const {
+        double ms = 0.0;
+        if (uph_fleet_kernel_ms(ctx_, &ms) != UPH_OK) throw std::runtime_error(std::string("uph_fleet_kernel_ms: ") + uph_last_error());
+        return ms;
+    }
+
+private:
+    int cap_xy_ = 0, cap_yaw_ = 0;
 };
 
 

@@ -202,6 +202,13 @@ SYMBOLS = {
     "uph_footprint_delays_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.POINTER(_I32), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                              _I32, C.POINTER(_I32), DP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_delay_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_fleet_bytes": (C.c_int, [_I32, _I32, _I32, C.POINTER(_I64)]),
+    "uph_fleet_create": (C.c_int, [_VP, C.POINTER(OptParams), _I32, _I32, _I32, C.POINTER(_VP)]),
+    "uph_fleet_adopt": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP]),
+    "uph_fleet_release": (C.c_int, [_VP, _I32, C.POINTER(_I32)]),
+    "uph_fleet_info": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), DP]),
+    "uph_fleet_get": (C.c_int, [_VP, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), DP, DP, C.POINTER(_I32), DP, DP]),
+    "uph_fleet_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None
@@ -221,7 +228,9 @@ DELAY_MAX = 4096           # include/uneven_hip.h: delays of one table
 DELAY_MAX_WORK = 1 << 26   # include/uneven_hip.h: samples times delays of one query
 DELAY_ROWS = 1 << 20       # include/uneven_hip.h: sweep rows on the device at a time
 DELAY_TILE = 128           # include/uneven_hip.h UPH_DELAY_TILE: samples of a tile of the sweep kernel
-TRAJ_STATE_COLS = 10       # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
+FLEET_SLOT_ROW_BYTES = 440  # include/uneven_hip.h UPH_FLEET_SLOT_ROW_BYTES: the descriptor and state rows of one fleet slot
+UPH_RET_UNSUPPORTED = 4    # include/uneven_hip.h: ret_code of a slot without a trajectory (an empty fleet slot in uph_fleet_get)
+TRAJ_STATE_COLS = 10      # uph_traj_states / uph_refine_upload rows: replan's nine switch-state columns + the raw yaw
 
 
 class UnevenHipError(RuntimeError):

@@ -1337,3 +1337,158 @@ class ALMTrajOpt:
         out = np.zeros((self._B, self._trace_cap_up))
         _lib.check(self.L.uph_ctx_get_trace(self.h, _dp(out)), "uph_ctx_get_trace")
         return out
+
+
+# ---- a fleet of resident trajectories (uph_fleet_*) ---------------------------------------------------------------------------------------------------------
+def fleet_bytes(slots, cap_xy=_lib.UPH_MAX_PIECE_XY, cap_yaw=_lib.UPH_MAX_PIECE_YAW):
+    """device memory of a TrajFleet of that shape (uph_fleet_bytes; pure host arithmetic): slots * (96 cap_xy + 48 cap_yaw + FLEET_SLOT_ROW_BYTES)"""
+    b = C.c_int64(0)
+    _lib.check(_lib.load().uph_fleet_bytes(int(slots), int(cap_xy), int(cap_yaw), C.byref(b)), "uph_fleet_bytes")
+    return int(b.value)
+
+
+def _fleet_shape(slots, cap_xy, cap_yaw):
+    """TrajFleet's argument check, before any device call: the shape as integers, or a raise"""
+    try:
+        s, cx, cy = int(slots), int(cap_xy), int(cap_yaw)
+    except (TypeError, ValueError):
+        raise _lib.UnevenHipError("TrajFleet: slots, cap_xy and cap_yaw must be integers")
+    if s != slots or cx != cap_xy or cy != cap_yaw:
+        raise _lib.UnevenHipError("TrajFleet: slots, cap_xy and cap_yaw must be integers")
+    if s < 1 or not (1 <= cx <= _lib.UPH_MAX_PIECE_XY) or not (1 <= cy <= _lib.UPH_MAX_PIECE_YAW):
+        raise _lib.UnevenHipError("TrajFleet: slots >= 1, 1 <= cap_xy <= %d and 1 <= cap_yaw <= %d" % (_lib.UPH_MAX_PIECE_XY, _lib.UPH_MAX_PIECE_YAW))
+    return s, cx, cy
+
+
+def _adopt_arrays(src_traj, slot, t0):
+    """adopt()'s argument check, before any device call: (src_traj, slot, t0 or None) as the arrays the C call takes"""
+    tr = np.ascontiguousarray(src_traj, dtype=np.int32).reshape(-1)
+    sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+    n = tr.shape[0]
+    if n == 0 or sl.shape[0] != n:
+        raise _lib.UnevenHipError("adopt: src_traj and slot must be the same non-empty length")
+    if np.unique(sl).shape[0] != n:
+        raise _lib.UnevenHipError("adopt: a slot is named twice in one call")
+    ts = None
+    if t0 is not None:
+        ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (n,)))
+        if not np.isfinite(ts).all():
+            raise _lib.UnevenHipError("adopt: t0 must be finite")
+    return tr, sl, ts
+
+
+class TrajFleet(ALMTrajOpt):
+    """A long-lived set of resident trajectories on one map: `slots` slots of fixed stride (cap_xy / cap_yaw pieces at most) that solved trajectories of
+    ALMTrajOpt objects on the same map -- or of another TrajFleet -- are adopted into on the device (uph_fleet_adopt: one kernel launch, no coefficient
+    crosses the host).  It answers every query ALMTrajOpt answers on its resident batch -- traj_states, rollout, check, locate, within, extent, separation,
+    conflicts, footprint_*, delay* --, is accepted as `other=` and as `src` of refine / replan_goals, and takes no upload or solve: those methods raise.
+    In the fleet-wide wrappers (extent, conflicts, delays, their footprint and delay forms) t0 = None means the starts stored at adoption."""
+
+    def __init__(self, uneven_map, slots, cap_xy=_lib.UPH_MAX_PIECE_XY, cap_yaw=_lib.UPH_MAX_PIECE_YAW, params=None):
+        self.slots, self.cap_xy, self.cap_yaw = _fleet_shape(slots, cap_xy, cap_yaw)
+        super().__init__(uneven_map, params)
+
+    def setEnvironment(self, env):
+        self.uneven_map = env
+        if self.h:
+            self.L.uph_ctx_destroy(self.h)
+            self.h = None
+        p = _lib.OptParams(**{k: (int(getattr(self, k)) if k in _INT_FIELDS else float(getattr(self, k))) for k in self._pnames})
+        h = C.c_void_p()
+        _lib.check(self.L.uph_fleet_create(env.h, C.byref(p), self.slots, self.cap_xy, self.cap_yaw, C.byref(h)), "uph_fleet_create")
+        self.h = h
+
+    # ---- slots ---------------------------------------------------------------------------------------------------------------------------------------------
+    def adopt(self, src, src_traj, slot, t0=None):
+        """trajectory src_traj[q] of `src`'s resident batch (an ALMTrajOpt or TrajFleet on the same map) into slot[q], started at t0[q] on the common clock
+        (a scalar is broadcast; None: 0).  All or nothing: a refusal leaves the fleet as it was."""
+        tr, sl, ts = _adopt_arrays(src_traj, slot, t0)
+        if not isinstance(src, ALMTrajOpt) or src.h is None:
+            raise _lib.UnevenHipError("adopt: src must be an ALMTrajOpt or a TrajFleet with a device context")
+        _lib.check(self.L.uph_fleet_adopt(self.h, src.h, tr.shape[0], _ip(tr), _ip(sl), None if ts is None else _dp(ts)), "uph_fleet_adopt")
+
+    def release(self, slot):
+        """empty the slots (idempotent)"""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        if sl.shape[0] == 0:
+            raise _lib.UnevenHipError("release: no slot")
+        _lib.check(self.L.uph_fleet_release(self.h, sl.shape[0], _ip(sl)), "uph_fleet_release")
+
+    def _info(self):
+        occ, t0 = np.zeros(self.slots, dtype=np.int32), np.zeros(self.slots)
+        _lib.check(self.L.uph_fleet_info(self.h, None, None, None, _ip(occ), _dp(t0)), "uph_fleet_info")
+        return occ.astype(bool), t0
+
+    @property
+    def occupied(self):
+        """(slots,) bool: the slot holds a trajectory"""
+        return self._info()[0]
+
+    @property
+    def t0(self):
+        """(slots,) the start of each slot's trajectory on the common clock as stored at adoption (0 for an empty slot)"""
+        return self._info()[1]
+
+    def get(self, slot):
+        """uph_fleet_get: dict of n_xy, n_yaw, T_xy, T_yaw, ret (n,) and the slots' WHOLE coefficient regions c_xy (n, 12 cap_xy), c_yaw (n, 6 cap_yaw), map
+        coordinates; the first 12 n_xy / 6 n_yaw doubles of a row are the trajectory"""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        n = sl.shape[0]
+        if n == 0:
+            raise _lib.UnevenHipError("get: no slot")
+        out = dict(n_xy=np.zeros(n, dtype=np.int32), n_yaw=np.zeros(n, dtype=np.int32), T_xy=np.zeros(n), T_yaw=np.zeros(n), ret=np.zeros(n, dtype=np.int32),
+                   c_xy=np.zeros((n, 12 * self.cap_xy)), c_yaw=np.zeros((n, 6 * self.cap_yaw)))
+        _lib.check(self.L.uph_fleet_get(self.h, n, _ip(sl), _ip(out["n_xy"]), _ip(out["n_yaw"]), _dp(out["T_xy"]), _dp(out["T_yaw"]), _ip(out["ret"]),
+                                        _dp(out["c_xy"]), _dp(out["c_yaw"])), "uph_fleet_get")
+        return out
+
+    def getTraj(self, slot=0):
+        g = self.get([int(slot)])
+        if g["n_xy"][0] == 0:
+            raise _lib.UnevenHipError("getTraj: slot %d of the fleet is empty" % int(slot))
+        nx, ny = int(g["n_xy"][0]), int(g["n_yaw"][0])
+        return SE2Traj(g["c_xy"][0, :12 * nx].reshape(-1, 2).copy(), g["c_yaw"][0, :6 * ny].copy(), float(g["T_xy"][0]), float(g["T_yaw"][0]))
+
+    def adopt_kernel_ms(self):
+        """milliseconds of uph_fleet_adopt_kernel in the last adopt() (events on the fleet's stream)"""
+        return self._kernel_ms("uph_fleet_kernel_ms")
+
+    # ---- the fleet-wide wrappers: t0 = None means the stored starts ------------------------------------------------------------------------------------------
+    def _starts(self, traj, t0):
+        return self.t0[np.ascontiguousarray(traj, dtype=np.int32).reshape(-1)] if t0 is None else t0
+
+    def extent(self, traj, t_from, t_to, t0=None, dt=0.01):
+        return super().extent(traj, t_from, t_to, t0=self._starts(traj, t0), dt=dt)
+
+    def conflicts(self, traj, radius, t_from, t_to, t0=None, dt=0.05, cap=None):
+        return super().conflicts(traj, radius, t_from, t_to, t0=self._starts(traj, t0), dt=dt, cap=cap)
+
+    def footprint_conflicts(self, traj, shape, margin, t_from, t_to, t0=None, dt=0.05, cap=None):
+        return super().footprint_conflicts(traj, shape, margin, t_from, t_to, t0=self._starts(traj, t0), dt=dt, cap=cap)
+
+    def delay_extent(self, traj, t_from, t_to, delay0, delay_step, D, t0=None, dt=0.01):
+        return super().delay_extent(traj, t_from, t_to, delay0, delay_step, D, t0=self._starts(traj, t0), dt=dt)
+
+    def delays(self, traj, radius, t_from, t_to, delay0, delay_step, D, t0=None, n_delays=None, dt=0.05):
+        return super().delays(traj, radius, t_from, t_to, delay0, delay_step, D, t0=self._starts(traj, t0), n_delays=n_delays, dt=dt)
+
+    def footprint_delays(self, traj, shape, margin, t_from, t_to, delay0, delay_step, D, t0=None, n_delays=None, dt=0.05):
+        return super().footprint_delays(traj, shape, margin, t_from, t_to, delay0, delay_step, D, t0=self._starts(traj, t0), n_delays=n_delays, dt=dt)
+
+
+def _fleet_refuses(name):
+    def method(self, *args, **kwargs):
+        raise _lib.UnevenHipError("%s: a TrajFleet takes no upload, solve, evaluation, report, download or batch state (adopt() fills its slots)" % name)
+    method.__name__ = name
+    method.__doc__ = "refused on a TrajFleet"
+    return method
+
+
+# the solve side of ALMTrajOpt: uploads, solves, evaluations, reports, downloads and the batch-state hooks
+FLEET_REFUSED = ("set_lanes", "set_xcd_locality", "set_wps", "set_sample_precision", "set_rho", "set_trial_abandon", "upload", "solve", "solve_async", "wait", "stats",
+                 "cycles", "origin", "download", "optimize_batch", "prepare_boundary", "optimize_boundary", "plan_goals_upload", "plan_goals", "replan_goals_upload",
+                 "replan_goals", "refine_upload", "refine", "plan_staged", "optimizeSE2Traj", "getTrajJerkCost", "getMaxVxAxAyCurAttSig", "x0_packed", "eval_batch",
+                 "penalty_batch", "init_scaling_batch", "set_state", "set_x", "alm_passes", "set_lbfgs_state", "lbfgs_resume", "get_lbfgs_state", "set_trace", "get_trace")
+for _name in FLEET_REFUSED:
+    setattr(TrajFleet, _name, _fleet_refuses(_name))
+del _name

@@ -933,6 +933,7 @@ int checkTrajQueries(const uph_ctx* c, int32_t n, const int32_t* traj, const dou
         const int32_t b = traj[q];
         if (b < 0 || b >= c->B) { setError(std::string(who) + ": query " + std::to_string(q) + " names no trajectory of the resident batch"); return UPH_ERR_INVALID; }
         if (!c->rejected.empty() && c->rejected[(size_t)b]) {
+            if (c->is_fleet) { setError(std::string(who) + ": query " + std::to_string(q) + " names an empty slot of the fleet (no trajectory)"); return UPH_ERR_INVALID; }
             setError(std::string(who) + ": query " + std::to_string(q) + " names an UPH_RET_UNSUPPORTED slot (no trajectory)"); return UPH_ERR_INVALID;
         }
         if (!std::isfinite(t[q])) { setError(std::string(who) + ": query " + std::to_string(q) + " has a non-finite time"); return UPH_ERR_INVALID; }

@@ -1064,7 +1064,7 @@ void uph_ctx_destroy(uph_ctx* c) {
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
                       &c->d_pen_gxy, &c->d_pen_gyaw, &c->d_pen_out, &c->d_roll_tt, &c->d_roll_traj, &c->d_roll_stage,
                       &c->d_plan_head, &c->d_plan_xy, &c->d_plan_yaw, &c->d_plan_goal, &c->d_plan_rec, &c->d_sw_q, &c->d_sw_out, &c->d_refine_rec, &c->d_win_q,
-                      &c->d_win_out, &c->d_delay};
+                      &c->d_win_out, &c->d_delay, &c->d_adopt_rec};
     for (DevBuf* b : bufs) b->release();
     HostBuf* hbufs[] = {&c->h_x, &c->h_cxy, &c->h_cyaw, &c->h_dual, &c->h_res, &c->h_scl};
     for (HostBuf* b : hbufs) b->release();
@@ -1081,23 +1081,25 @@ void uph_ctx_destroy(uph_ctx* c) {
 // lanes cooperating on one trajectory: 64, 256, or 0 = pick from the batch size (takes effect at the next upload)
 int uph_ctx_set_lanes(uph_ctx* c, int32_t lanes) {
     if (!c || (lanes != 0 && lanes != 64 && lanes != 128 && lanes != 256 && lanes != 512)) return UPH_ERR_INVALID;
+    NOT_ON_FLEET(c, "uph_ctx_set_lanes");
     c->lanes_forced = lanes;
     return UPH_OK;
 }
-int uph_ctx_set_xcd_locality(uph_ctx* c, int32_t group) { if (!c || group < 0) return UPH_ERR_INVALID; c->xcd_group = group; return UPH_OK; }
-int uph_ctx_set_wps(uph_ctx* c, int32_t wps) { if (!c || wps < 0 || wps > 2) return UPH_ERR_INVALID; c->wps_forced = wps; return UPH_OK; }
+int uph_ctx_set_xcd_locality(uph_ctx* c, int32_t group) { if (!c || group < 0) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_xcd_locality"); c->xcd_group = group; return UPH_OK; }
+int uph_ctx_set_wps(uph_ctx* c, int32_t wps) { if (!c || wps < 0 || wps > 2) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_wps"); c->wps_forced = wps; return UPH_OK; }
 int uph_ctx_set_sample_precision(uph_ctx* c, int32_t bits) {
     if (!c || (bits != 32 && bits != 64)) { setError("uph_ctx_set_sample_precision: 32 or 64"); return UPH_ERR_INVALID; }
+    NOT_ON_FLEET(c, "uph_ctx_set_sample_precision");
     c->sample_f32 = bits == 32;
     return UPH_OK;
 }
-int uph_ctx_set_rho(uph_ctx* c, double rho) { if (!c) return UPH_ERR_INVALID; c->rho = rho; return UPH_OK; }
+int uph_ctx_set_rho(uph_ctx* c, double rho) { if (!c) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_rho"); c->rho = rho; return UPH_OK; }
 // line-search trials whose Armijo rejection is certain stop early (Solver::eval; default on); takes effect at the next launch (the parameter block is uploaded per launch)
-int uph_ctx_set_trial_abandon(uph_ctx* c, int32_t on) { if (!c || (on != 0 && on != 1)) return UPH_ERR_INVALID; c->P.no_trial_abandon = on ? 0 : 1; return UPH_OK; }
+int uph_ctx_set_trial_abandon(uph_ctx* c, int32_t on) { if (!c || (on != 0 && on != 1)) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_trial_abandon"); c->P.no_trial_abandon = on ? 0 : 1; return UPH_OK; }
 int uph_ctx_get_rho(uph_ctx* c, double* rho) { if (!c || !rho) return UPH_ERR_INVALID; *rho = c->rho; return UPH_OK; }
 
 // diagnostic: keep the first `cap` entries of every trajectory's cost trace (0 = off); read back with uph_ctx_get_trace
-int uph_ctx_set_trace(uph_ctx* c, int32_t cap) { if (!c || cap < 0) return UPH_ERR_INVALID; c->trace_cap = cap; return UPH_OK; }
+int uph_ctx_set_trace(uph_ctx* c, int32_t cap) { if (!c || cap < 0) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_trace"); c->trace_cap = cap; return UPH_OK; }
 int uph_ctx_get_trace(uph_ctx* c, double* out /* B x cap */) {
     if (c && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (!c || !out || c->trace_cap_up <= 0 || c->B <= 0) return UPH_ERR_INVALID;
@@ -1336,6 +1338,7 @@ static int commitBatch(uph_ctx* c, int32_t B) {
 
 int uph_batch_upload(uph_ctx* c, int32_t B, const uph_problem* probs) {
     if (!c || B <= 0 || !probs) { setError("uph_batch_upload: bad arguments"); return UPH_ERR_INVALID; }
+    NOT_ON_FLEET(c, "uph_batch_upload");
     if (c->pending) { setError("uph_batch_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     std::vector<ProblemHead> heads(B);
@@ -1487,6 +1490,7 @@ int uph_plan_upload(uph_kino* k, uph_ctx* c, const uph_manager_params* mp, int32
     if (!k || !c || !mp || B <= 0 || !starts || !goals || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
         setError("uph_plan_upload: bad arguments"); return UPH_ERR_INVALID;
     }
+    NOT_ON_FLEET(c, "uph_plan_upload");
     if (uphKinoMap(k) != c->map) { setError("uph_plan_upload: the search context and the optimiser context are bound to different maps"); return UPH_ERR_INVALID; }
     if (c->pending) { setError("uph_plan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     return planUpload(k, c, mp, B, starts, goals, path_cap, nullptr, nullptr, "uph_plan_upload", status, traj_of, n_inner_xy, n_inner_yaw);
@@ -1500,6 +1504,7 @@ int uph_replan_upload(uph_kino* k, uph_ctx* src, uph_ctx* dst, const uph_manager
     if (!k || !src || !dst || !mp || B <= 0 || !src_traj || !t_switch || path_cap < 0 || !status || !traj_of || !n_inner_xy || !n_inner_yaw || !managerParamsOk(mp)) {
         setError("uph_replan_upload: bad arguments"); return UPH_ERR_INVALID;
     }
+    NOT_ON_FLEET(dst, "uph_replan_upload: dst");
     if (uphKinoMap(k) != src->map || dst->map != src->map) { setError("uph_replan_upload: the search context and the optimiser contexts are bound to different maps"); return UPH_ERR_INVALID; }
     if (src->pending || dst->pending) { setError("uph_replan_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     int r = checkTrajQueries(src, B, src_traj, t_switch, "uph_replan_upload");
@@ -1537,6 +1542,7 @@ int uph_refine_upload(uph_ctx* src, uph_ctx* dst, int32_t B, const int32_t* src_
     if (!src || !dst || B <= 0 || !src_traj || !t_switch || !status || !traj_of || !n_inner_xy || !n_inner_yaw) {
         setError("uph_refine_upload: bad arguments"); return UPH_ERR_INVALID;
     }
+    NOT_ON_FLEET(dst, "uph_refine_upload: dst");
     if (dst->map != src->map) { setError("uph_refine_upload: the source and destination contexts are bound to different maps"); return UPH_ERR_INVALID; }
     if (src->pending || dst->pending) { setError("uph_refine_upload: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     int r = checkTrajQueries(src, B, src_traj, t_switch, "uph_refine_upload");
@@ -1642,6 +1648,7 @@ int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy
     if (!c || cap_xy < 0 || cap_yaw < 0 || !init_xy || !end_xy || !init_yaw || !end_yaw || !inner_xy || !inner_yaw || !n_inner_xy || !n_inner_yaw || !total_time) {
         setError("uph_plan_staged: bad arguments"); return UPH_ERR_INVALID;
     }
+    NOT_ON_FLEET(c, "uph_plan_staged");
     if (c->B <= 0 || !c->planned) { setError("uph_plan_staged: the resident batch did not come from uph_plan_upload"); return UPH_ERR_INVALID; }
     if (c->pending) { setError("uph_plan_staged: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
@@ -1666,6 +1673,7 @@ int uph_plan_staged(uph_ctx* c, int32_t cap_xy, int32_t cap_yaw, double* init_xy
 // enqueue one solve of the uploaded batch on the context's stream and return: reset + initScaling kernel, then the ALM kernel.  Two
 // contexts driven this way overlap on the GPU -- the second batch's workgroups fill the CUs the first one's tail leaves idle.
 int uph_batch_solve_async(uph_ctx* c) {
+    NOT_ON_FLEET(c, "uph_batch_solve_async");
     if (!c || c->B <= 0) { setError("uph_batch_solve_async: no batch uploaded"); return UPH_ERR_INVALID; }
     if (c->pending) { setError("uph_batch_solve_async: the previous asynchronous solve has not been waited for"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
@@ -1681,6 +1689,7 @@ int uph_batch_solve_async(uph_ctx* c) {
 }
 
 int uph_batch_wait(uph_ctx* c) {
+    NOT_ON_FLEET(c, "uph_batch_wait");
     if (!c || !c->pending) { setError("uph_batch_wait: no asynchronous solve in flight"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     c->pending = false;
@@ -1709,6 +1718,7 @@ int uph_batch_wait(uph_ctx* c) {
 }
 
 int uph_batch_solve(uph_ctx* c) {
+    NOT_ON_FLEET(c, "uph_batch_solve");
     const int r = uph_batch_solve_async(c);
     return r != UPH_OK ? r : uph_batch_wait(c);
 }
@@ -1716,6 +1726,7 @@ int uph_batch_solve(uph_ctx* c) {
 int uph_batch_count(const uph_ctx* c) { return c ? c->B : UPH_ERR_INVALID; }
 // for a batch loaded by uph_optimize_batch_multi: idx[k] = the caller's index of problem k of this context's share (identity otherwise)
 int uph_batch_origin(const uph_ctx* c, int32_t* idx) {
+    NOT_ON_FLEET(c, "uph_batch_origin");
     if (!c || !idx || c->B <= 0) { setError("uph_batch_origin: no batch uploaded"); return UPH_ERR_INVALID; }
     for (int b = 0; b < c->B; b++) idx[b] = c->origin.empty() ? b : c->origin[b];
     return UPH_OK;
@@ -1723,6 +1734,7 @@ int uph_batch_origin(const uph_ctx* c, int32_t* idx) {
 
 int uph_batch_stats(uph_ctx* c, double* kernel_ms, int64_t* evals, int64_t* sample_evals, int64_t* lbfgs_iters, int64_t* hist_bytes) {
     if (!c) return UPH_ERR_INVALID;
+    NOT_ON_FLEET(c, "uph_batch_stats");
     if (kernel_ms) *kernel_ms = c->last_ms;
     if (evals) *evals = c->last_evals;
     if (sample_evals) *sample_evals = c->last_sample_evals;
@@ -1749,6 +1761,7 @@ int uph_batch_cycles(uph_ctx* c, long long* out) {
 
 int uph_batch_download(uph_ctx* c, uph_result* results) {
     if (!c || c->B <= 0 || !results) { setError("uph_batch_download: bad arguments"); return UPH_ERR_INVALID; }
+    NOT_ON_FLEET(c, "uph_batch_download");
     if (c->pending) { setError("uph_batch_download: an asynchronous solve is in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     int r = refreshStates(c);
@@ -1821,6 +1834,7 @@ int uph_batch_download(uph_ctx* c, uph_result* results) {
 }
 
 int uph_optimize_batch(uph_ctx* c, int32_t B, const uph_problem* probs, uph_result* results) {
+    NOT_ON_FLEET(c, "uph_optimize_batch");
     int r = uph_batch_upload(c, B, probs);
     if (r != UPH_OK) return r;
     r = uph_batch_solve(c);
@@ -1865,6 +1879,7 @@ int uph_optimize_batch_multi(uph_ctx* const* ctxs, int32_t n_gpus, int32_t B, co
     if (!ctxs || n_gpus < 1 || B <= 0 || !probs || !results) { setError("uph_optimize_batch_multi: bad arguments"); return UPH_ERR_INVALID; }
     for (int g = 0; g < n_gpus; g++) {
         if (!ctxs[g]) { setError("uph_optimize_batch_multi: null context"); return UPH_ERR_INVALID; }
+        NOT_ON_FLEET(ctxs[g], "uph_optimize_batch_multi");
         for (int h = 0; h < g; h++) if (ctxs[h] == ctxs[g]) { setError("uph_optimize_batch_multi: the same context twice"); return UPH_ERR_INVALID; }
         if (ctxs[g]->pending) { setError("uph_optimize_batch_multi: context " + std::to_string(g) + " has an asynchronous solve in flight (uph_batch_wait first)"); return UPH_ERR_INVALID; }
     }
@@ -1914,6 +1929,7 @@ int uph_optimize_batch_multi(uph_ctx* const* ctxs, int32_t n_gpus, int32_t B, co
 }
 
 int uph_batch_set_state(uph_ctx* c, const double* lambda, const double* mu, const double* scale_cx, const double* scale_fx, const double* rho) {
+    NOT_ON_FLEET(c, "uph_batch_set_state");
     if (c && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (c && c->n_rejected) { setError("packed-array hooks need a batch without unsupported problems (uph_result.ret_code == UPH_RET_UNSUPPORTED)"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0) { setError("uph_batch_set_state: no batch uploaded"); return UPH_ERR_INVALID; }
@@ -1945,6 +1961,7 @@ int uph_batch_set_state(uph_ctx* c, const double* lambda, const double* mu, cons
 }
 
 int uph_eval_batch(uph_ctx* c, const double* x_packed, double* f, double* grad_packed, int32_t repeat) {
+    NOT_ON_FLEET(c, "uph_eval_batch");
     if (c && c->n_rejected) { setError("packed-array hooks need a batch without unsupported problems (uph_result.ret_code == UPH_RET_UNSUPPORTED)"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0 || repeat < 1) { setError("uph_eval_batch: bad arguments"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
@@ -1966,6 +1983,7 @@ int uph_eval_batch(uph_ctx* c, const double* x_packed, double* f, double* grad_p
 // block row-major), gdCyaw [sum 6 Nyaw], gdT [B][2] = (sum_i gdTxy(i), sum_i gdTyaw(i)) out; store_residuals != 0: hx / gx are written by every call,
 // as the reference's function writes them (read them with uph_batch_download).  `repeat` calls inside one launch (measurement); any output may be NULL.
 int uph_penalty_batch(uph_ctx* c, int32_t repeat, int32_t store_residuals, double* cost, double* gdcxy_packed, double* gdcyaw_packed, double* gdT2) {
+    NOT_ON_FLEET(c, "uph_penalty_batch");
     if (c && c->n_rejected) { setError("packed-array hooks need a batch without unsupported problems (uph_result.ret_code == UPH_RET_UNSUPPORTED)"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0 || repeat < 1 || repeat > (1 << 20)) { setError("uph_penalty_batch: bad arguments"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
@@ -1991,12 +2009,14 @@ int uph_penalty_batch(uph_ctx* c, int32_t repeat, int32_t store_residuals, doubl
 // diagnostic: cost of the workgroup primitives (see Solver::microbench); read the result with uph_batch_cycles
 int uph_microbench_batch(uph_ctx* c, int32_t reps) {
     if (!c || c->B <= 0 || reps < 1) return UPH_ERR_INVALID;
+    NOT_ON_FLEET(c, "uph_microbench_batch");
     int r = launchSolver(c, 5, reps);
     if (r != UPH_OK) return r;
     return refreshStates(c);
 }
 
 int uph_init_scaling_batch(uph_ctx* c) {
+    NOT_ON_FLEET(c, "uph_init_scaling_batch");
     if (!c || c->B <= 0) { setError("uph_init_scaling_batch: no batch uploaded"); return UPH_ERR_INVALID; }
     int r = launchSolver(c, 4, 1);
     if (r != UPH_OK) return r;
@@ -2004,6 +2024,7 @@ int uph_init_scaling_batch(uph_ctx* c) {
 }
 
 int uph_report_batch(uph_ctx* c, double* out7) {
+    NOT_ON_FLEET(c, "uph_report_batch");
     if (!c || c->B <= 0 || !out7) { setError("uph_report_batch: bad arguments"); return UPH_ERR_INVALID; }
     int r = launchSolver(c, 3, 1);
     if (r != UPH_OK) return r;
@@ -2027,6 +2048,7 @@ static void collectSolveStats(uph_ctx* c) {
     }
 }
 int uph_batch_set_x(uph_ctx* c, const double* x_packed) {
+    NOT_ON_FLEET(c, "uph_batch_set_x");
     if (c && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (c && c->n_rejected) { setError("packed-array hooks need a batch without unsupported problems (uph_result.ret_code == UPH_RET_UNSUPPORTED)"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0 || !x_packed) { setError("uph_batch_set_x: bad arguments"); return UPH_ERR_INVALID; }
@@ -2036,6 +2058,7 @@ int uph_batch_set_x(uph_ctx* c, const double* x_packed) {
 // the ALM loop of optimizeSE2Traj (alm_traj_opt.cpp:234-271) from the RESIDENT x, duals, scales and rho -- no reset, no initScaling --
 // for at most max_passes passes (0 = until it ends); a solve stopped by the cap reports ret_code 3
 int uph_batch_alm_passes(uph_ctx* c, int32_t max_passes) {
+    NOT_ON_FLEET(c, "uph_batch_alm_passes");
     if (!c || c->B <= 0 || max_passes < 0) { setError("uph_batch_alm_passes: bad arguments"); return UPH_ERR_INVALID; }
     int r = launchSolver(c, 2, max_passes);
     if (r != UPH_OK) return r;
@@ -2048,6 +2071,7 @@ int uph_batch_alm_passes(uph_ctx* c, int32_t max_passes) {
 // as the reference holds it -- lm_s / lm_y column j of trajectory b at hist[off_b + j*n] with off_b = mem * sum_{b' < b} n_b', lm_ys
 // [B][mem] --; scal5 [B][5] = step, fx, k, end, bound.  x is the resident x (uph_batch_set_x).
 int uph_batch_set_lbfgs_state(uph_ctx* c, const double* g, const double* d, const double* pf, const double* lm_s, const double* lm_y, const double* lm_ys, const double* scal5) {
+    NOT_ON_FLEET(c, "uph_batch_set_lbfgs_state");
     if (c && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (c && c->n_rejected) { setError("packed-array hooks need a batch without unsupported problems (uph_result.ret_code == UPH_RET_UNSUPPORTED)"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0 || !g || !d || !pf || !lm_s || !lm_y || !lm_ys || !scal5) { setError("uph_batch_set_lbfgs_state: bad arguments"); return UPH_ERR_INVALID; }
@@ -2079,6 +2103,7 @@ int uph_batch_set_lbfgs_state(uph_ctx* c, const double* g, const double* d, cons
 // continue every trajectory's L-BFGS loop from the state set above for at most `budget` iterations (budget < 0: until it ends);
 // finish_pass != 0: when the loop ends by itself, the ALM's reaction follows (accepted code -> updateDualVars + judgeConvergence)
 int uph_batch_lbfgs_resume(uph_ctx* c, int32_t budget, int32_t finish_pass) {
+    NOT_ON_FLEET(c, "uph_batch_lbfgs_resume");
     if (!c || c->B <= 0 || !c->d_rs.p) { setError("uph_batch_lbfgs_resume: no state set"); return UPH_ERR_INVALID; }
     const int bud = budget < 0 ? (1 << 28) : budget;
     int r = launchSolver(c, 7, 2 * bud + (finish_pass ? 1 : 0));
@@ -2091,6 +2116,7 @@ int uph_batch_lbfgs_resume(uph_ctx* c, int32_t budget, int32_t finish_pass) {
 // the state after uph_batch_lbfgs_resume, same layout; scal8 [B][8] = step, fx, k, end, bound, L-BFGS code (999 = budget ran out),
 // accepted, converged.  x / hx / gx / duals / rho through uph_batch_download.
 int uph_batch_get_lbfgs_state(uph_ctx* c, double* g, double* d, double* pf, double* lm_s, double* lm_y, double* lm_ys, double* scal8) {
+    NOT_ON_FLEET(c, "uph_batch_get_lbfgs_state");
     if (c && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (!c || c->B <= 0 || !c->d_rs.p) { setError("uph_batch_get_lbfgs_state: no state set"); return UPH_ERR_INVALID; }
     HIPCHK(hipSetDevice(c->device));

@@ -124,7 +124,24 @@ struct uph_ctx {
     double last_ms = 0.0, last_prepare_ms = 0.0;
     int64_t last_evals = 0, last_sample_evals = 0, last_iters = 0, last_hist_bytes = 0;
     int64_t last_abandon[5] = {0, 0, 0, 0, 0};   // line-search trial counters of the last solve (uph_batch_abandon_stats): rejected, guarded, abandoned, chunks skipped, adjoints skipped
+    // fleet (uph_fleet_create, fleet.hip): the resident batch is B slots of fixed stride -- slot s owns 12 cap_xy doubles of d_cxy and 6 cap_yaw of d_cyaw --, filled by
+    // uph_fleet_adopt from other contexts; rejected[s] != 0 marks an EMPTY slot.  Never uploaded into, never solved.
+    bool is_fleet = false;
+    int fleet_cap_xy = 0, fleet_cap_yaw = 0;
+    std::vector<double> fleet_t0;          // [B] each slot's start on the common clock (0 for an empty slot)
+    DevBuf d_adopt_rec;                    // uph_fleet_adopt: the launch's records
+    double last_adopt_ms = 0.0;            // uph_fleet_adopt_kernel of the last uph_fleet_adopt (events on the fleet's stream)
 };
+// the refusal of an entry point that uploads into, solves, evaluates, reports on, downloads or sets the state of a batch, on a fleet (`who`: the call's own name)
+inline bool refusedOnFleet(const uph_ctx* c, const char* who) {
+    if (!c || !c->is_fleet) return false;
+    setError(std::string(who) + ": the context is a fleet (its slots are filled by uph_fleet_adopt; it takes no upload, solve, evaluation, report, download or batch state)");
+    return true;
+}
+#define NOT_ON_FLEET(c, who)                                  \
+    do {                                                      \
+        if (refusedOnFleet((c), (who))) return UPH_ERR_INVALID; \
+    } while (0)
 
 #define HIPCHK(call)                                                                               \
     do {                                                                                           \
