@@ -57,6 +57,8 @@
  *   uph_conflicts_batch     <- the pairs of a fleet on one map that come closer than their radii allow: extents, a host broad phase, separation
  *   uph_footprint_separation_batch / uph_footprint_conflicts_batch  <- the same two with the vehicles as oriented rectangles (front, rear, half width)
  *                              turned by the trajectory's yaw instead of discs
+ *   uph_footprint_check_batch  <- UnevenMap::isOccupancy / isOccupancyXY (uneven_map.h:471-488) at every column the vehicle's rectangle covers, not only the one
+ *                              under the trajectory's point, over time windows of chosen resident trajectories
  *   uph_delays_batch        <- the smallest start delay that clears each vehicle of a fleet against all vehicles ahead of it in priority order
  *   uph_footprint_delay_sweep_batch / uph_footprint_delays_batch  <- the delay sweep and the schedule with the vehicles as oriented rectangles
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
@@ -748,6 +750,61 @@ int uph_footprint_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, co
 /* milliseconds of the kernels of the last uph_footprint_separation_batch or uph_footprint_conflicts_batch of c (events on the context's stream) */
 int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
+/* ---- footprint check: the vehicle's rectangle swept over the map's occupancy layers as they are now.  uph_check_batch reads the occupancy at ONE place per
+ * sample, the column under the trajectory's point; this query reads every column the body covers and answers "does the body touch an occupied column, when
+ * first, and where".
+ *   samples        query q names trajectory traj[q] and the window [t_from[q], t_to[q]] (t_to == NULL: to the end): exactly uph_check_batch's samples (same
+ *                  time table, the end row at t = total when with_end is set; uph_check_window).
+ *   pose           per sample the STATE row at t: X, Y in map coordinates (uph_traj_states' columns 0, 1), psi the raw yaw (column 9), yawn the normalised yaw
+ *                  (column 6).  c = cos psi, s = sin psi by sincosFast, as the footprint metric above takes them; u = (c, s), v = (-s, c).
+ *   rectangle      hl = (front + rear) / 2, o = (front - rear) / 2, w = half_width, formed on the host as above.  The margin m >= 0 inflates both half extents:
+ *                  hl' = hl + m, w' = w + m, one rounded add each, on the host.  Centre C = (X + o c, Y + o s).
+ *   covered        column (ix, iy) is COVERED by the pose iff it is the column of the point itself -- ix = floor((X - origin_x) * xy_inv), iy the same in y,
+ *                  uph_check_batch's own statements -- or its centre P = (origin_x + (ix + 0.5) res, origin_y + (iy + 0.5) res) has
+ *                      |(P - C) . u| <= hl'   and   |(P - C) . v| <= w'
+ *                  with every product and every sum rounded on its own, in the order written (a dot product p . q is p_x q_x + p_y q_y; v's first component
+ *                  is the negated s).  The point's column makes an all-zero shape exactly uph_check_batch's occupancy read.  The test is on CELL CENTRES: a
+ *                  caller who wants "any part of the cell" adds res * sqrt(2) / 2 to the margin.
+ *   kinds          of a covered column, with iw = floor((yawn - origin_yaw) * yaw_inv), uph_check_batch's yaw bin:
+ *                      UPH_FOOT_OUTSIDE  ix, iy or iw outside the grid, or the row ix - x_off outside the rows a tile map holds (uph_check_batch's -1);
+ *                      UPH_FOOT_OCC_XY   otherwise, the byte of occ_r2 (uph_map_get_cells) at (ix, iy) is not 0;
+ *                      UPH_FOOT_OCC_YAW  otherwise, the byte of occ at (ix, iy, iw) is not 0.
+ *   hits           a column is a HIT when its kinds intersect `layers`, a non-empty subset of UPH_FOOT_ALL; a sample is a hit when any covered column is.
+ *   degenerate     a pose with X, Y, psi or yawn not finite, or with |ix|, |iy| or |iw| of its point at or above 2^30 (an index that would not fit 31 bits once
+ *                  the box's extent and pad are added), covers nothing and is of kind UPH_FOOT_OUTSIDE: a hit iff layers holds that bit, with no hit column.
+ *                  No float-to-int conversion of such a value is executed.
+ *   enumeration    the kernel tests the columns of the box floor((C_x -+ ex - origin_x) * xy_inv) -+ 1 by floor((C_y -+ ey - origin_y) * xy_inv) -+ 1 with
+ *                  ex = hl'|c| + w'|s|, ey = hl'|s| + w'|c|: the rectangle's hull and one column of pad -- 0.05 m on the reference's grids against roundings
+ *                  of about 1e-14 m.  The rule is the membership test; the box is the implementation.  A query whose box can exceed 2^14 columns is refused
+ *                  with UPH_ERR_LIMIT; the bound is uph_footprint_check_columns': side = floor(2 hypot(hl', w') (1 + 2^-40) / res) + 4, cols = side * side.
+ * Outputs per query, any of them may be NULL:
+ *   first_t, last_t [n]   t of the first and of the last hit sample (NaN: none)
+ *   first_mask [n]        OR of the kinds within `layers` over the hit columns of the first hit sample (0: none)
+ *   first_cell [n][2]     the lexicographically smallest (ix, iy) among the hit columns of the first hit sample: where the obstacle is.  (-1, -1): none (no
+ *                         hit sample, or a degenerate first one)
+ *   counts [n][5]         samples, hit samples, then samples with a covered column of kind XY, of kind YAW, of kind OUTSIDE -- these three regardless of layers
+ *   cells [n][2]          covered columns and hit columns, summed over the window's samples
+ * An empty window gives NaN, NaN, 0, (-1, -1) and zeros.  Not bit for bit against numpy where a centre lies within a rounding of the rectangle's edge -- a sine
+ * is involved -- but deterministic: every output is an integer sum or a selection under a total order, so no answer depends on the launch width, on how samples
+ * and columns are split over lanes or on the query's place in the batch.  Reads the occupancy layers on the map's own grid and no terrain cell.  Blocking, on the
+ * context's stream.  Refusals, all before anything is written: uph_check_batch's; a shape component or a margin that is negative or not finite; layers outside
+ * 1 .. UPH_FOOT_ALL; UPH_ERR_LIMIT as above and as uph_rollout_plan. */
+#define UPH_FOOT_OCC_XY 1
+#define UPH_FOOT_OCC_YAW 2
+#define UPH_FOOT_OUTSIDE 4
+#define UPH_FOOT_ALL 7
+/* host only, no device needed: cols[q] = the bound on the columns of one sample's box for shape[q] inflated by margin[q] on a map of mp's resolution (the rule
+ * above; saturates at 2^62).  UPH_ERR_INVALID: a NULL argument (margin == NULL: 0), n < 0, a resolution that is not positive and finite, a shape component or
+ * margin that is negative or not finite, a reach that is not finite. */
+int uph_footprint_check_columns(const uph_map_params* mp, int32_t n, const double* shape /* [n][3]: front, rear, half_width */, const double* margin /* [n], NULL: 0 */,
+                                int64_t* cols /* [n] */);
+int uph_footprint_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to /* NULL: to the end */, double dt, int32_t with_end,
+                              const double* shape /* [n][3] */, const double* margin /* [n], NULL: 0 */, int32_t layers, double* first_t /* [n], NaN: none */,
+                              double* last_t /* [n] */, int32_t* first_mask /* [n] */, int32_t* first_cell /* [n][2] */, int32_t* counts /* [n][5] */,
+                              int64_t* cells /* [n][2] */);
+/* milliseconds of the kernel(s) of the last uph_footprint_check_batch of c (events on the context's stream) */
+int uph_footprint_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
 /* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
  * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /
  * uph_extent_batch returns for the shifted start, bit for bit.
@@ -860,7 +917,7 @@ int uph_delay_kernel_ms(const uph_ctx* c, double* kernel_ms);
  *     work on a fleet, their numbers unchanged: uph_batch_count, uph_traj_states, uph_rollout_plan, uph_rollout_batch, uph_rollout_batch_dev, uph_check_limits,
  *                uph_check_batch, uph_locate_batch, uph_within_batch, uph_extent_batch, uph_separation_batch and uph_footprint_separation_batch (the fleet as
  *                side a, side b or both), uph_conflicts_batch, uph_footprint_conflicts_batch, uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch,
- *                uph_footprint_delay_sweep_batch, uph_footprint_delays_batch, every uph_*_kernel_ms getter, uph_ctx_get_rho, uph_ctx_destroy, and
+ *                uph_footprint_delay_sweep_batch, uph_footprint_delays_batch, uph_footprint_check_batch, every uph_*_kernel_ms getter, uph_ctx_get_rho, uph_ctx_destroy, and
  *                uph_replan_upload / uph_refine_upload with the fleet as src.  The t0 arguments of these calls are the caller's: uph_fleet_info returns the stored
  *                starts to pass.
  *     refused with UPH_ERR_INVALID ("... the context is a fleet"), the fleet untouched: everything that uploads into, solves, evaluates, reports on or downloads

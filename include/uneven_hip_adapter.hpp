@@ -18,6 +18,7 @@
 //   replanSE2TrajBatch             the same from states on the last batch's trajectories: re-planning a vehicle in motion (uph_replan_upload)
 //   refineSE2TrajBatch             the rest of the last batch's trajectories re-optimised from states at switch times, no search (uph_refine_upload)
 //   checkSE2TrajBatch              time windows of the last batch's trajectories held against limits on the map as it is now (uph_check_batch)
+//   footprintCheckSE2TrajBatch     the same windows with the vehicle's rectangle swept over the map's occupancy: first / last hit and where (uph_footprint_check_batch)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -733,6 +734,37 @@ public:
             return uph_footprint_conflicts_batch(ctx_, n, tr.data(), t0.data(), shape[0].data(), margin.data(), t_from, t_to, dt, room, pairs, rows, below, &out.n_conflicts,
                                                  &out.n_candidates);
         });
+        return out;
+    }
+    // the map changed: does the BODY of a vehicle touch an occupied column, when first, and where (uph_footprint_check_batch).  checkSE2TrajBatch reads the
+    // occupancy under the trajectory's point; this reads every column whose centre lies in the rectangle shape[q] = (front, rear, half_width) inflated by
+    // margin[q] (empty: 0) and turned by the raw yaw, over the samples of trajectory traj[q] with t in [t_from[q], t_to[q]] (t_to empty: to the end).  layers:
+    // the kinds (UPH_FOOT_OCC_XY, UPH_FOOT_OCC_YAW, UPH_FOOT_OUTSIDE) that make a column a hit.  The recipe after a map update: withinSE2TrajBatch with the
+    // changed rect grown by uph_footprint_radii's radius, this on the trajectories that enter it, refineSE2TrajBatch / replanSE2TrajBatch from before first_t.
+    struct TrajFootprintCheck {
+        std::vector<double> first_t, last_t;            // [n] t of the first / last hit sample (NaN: none)
+        std::vector<int32_t> first_mask;                // [n] the kinds within layers at the first hit sample
+        std::vector<std::array<int32_t, 2>> first_cell; // [n] the smallest (ix, iy) among its hit columns ((-1, -1): none)
+        std::vector<int32_t> counts;                    // [n][5] samples, hit samples, samples covering a column of kind XY / YAW / OUTSIDE
+        std::vector<int64_t> cells;                     // [n][2] covered columns, hit columns, summed over the samples
+        bool hits(size_t q) const { return counts[5 * q + 1] > 0; }
+    };
+    TrajFootprintCheck footprintCheckSE2TrajBatch(const std::vector<int>& traj, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                                  const std::vector<std::array<double, 3>>& shape, const std::vector<double>& margin = std::vector<double>(),
+                                                  int layers = UPH_FOOT_ALL, double dt = 0.01, bool with_end = true) {
+        if (t_from.size() != traj.size() || (!t_to.empty() && t_to.size() != traj.size()) || shape.size() != traj.size() || (!margin.empty() && margin.size() != traj.size()))
+            throw std::runtime_error("footprintCheckSE2TrajBatch: traj, t_from, t_to, shape and margin differ in number");
+        if (last_multi_) throw std::runtime_error("footprintCheckSE2TrajBatch: the last batch was split over several devices");
+        const int32_t n = (int32_t)traj.size();
+        TrajFootprintCheck out;
+        if (n == 0) return out;
+        std::vector<int32_t> tr(traj.begin(), traj.end());
+        out.first_t.assign((size_t)n, 0.0); out.last_t.assign((size_t)n, 0.0); out.first_mask.assign((size_t)n, 0);
+        out.first_cell.assign((size_t)n, std::array<int32_t, 2>{-1, -1}); out.counts.assign((size_t)5 * n, 0); out.cells.assign((size_t)2 * n, 0);
+        if (uph_footprint_check_batch(ctx_, n, tr.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, shape[0].data(),
+                                      margin.empty() ? nullptr : margin.data(), layers, out.first_t.data(), out.last_t.data(), out.first_mask.data(),
+                                      out.first_cell[0].data(), out.counts.data(), out.cells.data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_footprint_check_batch: ") + uph_last_error());
         return out;
     }
     // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are

@@ -190,6 +190,10 @@ SYMBOLS = {
     "uph_footprint_conflicts_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, DP, C.c_double, C.c_double, C.c_double, _I64, C.POINTER(_I32), DP,
                                                 C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64)]),
     "uph_footprint_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_footprint_check_columns": (C.c_int, [C.POINTER(MapParams), _I32, DP, DP, C.POINTER(_I64)]),
+    "uph_footprint_check_batch": (C.c_int, [_VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, _I32, DP, DP, _I32, DP, DP, C.POINTER(_I32), C.POINTER(_I32),
+                                            C.POINTER(_I32), C.POINTER(_I64)]),
+    "uph_footprint_check_kernel_ms": (C.c_int, [_VP, DP]),
     "uph_delay_times": (C.c_int, [C.c_double, C.c_double, _I32, DP]),
     "uph_delay_levels": (C.c_int, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32)]),
     "uph_delay_sweep_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, DP, DP, DP, C.c_double, DP, C.c_double, C.c_double, _I32, DP, DP,
@@ -223,6 +227,8 @@ UPH_ERR_INVALID, UPH_ERR_LIMIT = -1, -4
 UPH_KINO_OK = 0
 UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
 UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
+UPH_FOOT_OCC_XY, UPH_FOOT_OCC_YAW, UPH_FOOT_OUTSIDE, UPH_FOOT_ALL = 1, 2, 4, 7   # include/uneven_hip.h: kinds of a column the footprint check covers
+FOOT_CHECK_MAX_COLUMNS = 1 << 14     # include/uneven_hip.h: columns of one sample's box in uph_footprint_check_batch
 SEPARATION_MAX_SAMPLES = 1 << 22     # include/uneven_hip.h: samples of one query on the common clock
 DELAY_MAX = 4096           # include/uneven_hip.h: delays of one table
 DELAY_MAX_WORK = 1 << 26   # include/uneven_hip.h: samples times delays of one query

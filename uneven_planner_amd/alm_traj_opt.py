@@ -492,6 +492,120 @@ def footprint_rows(tau, xy_a, yaw_a, shape_a, xy_b, yaw_b, shape_b, margin):
                 counts=np.array([tau.shape[0], below.size, np.count_nonzero(over)], dtype=np.int32))
 
 
+# uph_footprint_check_columns / uph_footprint_check_batch (include/uneven_hip.h): numpy mirrors written from the rule.  Every product and every sum is rounded on
+# its own, in the order the header gives; against the device only the sine and the cosine differ.
+FOOT_OCC_XY, FOOT_OCC_YAW, FOOT_OUTSIDE, FOOT_ALL = _lib.UPH_FOOT_OCC_XY, _lib.UPH_FOOT_OCC_YAW, _lib.UPH_FOOT_OUTSIDE, _lib.UPH_FOOT_ALL
+FOOT_INDEX_MAX = 2.0 ** 30
+
+
+def footprint_grid(uneven_map):
+    """the geometry footprint_cover / footprint_check_rows need of an UnevenMap: origin (3,), res, yaw_res, nx, ny, nyaw, and the rows held (x_off, nx_hold)"""
+    nx, ny, nyaw = (int(v) for v in uneven_map.voxel_num)
+    x_off = 0 if uneven_map.tile is None else uneven_map.tile[0]
+    return dict(origin=np.asarray(uneven_map.map_origin, dtype=np.float64).copy(), res=float(uneven_map.xy_resolution), yaw_res=float(uneven_map.yaw_resolution),
+                nx=nx, ny=ny, nyaw=nyaw, x_off=x_off, nx_hold=int(uneven_map.rows_held))
+
+
+def _inflated(shape, margin, who):
+    f, r, h = _shapes(shape, 1, who)[0]
+    m = np.float64(margin)
+    if not (np.isfinite(m) and m >= 0.0):
+        raise _lib.UnevenHipError(who + ": the margin is negative or not finite")
+    return 0.5 * (f + r) + m, 0.5 * (f - r), h + m
+
+
+def footprint_check_columns(shape, margin, res):
+    """Host mirror of uph_footprint_check_columns for one shape: the bound on the columns of one sample's enumeration box, side * side with
+    side = floor(2 hypot(hl', w') (1 + 2^-40) / res) + 4 (saturating at 2^62)."""
+    hl, _, w = _inflated(shape, margin, "footprint_check_columns")
+    reach = np.hypot(hl, w) * (1.0 + 2.0 ** -40)
+    if not np.isfinite(reach):
+        raise _lib.UnevenHipError("footprint_check_columns: the reach is not finite")
+    side = np.floor(2.0 * reach / np.float64(res)) + 4.0
+    return int(side) ** 2 if side < 2.0 ** 31 else 1 << 62
+
+
+def footprint_cover(pose, yawn, shape, margin, grid, pad=1):
+    """Host mirror of the footprint check's cover rule at n poses: pose (n, 3) = X, Y, psi (traj_states' columns 0, 1 and 9), yawn (n,) the normalised yaw
+    (column 6), shape = (front, rear, half_width) inflated by margin, grid = footprint_grid(map).  For every pose the S columns of one common box around the
+    rectangle's hull with `pad` columns of pad (at least the kernel's one): ix, iy (n, S), their gap g = max(|(P - C) . u| - hl', |(P - C) . v| - w') (n, S)
+    -- a column is covered iff g <= 0 or it is the point's --, point (n, 2) the point's own column, iw (n,) the yaw bin and ok (n,): False for a degenerate
+    pose (a value not finite or an index at or above 2^30), which covers nothing; its rows hold zeros and g = +inf."""
+    p = np.asarray(pose, dtype=np.float64).reshape(-1, 3)
+    n = p.shape[0]
+    wn = np.ascontiguousarray(np.broadcast_to(np.asarray(yawn, dtype=np.float64), (n,)))
+    hl, o, w = _inflated(shape, margin, "footprint_cover")
+    org, res = np.asarray(grid["origin"], dtype=np.float64), np.float64(grid["res"])
+    inv, yinv = 1.0 / res, 1.0 / np.float64(grid["yaw_res"])
+    with np.errstate(over="ignore", invalid="ignore"):
+        X, Y, psi = p[:, 0], p[:, 1], p[:, 2]
+        fp = np.stack([np.floor((X - org[0]) * inv), np.floor((Y - org[1]) * inv), np.floor((wn - org[2]) * yinv)], axis=1)
+        ok = np.isfinite(p).all(axis=1) & np.isfinite(wn) & (np.abs(fp) < FOOT_INDEX_MAX).all(axis=1)       # (a NaN index compares false)
+        X, Y, psi, fp = np.where(ok, X, 0.0), np.where(ok, Y, 0.0), np.where(ok, psi, 0.0), np.where(ok[:, None], fp, 0.0)
+        c, s = np.cos(psi), np.sin(psi)
+        Cx, Cy = X + o * c, Y + o * s
+        ex, ey = hl * np.abs(c) + w * np.abs(s), hl * np.abs(s) + w * np.abs(c)
+        x0, x1 = np.floor(((Cx - ex) - org[0]) * inv) - pad, np.floor(((Cx + ex) - org[0]) * inv) + pad
+        y0, y1 = np.floor(((Cy - ey) - org[1]) * inv) - pad, np.floor(((Cy + ey) - org[1]) * inv) + pad
+    point, iw = fp[:, :2].astype(np.int64), fp[:, 2].astype(np.int64)
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    sx, sy = (int((x1.astype(np.int64) - x0).max()) + 1, int((y1.astype(np.int64) - y0).max()) + 1) if n else (0, 0)
+    ix = np.repeat(x0[:, None] + np.arange(sx)[None, :], sy, axis=1)                  # (n, sx * sy), iy fastest
+    iy = np.tile(y0[:, None] + np.arange(sy)[None, :], (1, sx))
+    Px, Py = org[0] + (ix + 0.5) * res, org[1] + (iy + 0.5) * res
+    dx, dy = Px - Cx[:, None], Py - Cy[:, None]
+    c, s = c[:, None], s[:, None]
+    g = np.maximum(np.abs(dx * c + dy * s) - hl, np.abs(dx * (-s) + dy * c) - w)
+    g = np.where(ok[:, None], g, np.inf)
+    return dict(ix=np.where(ok[:, None], ix, 0), iy=np.where(ok[:, None], iy, 0), g=g, point=point, iw=np.where(ok, iw, -1), ok=ok)
+
+
+def _foot_reduce(t, ok, layers, kinds, cov, ix, iy):
+    """one version (surely / possibly) of a footprint check query's outputs from its samples' covered columns cov (n, S) and their kinds (n, S)"""
+    n = t.shape[0]
+    hitcol = cov & ((kinds & layers) != 0)
+    has = lambda bit: (cov & ((kinds & bit) != 0)).any(axis=1) if n else np.zeros(0, dtype=bool)
+    kind = [has(FOOT_OCC_XY), has(FOOT_OCC_YAW), has(FOOT_OUTSIDE) | ~ok]
+    m = (kind[0] * FOOT_OCC_XY + kind[1] * FOOT_OCC_YAW + kind[2] * FOOT_OUTSIDE) & layers
+    hit = m != 0
+    at = np.nonzero(hit)[0]
+    out = dict(first_t=np.nan, last_t=np.nan, first_mask=0, first_cell=np.array([-1, -1], dtype=np.int32), hit=hit, hitcol=hitcol,
+               counts=np.array([n, at.size] + [int(np.count_nonzero(k)) for k in kind], dtype=np.int32),
+               cells=np.array([np.count_nonzero(cov), np.count_nonzero(hitcol)], dtype=np.int64))
+    if at.size:
+        j = at[0]
+        out["first_t"], out["last_t"], out["first_mask"] = t[j], t[at[-1]], int(m[j])
+        k = np.nonzero(hitcol[j])[0]
+        if k.size:
+            out["first_cell"] = np.array(min(zip(ix[j, k].tolist(), iy[j, k].tolist())), dtype=np.int32)
+    return out
+
+
+def footprint_check_rows(t, poses, yawn, shape, margin, grid, occ, occ_r2, layers=FOOT_ALL, tol=0.0, pad=1):
+    """Host mirror of one uph_footprint_check_batch query, written from the rule: t (n,) the window's sample times, poses (n, 3) = X, Y, psi and yawn (n,) the
+    states there (traj_states' columns 0, 1, 9 and 6), the shape inflated by margin, grid = footprint_grid(map), occ (nx_hold * ny * nyaw) and occ_r2
+    (nx_hold * ny) the map's occupancy bytes, layers a non-empty subset of FOOT_ALL.  A column whose centre has the gap g of footprint_cover is SURELY covered
+    when g < -tol (tol = 0: when g <= 0, the rule itself) and POSSIBLY covered when g <= tol; the point's own column is both.  Returns dict(sure=..., poss=...):
+    each the query's outputs first_t, last_t, first_mask, first_cell (2,), counts (5,), cells (2,) under that reading, with hit (n,) the samples that are hits
+    and hitcol (n, S) the hit columns; and cover = footprint_cover's dict (ix, iy index hitcol's columns)."""
+    layers = int(layers)
+    if not 1 <= layers <= FOOT_ALL:
+        raise _lib.UnevenHipError("footprint_check_rows: layers must be a non-empty subset of FOOT_ALL")
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    cv = footprint_cover(np.asarray(poses, dtype=np.float64).reshape(-1, 3), yawn, shape, margin, grid, pad=pad)
+    ix, iy, g, ok, iw = cv["ix"], cv["iy"], cv["g"], cv["ok"], cv["iw"]
+    nx, ny, nyaw, x_off, nx_hold = (int(grid[k]) for k in ("nx", "ny", "nyaw", "x_off", "nx_hold"))
+    occ, occ_r2 = np.asarray(occ).reshape(nx_hold, ny, nyaw), np.asarray(occ_r2).reshape(nx_hold, ny)
+    ixh = ix - x_off
+    inside = (ix >= 0) & (iy >= 0) & (ix <= nx - 1) & (iy <= ny - 1) & (ixh >= 0) & (ixh <= nx_hold - 1) & ((iw >= 0) & (iw <= nyaw - 1))[:, None]
+    a, b, w = np.where(inside, ixh, 0), np.where(inside, iy, 0), np.broadcast_to(np.clip(iw, 0, nyaw - 1)[:, None], ix.shape)
+    kinds = np.where(inside, (occ_r2[a, b] != 0) * FOOT_OCC_XY + (occ[a, b, w] != 0) * FOOT_OCC_YAW, FOOT_OUTSIDE)
+    is_point = (ix == cv["point"][:, :1]) & (iy == cv["point"][:, 1:]) & ok[:, None]
+    sure = is_point | ((g < -tol) if tol > 0.0 else (g <= 0.0))
+    poss = is_point | (g <= tol)
+    return dict(sure=_foot_reduce(t, ok, layers, kinds, sure, ix, iy), poss=_foot_reduce(t, ok, layers, kinds, poss, ix, iy), cover=cv)
+
+
 # uph_delay_times / uph_delay_levels / uph_delays_batch (include/uneven_hip.h): numpy mirrors written from the rule
 def delay_times(delay0, delay_step, D):
     """Host mirror of the table of start delays: delta_j = delay0 + j * delay_step (the product rounded, then the sum) for 0 <= j < D.  Raises for
@@ -1158,6 +1272,29 @@ class ALMTrajOpt:
     def footprint_kernel_ms(self):
         """milliseconds of the kernels of the last footprint_separation() or footprint_conflicts() (events on the context's stream)"""
         return self._kernel_ms("uph_footprint_kernel_ms")
+
+    # ---- the vehicle's rectangle swept over the map's occupancy as it is now (uph_footprint_check_batch) -----------------------------------------------
+    def footprint_check(self, traj, shape, margin=0.0, t_from=0.0, t_to=None, dt=0.01, with_end=True, layers=FOOT_ALL):
+        """check()'s occupancy read with the vehicle as a rectangle: over the rollout(dt, with_end) samples of resident trajectory traj[q] with t in [t_from[q],
+        t_to[q]] (scalars and one shape of (3,) are broadcast; t_to = None: to the end), every column of the map whose centre lies in the rectangle shape[q] =
+        (front, rear, half_width) inflated by margin[q] and turned by the raw yaw, and the column under the point itself, is looked up in the occupancy layers.
+        A column's kinds are FOOT_OCC_XY, FOOT_OCC_YAW or FOOT_OUTSIDE; it is a hit when they intersect `layers`.  Returns a dict of arrays over the queries:
+        first_t / last_t (t of the first / last sample with a hit column, NaN: none), first_mask (the kinds within layers at the first), first_cell (n, 2: the
+        lexicographically smallest hit column of the first hit sample, (-1, -1): none), counts (n, 5: samples, hit samples, samples that cover a column of
+        kind XY / YAW / OUTSIDE) and cells (n, 2: covered and hit columns summed over the samples).  See footprint_check_rows for the rule."""
+        tr, n, tf, tt, _ = self._windows(traj, t_from, t_to, None, 0, "footprint_check")
+        sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shape, dtype=np.float64), (n, 3)))
+        mg = np.ascontiguousarray(np.broadcast_to(np.asarray(margin, dtype=np.float64), (n,)))
+        out = dict(first_t=np.full(n, np.nan), last_t=np.full(n, np.nan), first_mask=np.zeros(n, dtype=np.int32), first_cell=np.full((n, 2), -1, dtype=np.int32),
+                   counts=np.zeros((n, 5), dtype=np.int32), cells=np.zeros((n, 2), dtype=np.int64))
+        _lib.check(self.L.uph_footprint_check_batch(self.h, n, _ip(tr), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)), _dp(sh), _dp(mg),
+                                                    int(layers), _dp(out["first_t"]), _dp(out["last_t"]), _ip(out["first_mask"]), _ip(out["first_cell"]),
+                                                    _ip(out["counts"]), out["cells"].ctypes.data_as(C.POINTER(C.c_int64))), "uph_footprint_check_batch")
+        return out
+
+    def footprint_check_kernel_ms(self):
+        """milliseconds of the kernel(s) of the last footprint_check() (events on the context's stream)"""
+        return self._kernel_ms("uph_footprint_check_kernel_ms")
 
     # ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch) ----------------------------------------------------------------
     def delay_sweep(self, traj_a, traj_b, t_from, t_to, radius, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):

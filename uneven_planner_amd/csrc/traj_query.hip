@@ -1,12 +1,14 @@
 // libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
-// separation / extent / conflicts, the same with oriented rectangles, and the start delays on a common clock (include/uneven_hip.h uph_rollout_*, uph_check_*,
-// uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*, uph_footprint_*, uph_delay*, uph_footprint_delay*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// separation / extent / conflicts, the same with oriented rectangles, the start delays on a common clock, and the footprint swept over the map's occupancy
+// (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*,
+// uph_footprint_*, uph_delay*, uph_footprint_delay*, uph_footprint_check_*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
 // window of the rollout's time table and the end point; ClockQuery: samples t_from + k dt of a clock several vehicles share, for each of the D delays of the
 // launch's table (D = 1 and a null table without one) --, lanes striding over the samples (over the delays, in the delay kernels), their accumulators (Span,
-// Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  The queries on a pair of vehicles are one family: one
+// Box, a (value, sample) selection) reduced by wave_dev.hpp's workgroupReduce, thread 0 writes the row.  The footprint check (FootCheckQuery, a WinQuery with a
+// shape) is the one window query whose lanes share a sample: a wave walks its samples and strides over each one's box of map columns.  The queries on a pair of vehicles are one family: one
 // record (SepQuery; FootQuery adds the two shapes), one argument block (PairArgs), one body (pairBody) over a metric -- discs or oriented rectangles.  Host:
 // trajFrame (the frame of a trajectory, for every record and argument block), checkTrajQueries (the refusals every query passes), formWindowQueries / pairQueries /
 // fleetCandidates / extentCall (a call shape's refusals in order, its records, its uploads), clockRun (the clock records in launch order), pairRun (the pair
@@ -906,6 +908,177 @@ __global__ __launch_bounds__(NT) void uph_delay_extent_kernel(ExtArgs a) {
     extentRow<NT>(a, eq, body.box);
 }
 
+// ---- footprint check (uph_footprint_check_batch): the window query of the check with the vehicle as an oriented rectangle swept over the map's occupancy layers.
+// The rule is include/uneven_hip.h's: a sample's pose covers the column of its point and every column whose centre lies in the rectangle inflated by the margin;
+// a covered column has kinds (XY, YAW, OUTSIDE), a sample is a hit when a kind of a covered column is in `layers`.  One workgroup per query, two stages per chunk of
+// NT samples: lane l evaluates the pose of its sample (one trajectory evaluation, one sincosFast, the enumeration box), then each wave walks its up to 64 samples one
+// after another -- the sample's values are read from the owning lane (readlane: wave-uniform by construction), the 64 lanes stride over the box's columns along iy,
+// so that the byte loads of occ_r2 are consecutive, three ballots give the sample's kinds, and only the first hit sample of a wave pays a wave reduction for its
+// smallest hit cell.  What a sample contributes lands in the owning lane's accumulators; the column sums stay in the lanes that counted them.  Everything is an integer
+// sum, an OR decided by a ballot or a selection under a total order: neither the launch width nor the lane split can show.  Reads occ / occ_r2 on the map's own grid
+// and no terrain cell: local frames enter through mapX / mapY only.
+struct FootCheckQuery : WinQuery {
+    double hl, o, w;            // footShape's, hl and w inflated by the margin on the host (one rounded add each)
+    int32_t layers, pad2;       // UPH_FOOT_* kinds that make a column a hit
+};
+struct FootCheckOut {           // one row per query
+    double first_t, last_t;     // NaN: no hit sample
+    unsigned long long cells[2];        // covered columns, hit columns, summed over the window
+    int32_t first_mask, first_cell[2], counts[5];       // counts: samples, hit samples, samples with a covered column of kind XY / YAW / OUTSIDE
+};
+struct FootCheckGrid {          // what the kernel reads of the map's own grid descriptor
+    int nx, ny, nyaw, x_off, nx_hold;
+    double origin[3], xy_res, xy_inv, yaw_inv;
+};
+struct FootCheckArgs {
+    ResidentDev r;
+    const FootCheckQuery* qs;
+    FootCheckOut* out;
+    const char* occ;            // [nx_hold][ny][nyaw]
+    const char* occ_r2;         // [nx_hold][ny]
+    FootCheckGrid g;
+    int framed, q0;             // as LocArgs
+};
+constexpr double FOOT_INDEX_MAX = 1073741824.0;         // 2^30: a point's column index at or beyond it does not "fit 31 bits" with the box's pad and extent
+constexpr unsigned long long FOOT_NO_CELL = ~0ull;
+// (ix, iy) as one key whose unsigned order is the lexicographic order of the signed pair
+__device__ __forceinline__ unsigned long long footCellKey(int ix, int iy) {
+    return ((unsigned long long)((unsigned)ix ^ 0x80000000u) << 32) | ((unsigned)iy ^ 0x80000000u);
+}
+// the rectangle's centre and the half extents of its axis-aligned hull, every product and sum rounded on its own
+__device__ __forceinline__ void footHull(double X, double Y, double c, double s, double hl, double o, double w, double& Cx, double& Cy, double& ex, double& ey) {
+#pragma clang fp contract(off)
+    Cx = X + o * c; Cy = Y + o * s;
+    ex = hl * fabs(c) + w * fabs(s);
+    ey = hl * fabs(s) + w * fabs(c);
+}
+// floor((C -+ e - origin) * inv) -+ 1, as doubles (no conversion here: the caller converts what it has found to fit)
+__device__ __forceinline__ void footBoxAxis(double C, double e, double origin, double inv, double& lo, double& hi) {
+#pragma clang fp contract(off)
+    lo = floor(((C - e) - origin) * inv) - 1.0;
+    hi = floor(((C + e) - origin) * inv) + 1.0;
+}
+// whether the centre of column (ix, iy) lies in the rectangle: the membership test of the rule, every product and sum rounded on its own
+__device__ __forceinline__ bool footCentreIn(const FootCheckGrid& g, int ix, int iy, double Cx, double Cy, double c, double s, double hl, double w) {
+#pragma clang fp contract(off)
+    const double Px = g.origin[0] + ((double)ix + 0.5) * g.xy_res, Py = g.origin[1] + ((double)iy + 0.5) * g.xy_res;
+    const double dx = Px - Cx, dy = Py - Cy;
+    return fabs(dx * c + dy * s) <= hl && fabs(dx * (-s) + dy * c) <= w;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_footprint_check_kernel(FootCheckArgs a) {
+    const FootCheckQuery fq = a.qs[a.q0 + blockIdx.x];
+    const TrajView tr = trajView(a.r, fq.b, a.framed != 0, fq.shift);
+    const FootCheckGrid& g = a.g;
+    const int n = winCount(fq);
+    const int lane = (int)threadIdx.x & 63, wave0 = uni((int)threadIdx.x & ~63);
+    const int layers = fq.layers;
+    Span hit;
+    unsigned long long first = CHECK_NONE, cell = FOOT_NO_CELL, ncov = 0, nhit = 0;
+    int nxy = 0, nyw = 0, nout = 0;
+    bool had = false;           // this wave has met a hit sample (wave-uniform): a later one cannot be the window's first
+    for (int c0 = 0; c0 < n; c0 += NT) {
+        // stage 1: the pose of this lane's sample and what the walk needs of it
+        const int j = c0 + (int)threadIdx.x;
+        double Cx = 0.0, Cy = 0.0, cs = 1.0, sn = 0.0;
+        int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1, px = 0, py = 0, iw = -1, ok = 0;
+        if (j < n) {
+            TrajSample s;
+            double X, Y;
+            locSample(tr, winTime(fq, a.r.tt, j), s, X, Y);
+            double psi = s.yaw, yawn = s.yawn;
+            asm volatile("" : "+v"(psi), "+v"(yawn));
+            sincosFast(psi, sn, cs);
+            double ex, ey, fx0, fx1, fy0, fy1;
+            footHull(X, Y, cs, sn, fq.hl, fq.o, fq.w, Cx, Cy, ex, ey);
+            footBoxAxis(Cx, ex, g.origin[0], g.xy_inv, fx0, fx1);
+            footBoxAxis(Cy, ey, g.origin[1], g.xy_inv, fy0, fy1);
+            // check's own floor statements on X, Y and the normalised yaw, kept in double until they are known to fit
+            const double fpx = floor((X - g.origin[0]) * g.xy_inv), fpy = floor((Y - g.origin[1]) * g.xy_inv), fpw = floor((yawn - g.origin[2]) * g.yaw_inv);
+            const bool fits = footFinite(X, Y, psi) && fabs(fpx) < FOOT_INDEX_MAX && fabs(fpy) < FOOT_INDEX_MAX && fabs(fpw) < FOOT_INDEX_MAX;     // (a NaN yawn: false)
+            ok = fits ? 1 : 0;
+            // a pose that does not fit converts zeros: its box is empty.  One that fits has its box within 2^14 columns of its point (the host's limit): the corners fit too
+            px = (int)(fits ? fpx : 0.0); py = (int)(fits ? fpy : 0.0); iw = (int)(fits ? fpw : -1.0);
+            bx0 = (int)(fits ? fx0 : 0.0); bx1 = (int)(fits ? fx1 : -1.0); by0 = (int)(fits ? fy0 : 0.0); by1 = (int)(fits ? fy1 : -1.0);
+        }
+        // stage 2: the wave walks its samples c0 + wave0 + k
+        const int left = n - (c0 + wave0), mine = left < 0 ? 0 : (left < 64 ? left : 64);
+        for (int k = 0; k < mine; k++) {
+            const double uCx = readLane(Cx, k), uCy = readLane(Cy, k), uc = readLane(cs, k), us = readLane(sn, k);
+            const int ux0 = readLane(bx0, k), ux1 = readLane(bx1, k), uy0 = readLane(by0, k), uy1 = readLane(by1, k);
+            const int upx = readLane(px, k), upy = readLane(py, k), uiw = readLane(iw, k), uok = readLane(ok, k);
+            const int nby = uy1 - uy0 + 1, total = (ux1 - ux0 + 1) * nby;      // (an empty box: ux1 - ux0 + 1 = 0)
+            const bool w_in = uiw >= 0 && uiw <= g.nyaw - 1;
+            int kinds = 0, cov = 0, hits = 0;
+            unsigned long long low = FOOT_NO_CELL;
+            // column i of the box: (ux0 + i / nby, uy0 + i % nby), stepped by 64 without a division per column
+            int rx = nby > 0 ? lane / nby : 0, ry = nby > 0 ? lane - rx * nby : 0;
+            const int sx = nby > 0 ? 64 / nby : 0, sy = nby > 0 ? 64 - sx * nby : 0;
+            for (int i = lane; i < total; i += 64) {
+                const int ix = ux0 + rx, iy = uy0 + ry;
+                if ((ix == upx && iy == upy) || footCentreIn(g, ix, iy, uCx, uCy, uc, us, fq.hl, fq.w)) {
+                    const int ixh = ix - g.x_off;
+                    const bool in = ix >= 0 && iy >= 0 && w_in && ix <= g.nx - 1 && iy <= g.ny - 1 && ixh >= 0 && ixh <= g.nx_hold - 1;       // check's `in`
+                    int kind = UPH_FOOT_OUTSIDE;
+                    if (in) {
+                        const size_t col = (size_t)ixh * g.ny + iy;
+                        kind = (a.occ_r2[col] != 0 ? UPH_FOOT_OCC_XY : 0) | (a.occ[col * g.nyaw + uiw] != 0 ? UPH_FOOT_OCC_YAW : 0);
+                    }
+                    kinds |= kind; cov++;
+                    if (kind & layers) {
+                        hits++;
+                        const unsigned long long key = footCellKey(ix, iy);
+                        low = key < low ? key : low;
+                    }
+                }
+                rx += sx; ry += sy;
+                if (ry >= nby) { ry -= nby; rx++; }
+            }
+            ncov += (unsigned long long)cov; nhit += (unsigned long long)hits;
+            // the sample's kinds: an OR over the wave, bit by bit (a pose that does not fit covers nothing and is of kind OUTSIDE)
+            const int m = (__ballot(kinds & UPH_FOOT_OCC_XY) ? UPH_FOOT_OCC_XY : 0) | (__ballot(kinds & UPH_FOOT_OCC_YAW) ? UPH_FOOT_OCC_YAW : 0) |
+                          (__ballot(kinds & UPH_FOOT_OUTSIDE) || !uok ? UPH_FOOT_OUTSIDE : 0);
+            const int mask = m & layers;
+            unsigned long long lowest = FOOT_NO_CELL;
+            if (mask != 0 && !had) {        // (wave-uniform)
+                const auto least = [](unsigned long long& x, unsigned long long o) { x = o < x ? o : x; };
+                rowReduce(least, low);
+                rowLeaders(least, low);
+                lowest = low;
+                had = true;
+            }
+            if (lane == k) {
+                const int jk = c0 + wave0 + k;
+                nxy += m & UPH_FOOT_OCC_XY ? 1 : 0; nyw += m & UPH_FOOT_OCC_YAW ? 1 : 0; nout += m & UPH_FOOT_OUTSIDE ? 1 : 0;
+                if (mask != 0) {
+                    hit.take(jk);
+                    if (first == CHECK_NONE) { first = ((unsigned long long)(unsigned)jk << 8) | (unsigned)mask; cell = lowest; }
+                }
+            }
+        }
+    }
+    // the first hit sample's key carries its cell along; the rest are sums and the span
+    const auto fold = [](unsigned long long& f, unsigned long long& ce, unsigned long long& nc, unsigned long long& nh, int& lo, int& hi, int& c, int& x, int& y, int& o,
+                         unsigned long long of, unsigned long long oce, unsigned long long onc, unsigned long long onh, int olo, int ohi, int oc, int ox, int oy, int oo) {
+        ce = of < f ? oce : ce; f = of < f ? of : f;
+        nc += onc; nh += onh;
+        SpanFold()(lo, hi, c, olo, ohi, oc);
+        x += ox; y += oy; o += oo;
+    };
+    if (!workgroupReduce<NT>(fold, first, cell, ncov, nhit, hit.first, hit.last, hit.cnt, nxy, nyw, nout)) return;
+    const double nan = __builtin_nan("");
+    FootCheckOut o;
+    o.first_t = hit.cnt == 0 ? nan : winTime(fq, a.r.tt, hit.first);
+    o.last_t = hit.cnt == 0 ? nan : winTime(fq, a.r.tt, hit.last);
+    o.cells[0] = ncov; o.cells[1] = nhit;
+    o.first_mask = first == CHECK_NONE ? 0 : (int)(first & 0xff);
+    o.first_cell[0] = cell == FOOT_NO_CELL ? -1 : (int)((unsigned)(cell >> 32) ^ 0x80000000u);
+    o.first_cell[1] = cell == FOOT_NO_CELL ? -1 : (int)((unsigned)cell ^ 0x80000000u);
+    o.counts[0] = n; o.counts[1] = hit.cnt; o.counts[2] = nxy; o.counts[3] = nyw; o.counts[4] = nout;
+    a.out[fq.out] = o;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static ResidentDev residentDev(uph_ctx* c) {
     ResidentDev r;
@@ -1533,6 +1706,28 @@ static int footRadii(const std::string& who, int32_t n, const double* shape, con
     }
     return UPH_OK;
 }
+// ---- footprint check (include/uneven_hip.h uph_footprint_check_*): the rectangle inflated by the margin, and the bound on the columns of a sample's box
+constexpr int64_t FOOT_CHECK_MAX_COLUMNS = (int64_t)1 << 14;
+struct FootCheckShape {
+    double hl, o, w;            // footShape's hl and w, each + margin (one rounded add)
+};
+static FootCheckShape footCheckShape(const double* s3, double margin) {
+#pragma clang fp contract(off)
+    const FootShape f = footShape(s3);
+    FootCheckShape s;
+    s.hl = f.hl + margin; s.o = f.o; s.w = f.w + margin;
+    return s;
+}
+// cols = side * side, side = floor(2 hypot(hl', w') (1 + 2^-40) / res) + 4: the hull's half extents hl'|c| + w'|s| and hl'|s| + w'|c| are at most hypot(hl', w') to
+// the roundings 2^-40 pays for, two floors that far apart differ by at most floor(2 e / res) + 1, and the pad adds a column on either side.  Saturates at 2^62.
+static int footCheckColumns(const std::string& who, int32_t q, const FootCheckShape& s, double res, int64_t& cols) {
+#pragma clang fp contract(off)
+    const double reach = std::hypot(s.hl, s.w) * (1.0 + 0x1p-40);
+    if (!std::isfinite(reach)) { setError(whoQuery(who, q) + " has a shape and margin whose reach is not finite"); return UPH_ERR_INVALID; }
+    const double side = std::floor(2.0 * reach / res) + 4.0;
+    cols = side < 0x1p31 ? (int64_t)side * (int64_t)side : (int64_t)1 << 62;
+    return UPH_OK;
+}
 // What the schedule calls (uph_delays_batch, uph_footprint_delays_batch) are behind their own refusals: fleetCandidates on swept boxes with the broad-phase radii,
 // the candidates' levels, a round per level -- the sweep record of every candidate of the level, form(K, dl, h, start_h, i) with h at its effective start, through
 // a sweep kernel whose rows carry `below` --, the sequential greedy's choice per vehicle, the kernels' time to the context's last_delay_ms
@@ -1855,6 +2050,72 @@ int uph_footprint_conflicts_batch(uph_ctx* c, int32_t n, const int32_t* traj, co
 }
 
 int uph_footprint_kernel_ms(const uph_ctx* c, double* kernel_ms) { return kernelMs("uph_footprint_kernel_ms", c, &uph_ctx::last_foot_ms, kernel_ms); }
+
+// ---- footprint check (include/uneven_hip.h) ------------------------------------------------------------------------------------------------------------
+int uph_footprint_check_columns(const uph_map_params* mp, int32_t n, const double* shape, const double* margin, int64_t* cols) {
+    const std::string who = "uph_footprint_check_columns";
+    if (!mp || n < 0 || (n > 0 && (!shape || !cols))) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    if (!(mp->xy_resolution > 0.0) || !std::isfinite(mp->xy_resolution)) { setError(who + ": the map's xy_resolution must be positive and finite"); return UPH_ERR_INVALID; }
+    int r = footAdmit(who, n, shape, "shape", margin);
+    if (r != UPH_OK) return r;
+    std::vector<int64_t> out((size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        const FootCheckShape s = footCheckShape(shape + 3 * (size_t)q, margin ? margin[q] : 0.0);
+        if ((r = footCheckColumns(who, q, s, mp->xy_resolution, out[(size_t)q])) != UPH_OK) return r;
+    }
+    std::copy(out.begin(), out.end(), cols);
+    return UPH_OK;
+}
+
+int uph_footprint_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end, const double* shape,
+                              const double* margin, int32_t layers, double* first_t, double* last_t, int32_t* first_mask, int32_t* first_cell, int32_t* counts,
+                              int64_t* cells) {
+    const std::string who = "uph_footprint_check_batch";
+    if (!c || n <= 0 || !traj || !t_from || !shape) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    if (layers < 1 || layers > UPH_FOOT_ALL) { setError(who + ": layers must be a non-empty subset of UPH_FOOT_ALL (1 .. 7)"); return UPH_ERR_INVALID; }
+    int r = footAdmit(who, n, shape, "shape", margin);
+    if (r != UPH_OK) return r;
+    const double res = uphMapGrid(c->map).xy_res;
+    std::vector<FootCheckQuery> qs;
+    r = formWindowQueries(c, n, traj, t_from, t_to, dt, with_end, who.c_str(), qs, [&](int32_t q, FootCheckQuery& k) {
+        const FootCheckShape s = footCheckShape(shape + 3 * (size_t)q, margin ? margin[q] : 0.0);
+        int64_t cols = 0;
+        const int rc = footCheckColumns(who, q, s, res, cols);
+        if (rc != UPH_OK) return rc;
+        if (cols > FOOT_CHECK_MAX_COLUMNS) { setError(whoQuery(who, q) + " has a shape and margin whose box can exceed 2^14 columns of the map"); return (int)UPH_ERR_LIMIT; }
+        k.hl = s.hl; k.o = s.o; k.w = s.w; k.layers = layers; k.pad2 = 0;
+        return (int)UPH_OK;
+    });
+    if (r != UPH_OK) return r;
+    GridDev grid;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    if (c->d_win_out.ensure(sizeof(FootCheckOut) * (size_t)n)) return UPH_ERR_HIP;
+    FootCheckArgs a;
+    a.r = residentDev(c); a.qs = c->d_win_q.as<FootCheckQuery>(); a.out = c->d_win_out.as<FootCheckOut>(); a.framed = trajFrame(c); a.q0 = 0;
+    uphMapOcc(c->map, &a.occ, &a.occ_r2);
+    a.g.nx = grid.nx; a.g.ny = grid.ny; a.g.nyaw = grid.nyaw; a.g.x_off = grid.x_off; a.g.nx_hold = grid.nx_hold;
+    for (int d = 0; d < 3; d++) a.g.origin[d] = grid.origin[d];
+    a.g.xy_res = grid.xy_res; a.g.xy_inv = grid.xy_inv; a.g.yaw_inv = grid.yaw_inv;
+    std::vector<FootCheckOut> out((size_t)n);
+    const auto work = [&](size_t q) { return qs[q].n_tab + qs[q].end_row; };
+    r = runQueryLaunch(c, twoWidths(c, (size_t)n, work, a, uph_footprint_check_kernel<256>, uph_footprint_check_kernel<64>), out, c->last_foot_check_ms);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const FootCheckOut& o = out[(size_t)q];
+        if (first_t) first_t[q] = o.first_t;
+        if (last_t) last_t[q] = o.last_t;
+        if (first_mask) first_mask[q] = o.first_mask;
+        if (first_cell) for (int k = 0; k < 2; k++) first_cell[2 * (size_t)q + k] = o.first_cell[k];
+        if (counts) for (int k = 0; k < 5; k++) counts[5 * (size_t)q + k] = o.counts[k];
+        if (cells) for (int k = 0; k < 2; k++) cells[2 * (size_t)q + k] = (int64_t)o.cells[k];
+    }
+    return UPH_OK;
+}
+
+int uph_footprint_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    return kernelMs("uph_footprint_check_kernel_ms", c, &uph_ctx::last_foot_check_ms, kernel_ms);
+}
 
 // ---- start delays (include/uneven_hip.h) -----------------------------------------------------------------------------------------------------------------
 int uph_delay_times(double delay0, double delay_step, int32_t D, double* delta) {
