@@ -75,6 +75,7 @@ extern "C" {
 typedef struct uph_map uph_map;   /* device-resident SE(2) -> R x S2+ terrain grid            */
 typedef struct uph_ctx uph_ctx;   /* optimiser context bound to one map, one device, one stream */
 typedef struct uph_kino uph_kino; /* front-end search context bound to one map: per-query workspaces (node pools, open heaps) in HBM */
+typedef struct uph_body_layer uph_body_layer; /* the occupancy of one map dilated by a vehicle rectangle, one byte per (ix, iy, iyaw), in HBM */
 
 /* ---- status codes */
 #define UPH_OK 0
@@ -804,6 +805,66 @@ int uph_footprint_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const 
                               int64_t* cells /* [n][2] */);
 /* milliseconds of the kernel(s) of the last uph_footprint_check_batch of c (events on the context's stream) */
 int uph_footprint_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
+
+/* ---- body layer: the map's occupancy dilated by the vehicle's rectangle, one slice per yaw bin (csrc/body_occ.hip).  The front-end search tests a
+ * POINT: every collision sample, the goal and every one-shot sample read one byte of occ_r2 (isOccupancyXY).  The body layer is the configuration-space obstacle
+ * of the rectangle on the map's own lattice: body[ix][iy][iw] = 1 iff the rectangle posed at the centre of cell (ix, iy, iw) covers an occupied column or one
+ * outside the grid.  uph_kino_set_body_layer makes the search read it where it reads occ_r2, so that a path is searched in the space where the body fits.  The
+ * reference marks the place: kino_astar.cpp:178 carries `// occ = uneven_map->isOccupancy(xt);`, a per-yaw read tried and left commented out.
+ *   shape          (front, rear, half_width) and a margin m >= 0, admitted as uph_footprint_check_columns admits them.  Inflated as the footprint check does:
+ *                  hl' = (front + rear) / 2 + m, o = (front - rear) / 2, w' = half_width + m, one rounded add each.
+ *   bin pose       psi_iw = origin_yaw + (iw + 0.5) * yaw_resolution (one multiply, one add), c = cos(psi_iw), s = sin(psi_iw) by the host's libm.  The table
+ *                  cs [nyaw][2] is an OUTPUT of uph_body_stencil; the numpy mirror (uneven_planner_amd/body_layer.py) takes it as input.
+ *   covered        the integer offset (dx, dy) is COVERED in bin iw iff, with qx = dx * res - o * c and qy = dy * res - o * s,
+ *                      |qx * c + qy * s| <= hl'   and   |qx * (-s) + qy * c| <= w'
+ *                  with every product and every sum rounded on its own, in the order written: the footprint check's centre test with the pose at a cell centre,
+ *                  written in offsets, so that it is translation-invariant by definition.
+ *   stencil        R = floor(hypot(max(front, rear) + m, half_width + m) * (1 + 2^-40) / res) + 1.  For every iw and every row dx in [-R, R]: lo[iw][dx + R] and
+ *                  hi[iw][dx + R] are the smallest and the largest covered dy in [-R, R]; an empty row has lo = 1, hi = 0.  The rule IS the interval per row (a
+ *                  convex rectangle gives an interval; tests/test_body_layer_cpu.py shows that rounding never breaks one).
+ *   limits         UPH_ERR_LIMIT when uph_footprint_check_columns' bound for the shape and margin exceeds 2^14 (the footprint check's own limit), or when R
+ *                  exceeds UPH_BODY_MAX_R: the column bound is on (front + rear) / 2, R on max(front, rear), so a one-sided shape (front = 6 m, rear = 0 at res = 0.05) can
+ *                  pass the first and not the second.
+ *   layer          body[(ix * ny + iy) * nyaw + iw], one byte, laid out as occ (uph_map_get_cells), is 1 iff some covered (dx, dy) names a column
+ *                  (ix + dx, iy + dy) that is inside the grid with occ_r2 != 0, when `layers` holds UPH_FOOT_OCC_XY, or outside [0, nx) x [0, ny), when `layers`
+ *                  holds UPH_FOOT_OUTSIDE.  layers: UPH_FOOT_OCC_XY, UPH_FOOT_OUTSIDE or both; UPH_FOOT_OCC_YAW is refused (occ_r2 is already the OR of occ over
+ *                  yaw).  An all-zero shape with m = 0 and layers = UPH_FOOT_OCC_XY makes every yaw slice equal to occ_r2.
+ *   margin         uph_body_layer_margin = (res * sqrt(2) / 2 + 2 * hypot(max(front, rear), half_width) * sin(yaw_resolution / 4)) * (1 + 2^-40).  With this margin
+ *                  a 0 at (ix, iy, iw) says of EVERY pose in that cell -- any position in the column, any yaw in the bin -- that the rectangle at margin 0, as
+ *                  the footprint check defines it, covers no occupied column centre: such a pose is within res * sqrt(2) / 2 of the cell's centre pose, a body
+ *                  point at radius r moves at most 2 r sin(e / 2) under a yaw change e <= yaw_resolution / 2, and inflating both half extents by d contains
+ *                  everything within d of the rectangle.
+ *   freshness      the map counts the writes of its occupancy (every commit: uph_map_set_cells, uph_map_build*, uph_map_update, uph_map_load_cache,
+ *                  uph_map_commit, uph_map_import_cells_dev, uph_map_fill_fbm and the multi-GPU calls).  build and set stamp the layer with that count;
+ *                  update is accepted only from a layer that is fresh or exactly one write behind -- the rect is the caller's statement of what that write
+ *                  changed, normally uph_map_update_info.changed -- and otherwise refused with UPH_ERR_INVALID ("rebuild").  A search with a stale layer is
+ *                  refused before anything is launched.  The layer does not follow the map by itself.
+ * Every byte is an OR of integer comparisons on the stencil and occ_r2: neither the kernel's tiling nor the launch width can show, and update(rect) equals a
+ * fresh build bit for bit when the rect holds every column whose occ_r2 changed.  Refusals, all before any device write: a tile map (uph_map_tile not the whole
+ * grid); the shape, margin and layers as above; a rect that is reversed or leaves the grid (an empty rect is accepted and writes nothing); uph_body_layer_destroy
+ * while a search context still names the layer.  Maps with fp32 cell storage are accepted: occupancy is bytes either way. */
+#define UPH_BODY_MAX_R 64
+/* host only, no device needed.  *R and *nyaw (the map's yaw bins, ceil((2 pi + 0.05) / yaw_resolution)) first, then cs [nyaw][2], lo and hi [nyaw][2R + 1];
+ * any output may be NULL, so that R and nyaw can be asked first. */
+int uph_body_stencil(const uph_map_params* mp, const double* shape /* [3]: front, rear, half_width */, double margin, int32_t* R, int32_t* nyaw, double* cs, int32_t* lo,
+                     int32_t* hi);
+int uph_body_layer_margin(const uph_map_params* mp, const double* shape /* [3] */, double* margin);
+/* allocates nx * ny * nyaw bytes on the map's device, uploads the stencil and builds.  The map must outlive the layer. */
+int uph_body_layer_create(uph_map* m, const double* shape /* [3] */, double margin, int32_t layers, uph_body_layer** out);
+int uph_body_layer_build(uph_body_layer* l);                            /* the whole grid, from the map's occ_r2 as it is now.  Blocking. */
+/* rect = (x0, x1, y0, y1), half-open, of the columns whose occ_r2 changed: rewrites exactly the outputs inside the rect grown by R and clipped.  Blocking. */
+int uph_body_layer_update(uph_body_layer* l, const int32_t rect[4]);
+int uph_body_layer_get(uph_body_layer* l, char* bytes /* [nx * ny * nyaw] */);
+int uph_body_layer_set(uph_body_layer* l, const char* bytes);           /* the caller's own layer, every byte 0 (free) or 1 (occupied), else UPH_ERR_INVALID and nothing written: stamped fresh */
+/* any output may be NULL.  behind: occupancy writes of the map since the layer was made (0: fresh; saturates at 2^31 - 1) */
+int uph_body_layer_info(const uph_body_layer* l, double* shape3, double* margin, int32_t* layers, int32_t* R, int32_t* dims3, int32_t* behind);
+int uph_body_layer_kernel_ms(const uph_body_layer* l, double* kernel_ms);   /* HIP-event milliseconds of the last build or update kernel */
+int uph_body_layer_destroy(uph_body_layer* l);                          /* UPH_ERR_INVALID while a search context names the layer; NULL is accepted */
+/* the search reads `layer` (of the same map as k) wherever it reads occ_r2 by default: the goal test, the one-shot samples and the collision samples of the
+ * primitives, each at its own yaw bin as isOccupancy forms it.  The start test stays on occ (the vehicle is where it is), and everything else is the
+ * reference's, its sampling gaps included: end states are not sampled, v = 0 primitives have no samples.  layer = NULL: back to occ_r2.  uph_plan_upload and
+ * uph_replan_upload search through k and follow it.  Results with an all-zero-shape layer (m = 0, UPH_FOOT_OCC_XY) are the default search's. */
+int uph_kino_set_body_layer(uph_kino* k, uph_body_layer* layer);
 
 /* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
  * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /

@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
@@ -1081,6 +1082,69 @@ private:
 };
 
 
+// The body layer (include/uneven_hip.h uph_body_*, no counterpart in the reference beyond the commented-out per-yaw read of kino_astar.cpp:178): the map's
+// occupancy dilated by the vehicle's rectangle (front, rear, half_width) inflated by `margin`, one slice per yaw bin, on the map's device.  Owns a
+// uph_body_layer; the map must outlive it, and it must outlive every KinoAstar::setBodyLayer that names it (the destructor cannot refuse: it reports to stderr
+// what uph_body_layer_destroy refused).  The layer does not follow the map: after UnevenMapHandle::updateMap call updateChanged(info), after anything else
+// that writes the map call build().
+class BodyLayer {
+public:
+    struct Info {
+        std::array<double, 3> shape{};
+        double margin = 0.0;
+        int32_t layers = 0, R = 0;
+        std::array<int32_t, 3> dims{};
+        int32_t behind = 0;             // occupancy writes of the map since the layer was made (0: fresh)
+        bool fresh() const { return behind == 0; }
+    };
+    // the margin with which a 0 of the layer holds for every pose inside the cell (uph_body_layer_margin)
+    static double conservativeMargin(const uph_map_params& mp, const std::array<double, 3>& shape) {
+        double m = 0.0;
+        if (uph_body_layer_margin(&mp, shape.data(), &m) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_margin: ") + uph_last_error());
+        return m;
+    }
+    BodyLayer(UnevenMapHandle& map, const std::array<double, 3>& shape, double margin, int32_t layers = UPH_FOOT_OCC_XY | UPH_FOOT_OUTSIDE) {
+        if (uph_body_layer_create(map.get(), shape.data(), margin, layers, &l_) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_create: ") + uph_last_error());
+    }
+    ~BodyLayer() {
+        if (l_ && uph_body_layer_destroy(l_) != UPH_OK) std::fprintf(stderr, "uneven_hip::BodyLayer: %s\n", uph_last_error());
+    }
+    BodyLayer(const BodyLayer&) = delete;
+    BodyLayer& operator=(const BodyLayer&) = delete;
+    void build() { if (uph_body_layer_build(l_) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_build: ") + uph_last_error()); }
+    // rect = {x0, x1, y0, y1}, half-open: the columns whose occupancy changed (uph_map_update_info::changed)
+    void update(const std::array<int32_t, 4>& rect) {
+        if (uph_body_layer_update(l_, rect.data()) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_update: ") + uph_last_error());
+    }
+    void updateChanged(const uph_map_update_info& info) { update(std::array<int32_t, 4>{info.changed[0], info.changed[1], info.changed[2], info.changed[3]}); }
+    Info info() const {
+        Info i;
+        if (uph_body_layer_info(l_, i.shape.data(), &i.margin, &i.layers, &i.R, i.dims.data(), &i.behind) != UPH_OK)
+            throw std::runtime_error(std::string("uph_body_layer_info: ") + uph_last_error());
+        return i;
+    }
+    std::vector<char> get() const {                 // [nx][ny][nyaw], laid out as the map's occ
+        const Info i = info();
+        std::vector<char> b((size_t)i.dims[0] * (size_t)i.dims[1] * (size_t)i.dims[2]);
+        if (uph_body_layer_get(l_, b.data()) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_get: ") + uph_last_error());
+        return b;
+    }
+    void set(const std::vector<char>& bytes) {
+        const Info i = info();
+        if (bytes.size() != (size_t)i.dims[0] * (size_t)i.dims[1] * (size_t)i.dims[2]) throw std::runtime_error("BodyLayer::set: a layer has nx * ny * nyaw bytes");
+        if (uph_body_layer_set(l_, bytes.data()) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_set: ") + uph_last_error());
+    }
+    double kernelMs() const {
+        double ms = 0.0;
+        if (uph_body_layer_kernel_ms(l_, &ms) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_kernel_ms: ") + uph_last_error());
+        return ms;
+    }
+    uph_body_layer* handle() const { return l_; }
+
+private:
+    uph_body_layer* l_ = nullptr;
+};
+
 // KinoAstar (front_end/include/front_end/kino_astar.h:99-168): the front-end PlanManager calls right before the back-end
 // (`kino_astar->plan(start_state, end_state)`, plan_manager.cpp:59-60).  Same public parameter members as the reference reads from rosparam
 // (kino_astar.cpp:7-20; defaults = run_hill.yaml:16-30), same plan() signature; the search runs on the device, one wave64 per query.
@@ -1174,6 +1238,12 @@ public:
     std::vector<int32_t> status, iter_num;      // of the last plan / planBatch
     void visFrontEnd() {}                        // RViz output stays with the host (no device side)
     void visExpanded() {}
+    // the search reads `layer` (of the same map) where it reads occ_r2 by default -- goal test, one-shot samples, collision samples --; nullptr: back to occ_r2.
+    // plan / planBatch and ALMTrajOpt::planSE2TrajBatch / replanSE2TrajBatch through this object follow it; a stale layer makes them throw.
+    void setBodyLayer(BodyLayer* layer) {
+        if (!k_) throw std::runtime_error("KinoAstar: setEnvironment has not been called");
+        if (uph_kino_set_body_layer(k_, layer ? layer->handle() : nullptr) != UPH_OK) throw std::runtime_error(std::string("uph_kino_set_body_layer: ") + uph_last_error());
+    }
     uph_kino* handle() const { return k_; }      // the search context (ALMTrajOpt::planSE2TrajBatch)
 
 private:

@@ -213,6 +213,17 @@ SYMBOLS = {
     "uph_fleet_info": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), DP]),
     "uph_fleet_get": (C.c_int, [_VP, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), DP, DP, C.POINTER(_I32), DP, DP]),
     "uph_fleet_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_body_stencil": (C.c_int, [C.POINTER(MapParams), DP, C.c_double, C.POINTER(_I32), C.POINTER(_I32), DP, C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_body_layer_margin": (C.c_int, [C.POINTER(MapParams), DP, DP]),
+    "uph_body_layer_create": (C.c_int, [_VP, DP, C.c_double, _I32, C.POINTER(_VP)]),
+    "uph_body_layer_build": (C.c_int, [_VP]),
+    "uph_body_layer_update": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "uph_body_layer_get": (C.c_int, [_VP, C.c_char_p]),
+    "uph_body_layer_set": (C.c_int, [_VP, C.c_char_p]),
+    "uph_body_layer_info": (C.c_int, [_VP, DP, DP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_body_layer_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_body_layer_destroy": (C.c_int, [_VP]),
+    "uph_kino_set_body_layer": (C.c_int, [_VP, _VP]),
 }
 
 _LIB = None
@@ -228,6 +239,7 @@ UPH_KINO_OK = 0
 UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of a query switched at or past its trajectory's end (not uploaded)
 UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
 UPH_FOOT_OCC_XY, UPH_FOOT_OCC_YAW, UPH_FOOT_OUTSIDE, UPH_FOOT_ALL = 1, 2, 4, 7   # include/uneven_hip.h: kinds of a column the footprint check covers
+UPH_BODY_MAX_R = 64        # include/uneven_hip.h: stencil radius in columns of a body layer
 FOOT_CHECK_MAX_COLUMNS = 1 << 14     # include/uneven_hip.h: columns of one sample's box in uph_footprint_check_batch
 SEPARATION_MAX_SAMPLES = 1 << 22     # include/uneven_hip.h: samples of one query on the common clock
 DELAY_MAX = 4096           # include/uneven_hip.h: delays of one table

@@ -152,6 +152,13 @@ __device__ __forceinline__ int kOcc(const GridDev& g, const char* __restrict__ o
     if (ix < 0 || iy < 0 || iw < 0 || ix > g.nx - 1 || iy > g.ny - 1 || iw > g.nyaw - 1) return -1;
     return (int)occ[((size_t)ix * g.ny + iy) * g.nyaw + iw];
 }
+// the search's collision read: isOccupancyXY by default; BODY: the same test on a per-yaw layer laid out as occ (a body layer, body_occ.hip), handed in where
+// occ_r2 is by default -- the per-yaw read kino_astar.cpp:178 left commented out
+template <bool BODY>
+__device__ __forceinline__ int kOccRead(const GridDev& g, const char* __restrict__ occ2, double x, double y, double w) {
+    if (BODY) return kOcc(g, occ2, x, y, w);
+    return kOccXY(g, occ2, x, y, w);
+}
 __device__ __forceinline__ double kTerrainSig(const GridDev& g, double x, double y, double w) {      // getTerrainSig, uneven_map.h:389-396
     if (isnan(x) || isnan(y)) return __longlong_as_double(0x7ff8000000000000ll);      // isInMap(NaN) is true, the trilinear weights are NaN
     Corners c;
@@ -342,7 +349,8 @@ __device__ __forceinline__ void kHeapPop(const KHeapRef<TOPN>& heap, int* pos, i
 #else
 #define KPROF(k) do { } while (0)
 #endif
-template <int WPS, bool FAST>
+// BODY = occ2 is a body layer [nx][ny][nyaw] instead of occ_r2 [nx][ny] (uph_kino_set_body_layer): the goal test and every collision sample read it at their yaw bin
+template <int WPS, bool FAST, bool BODY>
 __global__ __launch_bounds__(64, WPS) void uph_kino_kernel(GridDev g, const char* __restrict__ occ, const char* __restrict__ occ2, const KinoDev* __restrict__ Pp, KinoWork W, size_t node_stride,
                                                       size_t heap_stride, size_t table_stride, KinoIO io, int B) {
     const int lane = threadIdx.x;
@@ -390,7 +398,7 @@ __global__ __launch_bounds__(64, WPS) void uph_kino_kernel(GridDev g, const char
         long long kprof[6] = {0, 0, 0, 0, 0, 0}, kprof_t = (long long)__builtin_readcyclecounter();
 #endif
         if (kOcc(g, occ, sx0, sy0, sw0) == 1) status = 1;                                  // kino_astar.cpp:86-90
-        else if (kOccXY(g, occ2, gx, gy, gw) == 1) status = 2;                             // :91-95
+        else if (kOccRead<BODY>(g, occ2, gx, gy, gw) == 1) status = 2;                             // :91-95
         if (status < 0) {
             {                                                                              // expanded_nodes.clear(): 16-byte stores (the row stride is a multiple of 16 ints)
                 int4* t4 = (int4*)table;
@@ -435,7 +443,7 @@ __global__ __launch_bounds__(64, WPS) void uph_kino_kernel(GridDev g, const char
                             for (; k < s; k++) l += P.coll_interval;                       // the running sum the reference forms
                             double sp[3];
                             kDubinsInterpolate(P, from, to, path, l / len, sp);
-                            if (kOccXY(g, occ2, sp[0], sp[1], sp[2]) == 1) blocked = true;
+                            if (kOccRead<BODY>(g, occ2, sp[0], sp[1], sp[2]) == 1) blocked = true;
                         }
                     }
                     if (!__ballot(blocked) && M > 0) {
@@ -477,7 +485,7 @@ __global__ __launch_bounds__(64, WPS) void uph_kino_kernel(GridDev g, const char
             int occ_samp = 0;                                        // spread form: this lane's collision sample (1 = occupied)
             bool inmap = false;
             if (pvalid) kStateTransit<FAST>(cx, cy, cw, csw, ccw, is, l_s, l_y, l_r, px, py, pw);
-            if (l_samp) occ_samp = kOccXY(g, occ2, px, py, pw);
+            if (l_samp) occ_samp = kOccRead<BODY>(g, occ2, px, py, pw);
             if (pvalid && sgrp == 0 && isInMap<double>(g, px, py, pw)) {                   // :154-158
                 int id3[3];
                 inmap = true;
@@ -509,7 +517,7 @@ __global__ __launch_bounds__(64, WPS) void uph_kino_kernel(GridDev g, const char
                     for (int s = 0; s < nt && !closed; s++) {                              // :171-185
                         double xt, yt, wt;
                         kStateTransit<FAST>(cx, cy, cw, csw, ccw, is, P.in_s[lane][s + 1], P.in_y[lane][s + 1], P.in_r[lane][s + 1], xt, yt, wt);
-                        if (kOccXY(g, occ2, xt, yt, wt) == 1) { blocked = true; break; }
+                        if (kOccRead<BODY>(g, occ2, xt, yt, wt) == 1) { blocked = true; break; }
                     }
                 }
                 if (!closed && !blocked) {
@@ -669,6 +677,7 @@ struct uph_kino {
     size_t io_cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double last_ms = 0.0;
+    uph_body_layer* body = nullptr;      // uph_kino_set_body_layer: the layer the collision reads go to instead of occ_r2 (nullptr: the reference's reads)
 };
 
 // (re)allocate the per-query workspaces for `want` concurrent queries; when the device cannot hold them, for half as many, and so on
@@ -797,6 +806,7 @@ int uph_kino_create(uph_map* m, const uph_kino_params* kp, int32_t slots, uph_ki
 void uph_kino_destroy(uph_kino* k) {
     if (!k) return;
     hipSetDevice(k->device);
+    if (k->body) uphBodyLayerUse(k->body, -1);
     hipFree(k->d_P);
     kinoFreeWork(k);
     for (int i = 0; i < 10; i++) hipFree(k->d_io[i]);
@@ -816,11 +826,23 @@ int uph_kino_set_wps(uph_kino* k, int32_t wps) {
     return UPH_OK;
 }
 int uph_kino_primitives(const uph_kino* k) { return k ? k->P.n_inputs : UPH_ERR_INVALID; }
+int uph_kino_set_body_layer(uph_kino* k, uph_body_layer* layer) {
+    if (!k) { setError("uph_kino_set_body_layer: bad arguments"); return UPH_ERR_INVALID; }
+    if (layer && uphBodyLayerMap(layer) != k->map) { setError("uph_kino_set_body_layer: the layer belongs to another map than the search context"); return UPH_ERR_INVALID; }
+    if (layer) uphBodyLayerUse(layer, 1);
+    if (k->body) uphBodyLayerUse(k->body, -1);
+    k->body = layer;
+    return UPH_OK;
+}
 
 }  // extern "C"
 
 // the search of uph_kino_plan_batch without the downloads: the B queries' results stay in the context's device buffers (valid until its next search)
 int uphKinoSearch(uph_kino* k, int32_t B, const double* starts, const double* goals, int32_t path_cap, int32_t max_expand, int32_t exp_cap, UphKinoOut& out) {
+    if (k->body && !uphBodyLayerFresh(k->body)) {
+        setError("uph_kino_plan_batch: the body layer is stale (the map's occupancy was written after the layer was made): uph_body_layer_update or uph_body_layer_build");
+        return UPH_ERR_INVALID;
+    }
     KHIPCHK(hipSetDevice(k->device));
     if (k->auto_slots && k->slots < std::min((int)B, k->slots_cap)) {
         // automatic workspaces follow the batch, GEOMETRICALLY: first call, or a larger batch than any before -> at least twice the previous capacity, so a
@@ -863,15 +885,19 @@ int uphKinoSearch(uph_kino* k, int32_t B, const double* starts, const double* go
     W.table_len = ((size_t)k->P.nxy + 1) * k->P.nyawk;
     const char *occ = nullptr, *occ2 = nullptr;
     uphMapOcc(k->map, &occ, &occ2);
+    const bool body = k->body != nullptr;
+    if (body) occ2 = uphBodyLayerBytes(k->body);      // the kernel's occ2 argument carries the layer in body mode
     const int grid = std::min((int)B, k->slots);
     if (grid < 1) { setError("uph_kino_plan_batch: no workspace"); return UPH_ERR_HIP; }
     KHIPCHK(hipEventRecord(k->e0, 0));
-#define UPH_KINO_LAUNCH2(WPS_, F_) hipLaunchKernelGGL((uph_kino_kernel<WPS_, F_>), dim3(grid), dim3(64), 0, 0, uphMapGrid(k->map), occ, occ2, (const KinoDev*)k->d_P, W, k->node_stride, k->heap_stride, k->table_stride, io, (int)B)
+#define UPH_KINO_LAUNCH3(WPS_, F_, B_) hipLaunchKernelGGL((uph_kino_kernel<WPS_, F_, B_>), dim3(grid), dim3(64), 0, 0, uphMapGrid(k->map), occ, occ2, (const KinoDev*)k->d_P, W, k->node_stride, k->heap_stride, k->table_stride, io, (int)B)
+#define UPH_KINO_LAUNCH2(WPS_, F_) do { if (body) UPH_KINO_LAUNCH3(WPS_, F_, true); else UPH_KINO_LAUNCH3(WPS_, F_, false); } while (0)
 #define UPH_KINO_LAUNCH(WPS_) do { if (k->flags & 2) UPH_KINO_LAUNCH2(WPS_, true); else UPH_KINO_LAUNCH2(WPS_, false); } while (0)
     if (k->wps == 2) UPH_KINO_LAUNCH(2);
     else if (k->wps == 6) UPH_KINO_LAUNCH(6);
     else if (k->wps == 8) UPH_KINO_LAUNCH(8);
     else UPH_KINO_LAUNCH(4);
+#undef UPH_KINO_LAUNCH3
 #undef UPH_KINO_LAUNCH2
 #undef UPH_KINO_LAUNCH
     KHIPCHK(hipGetLastError());

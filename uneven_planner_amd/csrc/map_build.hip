@@ -47,6 +47,7 @@ struct uph_map {
     double* d_c = nullptr;       // c_buffer (fp64 storage only)
     char* d_occ = nullptr;       // ncell
     char* d_occ2 = nullptr;      // nx * ny
+    unsigned long long occ_version = 0;      // counts the launches that write d_occ / d_occ2 (the two commit kernels): what a body layer (body_occ.hip) is stamped with
     void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};      // query scratch (uphMapScratch)
     size_t scratch_cap[4] = {0, 0, 0, 0};
     double last_build_ms = 0.0, last_query_ms = 0.0;
@@ -83,6 +84,7 @@ void* uphMapScratch(uph_map* m, int slot, size_t bytes) {
 }
 GridDev uphMapGrid(const uph_map* m) { return m->g; }
 void uphMapOcc(const uph_map* m, const char** occ, const char** occ_r2) { *occ = m->d_occ; *occ_r2 = m->d_occ2; }
+unsigned long long uphMapOccVersion(const uph_map* m) { return m->occ_version; }
 
 // ------------------------------------------------------------------------------------------------ device code
 struct CloudDev {
@@ -694,6 +696,7 @@ HostCloud cropAndVoxel(const float* xyz, int64_t n) {
 int commitMap(uph_map* m) {
     const GridDev& g = m->g;
     const int ncol = g.nx_hold * g.ny;
+    m->occ_version++;
     hipLaunchKernelGGL(uph_map_commit_kernel, dim3((ncol + 255) / 256), dim3(256), 0, 0, g.nx_hold, g.ny, g.nyaw, m->d_cells, m->d_cells32, m->d_c, m->d_occ,
                        m->d_occ2, m->mp.min_cnormal, m->mp.max_rho);
     HIPCHK(hipGetLastError());
@@ -1356,6 +1359,7 @@ int uph_map_update(uph_map* m, const float box[4], const float* xyz, int64_t n, 
         if (hipEventElapsedTime(&ms, m->bev0, m->bev1) != hipSuccess) ms = 0.f;
         (void)lap();
         // ---- windowed commit: c, occ, occ2 of the listed columns; changed columns reduced with integer min / max / count
+        m->occ_version++;
         hipLaunchKernelGGL(uph_map_commit_list_kernel, dim3((unsigned)((n_refit + 255) / 256)), dim3(256), 0, 0, g.ny, g.nyaw, m->d_cells, m->d_c, m->d_occ, m->d_occ2,
                            m->mp.min_cnormal, m->mp.max_rho, d_list, n_refit, d_changed, (int*)(d_small + 11));
         if (hipGetLastError() != hipSuccess || hipMemcpy(got, d_small + 11, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { setError("uph_map_update: the commit failed"); return fail(UPH_ERR_HIP); }

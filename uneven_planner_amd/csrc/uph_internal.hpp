@@ -20,6 +20,14 @@ struct UphPtr {                 // non-owning view of a scratch slot
 uph::GridDev uphMapGrid(const uph_map* m);
 // device occupancy layers of the map (uneven_map.cpp:170-179): occ [ncell], occ_r2 [nx * ny]; read by the front-end search (kino_search.hip)
 void uphMapOcc(const uph_map* m, const char** occ, const char** occ_r2);
+// how often the occupancy layers have been written (every launch of the two commit kernels of map_build.hip counts once): the stamp of a body layer
+unsigned long long uphMapOccVersion(const uph_map* m);
+// the body layer (body_occ.hip) as the search reads it: its map, its device bytes [nx][ny][nyaw], whether it was made from the map's occupancy as it is
+// now, and the count of search contexts that name it (uph_body_layer_destroy refuses while it is not zero)
+const uph_map* uphBodyLayerMap(const uph_body_layer* l);
+const char* uphBodyLayerBytes(const uph_body_layer* l);
+bool uphBodyLayerFresh(const uph_body_layer* l);
+void uphBodyLayerUse(uph_body_layer* l, int delta);
 
 // scope guards for the temporaries of the extern "C" entry points: every early return (HIPCHK) releases them
 struct UphDevTmp {

@@ -34,6 +34,7 @@ class KinoAstar:
         self.uneven_map = None
         self.front_end_path = np.zeros((0, 3))
         self.last = None
+        self.body_layer = None
         if uneven_map is not None:
             self.setEnvironment(uneven_map)
 
@@ -56,10 +57,17 @@ class KinoAstar:
         """experiment knob: bit 0 dynamic query hand-out, bit 1 sincosFast (both on by default)"""
         _lib.check(self.L.uph_kino_set_flags(self.h, int(flags)), "uph_kino_set_flags")
 
+    def set_body_layer(self, layer):
+        """the search reads `layer` (a body_layer.BodyLayer of the same map) where it reads occ_r2 by default: the goal test, the one-shot samples and the
+        primitives' collision samples; None: back to occ_r2.  A stale layer makes plan_batch raise."""
+        _lib.check(self.L.uph_kino_set_body_layer(self.h, layer.h if layer is not None else None), "uph_kino_set_body_layer")
+        self.body_layer = layer          # (keeps the layer alive while the context names it)
+
     def close(self):
         if getattr(self, "h", None):
             self.L.uph_kino_destroy(self.h)
             self.h = None
+            self.body_layer = None
 
     def __del__(self):
         try:
