@@ -59,6 +59,8 @@
  *                              turned by the trajectory's yaw instead of discs
  *   uph_footprint_check_batch  <- UnevenMap::isOccupancy / isOccupancyXY (uneven_map.h:471-488) at every column the vehicle's rectangle covers, not only the one
  *                              under the trajectory's point, over time windows of chosen resident trajectories
+ *   uph_clearance_* / uph_clearance_check_batch  <- no counterpart (UnevenMap keeps occupancy bits only): the squared distance transform of a body layer per yaw
+ *                              slice, and its value along time windows of chosen resident trajectories -- how close, when and where
  *   uph_delays_batch        <- the smallest start delay that clears each vehicle of a fleet against all vehicles ahead of it in priority order
  *   uph_footprint_delay_sweep_batch / uph_footprint_delays_batch  <- the delay sweep and the schedule with the vehicles as oriented rectangles
  *   uph_kino_params         <- rosparam kino_astar/...  kino_astar.cpp:7-20, values of plan_manager/params/run_hill.yaml:16-30
@@ -865,6 +867,74 @@ int uph_body_layer_destroy(uph_body_layer* l);                          /* UPH_E
  * reference's, its sampling gaps included: end states are not sampled, v = 0 primitives have no samples.  layer = NULL: back to occ_r2.  uph_plan_upload and
  * uph_replan_upload search through k and follow it.  Results with an all-zero-shape layer (m = 0, UPH_FOOT_OCC_XY) are the default search's. */
 int uph_kino_set_body_layer(uph_kino* k, uph_body_layer* layer);
+/* how often the layer's bytes have been written: uph_body_layer_build (the one inside create included), uph_body_layer_update (an empty rect too) and
+ * uph_body_layer_set count one each.  The stamp of a clearance layer (below). */
+int uph_body_layer_writes(const uph_body_layer* l, uint64_t* writes);
+
+/* ---- clearance layer: the exact, truncated, squared Euclidean distance transform of a body layer, one field per yaw slice (csrc/clearance.hip).
+ * A body layer answers one bit per cell at one margin chosen in advance; the clearance layer says how much room a cell has, and uph_clearance_check_batch reads it
+ * along resident trajectories: how close, when and where.
+ *   source         a body layer body[(ix * ny + iy) * nyaw + iw], bytes 0 / 1.  An all-zero-shape layer is occ_r2 per slice: the point case needs nothing extra.
+ *   feature        under polarity UPH_CLEAR_TO_OCCUPIED (0) a cell is a FEATURE when its byte is 1; under UPH_CLEAR_TO_FREE (1) when its byte is 0 -- the depth
+ *                  inside the obstacle, and with the other polarity a signed field.  Cells outside [0, nx) x [0, ny) are never features: the border enters through
+ *                  the body layer's own UPH_FOOT_OUTSIDE bit.
+ *   value          with the truncation radius rmax in cells, 1 <= rmax <= UPH_CLEAR_MAX_R:
+ *                      m(ix, iy, iw) = min{ dx^2 + dy^2 : |dx| <= rmax, |dy| <= rmax, (ix + dx, iy + dy) inside the grid and a feature in slice iw }
+ *                      D = m if such a feature exists and m <= rmax^2, else UPH_CLEAR_FAR
+ *                  D is a uint16 laid out as the body layer.  A feature cell has D = 0; slices never mix.  In metres: res * sqrt(D).  The min over the square
+ *                  window filtered by <= rmax^2 equals the min over the disc, so the separable evaluation is the rule and not an approximation: pass 1 along iy
+ *                  finds g, the distance to the nearest feature of the row within rmax (255: none -- why rmax <= 254); pass 2 along ix takes min dx^2 + g^2.
+ *   guarantee      a position in column (ix, iy) moved by any vector shorter than res * (sqrt(D) - sqrt(2)) lands in a column whose byte in slice iw is not a
+ *                  feature: both positions are within res * sqrt(2) / 2 of their columns' centres, so a feature column reached that way would have its centre
+ *                  nearer than res * sqrt(D).  For D = UPH_CLEAR_FAR take sqrt(rmax^2 + 1) for sqrt(D): every feature lies beyond the disc, and
+ *                  the nearest place beyond it is that far, not rmax + 1 (the offset (rmax, 1)).  Under UPH_CLEAR_TO_OCCUPIED, with the body
+ *                  layer built at uph_body_layer_margin, this is a statement about the real rectangle at every pose of those cells.
+ *   rect update    when the body layer's bytes changed only inside rect (x0, x1, y0, y1), D can change only inside the rect grown by rmax and clipped:
+ *                  uph_clearance_update rewrites exactly those outputs and equals a fresh build bit for bit.  uph_clearance_grow_rect serves both steps of the
+ *                  chain: the map's `changed` rect grown by the body layer's R is what uph_body_layer_update rewrote; that rect grown by rmax is what
+ *                  uph_clearance_update rewrites.
+ *   freshness      create and build stamp the layer with the body layer's write count (uph_body_layer_writes).  update is accepted from a layer that is fresh or
+ *                  exactly one write behind -- the rect is the caller's statement of what that write changed -- and otherwise refused with UPH_ERR_INVALID
+ *                  ("rebuild"): the rule the body layer has towards the map.  uph_body_layer_destroy is refused while a clearance layer names the body layer.
+ * Every value is a min of integer sums: neither tiling nor launch width can show.  Refusals, before any device write: rmax outside 1 .. UPH_CLEAR_MAX_R, a polarity
+ * other than the two, a rect that is reversed or leaves the grid (an empty rect is accepted and writes nothing). */
+#define UPH_CLEAR_TO_OCCUPIED 0
+#define UPH_CLEAR_TO_FREE 1
+#define UPH_CLEAR_MAX_R 254
+#define UPH_CLEAR_FAR 65535
+typedef struct uph_clearance uph_clearance;
+/* host only, no device needed: out = rect = (x0, x1, y0, y1) grown by r >= 0 on every side and clipped to dims2 = (nx, ny).  An empty rect stays empty (out = rect).
+ * UPH_ERR_INVALID: a NULL argument, r < 0, dims not positive, a rect that is reversed or leaves the grid. */
+int uph_clearance_grow_rect(const int32_t dims2[2], const int32_t rect[4], int32_t r, int32_t out[4]);
+/* allocates nx * ny * nyaw uint16 and as many scratch bytes on the body layer's device, and builds.  The body layer must outlive the clearance layer. */
+int uph_clearance_create(uph_body_layer* body, int32_t rmax, int32_t polarity, uph_clearance** out);
+int uph_clearance_build(uph_clearance* l);                              /* the whole grid, from the body layer's bytes as they are now.  Blocking. */
+/* rect = (x0, x1, y0, y1), half-open, of the columns whose body bytes changed: rewrites exactly the outputs inside the rect grown by rmax and clipped.  Blocking. */
+int uph_clearance_update(uph_clearance* l, const int32_t rect[4]);
+int uph_clearance_get(uph_clearance* l, uint16_t* d /* [nx * ny * nyaw] */);
+/* any output may be NULL.  behind: writes of the body layer since the clearance layer was made (0: fresh; saturates at 2^31 - 1) */
+int uph_clearance_info(const uph_clearance* l, int32_t* rmax, int32_t* polarity, int32_t* dims3, int32_t* behind);
+int uph_clearance_kernel_ms(const uph_clearance* l, double* kernel_ms);    /* HIP-event milliseconds of the two passes of the last build or update */
+int uph_clearance_destroy(uph_clearance* l);                            /* NULL is accepted */
+/* The query: the clearance along resident trajectories.  c is a context or a fleet bound to the layer's map (anything else: UPH_ERR_INVALID).
+ *   samples        exactly uph_check_batch's: the same time table, end row and uph_check_window.
+ *   cell           per sample (ix, iy, iw) by the footprint check's own floor statements on X, Y and the normalised yaw, with the same degenerate rule: a value
+ *                  not finite or an index at or above 2^30 means that no float-to-int conversion is executed, and the sample counts as outside.
+ *   value          a sample inside the grid has v = D[cell]; a sample outside has v = 0 and is counted as outside.
+ * Outputs per query, any of them may be NULL:
+ *   min_d2 [n]            the smallest v; -1 for an empty window
+ *   min_t [n], min_cell [n][3]   t and cell of the EARLIEST sample that attains the min; NaN and (-1, -1, -1) for an empty window, the cell (-1, -1, -1) when that
+ *                         sample is outside
+ *   first_t, last_t [n]   t of the first and of the last sample with v < below2[q] (NaN: none)
+ *   counts [n][4]         samples, below, outside, far (v == UPH_CLEAR_FAR)
+ * Every output is an integer sum or a selection under the total order (value, sample index): launch width and lane split cannot show.  Reads no terrain cell.
+ * Blocking, on the context's stream.  Refusals, all before any launch: uph_check_batch's; below2[q] < 0; a clearance layer behind its body layer; a body layer
+ * behind the map; a context on another map. */
+int uph_clearance_check_batch(uph_ctx* c, uph_clearance* layer, int32_t n, const int32_t* traj, const double* t_from, const double* t_to /* NULL: to the end */,
+                              double dt, int32_t with_end, const int32_t* below2 /* [n] */, int32_t* min_d2 /* [n] */, double* min_t /* [n] */,
+                              int32_t* min_cell /* [n][3] */, double* first_t /* [n] */, double* last_t /* [n] */, int32_t* counts /* [n][4] */);
+/* milliseconds of the kernel(s) of the last uph_clearance_check_batch of c (events on the context's stream) */
+int uph_clearance_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
 /* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
  * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /

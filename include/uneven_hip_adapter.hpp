@@ -19,6 +19,7 @@
 //   refineSE2TrajBatch             the rest of the last batch's trajectories re-optimised from states at switch times, no search (uph_refine_upload)
 //   checkSE2TrajBatch              time windows of the last batch's trajectories held against limits on the map as it is now (uph_check_batch)
 //   footprintCheckSE2TrajBatch     the same windows with the vehicle's rectangle swept over the map's occupancy: first / last hit and where (uph_footprint_check_batch)
+//   clearanceSE2TrajBatch          the same windows read in a ClearanceLayer, the distance transform of a BodyLayer: how close, when and where (uph_clearance_check_batch)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
 // (Eigen::MatrixXd / Eigen::VectorXd in the ROS workspace; the tiny Mat/Vec below where Eigen is not installed, as in this
@@ -39,6 +40,7 @@
 namespace uneven_hip {
 
 class KinoAstar;
+class ClearanceLayer;
 
 struct Mat {                       // minimal column-major stand-in with the Eigen accessors the adapter touches
     int r = 0, c = 0;
@@ -768,6 +770,19 @@ public:
             throw std::runtime_error(std::string("uph_footprint_check_batch: ") + uph_last_error());
         return out;
     }
+    // how much room the body has along the last batch's trajectories (uph_clearance_check_batch): the ClearanceLayer's value at the cell of every sample's point
+    // and yaw bin, over the samples of trajectory traj[q] with t in [t_from[q], t_to[q]] (t_to empty: to the end).  below2[q], in squared cells, marks the
+    // samples that count as close (ClearanceLayer::below2 converts metres).  The layer must be fresh and of this optimiser's map.
+    struct TrajClearance {
+        std::vector<int32_t> min_d2;                    // [n] the smallest value (-1: empty window; UPH_CLEAR_FAR: nothing within rmax)
+        std::vector<double> min_t;                      // [n] t of the earliest sample at the min (NaN: empty window)
+        std::vector<std::array<int32_t, 3>> min_cell;   // [n] its cell (ix, iy, iw) ((-1, -1, -1): empty window, or that sample is outside the grid)
+        std::vector<double> first_t, last_t;            // [n] t of the first / last sample with a value below below2[q] (NaN: none)
+        std::vector<int32_t> counts;                    // [n][4] samples, below, outside, far
+        double metres(size_t q, double res) const { return min_d2[q] < 0 ? std::nan("") : min_d2[q] == UPH_CLEAR_FAR ? HUGE_VAL : res * std::sqrt((double)min_d2[q]); }
+    };
+    TrajClearance clearanceSE2TrajBatch(const ClearanceLayer& layer, const std::vector<int>& traj, const std::vector<double>& t_from, const std::vector<double>& t_to,
+                                        const std::vector<int32_t>& below2, double dt = 0.01, bool with_end = true);
     // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are
     // delta_j = delay0 + j * delay_step, 0 <= j < D.  separationSE2TrajBatch of a against b started at t0_b[q] + delta_j, for every j, in one call
     // (uph_delay_sweep_batch).
@@ -1139,11 +1154,87 @@ public:
         if (uph_body_layer_kernel_ms(l_, &ms) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_kernel_ms: ") + uph_last_error());
         return ms;
     }
+    uint64_t writes() const {                       // build, update and set count one each: what a ClearanceLayer is stamped with
+        uint64_t w = 0;
+        if (uph_body_layer_writes(l_, &w) != UPH_OK) throw std::runtime_error(std::string("uph_body_layer_writes: ") + uph_last_error());
+        return w;
+    }
     uph_body_layer* handle() const { return l_; }
 
 private:
     uph_body_layer* l_ = nullptr;
 };
+
+// The clearance layer (include/uneven_hip.h uph_clearance_*, no counterpart in the reference): the exact squared Euclidean distance transform of a BodyLayer,
+// truncated at rmax cells, one field per yaw slice, on the body layer's device.  Owns a uph_clearance; the body layer must outlive it (declare it first:
+// uph_body_layer_destroy is refused while a clearance layer names it).  The layer does not follow the body layer: after BodyLayer::update(rect) call
+// update(growRect(dims, rect, R)), after BodyLayer::build or set call build().
+class ClearanceLayer {
+public:
+    struct Info {
+        int32_t rmax = 0, polarity = 0;
+        std::array<int32_t, 3> dims{};
+        int32_t behind = 0;             // writes of the body layer since the clearance layer was made (0: fresh)
+        bool fresh() const { return behind == 0; }
+    };
+    // rect = {x0, x1, y0, y1} grown by r and clipped to the grid (uph_clearance_grow_rect): the map's changed rect grown by BodyLayer::Info::R is what
+    // BodyLayer::update rewrote, and that rect is what update() below takes
+    static std::array<int32_t, 4> growRect(const std::array<int32_t, 3>& dims, const std::array<int32_t, 4>& rect, int32_t r) {
+        std::array<int32_t, 4> out{};
+        if (uph_clearance_grow_rect(dims.data(), rect.data(), r, out.data()) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_grow_rect: ") + uph_last_error());
+        return out;
+    }
+    // a distance in metres as the query's threshold in squared cells: ceil((below / res)^2)
+    static int32_t below2(double below, double res) { const double q = below / res; return (int32_t)std::min(std::ceil(q * q), 2147483647.0); }
+    ClearanceLayer(BodyLayer& body, int32_t rmax, int32_t polarity = UPH_CLEAR_TO_OCCUPIED) {
+        if (uph_clearance_create(body.handle(), rmax, polarity, &l_) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_create: ") + uph_last_error());
+    }
+    ~ClearanceLayer() { uph_clearance_destroy(l_); }
+    ClearanceLayer(const ClearanceLayer&) = delete;
+    ClearanceLayer& operator=(const ClearanceLayer&) = delete;
+    void build() { if (uph_clearance_build(l_) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_build: ") + uph_last_error()); }
+    // rect = {x0, x1, y0, y1}, half-open: the columns whose body bytes changed
+    void update(const std::array<int32_t, 4>& rect) {
+        if (uph_clearance_update(l_, rect.data()) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_update: ") + uph_last_error());
+    }
+    Info info() const {
+        Info i;
+        if (uph_clearance_info(l_, &i.rmax, &i.polarity, i.dims.data(), &i.behind) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_info: ") + uph_last_error());
+        return i;
+    }
+    std::vector<uint16_t> get() const {             // [nx][ny][nyaw], laid out as the body layer
+        const Info i = info();
+        std::vector<uint16_t> d((size_t)i.dims[0] * (size_t)i.dims[1] * (size_t)i.dims[2]);
+        if (uph_clearance_get(l_, d.data()) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_get: ") + uph_last_error());
+        return d;
+    }
+    double kernelMs() const {
+        double ms = 0.0;
+        if (uph_clearance_kernel_ms(l_, &ms) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_kernel_ms: ") + uph_last_error());
+        return ms;
+    }
+    uph_clearance* handle() const { return l_; }
+
+private:
+    uph_clearance* l_ = nullptr;
+};
+
+inline ALMTrajOpt::TrajClearance ALMTrajOpt::clearanceSE2TrajBatch(const ClearanceLayer& layer, const std::vector<int>& traj, const std::vector<double>& t_from,
+                                                                   const std::vector<double>& t_to, const std::vector<int32_t>& below2, double dt, bool with_end) {
+    if (t_from.size() != traj.size() || (!t_to.empty() && t_to.size() != traj.size()) || below2.size() != traj.size())
+        throw std::runtime_error("clearanceSE2TrajBatch: traj, t_from, t_to and below2 differ in number");
+    if (last_multi_) throw std::runtime_error("clearanceSE2TrajBatch: the last batch was split over several devices");
+    const int32_t n = (int32_t)traj.size();
+    TrajClearance out;
+    if (n == 0) return out;
+    std::vector<int32_t> tr(traj.begin(), traj.end());
+    out.min_d2.assign((size_t)n, -1); out.min_t.assign((size_t)n, 0.0); out.min_cell.assign((size_t)n, std::array<int32_t, 3>{-1, -1, -1});
+    out.first_t.assign((size_t)n, 0.0); out.last_t.assign((size_t)n, 0.0); out.counts.assign((size_t)4 * n, 0);
+    if (uph_clearance_check_batch(ctx_, layer.handle(), n, tr.data(), t_from.data(), t_to.empty() ? nullptr : t_to.data(), dt, with_end ? 1 : 0, below2.data(),
+                                  out.min_d2.data(), out.min_t.data(), out.min_cell[0].data(), out.first_t.data(), out.last_t.data(), out.counts.data()) != UPH_OK)
+        throw std::runtime_error(std::string("uph_clearance_check_batch: ") + uph_last_error());
+    return out;
+}
 
 // KinoAstar (front_end/include/front_end/kino_astar.h:99-168): the front-end PlanManager calls right before the back-end
 // (`kino_astar->plan(start_state, end_state)`, plan_manager.cpp:59-60).  Same public parameter members as the reference reads from rosparam

@@ -224,6 +224,18 @@ SYMBOLS = {
     "uph_body_layer_kernel_ms": (C.c_int, [_VP, DP]),
     "uph_body_layer_destroy": (C.c_int, [_VP]),
     "uph_kino_set_body_layer": (C.c_int, [_VP, _VP]),
+    "uph_body_layer_writes": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    "uph_clearance_grow_rect": (C.c_int, [C.POINTER(_I32), C.POINTER(_I32), _I32, C.POINTER(_I32)]),
+    "uph_clearance_create": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP)]),
+    "uph_clearance_build": (C.c_int, [_VP]),
+    "uph_clearance_update": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "uph_clearance_get": (C.c_int, [_VP, C.POINTER(C.c_uint16)]),
+    "uph_clearance_info": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "uph_clearance_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_clearance_destroy": (C.c_int, [_VP]),
+    "uph_clearance_check_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, C.POINTER(_I32), DP, DP,
+                                            C.POINTER(_I32)]),
+    "uph_clearance_check_kernel_ms": (C.c_int, [_VP, DP]),
 }
 
 _LIB = None
@@ -240,7 +252,9 @@ UPH_REFINE_AT_END = 7      # include/uneven_hip.h: uph_refine_upload's status of
 UPH_CHECK_OCC_BIT = 7      # include/uneven_hip.h: bit of uph_check_batch's masks that stands for occupancy (bits 0-6: the seven terms)
 UPH_FOOT_OCC_XY, UPH_FOOT_OCC_YAW, UPH_FOOT_OUTSIDE, UPH_FOOT_ALL = 1, 2, 4, 7   # include/uneven_hip.h: kinds of a column the footprint check covers
 UPH_BODY_MAX_R = 64        # include/uneven_hip.h: stencil radius in columns of a body layer
-FOOT_CHECK_MAX_COLUMNS = 1 << 14     # include/uneven_hip.h: columns of one sample's box in uph_footprint_check_batch
+UPH_CLEAR_TO_OCCUPIED, UPH_CLEAR_TO_FREE = 0, 1   # include/uneven_hip.h: what a clearance layer measures the distance to
+UPH_CLEAR_MAX_R, UPH_CLEAR_FAR = 254, 65535       # include/uneven_hip.h: the largest truncation radius in cells; the value of a cell with no feature within it
+FOOT_CHECK_MAX_COLUMNS = 1 << 14    # include/uneven_hip.h: columns of one sample's box in uph_footprint_check_batch
 SEPARATION_MAX_SAMPLES = 1 << 22     # include/uneven_hip.h: samples of one query on the common clock
 DELAY_MAX = 4096           # include/uneven_hip.h: delays of one table
 DELAY_MAX_WORK = 1 << 26   # include/uneven_hip.h: samples times delays of one query

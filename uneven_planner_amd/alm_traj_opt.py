@@ -1296,6 +1296,35 @@ class ALMTrajOpt:
         """milliseconds of the kernel(s) of the last footprint_check() (events on the context's stream)"""
         return self._kernel_ms("uph_footprint_check_kernel_ms")
 
+    # ---- how much room the body has along resident trajectories (uph_clearance_check_batch) ------------------------------------------------------------------
+    def clearance(self, layer, traj, below=None, below2=None, t_from=0.0, t_to=None, dt=0.01, with_end=True):
+        """Read the ClearanceLayer `layer` (of this context's map, fresh) at the rollout(dt, with_end) samples of resident trajectory traj[q] with t in
+        [t_from[q], t_to[q]] (scalars are broadcast; t_to = None: to the end): per sample the value v = D at the cell of its point and yaw bin, 0 for a sample
+        outside the grid.  `below` is a distance in metres, converted to below2 = ceil((below / res)^2); below2, in squared cells, is also accepted directly
+        (exactly one of the two).  Returns a dict of arrays over the queries: min_d2 (-1: empty window), min_d = res * sqrt(min_d2) in metres (NaN: empty window,
+        inf: CLEAR_FAR, nothing within rmax), min_t and min_cell (n, 3) of the earliest sample at the min, first_t / last_t of the samples with v < below2 (NaN:
+        none), counts (n, 4: samples, below, outside, far) and below2 as used.  See clearance.clearance_check_rows for the rule."""
+        from . import clearance as _cl
+        tr, n, tf, tt, _ = self._windows(traj, t_from, t_to, None, 0, "clearance")
+        if (below is None) == (below2 is None):
+            raise _lib.UnevenHipError("clearance: give exactly one of below (metres) and below2 (squared cells)")
+        res = float(layer.body_layer.uneven_map.xy_resolution)
+        b2 = _cl.below2_of(below, res) if below2 is None else np.asarray(below2, dtype=np.int32)
+        b2 = np.ascontiguousarray(np.broadcast_to(b2, (n,)), dtype=np.int32)
+        out = dict(min_d2=np.full(n, -1, dtype=np.int32), min_t=np.full(n, np.nan), min_cell=np.full((n, 3), -1, dtype=np.int32), first_t=np.full(n, np.nan),
+                   last_t=np.full(n, np.nan), counts=np.zeros((n, 4), dtype=np.int32))
+        _lib.check(self.L.uph_clearance_check_batch(self.h, layer.h, n, _ip(tr), _dp(tf), None if tt is None else _dp(tt), float(dt), int(bool(with_end)), _ip(b2),
+                                                    _ip(out["min_d2"]), _dp(out["min_t"]), _ip(out["min_cell"]), _dp(out["first_t"]), _dp(out["last_t"]),
+                                                    _ip(out["counts"])), "uph_clearance_check_batch")
+        d2 = out["min_d2"].astype(np.float64)
+        out["min_d"] = np.where(d2 < 0, np.nan, np.where(d2 == _cl.CLEAR_FAR, np.inf, res * np.sqrt(np.maximum(d2, 0.0))))
+        out["below2"] = b2
+        return out
+
+    def clearance_kernel_ms(self):
+        """milliseconds of the kernel(s) of the last clearance() (events on the context's stream)"""
+        return self._kernel_ms("uph_clearance_check_kernel_ms")
+
     # ---- start delays (uph_delay_sweep_batch, uph_delay_extent_batch, uph_delays_batch) ----------------------------------------------------------------
     def delay_sweep(self, traj_a, traj_b, t_from, t_to, radius, delay0, delay_step, D, t0_a=0.0, t0_b=0.0, other=None, dt=0.01):
         """separation() of vehicle a against vehicle b for every start t0_b[q] + delay_times(delay0, delay_step, D)[j] of b, on the device in one call:

@@ -176,6 +176,13 @@ class BodyLayer:
         _lib.check(self.L.uph_body_layer_info(self.h, _dp(sh), C.byref(m), C.byref(lay), C.byref(R), d, C.byref(behind)), "uph_body_layer_info")
         return dict(shape=sh, margin=m.value, layers=lay.value, R=R.value, dims=[int(v) for v in d], behind=behind.value, fresh=behind.value == 0)
 
+    def writes(self):
+        """how often the layer's bytes have been written: build (the one of the constructor included), update and set count one each -- the stamp of a
+        ClearanceLayer"""
+        w = C.c_uint64(0)
+        _lib.check(self.L.uph_body_layer_writes(self.h, C.byref(w)), "uph_body_layer_writes")
+        return int(w.value)
+
     def kernel_ms(self):
         ms = C.c_double(0)
         _lib.check(self.L.uph_body_layer_kernel_ms(self.h, C.byref(ms)), "uph_body_layer_kernel_ms")

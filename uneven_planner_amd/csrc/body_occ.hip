@@ -187,6 +187,8 @@ struct uph_body_layer {
     unsigned long long version = 0;     // the map's occupancy version the bytes were made from
     bool stamped = false;
     int users = 0;                      // search contexts that name the layer
+    int dependants = 0;                 // clearance layers made from the layer
+    unsigned long long writes = 0;      // build, update and set count one each: the stamp of a clearance layer
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double last_ms = 0.0;
 };
@@ -223,6 +225,10 @@ const uph_map* uphBodyLayerMap(const uph_body_layer* l) { return l->map; }
 const char* uphBodyLayerBytes(const uph_body_layer* l) { return l->d_bytes; }
 bool uphBodyLayerFresh(const uph_body_layer* l) { return bodyBehind(l) == 0; }
 void uphBodyLayerUse(uph_body_layer* l, int delta) { l->users += delta; }
+int uphBodyLayerDevice(const uph_body_layer* l) { return l->device; }
+void uphBodyLayerDims(const uph_body_layer* l, int dims3[3]) { dims3[0] = l->nx; dims3[1] = l->ny; dims3[2] = l->nyaw; }
+unsigned long long uphBodyLayerWrites(const uph_body_layer* l) { return l->writes; }
+void uphBodyLayerDepend(uph_body_layer* l, int delta) { l->dependants += delta; }
 
 extern "C" {
 
@@ -297,6 +303,7 @@ int uph_body_layer_build(uph_body_layer* l) {
     BHIPCHK(hipSetDevice(l->device));
     const unsigned long long v = uphMapOccVersion(l->map);
     l->stamped = false;
+    l->writes++;
     const int r = bodyLaunch(l, 0, l->nx, 0, l->ny);
     if (r != UPH_OK) return r;
     l->version = v; l->stamped = true;
@@ -312,6 +319,7 @@ int uph_body_layer_update(uph_body_layer* l, const int32_t rect[4]) {
     if (bodyBehind(l) > 1) { setError(who + ": the layer is more than one occupancy version behind the map: rebuild (uph_body_layer_build)"); return UPH_ERR_INVALID; }
     BHIPCHK(hipSetDevice(l->device));
     const unsigned long long v = uphMapOccVersion(l->map);
+    l->writes++;
     if (rect[0] < rect[1] && rect[2] < rect[3]) {
         const int x0 = std::max(0, rect[0] - l->R), x1 = std::min(l->nx, rect[1] + l->R), y0 = std::max(0, rect[2] - l->R), y1 = std::min(l->ny, rect[3] + l->R);
         l->stamped = false;
@@ -336,6 +344,7 @@ int uph_body_layer_set(uph_body_layer* l, const char* bytes) {
         if (bytes[i] != 0 && bytes[i] != 1) { setError("uph_body_layer_set: layer bytes must be 0 (free) or 1 (occupied)"); return UPH_ERR_INVALID; }
     BHIPCHK(hipSetDevice(l->device));
     l->stamped = false;
+    l->writes++;
     BHIPCHK(hipMemcpy(l->d_bytes, bytes, l->ncell, hipMemcpyHostToDevice));
     l->version = uphMapOccVersion(l->map); l->stamped = true;
     return UPH_OK;
@@ -358,9 +367,16 @@ int uph_body_layer_kernel_ms(const uph_body_layer* l, double* kernel_ms) {
     return UPH_OK;
 }
 
+int uph_body_layer_writes(const uph_body_layer* l, uint64_t* writes) {
+    if (!l || !writes) { setError("uph_body_layer_writes: bad arguments"); return UPH_ERR_INVALID; }
+    *writes = l->writes;
+    return UPH_OK;
+}
+
 int uph_body_layer_destroy(uph_body_layer* l) {
     if (!l) return UPH_OK;
     if (l->users > 0) { setError("uph_body_layer_destroy: a search context still names the layer (uph_kino_set_body_layer(k, NULL) or destroy it first)"); return UPH_ERR_INVALID; }
+    if (l->dependants > 0) { setError("uph_body_layer_destroy: a clearance layer is still made from the layer (uph_clearance_destroy it first)"); return UPH_ERR_INVALID; }
     hipSetDevice(l->device);
     hipFree(l->d_bytes); hipFree(l->d_st);
     if (l->e0) hipEventDestroy(l->e0);

@@ -1,7 +1,7 @@
 // libunevenhip.so -- the queries on the resident trajectories of an optimiser context: rollout, check, locate / within, the switch / trajectory states and
-// separation / extent / conflicts, the same with oriented rectangles, the start delays on a common clock, and the footprint swept over the map's occupancy
-// (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*, uph_extent_batch, uph_conflict*,
-// uph_footprint_*, uph_delay*, uph_footprint_delay*, uph_footprint_check_*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
+// separation / extent / conflicts, the same with oriented rectangles, the start delays on a common clock, the footprint swept over the map's occupancy and the
+// clearance layer read along the windows (include/uneven_hip.h uph_rollout_*, uph_check_*, uph_locate_batch, uph_within_batch, uph_traj_states, uph_separation_*,
+// uph_extent_batch, uph_conflict*, uph_footprint_*, uph_delay*, uph_footprint_delay*, uph_footprint_check_*, uph_clearance_check_*).  Kernels for gfx950 and their host side; the context, its buffers and the solver live in
 // unevenhip.hip (uph_ctx.hpp is what the two share).
 //
 // One skeleton.  Device: the resident batch as a pointer block (ResidentDev), one view of a trajectory (TrajView), one query record per family -- WinQuery: a
@@ -965,6 +965,14 @@ __device__ __forceinline__ bool footCentreIn(const FootCheckGrid& g, int ix, int
     const double dx = Px - Cx, dy = Py - Cy;
     return fabs(dx * c + dy * s) <= hl && fabs(dx * (-s) + dy * c) <= w;
 }
+// the cell (px, py, iw) of a pose's point: check's own floor statements on X, Y and the normalised yaw, kept in double until they are known to fit.  Returns
+// whether the pose fits (finite, every index below 2^30 in magnitude; a NaN yawn: false); one that does not converts constants: (0, 0, -1)
+__device__ __forceinline__ bool footPointCell(const FootCheckGrid& g, double X, double Y, double psi, double yawn, int& px, int& py, int& iw) {
+    const double fpx = floor((X - g.origin[0]) * g.xy_inv), fpy = floor((Y - g.origin[1]) * g.xy_inv), fpw = floor((yawn - g.origin[2]) * g.yaw_inv);
+    const bool fits = footFinite(X, Y, psi) && fabs(fpx) < FOOT_INDEX_MAX && fabs(fpy) < FOOT_INDEX_MAX && fabs(fpw) < FOOT_INDEX_MAX;
+    px = (int)(fits ? fpx : 0.0); py = (int)(fits ? fpy : 0.0); iw = (int)(fits ? fpw : -1.0);
+    return fits;
+}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void uph_footprint_check_kernel(FootCheckArgs a) {
@@ -994,12 +1002,9 @@ __global__ __launch_bounds__(NT) void uph_footprint_check_kernel(FootCheckArgs a
             footHull(X, Y, cs, sn, fq.hl, fq.o, fq.w, Cx, Cy, ex, ey);
             footBoxAxis(Cx, ex, g.origin[0], g.xy_inv, fx0, fx1);
             footBoxAxis(Cy, ey, g.origin[1], g.xy_inv, fy0, fy1);
-            // check's own floor statements on X, Y and the normalised yaw, kept in double until they are known to fit
-            const double fpx = floor((X - g.origin[0]) * g.xy_inv), fpy = floor((Y - g.origin[1]) * g.xy_inv), fpw = floor((yawn - g.origin[2]) * g.yaw_inv);
-            const bool fits = footFinite(X, Y, psi) && fabs(fpx) < FOOT_INDEX_MAX && fabs(fpy) < FOOT_INDEX_MAX && fabs(fpw) < FOOT_INDEX_MAX;     // (a NaN yawn: false)
+            const bool fits = footPointCell(g, X, Y, psi, yawn, px, py, iw);
             ok = fits ? 1 : 0;
             // a pose that does not fit converts zeros: its box is empty.  One that fits has its box within 2^14 columns of its point (the host's limit): the corners fit too
-            px = (int)(fits ? fpx : 0.0); py = (int)(fits ? fpy : 0.0); iw = (int)(fits ? fpw : -1.0);
             bx0 = (int)(fits ? fx0 : 0.0); bx1 = (int)(fits ? fx1 : -1.0); by0 = (int)(fits ? fy0 : 0.0); by1 = (int)(fits ? fy1 : -1.0);
         }
         // stage 2: the wave walks its samples c0 + wave0 + k
@@ -1077,6 +1082,77 @@ __global__ __launch_bounds__(NT) void uph_footprint_check_kernel(FootCheckArgs a
     o.first_cell[1] = cell == FOOT_NO_CELL ? -1 : (int)((unsigned)cell ^ 0x80000000u);
     o.counts[0] = n; o.counts[1] = hit.cnt; o.counts[2] = nxy; o.counts[3] = nyw; o.counts[4] = nout;
     a.out[fq.out] = o;
+}
+
+// ---- clearance check (uph_clearance_check_batch): the window query of the check against a clearance layer (clearance.hip), the squared distance transform of a
+// body layer.  One lane per sample: the cell of the sample's point by the footprint check's own statements (footPointCell), one 16-bit load of D there -- 0 for a
+// sample outside the grid --, then the fold of (value, sample) for the min, a Span for the samples below the query's threshold and two counts.  The leader forms the
+// cell of the min's sample once more, by the same statements.  Reads no terrain cell and no occupancy byte.
+struct ClearQuery : WinQuery {
+    int32_t below2, pad2;       // a sample is below when its value is smaller
+};
+struct ClearOut {               // one row per query
+    double min_t, first_t, last_t;      // NaN: an empty window / no sample below
+    int32_t min_d2, min_cell[3], counts[4];     // -1 and (-1, -1, -1): an empty window; counts: samples, below, outside, far
+};
+struct ClearCheckArgs {
+    ResidentDev r;
+    const ClearQuery* qs;
+    ClearOut* out;
+    const unsigned short* D;    // [nx][ny][nyaw]
+    FootCheckGrid g;
+    int framed, q0;             // as LocArgs
+};
+// the value of the sample at t and its cell: D there, or 0 and `in` = false for a sample outside the grid (a degenerate pose included)
+__device__ __forceinline__ int clearSample(const ClearCheckArgs& a, const TrajView& tr, double t, int& px, int& py, int& iw, bool& in) {
+    TrajSample s;
+    double X, Y;
+    locSample(tr, t, s, X, Y);
+    double psi = s.yaw, yawn = s.yawn;
+    asm volatile("" : "+v"(psi), "+v"(yawn));
+    const FootCheckGrid& g = a.g;
+    const bool fits = footPointCell(g, X, Y, psi, yawn, px, py, iw);
+    in = fits && px >= 0 && py >= 0 && iw >= 0 && px <= g.nx - 1 && py <= g.ny - 1 && iw <= g.nyaw - 1;
+    return in ? (int)a.D[((size_t)px * g.ny + py) * g.nyaw + iw] : 0;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void uph_clearance_check_kernel(ClearCheckArgs a) {
+    const ClearQuery cq = a.qs[a.q0 + blockIdx.x];
+    const TrajView tr = trajView(a.r, cq.b, a.framed != 0, cq.shift);
+    const int n = winCount(cq);
+    int v = WIN_NONE, i = WIN_NONE, nout = 0, nfar = 0;
+    Span below;
+    for (int j = (int)threadIdx.x; j < n; j += NT) {
+        int px, py, iw;
+        bool in;
+        const int d = clearSample(a, tr, winTime(cq, a.r.tt, j), px, py, iw, in);
+        nout += in ? 0 : 1; nfar += d == UPH_CLEAR_FAR ? 1 : 0;
+        if (d < cq.below2) below.take(j);
+        if (d < v) { v = d; i = j; }        // (ascending j: the earliest of equal values stays)
+    }
+    const auto fold = [](int& v, int& i, int& lo, int& hi, int& c, int& no, int& nf, int ov, int oi, int olo, int ohi, int oc, int ono, int onf) {
+        const bool o = ov < v || (ov == v && oi < i);
+        v = o ? ov : v; i = o ? oi : i;
+        SpanFold()(lo, hi, c, olo, ohi, oc);
+        no += ono; nf += onf;
+    };
+    if (!workgroupReduce<NT>(fold, v, i, below.first, below.last, below.cnt, nout, nfar)) return;
+    const double nan = __builtin_nan("");
+    ClearOut o;
+    o.min_d2 = -1; o.min_t = nan;
+    o.min_cell[0] = o.min_cell[1] = o.min_cell[2] = -1;
+    if (i != WIN_NONE) {
+        int px, py, iw;
+        bool in;
+        o.min_t = winTime(cq, a.r.tt, i);
+        o.min_d2 = clearSample(a, tr, o.min_t, px, py, iw, in);
+        if (in) { o.min_cell[0] = px; o.min_cell[1] = py; o.min_cell[2] = iw; }
+    }
+    o.first_t = below.cnt == 0 ? nan : winTime(cq, a.r.tt, below.first);
+    o.last_t = below.cnt == 0 ? nan : winTime(cq, a.r.tt, below.last);
+    o.counts[0] = n; o.counts[1] = below.cnt; o.counts[2] = nout; o.counts[3] = nfar;
+    a.out[cq.out] = o;
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -2115,6 +2191,53 @@ int uph_footprint_check_batch(uph_ctx* c, int32_t n, const int32_t* traj, const 
 
 int uph_footprint_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
     return kernelMs("uph_footprint_check_kernel_ms", c, &uph_ctx::last_foot_check_ms, kernel_ms);
+}
+
+// ---- clearance check (include/uneven_hip.h uph_clearance_check_*) ------------------------------------------------------------------------------------------
+int uph_clearance_check_batch(uph_ctx* c, uph_clearance* layer, int32_t n, const int32_t* traj, const double* t_from, const double* t_to, double dt, int32_t with_end,
+                              const int32_t* below2, int32_t* min_d2, double* min_t, int32_t* min_cell, double* first_t, double* last_t, int32_t* counts) {
+    const std::string who = "uph_clearance_check_batch";
+    if (!c || !layer || n <= 0 || !traj || !t_from || !below2) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    const uph_body_layer* body = uphClearanceBody(layer);
+    if (uphBodyLayerMap(body) != c->map) { setError(who + ": the clearance layer belongs to another map than the context's"); return UPH_ERR_INVALID; }
+    if (!uphClearanceFresh(layer)) { setError(who + ": the clearance layer is behind its body layer (uph_clearance_update with the rewritten rect, or uph_clearance_build)"); return UPH_ERR_INVALID; }
+    if (!uphBodyLayerFresh(body)) { setError(who + ": the body layer is behind the map's occupancy (uph_body_layer_update / uph_body_layer_build, then the clearance layer's)"); return UPH_ERR_INVALID; }
+    std::vector<ClearQuery> qs;
+    int r = formWindowQueries(c, n, traj, t_from, t_to, dt, with_end, who.c_str(), qs, [&](int32_t q, ClearQuery& k) {
+        if (below2[q] < 0) { setError(whoQuery(who, q) + " has a negative below2"); return (int)UPH_ERR_INVALID; }
+        k.below2 = below2[q]; k.pad2 = 0;
+        return (int)UPH_OK;
+    });
+    if (r != UPH_OK) return r;
+    GridDev grid;
+    r = syncGridMem(c, grid);
+    if (r != UPH_OK) return r;
+    if (c->d_win_out.ensure(sizeof(ClearOut) * (size_t)n)) return UPH_ERR_HIP;
+    ClearCheckArgs a;
+    a.r = residentDev(c); a.qs = c->d_win_q.as<ClearQuery>(); a.out = c->d_win_out.as<ClearOut>(); a.framed = trajFrame(c); a.q0 = 0;
+    a.D = uphClearanceValues(layer);
+    // a body layer is made of a whole-grid map (no tile): the layer's dimensions are the grid's
+    a.g.nx = grid.nx; a.g.ny = grid.ny; a.g.nyaw = grid.nyaw; a.g.x_off = 0; a.g.nx_hold = grid.nx;
+    for (int d = 0; d < 3; d++) a.g.origin[d] = grid.origin[d];
+    a.g.xy_res = grid.xy_res; a.g.xy_inv = grid.xy_inv; a.g.yaw_inv = grid.yaw_inv;
+    std::vector<ClearOut> out((size_t)n);
+    const auto work = [&](size_t q) { return qs[q].n_tab + qs[q].end_row; };
+    r = runQueryLaunch(c, twoWidths(c, (size_t)n, work, a, uph_clearance_check_kernel<256>, uph_clearance_check_kernel<64>), out, c->last_clear_check_ms);
+    if (r != UPH_OK) return r;
+    for (int32_t q = 0; q < n; q++) {
+        const ClearOut& o = out[(size_t)q];
+        if (min_d2) min_d2[q] = o.min_d2;
+        if (min_t) min_t[q] = o.min_t;
+        if (min_cell) for (int k = 0; k < 3; k++) min_cell[3 * (size_t)q + k] = o.min_cell[k];
+        if (first_t) first_t[q] = o.first_t;
+        if (last_t) last_t[q] = o.last_t;
+        if (counts) for (int k = 0; k < 4; k++) counts[4 * (size_t)q + k] = o.counts[k];
+    }
+    return UPH_OK;
+}
+
+int uph_clearance_check_kernel_ms(const uph_ctx* c, double* kernel_ms) {
+    return kernelMs("uph_clearance_check_kernel_ms", c, &uph_ctx::last_clear_check_ms, kernel_ms);
 }
 
 // ---- start delays (include/uneven_hip.h) -----------------------------------------------------------------------------------------------------------------

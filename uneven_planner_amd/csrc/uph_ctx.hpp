@@ -117,6 +117,7 @@ struct uph_ctx {
     double last_delay_ms = 0.0;            // the kernels of the last of those three calls (events on the context's stream)
     double last_foot_ms = 0.0;             // the kernels of the last uph_footprint_separation_batch or uph_footprint_conflicts_batch (events on the context's stream)
     double last_foot_check_ms = 0.0;       // the kernel(s) of the last uph_footprint_check_batch (events on the context's stream)
+    double last_clear_check_ms = 0.0;      // the kernel(s) of the last uph_clearance_check_batch (events on the context's stream)
     int trace_cap = 0;                      // requested for the next upload
     int trace_cap_up = 0;                   // what the uploaded batch's trace buffer was sized for
     std::vector<TrajState> state_host;

@@ -28,6 +28,17 @@ const uph_map* uphBodyLayerMap(const uph_body_layer* l);
 const char* uphBodyLayerBytes(const uph_body_layer* l);
 bool uphBodyLayerFresh(const uph_body_layer* l);
 void uphBodyLayerUse(uph_body_layer* l, int delta);
+// what the clearance layer (clearance.hip) needs of the body layer it is made from: the device it lives on, its dimensions, its write count (build, update and
+// set count one each), and the count of clearance layers that name it (uph_body_layer_destroy refuses while it is not zero)
+int uphBodyLayerDevice(const uph_body_layer* l);
+void uphBodyLayerDims(const uph_body_layer* l, int dims3[3]);
+unsigned long long uphBodyLayerWrites(const uph_body_layer* l);
+void uphBodyLayerDepend(uph_body_layer* l, int delta);
+// the clearance layer as the query (traj_query.hip) reads it: its body layer, its device values [nx][ny][nyaw], whether it was made from the body layer's bytes
+// as they are now
+const uph_body_layer* uphClearanceBody(const uph_clearance* l);
+const unsigned short* uphClearanceValues(const uph_clearance* l);
+bool uphClearanceFresh(const uph_clearance* l);
 
 // scope guards for the temporaries of the extern "C" entry points: every early return (HIPCHK) releases them
 struct UphDevTmp {
