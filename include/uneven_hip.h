@@ -936,6 +936,32 @@ int uph_clearance_check_batch(uph_ctx* c, uph_clearance* layer, int32_t n, const
 /* milliseconds of the kernel(s) of the last uph_clearance_check_batch of c (events on the context's stream) */
 int uph_clearance_check_kernel_ms(const uph_ctx* c, double* kernel_ms);
 
+/* ---- the clearance term: a soft cost in the optimiser's objective that keeps the solve off obstacles.  The check reports a hit and the body search
+ * finds a path where the body fits; without this term the solve that follows has point terms only and pulls the path back onto the obstacle.
+ *   the field      c(x, y, yaw) in metres, from a clearance layer of polarity UPH_CLEAR_TO_OCCUPIED:
+ *                    yaw slice   iw by the footprint check's floor statement on the NORMALISED yaw.  The field is piecewise constant in yaw: it has no yaw gradient.
+ *                    cell value  d(cell) = res * sqrt(min(D, rmax^2 + 1)): UPH_CLEAR_FAR reads as the first distance beyond the disc, so the truncated field is
+ *                                continuous and bounded
+ *                    in xy       bilinear between the four nearest cell centres: u = (x - origin_x) / res - 0.5, i0 = floor(u), fx = u - i0, the same in y; the four
+ *                                corner indices are clamped to the grid (the border itself enters through the body layer's UPH_FOOT_OUTSIDE bit)
+ *                    gradient    (dc/dx, dc/dy): the exact gradient of the bilinear patch
+ *                    degenerate  a pose that is not finite or whose index is at or above 2^30: value and gradient 0, no float-to-int conversion is executed
+ *                  uph_clearance_field evaluates it at n poses (one lane per pose; UPH_ERR_INVALID for a layer of polarity UPH_CLEAR_TO_FREE).
+ *   the term       at every sample j of a piece (the K + 1 quadrature samples the surface-variation cost rho_ter * sigma^2 is summed over, with its weights):
+ *                  g = d_safe - c(position, yaw); where g > 0 the sample adds  om * g^2  to the cost, with om = (j == 0 or j == K ? 0.5 : 1) * weight * step * scale_fx,
+ *                  and -2 om g grad c to the position gradient; everything behind that (time gradient, way-point gradient) is the objective's own machinery.
+ *                  It is a cost, not a constraint: no multiplier, no residual, nothing in the stop rule; scale_fx and the constraint scales of initScaling do not see
+ *                  it.  It says nothing between samples, and nothing about yaw within a slice.
+ * uph_ctx_set_clearance_term persists on the context and applies to every later evaluation (uph_batch_eval), solve and uph_penalty_batch of it, whoever uploaded the
+ * batch (uph_optimize_batch, uph_plan_upload, uph_replan_upload, uph_refine_upload as dst); layer == NULL switches it off, and off is the code without the term.
+ * uph_clearance_destroy is refused while a context names the layer.  Refused with UPH_ERR_INVALID and a message, when the term is set or -- for what depends on the
+ * batch -- at the launch, before anything is launched: a layer of polarity UPH_CLEAR_TO_FREE; a layer on another map; d_safe <= 0, weight < 0 or a value that is not
+ * finite; d_safe > res * rmax (a cell with no obstacle within rmax must never be penalised); a clearance layer behind its body layer or a body layer behind the
+ * map ("rebuild"); 64 lanes per trajectory; the fp32 sample mode; the L-BFGS resume hook; a batch with per-trajectory local frames (tile / km^2 maps). */
+int uph_ctx_set_clearance_term(uph_ctx* c, uph_clearance* layer /* NULL: off */, double d_safe, double weight);
+int uph_ctx_clearance_term(const uph_ctx* c, uph_clearance** layer, double* d_safe, double* weight);     /* any output may be NULL; layer NULL: off */
+int uph_clearance_field(uph_clearance* l, int32_t n, const double* pos /* [n][3]: x, y, yaw */, double* value /* [n] */, double* grad /* [n][2] */);
+
 /* ---- start delays: clearing conflicts between resident trajectories without a new solve.  A vehicle that starts later drives the very same trajectory, so
  * every terrain term uph_check_batch has passed stays passed; only its start on the common clock moves.  Every number below is one uph_separation_batch /
  * uph_extent_batch returns for the shifted start, bit for bit.

@@ -19,6 +19,7 @@
 //   refineSE2TrajBatch             the rest of the last batch's trajectories re-optimised from states at switch times, no search (uph_refine_upload)
 //   checkSE2TrajBatch              time windows of the last batch's trajectories held against limits on the map as it is now (uph_check_batch)
 //   footprintCheckSE2TrajBatch     the same windows with the vehicle's rectangle swept over the map's occupancy: first / last hit and where (uph_footprint_check_batch)
+//   setClearanceTerm               a soft cost on the clearance field of a ClearanceLayer in every later solve (uph_ctx_set_clearance_term)
 //   clearanceSE2TrajBatch          the same windows read in a ClearanceLayer, the distance transform of a BodyLayer: how close, when and where (uph_clearance_check_batch)
 //
 // The matrix/vector types are template parameters: anything with data(), rows(), cols()/size() and column-major storage works
@@ -783,6 +784,20 @@ public:
     };
     TrajClearance clearanceSE2TrajBatch(const ClearanceLayer& layer, const std::vector<int>& traj, const std::vector<double>& t_from, const std::vector<double>& t_to,
                                         const std::vector<int32_t>& below2, double dt = 0.01, bool with_end = true);
+    // ---- the clearance term of the objective (uph_ctx_set_clearance_term, no counterpart in the reference): every sample closer than d_safe metres to an
+    // obstacle of `layer` (polarity UPH_CLEAR_TO_OCCUPIED, of this map, fresh) adds weight * step * scale_fx * (d_safe - c)^2 to the cost.  Persists on the
+    // context -- until setEnvironment makes a new one -- and applies to every later solve, whoever uploaded the batch; nullptr switches it off.  The layer
+    // must outlive the term: its destruction is refused while the context names it.
+    struct ClearanceTerm {
+        uph_clearance* layer = nullptr;     // nullptr: off
+        double d_safe = 0.0, weight = 0.0;
+    };
+    void setClearanceTerm(const ClearanceLayer* layer, double d_safe = 0.0, double weight = 0.0);
+    ClearanceTerm clearanceTerm() const {
+        ClearanceTerm t;
+        if (uph_ctx_clearance_term(ctx_, &t.layer, &t.d_safe, &t.weight) != UPH_OK) throw std::runtime_error(std::string("uph_ctx_clearance_term: ") + uph_last_error());
+        return t;
+    }
     // ---- clearing conflicts by starting later.  A delayed vehicle drives the same trajectory, so nothing the check has passed changes; the delays are
     // delta_j = delay0 + j * delay_step, 0 <= j < D.  separationSE2TrajBatch of a against b started at t0_b[q] + delta_j, for every j, in one call
     // (uph_delay_sweep_batch).
@@ -1213,11 +1228,28 @@ public:
         if (uph_clearance_kernel_ms(l_, &ms) != UPH_OK) throw std::runtime_error(std::string("uph_clearance_kernel_ms: ") + uph_last_error());
         return ms;
     }
+    // the continuous field the clearance term reads (uph_clearance_field): value [n] in metres and gradient [n] = {dc/dx, dc/dy} at poses {x, y, yaw}
+    struct Field {
+        std::vector<double> value;
+        std::vector<std::array<double, 2>> grad;
+    };
+    Field field(const std::vector<std::array<double, 3>>& pos) const {
+        Field f;
+        f.value.assign(pos.size(), 0.0); f.grad.assign(pos.size(), std::array<double, 2>{0.0, 0.0});
+        if (!pos.empty() && uph_clearance_field(l_, (int32_t)pos.size(), pos[0].data(), f.value.data(), f.grad[0].data()) != UPH_OK)
+            throw std::runtime_error(std::string("uph_clearance_field: ") + uph_last_error());
+        return f;
+    }
     uph_clearance* handle() const { return l_; }
 
 private:
     uph_clearance* l_ = nullptr;
 };
+
+inline void ALMTrajOpt::setClearanceTerm(const ClearanceLayer* layer, double d_safe, double weight) {
+    if (uph_ctx_set_clearance_term(ctx_, layer ? layer->handle() : nullptr, d_safe, weight) != UPH_OK)
+        throw std::runtime_error(std::string("uph_ctx_set_clearance_term: ") + uph_last_error());
+}
 
 inline ALMTrajOpt::TrajClearance ALMTrajOpt::clearanceSE2TrajBatch(const ClearanceLayer& layer, const std::vector<int>& traj, const std::vector<double>& t_from,
                                                                    const std::vector<double>& t_to, const std::vector<int32_t>& below2, double dt, bool with_end) {

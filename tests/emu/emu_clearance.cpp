@@ -1,0 +1,72 @@
+// TEST SCAFFOLDING -- not part of the product.  The emulator of emu_solver.cpp with one addition for the clearance-term tests: one objective evaluation of
+// the workgroup program instantiated WITH the term (Solver<HostWG, double, true>), the layer's values and the term's descriptor given by the caller.  The
+// descriptor lies behind OptParams in the block BatchDev::params_mem points to, as the library lays it out.
+#include "emu_solver.cpp"
+
+extern "C" {
+
+// the shared field function itself (clearance_dev.hpp), on the emulator's grid: pos [n][3] -> value [n], grad [n][2]
+void emu_clear_field(void* h, const unsigned short* D, int rmax, const double* pos, int n, double* value, double* grad) {
+    Emu* e = (Emu*)h;
+    const ClearGeom g = clearGeom(e->grid, rmax);
+    for (int i = 0; i < n; i++) clearanceField(g, D, pos[3 * i], pos[3 * i + 1], normSO2(pos[3 * i + 2]), value[i], grad[2 * i], grad[2 * i + 1]);
+}
+
+// one evaluation at x with duals, scales, rho and scale_fx as given (emu_run's mode 0).  on == 0: the plain program (CLR = false), D unread.
+// out: f, g [n], c_xy, c_yaw, T_xy / T_yaw in scal[4..5]
+void emu_clear_eval(void* h, int on, const unsigned short* D, int rmax, double d_safe, double weight, int n_inner_xy, int n_inner_yaw, const double* init_xy,
+                    const double* end_xy, const double* init_yaw, const double* end_yaw, const double* x_in, double* g_out, const double* lambda_in,
+                    const double* mu_in, const double* scale_cx_in, double* cxy_out, double* cyaw_out, double* scal) {
+    Emu* e = (Emu*)h;
+    TrajDesc td;
+    std::memset(&td, 0, sizeof(td));
+    td.Nxy = n_inner_xy + 1; td.Nyaw = n_inner_yaw + 1;
+    td.n = 2 * n_inner_xy + n_inner_yaw + 1; td.S = td.Nxy * (e->P.int_K + 1);
+    td.op_xy = 0; td.op_yaw = 1;
+    for (int k = 0; k < 6; k++) { td.init_xy[k] = init_xy[k]; td.end_xy[k] = end_xy[k]; }
+    for (int k = 0; k < 3; k++) { td.init_yaw[k] = init_yaw[k]; td.end_yaw[k] = end_yaw[k]; }
+    const int S = td.S, n = td.n;
+    std::vector<double> Mt0, Mr0, Mt1, Mr1;
+    buildMincoOp(td.Nxy, Mt0, Mr0);
+    buildMincoOp(td.Nyaw, Mt1, Mr1);
+    MincoOp ops[2] = {{td.Nxy, Mt0.data(), Mr0.data()}, {td.Nyaw, Mt1.data(), Mr1.data()}};
+    TrajState st;
+    std::memset(&st, 0, sizeof(st));
+    st.rho = scal[0]; st.scale_fx = scal[1];
+    std::vector<double> dual(7 * S), res(7 * S, 0.0), scl(7 * S), xg(x_in, x_in + n), x0copy(xg), gout(n, 0.0), cxy(12 * td.Nxy), cyaw(6 * td.Nyaw);
+    std::vector<double> hist((size_t)e->P.mem_size * histRowDoubles(n), 0.0), rep(7, 0.0), thomasTab, rsd(n, 0.0), rs(24, 0.0);
+    for (int s = 0; s < S; s++) {
+        dual[s] = lambda_in[s];
+        for (int q = 0; q < 6; q++) dual[(q + 1) * S + s] = mu_in[6 * s + q];
+        for (int q = 0; q < 7; q++) scl[q * S + s] = scale_cx_in[7 * s + q];
+    }
+    buildThomasTable(thomasTab);
+    // [OptParams | ClearTermDev], suitably aligned
+    std::vector<unsigned long long> block((sizeof(OptParams) + sizeof(ClearTermDev)) / 8 + 1, 0ull);
+    ClearTermDev cd;
+    std::memset(&cd, 0, sizeof(cd));
+    cd.D = D; cd.rmax = rmax; cd.d_safe = d_safe; cd.weight = weight;
+    std::memcpy(block.data(), &e->P, sizeof(OptParams));
+    std::memcpy((char*)block.data() + sizeof(OptParams), &cd, sizeof(ClearTermDev));
+    BatchDev bd;
+    std::memset(&bd, 0, sizeof(bd));
+    bd.B = 1; bd.desc = &td; bd.state = &st; bd.ops = ops; bd.x = xg.data(); bd.x0 = x0copy.data(); bd.gout = gout.data(); bd.dual = dual.data(); bd.res = res.data();
+    bd.scl = scl.data(); bd.cxy = cxy.data(); bd.cyaw = cyaw.data(); bd.hist = hist.data(); bd.thomas = thomasTab.data(); bd.report = rep.data();
+    bd.rs_d = rsd.data(); bd.rs = rs.data();
+    bd.params_mem = (const OptParams*)block.data();
+    std::vector<double> lds(Solver<HostWG>::ldsDoubles(td.Nxy, td.Nyaw, n, g_lanes, e->P.mem_size, e->P.int_K) + 64);
+    HostWG wg;
+    if (on) {
+        Solver<HostWG, double, true> sol(wg, e->grid, e->P, bd, 0, lds.data());
+        sol.evalOnly(st, 1);
+    } else {
+        Solver<HostWG> sol(wg, e->grid, e->P, bd, 0, lds.data());
+        sol.evalOnly(st, 1);
+    }
+    std::memcpy(g_out, gout.data(), 8 * n);
+    std::memcpy(cxy_out, cxy.data(), 8 * cxy.size());
+    std::memcpy(cyaw_out, cyaw.data(), 8 * cyaw.size());
+    scal[2] = st.f; scal[3] = st.jerk_cost; scal[4] = st.T_xy; scal[5] = st.T_yaw;
+}
+
+}  // extern "C"

@@ -236,6 +236,9 @@ SYMBOLS = {
     "uph_clearance_check_batch": (C.c_int, [_VP, _VP, _I32, C.POINTER(_I32), DP, DP, C.c_double, _I32, C.POINTER(_I32), C.POINTER(_I32), DP, C.POINTER(_I32), DP, DP,
                                             C.POINTER(_I32)]),
     "uph_clearance_check_kernel_ms": (C.c_int, [_VP, DP]),
+    "uph_ctx_set_clearance_term": (C.c_int, [_VP, _VP, C.c_double, C.c_double]),
+    "uph_ctx_clearance_term": (C.c_int, [_VP, C.POINTER(_VP), DP, DP]),
+    "uph_clearance_field": (C.c_int, [_VP, _I32, DP, DP, DP]),
 }
 
 _LIB = None

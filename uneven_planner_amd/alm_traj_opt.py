@@ -692,6 +692,7 @@ class ALMTrajOpt:
         if self.h:
             self.L.uph_ctx_destroy(self.h)
             self.h = None
+        self._clear_layer = None          # (a clearance term lived on the old context; released behind it: the layer cannot be closed while named)
         p = _lib.OptParams(**{k: (int(getattr(self, k)) if k in _INT_FIELDS else float(getattr(self, k))) for k in self._pnames})
         h = C.c_void_p()
         _lib.check(self.L.uph_ctx_create(env.h, C.byref(p), C.byref(h)), "uph_ctx_create")
@@ -711,6 +712,20 @@ class ALMTrajOpt:
     def set_sample_precision(self, bits):
         """32: fp32 arithmetic in the sample phase of the objective (configs[4] "fp32"; no 1e-9 parity with the double-only reference); 64: default"""
         _lib.check(self.L.uph_ctx_set_sample_precision(self.h, int(bits)), "uph_ctx_set_sample_precision")
+
+    def set_clearance_term(self, layer, d_safe=0.0, weight=0.0):
+        """The clearance term of the objective (uph_ctx_set_clearance_term): every sample closer than d_safe metres to an obstacle of the
+        ClearanceLayer `layer` (polarity CLEAR_TO_OCCUPIED, of this context's map, fresh) adds weight * step * scale_fx * (d_safe - c)^2 to the cost.  It
+        persists on the context (until setEnvironment makes a new one) and applies to every later evaluation, solve and penalty_batch, whoever uploaded
+        the batch; layer = None switches it off.  The layer cannot be closed while the context names it.  See clearance.clearance_term_rows for the rule."""
+        _lib.check(self.L.uph_ctx_set_clearance_term(self.h, None if layer is None else layer.h, float(d_safe), float(weight)), "uph_ctx_set_clearance_term")
+        self._clear_layer = layer
+
+    def clearance_term(self):
+        """(layer, d_safe, weight) of the clearance term; layer is None when it is off"""
+        h, d, w = C.c_void_p(), C.c_double(0), C.c_double(0)
+        _lib.check(self.L.uph_ctx_clearance_term(self.h, C.byref(h), C.byref(d), C.byref(w)), "uph_ctx_clearance_term")
+        return (getattr(self, "_clear_layer", None) if h.value else None), d.value, w.value
 
     def set_rho(self, rho):
         _lib.check(self.L.uph_ctx_set_rho(self.h, float(rho)), "uph_ctx_set_rho")

@@ -2,7 +2,8 @@
 body layer, one field per yaw slice, built and updated in a rect on the device and read along resident trajectories by ALMTrajOpt.clearance.
 
 `ClearanceLayer` binds the device object.  `clearance_rows`, `clearance_brute`, `clearance_check_rows` and `grow_rect_rows` are numpy mirrors written from the
-rule, for tests and for callers who want the field of a hypothetical layer on the host; they need no device."""
+rule, for tests and for callers who want the field of a hypothetical layer on the host; they need no device.  `clearance_field` and `clearance_term_rows`
+mirror the continuous field made of the values and the clearance term of the objective that reads it."""
 import ctypes as C
 
 import numpy as np
@@ -133,6 +134,111 @@ def below2_of(below, res):
     return np.minimum(np.ceil((b / float(res)) ** 2), 2.0 ** 31 - 1).astype(np.int32)
 
 
+def layer_geometry(uneven_map):
+    """the `geometry` the field's mirrors take, of a map: (origin (3,), xy_resolution, yaw_resolution)"""
+    return (np.asarray(uneven_map.map_origin, dtype=np.float64).copy(), float(uneven_map.xy_resolution), float(uneven_map.yaw_resolution))
+
+
+def _norm_so2(yaw):
+    """UnevenMap::normSO2 as the device runs it: + / - 2 pi until the angle lies in [-pi, pi], at most 4096 times each way; a NaN or an infinity stays"""
+    y = np.array(yaw, dtype=np.float64).reshape(-1)
+    two_pi = 2 * 3.14159265358979323846
+    with np.errstate(invalid="ignore"):
+        for _ in range(4096):
+            m = y < -3.14159265358979323846
+            if not m.any():
+                break
+            y[m] += two_pi
+        for _ in range(4096):
+            m = y > 3.14159265358979323846
+            if not m.any():
+                break
+            y[m] -= two_pi
+    return y
+
+
+def clearance_field(D, geometry, rmax, pos):
+    """Host mirror of uph_clearance_field (csrc/clearance_dev.hpp), written from the rule: the continuous clearance c in metres and its gradient (dc/dx, dc/dy)
+    at pos (n, 3) = x, y, yaw from the values D [nx][ny][nyaw] of a layer of polarity CLEAR_TO_OCCUPIED; geometry = layer_geometry(map).
+      yaw slice   iw = floor((normSO2(yaw) - origin_w) / yaw_res): piecewise constant in yaw, no yaw gradient
+      cell value  d = res * sqrt(min(D, rmax^2 + 1)): CLEAR_FAR reads as the first distance beyond the disc
+      in xy       bilinear between the four nearest cell centres, u = (x - origin_x) / res - 0.5, i0 = floor(u), fx = u - i0; indices clamped to the grid
+      degenerate  a pose that is not finite or whose index reaches 2^30: value and gradient 0
+    The quotients are products with 1 / res and 1 / yaw_res, the reciprocals the grid holds, and every operation is the device's in its order.
+    Returns (c (n,), grad (n, 2))."""
+    origin, res, yaw_res = geometry
+    D = np.asarray(D)
+    nx, ny, nyaw = D.shape
+    p = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    x, y, w = p[:, 0], p[:, 1], _norm_so2(p[:, 2])
+    xy_inv, yaw_inv = 1.0 / res, 1.0 / yaw_res
+    with np.errstate(invalid="ignore", over="ignore"):
+        u, v = (x - origin[0]) * xy_inv - 0.5, (y - origin[1]) * xy_inv - 0.5
+        fu, fv, fw = np.floor(u), np.floor(v), np.floor((w - origin[2]) * yaw_inv)
+        lim30 = 1073741824.0
+        ok = np.isfinite(x) & np.isfinite(y) & np.isfinite(w) & (np.abs(fu) < lim30) & (np.abs(fv) < lim30) & (np.abs(fw) < lim30)
+        fx, fy = np.where(ok, u - fu, 0.0), np.where(ok, v - fv, 0.0)
+    i0, j0, k0 = (np.where(ok, f, 0.0).astype(np.int64) for f in (fu, fv, fw))
+    xa, xb = np.clip(i0, 0, nx - 1), np.clip(i0 + 1, 0, nx - 1)
+    ya, yb = np.clip(j0, 0, ny - 1), np.clip(j0 + 1, 0, ny - 1)
+    iw = np.clip(k0, 0, nyaw - 1)
+    lim = int(rmax) * int(rmax) + 1
+    m = [res * np.sqrt(np.minimum(D[a, b, iw].astype(np.int64), lim).astype(np.float64)) for a, b in ((xa, ya), (xb, ya), (xa, yb), (xb, yb))]
+    lo, hi = m[0] * (1.0 - fx) + m[1] * fx, m[2] * (1.0 - fx) + m[3] * fx
+    c = lo * (1.0 - fy) + hi * fy
+    gx = ((m[1] - m[0]) * (1.0 - fy) + (m[3] - m[2]) * fy) * xy_inv
+    gy = (hi - lo) * xy_inv
+    return np.where(ok, c, 0.0), np.stack([np.where(ok, gx, 0.0), np.where(ok, gy, 0.0)], axis=1)
+
+
+def clearance_term_rows(D, geometry, rmax, d_safe, weight, c_xy, c_yaw, T_xy, T_yaw, K, scale_fx=1.0):
+    """Host mirror of what the clearance term (uph_ctx_set_clearance_term) adds to calConstrainCostGrad for ONE trajectory, from its downloaded piece
+    coefficients c_xy (6 Nxy, 2), c_yaw (6 Nyaw,) and piece durations, at the reference's own sample times: piece i, sample j = 0 .. K sits at the running sums
+    s1 (s1 += T_xy / K) and base (base += T_xy); its yaw comes from yaw piece min(int((s1 + base) / T_yaw), Nyaw - 1).  With g = d_safe - c(pos, yaw) and
+    om = (0.5 at j = 0 and j = K, else 1) * weight * (T_xy / K) * scale_fx, a sample with g > 0 adds om g^2 to the cost and grad_p = -2 om g grad c.
+    Returns a dict: cost; gdCxy (6 Nxy, 2) = per piece sum_j beta0(s1_j) (x) grad_p_j; gdT = the added sum of the time gradients of the xy pieces, sum_j
+    om g^2 / K + (grad_p . vel) j / K (the yaw pieces get none); c (Nxy, K + 1) the field at the samples; below (Nxy, K + 1) = g > 0."""
+    c_xy = np.asarray(c_xy, dtype=np.float64).reshape(-1, 2)
+    c_yaw = np.asarray(c_yaw, dtype=np.float64).reshape(-1)
+    Nxy, Nyaw, K = c_xy.shape[0] // 6, c_yaw.shape[0] // 6, int(K)
+    step = T_xy / K
+    s1 = np.zeros(K + 1)
+    for j in range(1, K + 1):
+        s1[j] = s1[j - 1] + step
+    base = np.zeros(Nxy)
+    for i in range(1, Nxy):
+        base[i] = base[i - 1] + T_xy
+    pw = np.stack([s1 ** 0, s1, s1 * s1, (s1 * s1) * s1, (s1 * s1) * (s1 * s1), ((s1 * s1) * (s1 * s1)) * s1], axis=1)       # (K + 1, 6): beta0
+    dpw = np.stack([0 * s1, s1 ** 0, 2.0 * s1, 3.0 * (s1 * s1), 4.0 * ((s1 * s1) * s1), 5.0 * ((s1 * s1) * (s1 * s1))], axis=1)
+    cx = c_xy.reshape(Nxy, 6, 2)
+    pos, vel = np.zeros((Nxy, K + 1, 2)), np.zeros((Nxy, K + 1, 2))
+    for k in range(6):                                          # the device's summation order
+        pos += cx[:, None, k, :] * pw[None, :, k, None]
+        vel += cx[:, None, k, :] * dpw[None, :, k, None]
+    now = s1[None, :] + base[:, None]
+    yi = np.clip((now / T_yaw).astype(np.int64), 0, Nyaw - 1)      # (the device's quotient from the stored reciprocal is the rounded quotient as well)
+    u = now - yi * T_yaw
+    cy = c_yaw.reshape(Nyaw, 6)[yi]
+    yaw = np.zeros_like(now)
+    up = np.ones_like(now)
+    for k in range(6):
+        yaw += cy[..., k] * up
+        up = up * u
+    pose = np.concatenate([pos.reshape(-1, 2), yaw.reshape(-1, 1)], axis=1)
+    c, gc = clearance_field(D, geometry, rmax, pose)
+    c, gc = c.reshape(Nxy, K + 1), gc.reshape(Nxy, K + 1, 2)
+    g = d_safe - c
+    below = g > 0.0
+    half = np.where((np.arange(K + 1) == 0) | (np.arange(K + 1) == K), 0.5, 1.0)
+    om = half * weight * step * scale_fx
+    cc = np.where(below, om[None, :] * g * g, 0.0)
+    gp = np.where(below[..., None], -(2.0 * om[None, :, None] * g[..., None] * gc), 0.0)
+    alpha = (1.0 / K) * np.arange(K + 1)
+    gdT = float(np.sum(cc / K + (gp * vel).sum(axis=2) * alpha[None, :]))
+    gdC = np.einsum("jk,ijd->ikd", pw, gp).reshape(6 * Nxy, 2)
+    return dict(cost=float(cc.sum()), gdCxy=gdC, gdT=gdT, c=c, below=below)
+
+
 class ClearanceLayer:
     def __init__(self, body_layer, rmax, polarity=CLEAR_TO_OCCUPIED):
         """the distance transform of body_layer truncated at rmax cells (1 .. CLEAR_MAX_R), built from the body layer's bytes as they are now.  The body layer
@@ -166,6 +272,16 @@ class ClearanceLayer:
         d = (C.c_int32 * 3)()
         _lib.check(self.L.uph_clearance_info(self.h, C.byref(rmax), C.byref(pol), d, C.byref(behind)), "uph_clearance_info")
         return dict(rmax=rmax.value, polarity=pol.value, dims=[int(v) for v in d], behind=behind.value, fresh=behind.value == 0)
+
+    def field(self, pos):
+        """uph_clearance_field: the continuous clearance c (n,) in metres and its gradient (n, 2) at pos (n, 3) = x, y, yaw, on the device -- the field the
+        clearance term of the objective reads (ALMTrajOpt.set_clearance_term).  See clearance_field for the rule."""
+        p = np.ascontiguousarray(np.asarray(pos, dtype=np.float64).reshape(-1, 3))
+        n = p.shape[0]
+        c, g = np.zeros(n), np.zeros((n, 2))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _lib.check(self.L.uph_clearance_field(self.h, n, dp(p), dp(c), dp(g)), "uph_clearance_field")
+        return c, g
 
     def kernel_ms(self):
         ms = C.c_double(0)

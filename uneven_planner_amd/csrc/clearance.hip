@@ -6,13 +6,15 @@
 // Reference: there is none.  UnevenMap keeps occupancy bits only (uneven_map.h:471-500) and the optimiser has no obstacle term; this is the field such a term
 // would read.
 //
-// Two parts: the two kernels of the separable evaluation (integers only), the layer object with its freshness stamp towards the body layer.
+// Two parts: the two kernels of the separable evaluation (integers only), the layer object with its freshness stamp towards the body layer.  And the
+// continuous field made of the values (clearance_dev.hpp), which the clearance term of the solve kernel reads: uph_clearance_field evaluates it at poses.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 
 #include "../../include/uneven_hip.h"
+#include "clearance_dev.hpp"
 #include "uph_internal.hpp"
 
 using namespace uph;
@@ -100,6 +102,17 @@ __global__ __launch_bounds__(CLEAR_NT) void uph_clearance_cols_kernel(ClearArgs 
     a.D[(size_t)ix * stride + col] = (unsigned short)(best < lim ? best : UPH_CLEAR_FAR);
 }
 
+// the continuous field at n poses (clearance_dev.hpp clearanceField): one lane per pose, the yaw normalised as the solve kernel normalises it (normSO2)
+__global__ __launch_bounds__(CLEAR_NT) void uph_clearance_field_kernel(ClearGeom g, const unsigned short* __restrict__ D, const double* __restrict__ pos, int n,
+                                                                       double* __restrict__ value, double* __restrict__ grad) {
+    const int i = blockIdx.x * CLEAR_NT + threadIdx.x;
+    if (i >= n) return;
+    double c, gx, gy;
+    clearanceField(g, D, pos[3 * (size_t)i], pos[3 * (size_t)i + 1], normSO2(pos[3 * (size_t)i + 2]), c, gx, gy);
+    value[i] = c;
+    grad[2 * (size_t)i] = gx; grad[2 * (size_t)i + 1] = gy;
+}
+
 // the rect grown by r and clipped (the rect is ordered, inside the grid and not empty)
 void growRect(int nx, int ny, const int32_t rect[4], int r, int32_t out[4]) {
     out[0] = std::max(0, rect[0] - r); out[1] = (int32_t)std::min<int64_t>(nx, (int64_t)rect[1] + r);
@@ -121,6 +134,7 @@ struct uph_clearance {
     unsigned short* d_D = nullptr;
     unsigned long long stamp = 0;       // the body layer's write count the values were made from
     bool stamped = false;
+    int users = 0;                      // optimiser contexts that name the layer in a clearance term
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double last_ms = 0.0;
 };
@@ -164,6 +178,7 @@ static unsigned long long clearBehind(const uph_clearance* l) {
 const uph_body_layer* uphClearanceBody(const uph_clearance* l) { return l->body; }
 const unsigned short* uphClearanceValues(const uph_clearance* l) { return l->d_D; }
 bool uphClearanceFresh(const uph_clearance* l) { return clearBehind(l) == 0; }
+void uphClearanceUse(uph_clearance* l, int delta) { l->users += delta; }
 
 extern "C" {
 
@@ -256,8 +271,33 @@ int uph_clearance_kernel_ms(const uph_clearance* l, double* kernel_ms) {
     return UPH_OK;
 }
 
+int uph_clearance_field(uph_clearance* l, int32_t n, const double* pos, double* value, double* grad) {
+    const std::string who = "uph_clearance_field";
+    if (!l || n < 0 || (n > 0 && (!pos || !value || !grad))) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    if (l->polarity != UPH_CLEAR_TO_OCCUPIED) { setError(who + ": the field is defined for a layer of polarity UPH_CLEAR_TO_OCCUPIED"); return UPH_ERR_INVALID; }
+    if (l->ncell > 0x7fffffffull) { setError(who + ": the layer has more than 2^31 - 1 entries (the field addresses it with 32-bit offsets)"); return UPH_ERR_LIMIT; }
+    if (n == 0) return UPH_OK;
+    CHIPCHK(hipSetDevice(l->device));
+    const ClearGeom g = clearGeom(uphMapGrid(uphBodyLayerMap(l->body)), l->rmax);
+    UphDevTmp dp, dv, dg;
+    if (hipMalloc(&dp.p, 24 * (size_t)n) != hipSuccess || hipMalloc(&dv.p, 8 * (size_t)n) != hipSuccess || hipMalloc(&dg.p, 16 * (size_t)n) != hipSuccess) {
+        setError(who + ": allocating the pose buffers failed");
+        (void)hipGetLastError();
+        return UPH_ERR_HIP;
+    }
+    CHIPCHK(hipMemcpy(dp.p, pos, 24 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(uph_clearance_field_kernel, dim3((unsigned)(((size_t)n + CLEAR_NT - 1) / CLEAR_NT)), dim3(CLEAR_NT), 0, 0, g, l->d_D, dp.as<double>(), (int)n,
+                       dv.as<double>(), dg.as<double>());
+    CHIPCHK(hipGetLastError());
+    CHIPCHK(hipDeviceSynchronize());
+    CHIPCHK(hipMemcpy(value, dv.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    CHIPCHK(hipMemcpy(grad, dg.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    return UPH_OK;
+}
+
 int uph_clearance_destroy(uph_clearance* l) {
     if (!l) return UPH_OK;
+    if (l->users > 0) { setError("uph_clearance_destroy: a context still names the layer in its clearance term (uph_ctx_set_clearance_term(c, NULL, 0, 0) or destroy it first)"); return UPH_ERR_INVALID; }
     hipSetDevice(l->device);
     hipFree(l->d_g); hipFree(l->d_D);
     if (l->e0) hipEventDestroy(l->e0);

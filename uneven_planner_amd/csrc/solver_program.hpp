@@ -28,6 +28,7 @@
 // wg.bcast(): on the device that is v_readfirstlane, which parks them in scalar registers -- see DevWG::uni in unevenhip.hip
 // for why this matters (scratch reloads of "uniform" VGPRs drain the memory pipeline).
 #pragma once
+#include "clearance_dev.hpp"
 #include "terrain_dev.hpp"
 #include "trajectory_dev.hpp"
 #include "uph_common.hpp"
@@ -102,8 +103,19 @@ UPH_HD void sampleChunk(WG& wg, int n, bool first, C compute, P commit) {
 template <class WG, class F>
 UPH_HD void pforOpen(WG& wg, int n, F f) { wg.pfor(n, f); }
 
+// Where a CLR sample issues the clearance field's four loads.  false (default): in front of the terrain gather, so that their round trip runs under it -- four
+// VGPRs and the two fractions live across the gather.  true: behind the penalties, where the term reads them -- nothing lives across the gather, the round trip
+// is exposed.  A workgroup object whose kernels are register-capped sets it (unevenhip.hip: 512 lanes, eight waves on four SIMDs, 256 VGPRs each).
+template <class WG>
+struct ClearLoadsLate { static constexpr bool value = false; };
+
 // SR = real type of the sample-phase arithmetic: double (the reference's, default) or f32r (fp32 sample mode, uph_common.hpp)
-template <class WG, class SR = double>
+// CLR = the clearance term: every sample of an evaluation (sampleCompute, RES != 1) adds a soft cost on the clearance field of a
+// clearance layer (clearance_dev.hpp), read through the descriptor behind OptParams in bd.params_mem (ClearTermDev).  Instantiations of its own, as the
+// fp32 sample mode has: with CLR = false no statement of the term exists.  What does NOT see the term: the residual pass (RES == 1: the term has no
+// residual, it is no ALM constraint), and sampleObjective / initScaling / prepare -- scale_fx and the constraint scales are those of the plain objective, so
+// MODE 1 (and 3, 4, 5) needs no CLR instantiation.
+template <class WG, class SR = double, bool CLR = false>
 struct Solver {
     WG& wg;
     const GridDev& grid;
@@ -408,11 +420,41 @@ struct Solver {
         R yawn, cw, sw;                 // wrapped yaw and its cos / sin (uneven_map.h:329-330)
         R zx, zy, gs[3], gzx[3], gzy[3]; // interpolated zb and the base gradients (penalty path)
         int yaw_idx;
+        ClearTaps ct;                   // CLR: the clearance field's entries and fractions at this sample, and the four values as loaded (clearIssue)
+        int cl_d[4];
     };
     typedef KinT<double> Kin;
     // penalty path: only (sigma, zb) and their gradients are gathered; the seven attitude terms follow from them here and their
     // gradients are never formed individually (sampleEval folds them into four scalar coefficients)
+    // CLR: the term's descriptor, through an opaque constant-address-space pointer as the limits are read (scalar loads at the point of use)
+    UPH_HD ClearTermDev clearDesc() const {
+        ClearTermDev cd;
+#if defined(__HIP_DEVICE_COMPILE__) && UPH_GRID_FROM_MEM
+        typedef const __attribute__((address_space(4))) unsigned long long* cw_t;
+        cw_t CT = (cw_t)(const void*)(bd.params_mem + 1);
+        asm volatile("" : "+s"(CT));
+        constexpr int CWORD = (int)(sizeof(ClearTermDev) / 8);
+        unsigned long long cw[CWORD];
+#pragma unroll
+        for (int q = 0; q < CWORD; q++) cw[q] = CT[q];
+        __builtin_memcpy(&cd, cw, sizeof(ClearTermDev));
+#else
+        __builtin_memcpy(&cd, (const void*)(bd.params_mem + 1), sizeof(ClearTermDev));
+#endif
+        return cd;
+    }
+    // CLR: the four loads of the clearance field at the sample's pose, issued IN FRONT of the terrain gather: they depend on the position and the wrapped yaw
+    // alone, so their round trip runs under the gather's sixteen.  Nobody reads cl_d before the term (sampleCompute), behind the penalties: four VGPRs
+    // that are live across the gather on purpose (a pair a load fills and nobody reads would stall its next writer: loadCell's note).
     template <class R>
+    UPH_HD void clearIssue(const GridDev& gl, KinT<R>& S_) const { clearIssue<R>(gl, clearDesc(), S_); }
+    template <class R>
+    UPH_HD void clearIssue(const GridDev& gl, const ClearTermDev& cd, KinT<R>& S_) const {
+        const ClearGeom cg = clearGeom(gl, cd.rmax);
+        clearLocate(cg, (double)S_.pos[0], (double)S_.pos[1], (double)S_.yawn, S_.ct);
+        clearLoad(cd.D, S_.ct, S_.cl_d);
+    }
+    template <class R, bool TAPS = false>
     UPH_HD void terrainValuesOnly(KinT<R>& S_) const {
         R sg;
 #if defined(__HIP_DEVICE_COMPILE__) && UPH_GRID_FROM_MEM
@@ -428,9 +470,11 @@ struct Solver {
         for (int k = 0; k < NWORD; k++) w[k] = T[k];
         GridDev gl;
         __builtin_memcpy(&gl, w, sizeof(GridDev));
+        if constexpr (TAPS) clearIssue<R>(gl, S_);
         terrainBase<R>(gl, S_.pos[0], S_.pos[1], S_.yawn, sg, S_.zx, S_.zy, S_.gs, S_.gzx, S_.gzy);
 #else
         const GridDev gl = framedGrid();
+        if constexpr (TAPS) clearIssue<R>(gl, S_);
         terrainBase<R>(gl, S_.pos[0], S_.pos[1], S_.yawn, sg, S_.zx, S_.zy, S_.gs, S_.gzx, S_.gzy);
 #endif
         const R zx = S_.zx, zy = S_.zy;
@@ -443,7 +487,7 @@ struct Solver {
         S_.sq = sq;
         S_.tv[0] = r; S_.tv[1] = -cc * t * r; S_.tv[2] = sq * inv_c; S_.tv[3] = s * r; S_.tv[4] = cc; S_.tv[5] = inv_c; S_.tv[6] = sg;
     }
-    template <bool WITH_GRADS = true, class R = double>
+    template <bool WITH_GRADS = true, class R = double, bool TAPS = false>
     UPH_HD void kin(int i, int j, KinT<R>& S_) const {
         const R s1 = bt[Nxy + 1 + j];                              // :713-714,987: the s1 += step accumulation (Q2), tabulated by generate()
         S_.s1 = s1;
@@ -492,7 +536,7 @@ struct Solver {
         S_.yawn = yawn; S_.cw = cw; S_.sw = sw;
         UPH_MARK("kin.terrain");
         if constexpr (WITH_GRADS) terrainAllWithGrad(framedGrid(), S_.pos[0], S_.pos[1], yawn, cw, sw, S_.tv, S_.tg);   // :778  (initScaling: R = double)
-        else terrainValuesOnly<R>(S_);
+        else terrainValuesOnly<R, TAPS>(S_);
         UPH_MARK("kin.after_terrain");
         S_.vx = S_.v_norm * S_.tv[0];                                   // :813-817
         S_.wz = dyaw * S_.tv[5];
@@ -584,7 +628,7 @@ struct Solver {
         for (int q = 0; q < 7; q++) { dl[q] = R(RES_ONLY ? 0.0 : dual[q * S + s]); sc7[q] = R(scl[q * S + s]); }
 #endif
         KinT<R> k;
-        kin<false, R>(i, j, k);
+        kin<false, R, CLR && !RES_ONLY && !ClearLoadsLate<WG>::value>(i, j, k);
         UPH_MARK("sampleEval.penalties");
 #if defined(UPH_LATE_DUALS) && UPH_LATE_DUALS
         {
@@ -696,6 +740,25 @@ struct Solver {
                 const R ag = augGrad<R>(gv, mu);
                 W[6] += ag * sc;
             } else cost += divR(R(-0.5 * mu * mu), R(rho), irho);
+        }
+        // clearance (CLR; no reference: UnevenMap has no obstacle term).  A quadrature cost like the surface-variation cost above, weight in rho_ter's place:
+        // g = d_safe - c(pos, yawn), and where g > 0: cost += om g^2, its Q3 time part as for user_cost, grad_p -= 2 om g grad c.  No yaw gradient (the field
+        // is piecewise constant in yaw), no dual, no residual.  The cost is never negative, so lb_dual (formDualBound) stays a bound.
+        if constexpr (CLR && !RES_ONLY) {
+            const ClearTermDev cd = clearDesc();
+            if constexpr (ClearLoadsLate<WG>::value) clearIssue<R>(grid, cd, k);    // (no local frames with the term: the kernel argument is the descriptor)
+            ClearGeom cg;
+            cg.xy_res = grid.xy_res; cg.xy_inv = grid.xy_inv; cg.rmax = cd.rmax;
+            double cv, cgx, cgy;
+            clearValue(cg, k.ct, k.cl_d, cv, cgx, cgy);
+            const double gq = cd.d_safe - cv;
+            if (gq > 0.0) {
+                const double om = ((j == 0 || j == K) ? 0.5 : 1.0) * cd.weight * ec_step * scale_fx;
+                const double cc = om * gq * gq;
+                cost += R(cc);
+                tx += R(cc / K);
+                grad_p[0] -= R(2.0 * om * gq * cgx); grad_p[1] -= R(2.0 * om * gq * cgy);
+            }
         }
         // process with vx, wz, ax                                       :948-964
 #pragma unroll
@@ -1565,6 +1628,7 @@ struct Solver {
         const double v = rho > 0.0 ? sq * (0.5 / rho) : __builtin_huge_val();
         wg.one([&]() { ab[0] = v; });           // (read in eval, behind the barriers of generate / expand)
     }
+    // (CLR: the clearance term adds a cost that is never negative to every sample, as omega sigma^2 does: lb_dual stays a valid bound with the term set)
     UPH_HD void formDualBound() {
         double sq[1];
         wg.template sum<1>(S, sq, [&](int s, double* acc) {

@@ -604,6 +604,13 @@ struct DevWG {
     }
 };
 
+// 512 lanes: every kernel is capped at 256 VGPRs, and the clearance term's loads held across the terrain gather spilled 8 - 10 of them to scratch
+// (profiles/clearance_term_resources.txt): they are issued where the term reads them instead
+namespace uph {
+template <>
+struct ClearLoadsLate<DevWG<512>> { static constexpr bool value = true; };
+}  // namespace uph
+
 // Solver's asideKnotSolve (solver_program.hpp) on the device: the idle wave's lanes instead of a parallel loop with a barrier
 template <int NT, class F>
 __device__ __forceinline__ void asideKnotSolve(DevWG<NT>& wg, int lenW, int lenX, int n, F f) { wg.aside(lenW, lenX, n, f); }
@@ -620,7 +627,9 @@ __device__ __forceinline__ void pforOpen(DevWG<NT>& wg, int n, F f) { wg.pforOpe
 // A compile-time MODE gives each phase its own register budget.
 // F32S: the sample phase of every objective evaluation computes in fp32 (Solver<WG, f32r>; BASELINE.json configs[4] "fp32"), everything else
 // -- MINCO, L-BFGS, ALM, the scatter and the accumulations -- stays fp64.  Own instantiations: the fp64 kernels are untouched by it.
-template <int NT, int WPS, int MODE, bool F32S = false>
+// CLR: the sample phase adds the clearance term (Solver<.., CLR = true>, uph_ctx_set_clearance_term).  Own instantiations again, for
+// MODE 0, 2 and 8 at 128, 256 and 512 lanes: every other kernel is what it was.
+template <int NT, int WPS, int MODE, bool F32S = false, bool CLR = false>
 __global__ __launch_bounds__(NT, WPS) void uph_solver_kernel(GridDev grid, OptParams P, BatchDev bd, int repeat) {
     extern __shared__ double lds[];
     const int w = blockIdx.x;
@@ -628,7 +637,7 @@ __global__ __launch_bounds__(NT, WPS) void uph_solver_kernel(GridDev grid, OptPa
     const int b = bd.order ? bd.order[w] : w;
     DevWG<NT> wg(lds);
     typedef typename std::conditional<F32S, f32r, double>::type SR;
-    Solver<DevWG<NT>, SR> sol(wg, grid, P, bd, b, lds + DevWG<NT>::SCRATCH);
+    Solver<DevWG<NT>, SR, CLR> sol(wg, grid, P, bd, b, lds + DevWG<NT>::SCRATCH);
     TrajState& st = bd.state[b];
     if (MODE == 0) sol.evalOnly(st, repeat);
     else if (MODE == 1) sol.prepare(st);
@@ -805,7 +814,10 @@ __global__ __launch_bounds__(64) void uph_refine_stage_kernel(const RefineStage*
 #ifndef UPH_OK_F32
 #define UPH_OK_F32 false
 #endif
-template __global__ void uph_solver_kernel<UPH_OK_NT, UPH_OK_WPS, UPH_OK_MODE, UPH_OK_F32>(GridDev, OptParams, BatchDev, int);
+#ifndef UPH_OK_CLR
+#define UPH_OK_CLR false
+#endif
+template __global__ void uph_solver_kernel<UPH_OK_NT, UPH_OK_WPS, UPH_OK_MODE, UPH_OK_F32, UPH_OK_CLR>(GridDev, OptParams, BatchDev, int);
 #else
 // ------------------------------------------------------------------------------------------------ host side
 namespace uph {
@@ -894,16 +906,33 @@ int refreshStates(uph_ctx* c) {
     return UPH_OK;
 }
 
+static int clearTermRefused(const uph_ctx* c, int mode);        // (with the term's entry points, below)
 // async: enqueue only (events evb / eve bracket the launch on the context's stream); the caller synchronises and reads the time later
 static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hipEvent_t evb = nullptr, hipEvent_t eve = nullptr) {
     if (!async && c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
     if (!evb) { evb = c->ev0; eve = c->ev1; }
+    // the clearance term: the kernels of an evaluation (0), a solve (2) and the penalty alone (8) have instantiations with it; scaling, report and the
+    // microbenchmark (1, 3, 4, 5) do not see it and run as they are.  Whatever the mode, a term that cannot run refuses the launch here, before anything is enqueued.
+    const bool clr = c->clear_layer != nullptr;
+    if (clr) { const int rc = clearTermRefused(c, mode); if (rc != UPH_OK) return rc; }
     HIPCHK(hipSetDevice(uphMapDevice(c->map)));
     GridDev grid;
     const int rg = syncGridMem(c, grid);
     if (rg != UPH_OK) return rg;
-    if (c->d_parammem.ensure(sizeof(OptParams))) return UPH_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_parammem.p, &c->P, sizeof(OptParams), hipMemcpyHostToDevice, c->stream));
+    // the parameter block: OptParams, and behind it the term's descriptor (read by CLR code alone; zeros without a term)
+    {
+        ClearTermDev cd;
+        std::memset(&cd, 0, sizeof(cd));
+        if (clr) {
+            int32_t rmax = 0;
+            uph_clearance_info(c->clear_layer, &rmax, nullptr, nullptr, nullptr);
+            cd.D = uphClearanceValues(c->clear_layer); cd.rmax = rmax; cd.d_safe = c->clear_d_safe; cd.weight = c->clear_weight;
+        }
+        std::memcpy(c->param_block, &c->P, sizeof(OptParams));
+        std::memcpy(c->param_block + sizeof(OptParams), &cd, sizeof(ClearTermDev));
+    }
+    if (c->d_parammem.ensure(sizeof(c->param_block))) return UPH_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_parammem.p, c->param_block, sizeof(c->param_block), hipMemcpyHostToDevice, c->stream));
     BatchDev bd = makeBatchDev(c);
     // lanes/occupancy variants: <64,1> one wave per trajectory; <256,1> four waves, one workgroup per CU (no spills, lowest latency);
     // <256,2> four waves, registers capped at 256 so that two workgroups share a CU (best throughput for large batches)
@@ -934,10 +963,12 @@ static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hi
         else if (mode == 5) UPH_LAUNCH(NTL, WPS, 5);                                                                                 \
         else UPH_LAUNCH(NTL, WPS, 4);                                                                                                \
     } while (0)
-#define UPH_LAUNCH32(NTL, WPS, MODE)                                                                                                   \
+#define UPH_LAUNCH32(NTL, WPS, MODE) UPH_LAUNCHX(NTL, WPS, MODE, true, false)
+#define UPH_LAUNCHCLR(NTL, WPS, MODE) UPH_LAUNCHX(NTL, WPS, MODE, false, true)
+#define UPH_LAUNCHX(NTL, WPS, MODE, F32, CLRF)                                                                                                 \
     do {                                                                                                                             \
         const size_t ldsmax = 160 * 1024;   /* the opt-in ceiling, not the launch size: constant, so that contexts on other host threads never lower it under a launch */ \
-        HIPCHK(hipFuncSetAttribute((const void*)uph_solver_kernel<NTL, WPS, MODE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax)); \
+        HIPCHK(hipFuncSetAttribute((const void*)uph_solver_kernel<NTL, WPS, MODE, F32, CLRF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax)); \
         HIPCHK(hipEventRecord(evb, c->stream));                                                                                   \
         BatchDev bm = bd;                                                                                                            \
         bm.B = c->n_main;                                                                                                            \
@@ -946,13 +977,23 @@ static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hi
             bb.B = c->B - c->n_main;                                                                                                 \
             bb.order = bd.order + c->n_main;                                                                                         \
             HIPCHK(hipStreamWaitEvent(c->stream2, evb, 0));                                                                       \
-            hipLaunchKernelGGL((uph_solver_kernel<NTL, WPS, MODE, true>), dim3(bb.B), dim3(NTL), c->lds_big, c->stream2, grid, c->P, bb, repeat); \
+            hipLaunchKernelGGL((uph_solver_kernel<NTL, WPS, MODE, F32, CLRF>), dim3(bb.B), dim3(NTL), c->lds_big, c->stream2, grid, c->P, bb, repeat); \
             HIPCHK(hipEventRecord(c->ev2, c->stream2));                                                                              \
         }                                                                                                                            \
-        hipLaunchKernelGGL((uph_solver_kernel<NTL, WPS, MODE, true>), dim3(c->n_main), dim3(NTL), c->lds_bytes, c->stream, grid, c->P, bm, repeat); \
+        hipLaunchKernelGGL((uph_solver_kernel<NTL, WPS, MODE, F32, CLRF>), dim3(c->n_main), dim3(NTL), c->lds_bytes, c->stream, grid, c->P, bm, repeat); \
         if (c->n_main < c->B) HIPCHK(hipStreamWaitEvent(c->stream, c->ev2, 0));                                                      \
     } while (0)
-    if (c->sample_f32 && (mode == 0 || mode == 2) && (c->lanes == 128 || c->lanes == 256 || c->lanes == 512)) {
+    if (clr && (mode == 0 || mode == 2 || mode == 8)) {
+        // the clearance term: 128 / 256 / 512 lanes (clearTermRefused has refused the rest).  Uncapped builds throughout: under the 256-register cap of
+        // <128, 2, .> and <256, 2, 2> the term's loads in flight across the terrain gather spill to scratch (36 - 44 bytes; the plain kernels have none),
+        // so a batch that would take <256, 2, 2> is routed to <256, 1, 2> and 128 lanes run <128, 1, .> (profiles/clearance_term_resources.txt)
+        if (c->lanes == 128) { if (mode == 0) UPH_LAUNCHCLR(128, 1, 0); else if (mode == 2) UPH_LAUNCHCLR(128, 1, 2); else UPH_LAUNCHCLR(128, 1, 8); }
+        else if (c->lanes == 512) { if (mode == 0) UPH_LAUNCHCLR(512, 1, 0); else if (mode == 2) UPH_LAUNCHCLR(512, 1, 2); else UPH_LAUNCHCLR(512, 1, 8); }
+        else if (mode == 0) UPH_LAUNCHCLR(256, 1, 0);
+        else if (mode == 2) UPH_LAUNCHCLR(256, 1, 2);
+        else UPH_LAUNCHCLR(256, 1, 8);
+    }
+    else if (c->sample_f32 && (mode == 0 || mode == 2) && (c->lanes == 128 || c->lanes == 256 || c->lanes == 512)) {
         // fp32 sample arithmetic: evaluation and solve kernels of the three production lane counts (scaling / report / hooks stay fp64)
         if (c->lanes == 128) { if (mode == 0) UPH_LAUNCH32(128, 2, 0); else UPH_LAUNCH32(128, 2, 2); }
         else if (c->lanes == 512) { if (mode == 0) UPH_LAUNCH32(512, 1, 0); else UPH_LAUNCH32(512, 1, 2); }
@@ -981,6 +1022,8 @@ static int launchSolver(uph_ctx* c, int mode, int repeat, bool async = false, hi
     else UPH_LAUNCH_MODE(256, 1);
 #undef UPH_LAUNCH_MODE
 #undef UPH_LAUNCH32
+#undef UPH_LAUNCHCLR
+#undef UPH_LAUNCHX
 #undef UPH_LAUNCH
     HIPCHK(hipGetLastError());
     if (mode == 0 || mode == 2 || mode == 4 || mode == 7) c->traj_resident = true;      // the launches that store the trajectory (Solver::storeTrajectory)
@@ -1059,6 +1102,7 @@ int uph_ctx_create(uph_map* m, const uph_opt_params* p, uph_ctx** out) {
 void uph_ctx_destroy(uph_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);             // not via c->map: the map may already have been destroyed by the caller
+    if (c->clear_layer) uphClearanceUse(c->clear_layer, -1);       // (alive: uph_clearance_destroy refuses while this context names it)
     for (void* p : c->op_allocs) hipFree(p);
     DevBuf* bufs[] = {&c->d_ops, &c->d_desc, &c->d_state, &c->d_x, &c->d_gout, &c->d_dual, &c->d_res, &c->d_scl, &c->d_cxy, &c->d_cyaw,
                       &c->d_hist, &c->d_report, &c->d_order, &c->d_trace, &c->d_x0, &c->d_thomas, &c->d_rsd, &c->d_rs, &c->d_gridmem, &c->d_parammem,
@@ -1091,6 +1135,65 @@ int uph_ctx_set_sample_precision(uph_ctx* c, int32_t bits) {
     if (!c || (bits != 32 && bits != 64)) { setError("uph_ctx_set_sample_precision: 32 or 64"); return UPH_ERR_INVALID; }
     NOT_ON_FLEET(c, "uph_ctx_set_sample_precision");
     c->sample_f32 = bits == 32;
+    return UPH_OK;
+}
+// ---- the clearance term.  What can be told of the layer and the values alone is refused when the term is set; what depends on the batch, on
+// the context's other switches or on writes to the map since (clearTermRefused) at every launch, in front of it.
+static int clearTermLayerCheck(const uph_ctx* c, const uph_clearance* layer, const std::string& who) {
+    int32_t rmax = 0, polarity = 0, dims[3] = {0, 0, 0};
+    uph_clearance_info(layer, &rmax, &polarity, dims, nullptr);
+    const uph_body_layer* body = uphClearanceBody(layer);
+    if (uphBodyLayerMap(body) != c->map) { setError(who + ": the clearance layer belongs to another map than the context's"); return UPH_ERR_INVALID; }
+    if (polarity != UPH_CLEAR_TO_OCCUPIED) { setError(who + ": the term reads a layer of polarity UPH_CLEAR_TO_OCCUPIED (this one is UPH_CLEAR_TO_FREE)"); return UPH_ERR_INVALID; }
+    if ((size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] > 0x7fffffffull) { setError(who + ": the layer has more than 2^31 - 1 entries (the field addresses it with 32-bit offsets)"); return UPH_ERR_LIMIT; }
+    if (!uphClearanceFresh(layer)) { setError(who + ": the clearance layer is behind its body layer: rebuild it (uph_clearance_update with the rewritten rect, or uph_clearance_build)"); return UPH_ERR_INVALID; }
+    if (!uphBodyLayerFresh(body)) { setError(who + ": the body layer is behind the map's occupancy: rebuild it (uph_body_layer_update / uph_body_layer_build), then the clearance layer"); return UPH_ERR_INVALID; }
+    return UPH_OK;
+}
+static int clearTermValueCheck(const uph_ctx* c, const uph_clearance* layer, double d_safe, double weight, const std::string& who) {
+    int32_t rmax = 0;
+    uph_clearance_info(layer, &rmax, nullptr, nullptr, nullptr);
+    if (!std::isfinite(d_safe) || !std::isfinite(weight)) { setError(who + ": d_safe and weight must be finite"); return UPH_ERR_INVALID; }
+    if (d_safe <= 0.0) { setError(who + ": d_safe must be positive"); return UPH_ERR_INVALID; }
+    if (weight < 0.0) { setError(who + ": weight must not be negative"); return UPH_ERR_INVALID; }
+    // a far cell reads res * sqrt(rmax^2 + 1) > res * rmax: with d_safe <= res * rmax it is never penalised
+    if (d_safe > uphMapGrid(c->map).xy_res * (double)rmax) { setError(who + ": d_safe exceeds the layer's reach (resolution * rmax): a cell with no obstacle within rmax must never be penalised"); return UPH_ERR_INVALID; }
+    return UPH_OK;
+}
+// a launch of `mode` with the term set that cannot run: the message is set, nothing has been launched
+static int clearTermRefused(const uph_ctx* c, int mode) {
+    const std::string who = "clearance term";
+    if (mode == 7) { setError(who + ": the L-BFGS resume hook has no instantiation with the term (uph_ctx_set_clearance_term(c, NULL, 0, 0) first)"); return UPH_ERR_INVALID; }
+    if (c->lanes != 128 && c->lanes != 256 && c->lanes != 512) { setError(who + ": built for 128, 256 and 512 lanes per trajectory, not for 64"); return UPH_ERR_INVALID; }
+    if (c->sample_f32) { setError(who + ": not built for the fp32 sample mode (uph_ctx_set_sample_precision(c, 64))"); return UPH_ERR_INVALID; }
+    if (!c->frames.empty()) { setError(who + ": the batch solves in per-trajectory local frames (a tile or km^2 map); the term reads the layer in map coordinates only"); return UPH_ERR_INVALID; }
+    int r = clearTermLayerCheck(c, c->clear_layer, who);
+    if (r != UPH_OK) return r;
+    return clearTermValueCheck(c, c->clear_layer, c->clear_d_safe, c->clear_weight, who);
+}
+
+int uph_ctx_set_clearance_term(uph_ctx* c, uph_clearance* layer, double d_safe, double weight) {
+    const std::string who = "uph_ctx_set_clearance_term";
+    if (!c) { setError(who + ": bad arguments"); return UPH_ERR_INVALID; }
+    NOT_ON_FLEET(c, "uph_ctx_set_clearance_term");
+    if (c->pending) { setError("an asynchronous solve is in flight on this context: call uph_batch_wait first"); return UPH_ERR_INVALID; }
+    if (layer) {
+        int r = clearTermLayerCheck(c, layer, who);
+        if (r != UPH_OK) return r;
+        r = clearTermValueCheck(c, layer, d_safe, weight, who);
+        if (r != UPH_OK) return r;
+        uphClearanceUse(layer, 1);
+    }
+    if (c->clear_layer) uphClearanceUse(c->clear_layer, -1);
+    c->clear_layer = layer;
+    c->clear_d_safe = layer ? d_safe : 0.0; c->clear_weight = layer ? weight : 0.0;
+    return UPH_OK;
+}
+int uph_ctx_clearance_term(const uph_ctx* c, uph_clearance** layer, double* d_safe, double* weight) {
+    if (!c) { setError("uph_ctx_clearance_term: bad arguments"); return UPH_ERR_INVALID; }
+    if (layer) *layer = c->clear_layer;
+    if (d_safe) *d_safe = c->clear_d_safe;
+    if (weight) *weight = c->clear_weight;
     return UPH_OK;
 }
 int uph_ctx_set_rho(uph_ctx* c, double rho) { if (!c) return UPH_ERR_INVALID; NOT_ON_FLEET(c, "uph_ctx_set_rho"); c->rho = rho; return UPH_OK; }

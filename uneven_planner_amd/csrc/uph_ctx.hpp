@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "clearance_dev.hpp"
 #include "uph_internal.hpp"
 
 using namespace uph;
@@ -85,6 +86,9 @@ struct uph_ctx {
     bool framed_valid = false;              // d_gridmem holds the framed descriptors of the current batch
     std::vector<int> origin;                // batch loaded by uph_optimize_batch_multi: the caller's index of each problem of this context's share (empty: identity)
     bool sample_f32 = false;                // fp32 sample arithmetic (uph_ctx_set_sample_precision)
+    uph_clearance* clear_layer = nullptr;   // the clearance term (uph_ctx_set_clearance_term): its layer (nullptr: off; counted on the layer while set) ...
+    double clear_d_safe = 0.0, clear_weight = 0.0;      // ... its safe distance in metres and its weight
+    unsigned char param_block[sizeof(OptParams) + sizeof(ClearTermDev)];   // source of the per-launch copy into d_parammem: the parameters, the term's descriptor behind them
     int xcd_group = 0;                      // experiment knob (uph_ctx_set_xcd_locality): > 0 = permute the launch order inside groups of that many workgroups for per-XCD L2 locality
     hipStream_t stream2 = nullptr;
     hipEvent_t evp0 = nullptr, evp1 = nullptr;      // prepare launch of an asynchronous solve

@@ -39,6 +39,8 @@ void uphBodyLayerDepend(uph_body_layer* l, int delta);
 const uph_body_layer* uphClearanceBody(const uph_clearance* l);
 const unsigned short* uphClearanceValues(const uph_clearance* l);
 bool uphClearanceFresh(const uph_clearance* l);
+// the count of optimiser contexts that name the layer in a clearance term (uph_ctx_set_clearance_term; uph_clearance_destroy refuses while it is not zero)
+void uphClearanceUse(uph_clearance* l, int delta);
 
 // scope guards for the temporaries of the extern "C" entry points: every early return (HIPCHK) releases them
 struct UphDevTmp {
