@@ -62,7 +62,42 @@ struct AlmTrajOpt {
     bool snap_valid = false;
     LbfgsState snap_state;
 
+    // ---- OPTIONAL clearance term (no counterpart in the reference; the rule is include/uneven_hip.h "the clearance term").  clr_D == nullptr: no term,
+    // and every result is what it is without these lines.  clr_D: [nx][ny][nyaw] squared cell distances of a clearance layer, in the grid's address order.
+    const unsigned short* clr_D = nullptr;
+    int clr_rmax = 0;
+    double clr_d_safe = 0.0, clr_weight = 0.0;
+
     explicit AlmTrajOpt(const AlmParams& pp = AlmParams()) : p(pp), rho(pp.rho) {}
+
+    // the field c(x, y, yaw) in metres and its gradient in x and y; yaw normalised by the caller
+    void clearanceField(const double se2[3], double& c, double grad[2]) const {
+        c = 0.0; grad[0] = 0.0; grad[1] = 0.0;
+        if (!std::isfinite(se2[0]) || !std::isfinite(se2[1]) || !std::isfinite(se2[2])) return;       // degenerate poses read 0
+        const double ux = (se2[0] - map->map_origin[0]) * map->xy_resolution_inv - 0.5;             // between cell centres
+        const double uy = (se2[1] - map->map_origin[1]) * map->xy_resolution_inv - 0.5;
+        const double ix = std::floor(ux), iy = std::floor(uy);
+        const double iyaw = std::floor((se2[2] - map->map_origin[2]) * map->yaw_resolution_inv);     // the slice: piecewise constant in yaw
+        const double big = 1073741824.0;                                                            // 2^30
+        if (std::fabs(ix) >= big || std::fabs(iy) >= big || std::fabs(iyaw) >= big) return;
+        const double dx = ux - ix, dy = uy - iy;
+        int idx[3] = {(int)ix, (int)iy, (int)iyaw};
+        idx[2] = std::max(std::min(idx[2], map->max_idx[2]), map->min_idx[2]);
+        const int far = clr_rmax * clr_rmax + 1;                                                    // the first squared distance beyond the disc
+        double values[2][2];
+        for (int x = 0; x < 2; x++)
+            for (int y = 0; y < 2; y++) {
+                int cx = std::max(std::min(idx[0] + x, map->max_idx[0]), map->min_idx[0]);          // clamped corner indices
+                int cy = std::max(std::min(idx[1] + y, map->max_idx[1]), map->min_idx[1]);
+                int d2 = clr_D[map->toAddress(cx, cy, idx[2])];
+                values[x][y] = map->xy_resolution * std::sqrt((double)std::min(d2, far));
+            }
+        double v0 = values[0][0] * (1 - dx) + values[1][0] * dx;
+        double v1 = values[0][1] * (1 - dx) + values[1][1] * dx;
+        c = v0 * (1 - dy) + v1 * dy;
+        grad[0] = ((values[1][0] - values[0][0]) * (1 - dy) + (values[1][1] - values[0][1]) * dy) * map->xy_resolution_inv;
+        grad[1] = (v1 - v0) * map->xy_resolution_inv;
+    }
 
     // ---- alm_traj_opt.h:232-261
     static double expC2(double tau) { return tau > 0.0 ? ((0.5 * tau + 1.0) * tau + 1.0) : 1.0 / ((0.5 * tau - 1.0) * tau + 1.0); }
@@ -152,7 +187,7 @@ struct AlmTrajOpt {
         double beta0_xy[6], beta1_xy[6], beta2_xy[6], beta3_xy[6];
         double beta0_yaw[6], beta1_yaw[6], beta2_yaw[6];
         double pos[2], vel[2], acc[2], jer[2];
-        double yaw, dyaw, d2yaw, cyaw, syaw, v_norm, xb[2], yb[2], lon_acc, lat_acc;
+        double yaw, yaw_norm, dyaw, d2yaw, cyaw, syaw, v_norm, xb[2], yb[2], lon_acc, lat_acc;
         double tv[7], tg[7][3];
         double vx, wz, ax, ay, curv_snorm;
         int yaw_idx;
@@ -187,6 +222,7 @@ struct AlmTrajOpt {
         S.yaw = yaw; S.dyaw = dyaw; S.d2yaw = d2yaw;
         double se2[3] = {S.pos[0], S.pos[1], yaw};                                // :767-775
         normSO2(se2[2]);
+        S.yaw_norm = se2[2];
         S.syaw = std::sin(yaw);
         S.cyaw = std::cos(yaw);
         S.v_norm = std::sqrt(S.vel[0] * S.vel[0] + S.vel[1] * S.vel[1]);
@@ -344,6 +380,23 @@ struct AlmTrajOpt {
                 for (int k = 0; k < 3; k++) grad_se2[k] += grad_ay * (gravity * g_spy[k] + g_icvy[k] * S.lat_acc);
                 grad_p[0] += grad_se2[0]; grad_p[1] += grad_se2[1];
                 grad_yaw += grad_se2[2];
+
+                // clearance term (optional, not in the reference): a cost on the same quadrature as the user cost, no dual, no residual, no yaw gradient
+                if (clr_D) {
+                    double pose[3] = {S.pos[0], S.pos[1], S.yaw_norm}, clr, clr_grad[2];
+                    clearanceField(pose, clr, clr_grad);
+                    double lack = clr_d_safe - clr;
+                    if (lack > 0) {
+                        double om;
+                        if (j == 0 || j == int_K) om = 0.5 * clr_weight * step * scale_fx;
+                        else om = clr_weight * step * scale_fx;
+                        double clr_cost = om * lack * lack;
+                        cost += clr_cost;
+                        gdTxy[i] += clr_cost / int_K;                             // Q3, as for the user cost
+                        grad_p[0] -= 2.0 * om * lack * clr_grad[0];
+                        grad_p[1] -= 2.0 * om * lack * clr_grad[1];
+                    }
+                }
 
                 // add all grad into C,T                                          :966-985
                 for (int k = 0; k < 6; k++)

@@ -182,6 +182,11 @@ void orc_alm_destroy(void* h) { delete (OrcAlm*)h; }
 void orc_alm_set_rho(void* h, double rho) { ((OrcAlm*)h)->opt.rho = rho; }
 double orc_alm_get_rho(void* h) { return ((OrcAlm*)h)->opt.rho; }
 void orc_alm_set_flat_debug(void* h, int on) { ((OrcAlm*)h)->opt.flat_debug = on != 0; }
+// the optional clearance term: D [nx * ny * nyaw] in the grid's address order, kept by the caller while the term is set; D == NULL: no term
+void orc_alm_set_clearance_term(void* h, const unsigned short* D, int rmax, double d_safe, double weight) {
+    AlmTrajOpt& a = ((OrcAlm*)h)->opt;
+    a.clr_D = D; a.clr_rmax = rmax; a.clr_d_safe = d_safe; a.clr_weight = weight;
+}
 
 // set up a problem exactly as optimizeSE2Traj cpp:180-216 does, WITHOUT solving; writes x0 (n) and returns n
 int orc_alm_setup(void* h, const double* init_xy, const double* end_xy, const double* inner_xy, int n_inner_xy,

@@ -67,6 +67,7 @@ def lib():
         L.orc_alm_get_rho.restype = d
         L.orc_alm_get_rho.argtypes = [vp]
         L.orc_alm_set_flat_debug.argtypes = [vp, i]
+        L.orc_alm_set_clearance_term.argtypes = [vp, C.POINTER(C.c_uint16), i, d, d]
         L.orc_alm_setup.restype = i
         L.orc_alm_setup.argtypes = [vp, dp, dp, dp, i, dp, dp, dp, i, d, dp]
         L.orc_alm_set_state.argtypes = [vp, dp, dp, dp, dp]
@@ -324,6 +325,18 @@ class OracleALM:
 
     def set_flat_debug(self, on):
         self.L.orc_alm_set_flat_debug(self.h, int(on))
+
+    def set_clearance_term(self, D, rmax=0, d_safe=0.0, weight=0.0):
+        """the optional clearance term (include/uneven_hip.h, "the clearance term") in calConstrainCostGrad: D [nx][ny][nyaw] uint16 as ClearanceLayer.get()
+        returns it, on this object's grid; None clears it.  initScaling does not see the term."""
+        if D is None:
+            self._clr_D = None
+            self.L.orc_alm_set_clearance_term(self.h, None, 0, 0.0, 0.0)
+            return
+        D = np.ascontiguousarray(D, dtype=np.uint16)
+        assert D.shape == tuple(self.grid.dims), (D.shape, self.grid.dims)
+        self._clr_D = D                              # (the library reads the caller's array)
+        self.L.orc_alm_set_clearance_term(self.h, D.ctypes.data_as(C.POINTER(C.c_uint16)), int(rmax), float(d_safe), float(weight))
 
     def set_state(self, lam=None, mu=None, scale_cx=None, scale_fx=None):
         sf = np.array([scale_fx], dtype=np.float64) if scale_fx is not None else None

@@ -1,6 +1,18 @@
 // TEST SCAFFOLDING -- not part of the product.  The emulator of emu_solver.cpp with one addition for the clearance-term tests: one objective evaluation of
 // the workgroup program instantiated WITH the term (Solver<HostWG, double, true>), the layer's values and the term's descriptor given by the caller.  The
 // descriptor lies behind OptParams in the block BatchDev::params_mem points to, as the library lays it out.
+//
+// -DEMU_CLEAR_LOADS_LATE builds the same emulator with ClearLoadsLate<HostWG> specialised to true: the statement order of the 512-lane device kernels (the
+// field's loads issued behind the penalties, the geometry taken from the solver's grid argument), which no other CPU build runs.  The field is a function
+// of the pose alone, so both orders must give the same bits.
+#ifdef EMU_CLEAR_LOADS_LATE
+#include "../../uneven_planner_amd/csrc/solver_program.hpp"
+struct HostWG;
+namespace uph {
+template <>
+struct ClearLoadsLate<HostWG> { static constexpr bool value = true; };
+}  // namespace uph
+#endif
 #include "emu_solver.cpp"
 
 extern "C" {
@@ -67,6 +79,70 @@ void emu_clear_eval(void* h, int on, const unsigned short* D, int rmax, double d
     std::memcpy(cxy_out, cxy.data(), 8 * cxy.size());
     std::memcpy(cyaw_out, cyaw.data(), 8 * cyaw.size());
     scal[2] = st.f; scal[3] = st.jerk_cost; scal[4] = st.T_xy; scal[5] = st.T_yaw;
+}
+
+// the switch of the trial abandonment (OptParams::no_trial_abandon; uph_ctx_set_trial_abandon on the device)
+void emu_clear_set_trial_abandon(void* h, int on) { ((Emu*)h)->P.no_trial_abandon = on ? 0 : 1; }
+int emu_clear_loads_late() { return ClearLoadsLate<HostWG>::value ? 1 : 0; }
+
+// emu_run's modes 0 (one evaluation at x, state as given) and 2 (prepare + optimize from x) with the program instantiated WITH the term; arguments and outputs as
+// emu_run's (residuals included), the layer's values and the term's descriptor in front
+void emu_clear_run(void* h, int mode, const unsigned short* D, int rmax, double d_safe, double weight, int n_inner_xy, int n_inner_yaw, const double* init_xy,
+                   const double* end_xy, const double* init_yaw, const double* end_yaw, double* x_io, double* g_out, double* lambda_io, double* mu_io,
+                   double* scale_cx_io, double* hx_out, double* gx_out, double* cxy_out, double* cyaw_out, double* scal, long long* istat) {
+    Emu* e = (Emu*)h;
+    TrajDesc td;
+    std::memset(&td, 0, sizeof(td));
+    td.Nxy = n_inner_xy + 1; td.Nyaw = n_inner_yaw + 1;
+    td.n = 2 * n_inner_xy + n_inner_yaw + 1; td.S = td.Nxy * (e->P.int_K + 1);
+    td.op_xy = 0; td.op_yaw = 1;
+    for (int k = 0; k < 6; k++) { td.init_xy[k] = init_xy[k]; td.end_xy[k] = end_xy[k]; }
+    for (int k = 0; k < 3; k++) { td.init_yaw[k] = init_yaw[k]; td.end_yaw[k] = end_yaw[k]; }
+    const int S = td.S, n = td.n;
+    std::vector<double> Mt0, Mr0, Mt1, Mr1;
+    buildMincoOp(td.Nxy, Mt0, Mr0);
+    buildMincoOp(td.Nyaw, Mt1, Mr1);
+    MincoOp ops[2] = {{td.Nxy, Mt0.data(), Mr0.data()}, {td.Nyaw, Mt1.data(), Mr1.data()}};
+    TrajState st;
+    std::memset(&st, 0, sizeof(st));
+    st.rho = scal[0]; st.scale_fx = scal[1];
+    std::vector<double> dual(7 * S), res(7 * S, 0.0), scl(7 * S), xg(x_io, x_io + n), x0copy(xg), gout(n, 0.0), cxy(12 * td.Nxy), cyaw(6 * td.Nyaw);
+    std::vector<double> hist((size_t)e->P.mem_size * histRowDoubles(n), 0.0), rep(7, 0.0), thomasTab, rsd(n, 0.0), rs(24, 0.0), trace(20000, 0.0);
+    for (int s = 0; s < S; s++) {
+        dual[s] = lambda_io[s];
+        for (int q = 0; q < 6; q++) dual[(q + 1) * S + s] = mu_io[6 * s + q];
+        for (int q = 0; q < 7; q++) scl[q * S + s] = scale_cx_io[7 * s + q];
+    }
+    buildThomasTable(thomasTab);
+    std::vector<unsigned long long> block((sizeof(OptParams) + sizeof(ClearTermDev)) / 8 + 1, 0ull);
+    ClearTermDev cd;
+    std::memset(&cd, 0, sizeof(cd));
+    cd.D = D; cd.rmax = rmax; cd.d_safe = d_safe; cd.weight = weight;
+    std::memcpy(block.data(), &e->P, sizeof(OptParams));
+    std::memcpy((char*)block.data() + sizeof(OptParams), &cd, sizeof(ClearTermDev));
+    BatchDev bd;
+    std::memset(&bd, 0, sizeof(bd));
+    bd.B = 1; bd.desc = &td; bd.state = &st; bd.ops = ops; bd.x = xg.data(); bd.x0 = x0copy.data(); bd.gout = gout.data(); bd.dual = dual.data(); bd.res = res.data();
+    bd.scl = scl.data(); bd.cxy = cxy.data(); bd.cyaw = cyaw.data(); bd.hist = hist.data(); bd.thomas = thomasTab.data(); bd.report = rep.data();
+    bd.trace = trace.data(); bd.trace_cap = (int)trace.size();
+    bd.rs_d = rsd.data(); bd.rs = rs.data();
+    bd.params_mem = (const OptParams*)block.data();
+    std::vector<double> lds(Solver<HostWG>::ldsDoubles(td.Nxy, td.Nyaw, n, g_lanes, e->P.mem_size, e->P.int_K) + 64);
+    HostWG wg;
+    Solver<HostWG, double, true> sol(wg, e->grid, e->P, bd, 0, lds.data());
+    if (mode == 0) sol.evalOnly(st, 1);
+    else { sol.prepare(st); sol.optimize(st); }
+    std::memcpy(x_io, xg.data(), 8 * n);
+    std::memcpy(g_out, gout.data(), 8 * n);
+    for (int s = 0; s < S; s++) {
+        lambda_io[s] = dual[s]; hx_out[s] = res[s];
+        for (int q = 0; q < 6; q++) { mu_io[6 * s + q] = dual[(q + 1) * S + s]; gx_out[6 * s + q] = res[(q + 1) * S + s]; }
+        for (int q = 0; q < 7; q++) scale_cx_io[7 * s + q] = scl[q * S + s];
+    }
+    std::memcpy(cxy_out, cxy.data(), 8 * cxy.size());
+    std::memcpy(cyaw_out, cyaw.data(), 8 * cyaw.size());
+    scal[0] = st.rho; scal[1] = st.scale_fx; scal[2] = st.f; scal[3] = st.jerk_cost; scal[4] = st.T_xy; scal[5] = st.T_yaw;
+    istat[0] = st.ret_code; istat[1] = st.alm_iters; istat[2] = st.lbfgs_iters; istat[3] = st.evals; istat[4] = st.last_lbfgs_ret; istat[5] = st.hist_reads;
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@ MIN_CASES = 440
 
 _LOCK = threading.Lock()
 _CACHE = {}
+COST_RAW = {}                                   # (test, variant) -> {(Nxy, Nyaw): dict(cost_raw, oracle_jump)}: the capped solves' cost of every case as measured
 MEASURED = {}                                   # (test, variant) -> {quantity: (worst error, where)}: filled by record(), written by write_report()
 
 
@@ -246,6 +247,200 @@ def oracle_reports(O, og, coeffs_by_case, tag):
         a.set_coeffs(d["c_xy"], d["c_yaw"], d["T_xy"], d["T_yaw"])
         return a.report()
     return _fill("report", str(tag), list(coeffs_by_case), make)
+
+
+# ---- the clearance term over the sweep (tests/test_clearance_sweep_cpu.py, tests/test_gpu_clearance_sweep.py) -----------------------------
+# The layer: hand-set body bytes on the sweep's 200 x 200 x 64 grid, a lattice that shifts every fourth yaw slice (reading the wrong slice changes the
+# answer), its distance transform truncated at CLR_RMAX cells.  CLR_WEIGHT: the sweep's objective at x0 is jerk-dominated (f 1e5 .. 6e7); the weight is
+# the one at which the term is a tenth or more of every case's f and of its largest gdCxy entry (asserted by the CPU tier from the oracle and the mirror).
+CLR_DIMS = (200, 200, 64)
+CLR_LATTICE = (7, 11, 5, 251)
+CLR_RMAX, CLR_D_SAFE, CLR_WEIGHT = 12, 0.3, 1.0e9
+CLR_SOLVE_WEIGHT = 1.0e9                        # of the capped solves (scale_fx is initScaling's there; the term carries it like the jerk cost does)
+CLR_SOLVE_LEFT_OUT = ()                         # solve cases unfit to test (solve_fitness; test_clearance_sweep_cpu asserts this is what it finds): none
+CLR_GEOM = (np.array([-5.0, -5.0, -(2.0 * np.pi + 5e-2) / 2.0]), 0.05, 0.1)      # (origin, res, yaw_res) of the sweep's 10 m x 10 m grid: clearance.layer_geometry's form
+
+
+def _key_of(D):
+    """cache key of a layer's values: shape and a digest of the bytes (two arrays with the same values share their answers; no stale entry for a new array)"""
+    import hashlib
+    D = np.ascontiguousarray(D)
+    return (D.shape, hashlib.sha1(D.tobytes()).hexdigest())
+
+
+def lattice_body(dims=CLR_DIMS, lattice=CLR_LATTICE):
+    """body bytes [nx][ny][nyaw]: 1 where (a ix + b iy + c (iw // 4)) % m == 0"""
+    a, b, c, m = lattice
+    ix, iy, iw = np.meshgrid(np.arange(dims[0]), np.arange(dims[1]), np.arange(dims[2]), indexing="ij")
+    return (((a * ix + b * iy + c * (iw // 4)) % m) == 0).astype(np.uint8)
+
+
+def clearance_layer(dims=CLR_DIMS, lattice=CLR_LATTICE, rmax=CLR_RMAX):
+    """the layer's values D [nx][ny][nyaw] by the host mirror of the distance transform (the device's layer.get() must equal it: the GPU tier asserts that)"""
+    key = ("clr_layer", tuple(dims), tuple(lattice), int(rmax))
+    with _LOCK:
+        if key not in _CACHE:
+            from uneven_planner_amd.clearance import clearance_rows
+            D = np.ascontiguousarray(clearance_rows(lattice_body(dims, lattice), rmax), dtype=np.uint16)
+            D.setflags(write=False)
+            _CACHE[key] = D
+    return _CACHE[key]
+
+
+def sample_poses(c_xy, c_yaw, T_xy, T_yaw, K=16):
+    """x, y and the normalised yaw at the quadrature samples of a trajectory given by its coefficients, at the reference's sample times (running sums
+    s1 += T_xy / K, base += T_xy; yaw piece min(int((s1 + base) / T_yaw), Nyaw - 1)): (Nxy, K + 1, 3).  For the generator conditions only."""
+    cx = np.asarray(c_xy, dtype=np.float64).reshape(-1, 6, 2)
+    cw = np.asarray(c_yaw, dtype=np.float64).reshape(-1, 6)
+    Nxy, Nyaw = cx.shape[0], cw.shape[0]
+    s1 = np.array([running_sum(T_xy / K, j) for j in range(K + 1)])
+    base = np.array([running_sum(T_xy, i) for i in range(Nxy)])
+    pw = np.stack([s1 ** k for k in range(6)], axis=1)
+    pos = np.einsum("jk,ikd->ijd", pw, cx)
+    now = s1[None, :] + base[:, None]
+    yi = np.clip((now / T_yaw).astype(np.int64), 0, Nyaw - 1)
+    u = now - yi * T_yaw
+    yaw = sum(cw[yi][..., k] * u ** k for k in range(6))
+    return np.concatenate([pos, norm_so2(yaw).reshape(Nxy, K + 1, 1)], axis=2)
+
+
+def term_rows(O, og, cases, D, term, geometry, int_K=16, tag="f64"):
+    """the mirror's rows (uneven_planner_amd.clearance.clearance_term_rows) of the term at the oracle's own coefficients at x0, per case, and the poses
+    of the samples: dict case -> dict(rows, poses).  term = (rmax, d_safe, weight); geometry = (origin, res, yaw_res)"""
+    from uneven_planner_amd.clearance import clearance_term_rows
+    ev = oracle_evals(O, og, cases, int_K, tag)
+    rmax, d_safe, weight = term
+
+    def make(case):
+        e, st = ev[case], case_state(case[0], case[1], int_K)
+        rows = clearance_term_rows(D, geometry, rmax, d_safe, weight, e["c_xy"], e["c_yaw"], e["T_xy"], e["T_yaw"], int_K, st["scale_fx"])
+        return dict(rows=rows, poses=sample_poses(e["c_xy"], e["c_yaw"], e["T_xy"], e["T_yaw"], int_K))
+    return _fill("clr_rows", (tag, int(int_K), _key_of(D), tuple(term)), list(cases), make)
+
+
+def oracle_eval_one(O, og, p, st, D=None, term=None, int_K=16):
+    """oracle_evals' answers for ONE problem p with the state st (sweep_state's dict), with the clearance term (D, term = (rmax, d_safe, weight)) or without"""
+    a = O.OracleALM(og, _params(int_K))
+    x0 = a.setup(p)
+    if term is not None:
+        a.set_clearance_term(D, *term)
+    a.set_state(lam=st["lam"], mu=st["mu"], scale_cx=st["scale_cx"], scale_fx=st["scale_fx"])
+    a.set_rho(st["rho"])
+    f, g, _ = a.eval(x0)
+    s = a.get_state()
+    cxy, cyaw, txy, tyaw, _ = a.coeffs()
+    cost, gcx, gtx, gcy, gty = a.constrain(x0)
+    s2 = a.get_state()
+    return dict(x0=x0, f=f, g=g, hx=s["hx"], gx=s["gx"], c_xy=cxy, c_yaw=cyaw, T_xy=txy, T_yaw=tyaw, pen_cost=cost, gdCxy=gcx, gdCyaw=gcy,
+                gdTxy=gtx, gdTyaw=gty, pen_hx=s2["hx"], pen_gx=s2["gx"])
+
+
+def oracle_evals_term(O, og, cases, D, term, int_K=16, tag="f64"):
+    """oracle_evals with the clearance term set: term = (rmax, d_safe, weight), D the layer's values (the caller keeps the array: the cache is keyed by it)"""
+    def make(case):
+        return oracle_eval_one(O, og, sweep_problem(*case), case_state(case[0], case[1], int_K), D, term, int_K)
+    return _fill("eval_term", (tag, int(int_K), _key_of(D), tuple(term)), list(cases), make)
+
+
+def solve_fitness(O, og, cells, D, term, nxys=None):
+    """Each solve case (ratio 2) solved by the oracle four times: with and without the term, in the default build and in the -DORACLE_EIGEN_REDUX=1 build.
+    dict nxy -> dict(counters_on, counters_off: the two builds agree in ret / lbfgs_iters / evals; dx_on, dx_off: their x apart (relative, infinity norm);
+    dcost_on, dcost_off: their returned costs apart; cost_jump: cost_jumps' figure of the default build; moved: x(on) against x(off) in the default build; fit: counters_on and dx_on <= max(10 dx_off, 1e-7))"""
+    key = ("clr_fitness", _key_of(D), _key_of(cells), tuple(term), tuple(nxys or SOLVE_NXY))
+    if key not in _CACHE:
+        cases = [(n, 2.0) for n in (nxys or SOLVE_NXY)]
+        on, off = oracle_solves_term(O, og, cases, D, term), oracle_solves_term(O, og, cases, D, None)
+        import sensitivity
+        with sensitivity.fma_session(*sensitivity.fma_session.EIGEN_ORDER) as F:
+            fg = F.OracleGrid()
+            fg.set_cells(cells)
+            eon, eoff = oracle_solves_term(F, fg, cases, D, term, tag="eig"), oracle_solves_term(F, fg, cases, D, None, tag="eig")
+        same = lambda a, b: all(a[k] == b[k] for k in ("ret", "lbfgs_iters", "evals"))
+        jump = cost_jumps(O, og, cases, D, term)
+        out = {}
+        for c in cases:
+            r = dict(counters_on=same(on[c], eon[c]), counters_off=same(off[c], eoff[c]), dx_on=rel(on[c]["x"], eon[c]["x"]), dx_off=rel(off[c]["x"], eoff[c]["x"]),
+                     moved=rel(off[c]["x"], on[c]["x"]), dcost_on=rel1(on[c]["cost"], eon[c]["cost"]), dcost_off=rel1(off[c]["cost"], eoff[c]["cost"]),
+                     cost_jump=jump[c])
+            r["fit"] = bool(r["counters_on"] and r["dx_on"] <= max(10.0 * r["dx_off"], 1e-7))
+            out[c[0]] = r
+        _CACHE[key] = out
+    return _CACHE[key]
+
+
+def cost_jumps(O, og, cases, D, term, tag="f64"):
+    """How far the oracle's own returned cost is from being a function of the returned x, per solve case: dict case -> relative jump (0.0 where the last
+    L-BFGS pass did not end in a failed line search).
+
+    After a failed line search (LBFGSERR_MAXIMUMLINESEARCH and its kin) lbfgs_optimize restores x and returns f at the search's last REJECTED trial
+    xp + stp d.  With the term, f is discontinuous -- the field is piecewise constant in yaw, f jumps where a sample's yaw crosses a slice edge across which
+    the layer differs -- and a search that bisects 64 times without meeting the Armijo test has converged onto such a jump: the side the last trial falls on
+    is rounding.  The jump is MEASURED here with the oracle alone: the failing iteration's state is captured (set_capture), its line search is replayed with
+    the oracle's evaluation (lbfgs.hpp:276-389 restated; the replay's last f must BE the solve's returned cost, bit for bit), and f is evaluated at
+    xp + stp (1 -+ 2^-30) d.  For a continuous f the two differ by about 2^-29 stp |g . d|; the measured relative difference is the reference's own error
+    of that cost, and the solve tests add it to their bar for the cost of that case (x and the counters keep their bars everywhere)."""
+    def make(case):
+        p = sweep_problem(*case)
+
+        def fresh():
+            a = O.OracleALM(og, SOLVE_PARAMS)
+            if term is not None:
+                a.set_clearance_term(D, *term)
+            return a
+        a = fresh()
+        a.set_capture(-1, -1, True)
+        r = a.optimize(p)
+        if not (r["last_lbfgs_ret"] < 0 and r["last_lbfgs_ret"] != -1008):
+            return 0.0
+        log = a.iter_log()
+        assert log[-1][2] == r["last_lbfgs_ret"]
+        b = fresh()
+        b.set_capture(int(log[-1][0]), int(log[-1][1]), True)
+        b.optimize(p)
+        st = b.capture()
+        assert st is not None
+        c = fresh()
+        c.init_scaling(c.setup(p))
+        c.set_state(lam=st["lam"], mu=st["mu"])
+        c.set_rho(st["rho"])
+        prm = dict(zip(O.PARAM_ORDER, c.pv))
+        xp, d, stp, finit = st["x"], st["d"], st["step"], st["fx"]
+        dginit = float(np.dot(st["g"], d))
+        dgtest, dstest = 1e-4 * dginit, 0.9 * dginit
+        mu_, nu, brackt, f = 0.0, 1e20, False, None
+        for count in range(1, 65):
+            f, g, _ = c.eval(xp + stp * d)
+            assert not (prm["past"] > 0 and abs(finit - f) / (abs(finit) + 1.0) < prm["delta"] / prm["past"])
+            if f > finit + stp * dgtest:
+                nu, brackt = stp, True
+            else:
+                assert float(np.dot(g, d)) < dstest
+                mu_ = stp
+            if count == 64:
+                break
+            stp = 0.5 * (mu_ + nu) if brackt else stp * 2.0
+        assert f == r["cost"], ("the replayed line search does not end where the solve did", case, f, r["cost"])
+        h = 2.0 ** -30
+        lo, hi = c.eval(xp + stp * (1.0 - h) * d)[0], c.eval(xp + stp * (1.0 + h) * d)[0]
+        return float(abs(hi - lo) / abs(r["cost"]))
+    return _fill("clr_cost_jump", (tag, _key_of(D), None if term is None else tuple(term)), list(cases), make)
+
+
+def cost_error(ref_cost, got_cost, jump):
+    """the relative error of a solve's returned cost, allowing for the reference's own jump (cost_jumps): the cost may lie on either side of it, so the error is
+    the smaller of |d| and | |d| - jump |.  With jump = 0 it is rel1."""
+    e = rel1(ref_cost, got_cost)
+    return float(min(e, abs(e - jump)))
+
+
+def oracle_solves_term(O, og, cases, D, term, tag="f64"):
+    """oracle_solves with the clearance term set (term = (rmax, d_safe, weight); None: the plain solve through the same entry)"""
+    def make(case):
+        a = O.OracleALM(og, SOLVE_PARAMS)
+        if term is not None:
+            a.set_clearance_term(D, *term)
+        return a.optimize(sweep_problem(*case))
+    return _fill("solve_term", (tag, _key_of(D), None if term is None else tuple(term)), list(cases), make)
 
 
 # ---- plain references of the kernels that read a resident trajectory back ------------------------------------------------------------------

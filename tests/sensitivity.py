@@ -23,14 +23,19 @@ def solve_many(make_alm, probs, threads=1):
 
 class fma_session:
     """`with fma_session() as O:` -- inside the block the module oracle.oracle_py is bound to the oracle rebuilt with -march=native -ffp-contract=fast
-    (grids and solvers created there live in that build); the plain build is restored on exit"""
+    (grids and solvers created there live in that build); the plain build is restored on exit.  fma_session(flags, tag): another second build, such as
+    EIGEN_ORDER = the -DORACLE_EIGEN_REDUX=1 build of solve_with_eigen_order_oracle"""
+    EIGEN_ORDER = (("-O3", "-DORACLE_EIGEN_REDUX=1"), "eig")
+
+    def __init__(self, flags=("-O3", "-march=native", "-ffp-contract=fast"), tag="fma"):
+        self.flags, self.tag = tuple(flags), tag
 
     def __enter__(self):
         from oracle import oracle_py as O
         self.O = O
-        so = "/tmp/liboracle_fma_%d.so" % os.getpid()
+        so = "/tmp/liboracle_%s_%d.so" % (self.tag, os.getpid())
         if not os.path.exists(so):
-            subprocess.check_call(["g++", "-O3", "-march=native", "-ffp-contract=fast", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "oracle", "oracle_capi.cpp")])
+            subprocess.check_call(["g++"] + list(self.flags) + ["-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "oracle", "oracle_capi.cpp")])
         self.saved, O._LIB = O._LIB, None
         self.real = O.os.path.join
         O.os.path.join = lambda *a, _r=self.real: so if a[-1] == "liboracle.so" else _r(*a)
